@@ -3,13 +3,17 @@
 AdamW, dropout on) of the audio GRU-256 x2 classifier on synthetic (B,T,F) = (512,300,256) per GPU
 (BASELINE.json configs[1]), weak-scaled over N GPUs with one RCCL gradient all-reduce per step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload audio_gru|text_bilstm|fusion]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload audio_gru|text_bilstm|fusion] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under torch.distributed.run (one rank per
 GPU, 127.0.0.1 rendezvous); the process group's size must equal --gpus or the run aborts.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the persistent recurrent sweep with the largest
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and reports the headline (`value`,
+`ms_per_step`, `final_loss`, which GRU forward ran); `--dump-outputs DIR` then writes what the last timed step computed
+(dump_outputs).  Everything below needs `--full` (`--profile-run`: the roofline only, no extra legs).
+
+`roofline` is for the dominant kernel (the persistent recurrent sweep with the largest
 total time): SURVEY 8(d)'s algorithmic flops per launch over its mean launch duration, measured with HIP events on the
 launch stream during the timed region, against the peak of the matrix pipe the sweep runs on (fp32 MFMA in exact mode; the
 bf16 pipe / 3 for the 3-term split) -- 8(d) shows the path is matrix-pipe bound, not HBM bound.  Beside it: `achieved_hbm`
@@ -97,7 +101,8 @@ def build_workload(name, dev, rank, world):
     torch.manual_seed(0)
     g = torch.Generator(device='cpu'); g.manual_seed(1234 + rank)
     y = torch.randint(0, 2, (B,), generator=g).to(dev)
-    out = {'mod': mod, 'B': B, 'T': T, 'F': F, 'H': H, 'y': y}
+    last = {}                                                 # what the latest step() computed (bench.py --dump-outputs)
+    out = {'mod': mod, 'B': B, 'T': T, 'F': F, 'H': H, 'y': y, 'last': last}
     if name == 'fusion':
         cfg = dict(mod.config); cfg.update(audio_embed_size=F, audio_hidden_dims=H, text_embed_size=1024, text_hidden_dims=128)
         model = mod.fusion_net(cfg['text_embed_size'], cfg['text_hidden_dims'], cfg['rnn_layers'], cfg['dropout'],
@@ -113,8 +118,9 @@ def build_workload(name, dev, rank, world):
             parallel.set_global_count(B * world)
             optimizer.zero_grad()
             tf, af = model.pretrained_feature((xa, xt))
-            model(_common.concat_features(tf, af))          # dep_copy2d x 2, as the product loop (fuse_net_whole.train)
+            o = model(_common.concat_features(tf, af))      # dep_copy2d x 2, as the product loop (fuse_net_whole.train)
             loss = criterion(tf, af, y, model)
+            last.update(text_feature=tf, audio_feature=af, output=o)
             loss.backward()
             optimizer.step()
             return loss
@@ -133,12 +139,43 @@ def build_workload(name, dev, rank, world):
             optimizer.zero_grad()
             o = model(x)
             loss = criterion(o, y)
+            last['output'] = o
             loss.backward()                                   # includes the RCCL all-reduce of the grad bucket
             optimizer.step()
             return loss
         out.update(x=x, eval_fn=lambda: model(x))
     out.update(model=model, optimizer=optimizer, criterion=criterion, cfg=cfg, step=step)
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, wl, final_loss):
+    """--dump-outputs: what the last timed step hands its caller, one DIR/<name>.npy each -- `output` (the model's probabilities;
+    the fusion workload also `text_feature` / `audio_feature`), `loss`, `param.<name>` (every state_dict entry after the optimizer
+    step) and `grad.<name>` (every gradient of that step).  fp64 stays fp64, other floats are written as fp32, integers as fp64."""
+    import numpy as np
+    arrays = {'loss': torch.tensor(final_loss, dtype=torch.float64)}
+    for k, v in wl['last'].items():
+        arrays[k] = v.data if isinstance(getattr(v, 'data', None), torch.Tensor) else v       # nn.Output -> its device tensor
+    for k, v in wl['model'].state_dict().items():
+        if torch.is_tensor(v):
+            arrays['param.' + k] = v
+    for k, p in wl['model'].named_parameters():
+        if p.grad is not None:
+            arrays['grad.' + k] = p.grad
+    host = {}
+    for k, v in arrays.items():
+        v = v.detach()
+        v = v if v.dtype == torch.float64 else (v.float() if v.is_floating_point() else v.double())
+        host[k] = v.cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}')
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + '.npy'), a)
 
 
 def dominant_sweep(prof, steps, name, B, T, H):
@@ -271,6 +308,103 @@ def time_other_workload(name, dev, L, steps=8, warmup=3):
     return res
 
 
+def roofline_figures(prof, args, L, B, T, H, value, world, ms_per_step):
+    """Roofline of the dominant kernel of the timed region (per-launch HIP-event timing: --full / --profile-run)."""
+    cats = {k: v for k, v in prof.items() if v[1] > 0}
+    sweeps = {k: v for k, v in cats.items() if 'sweep' in k}
+    dom = max(sweeps, key=lambda k: sweeps[k][0])
+    dom_ms = sweeps[dom][0] / sweeps[dom][1]
+    if dom.startswith('lstm'):
+        G, dirs, H = 4, 2, 128                                # the text encoder's hidden size in every workload
+    else:
+        G, dirs = 3, 1
+    launches_per_step = sweeps[dom][1] / args.steps          # 2 for per-layer sweeps, 1 for a launch that carries both layers
+    layers_per_launch = 2.0 / launches_per_step
+    # SURVEY 8(d) algorithmic work of ONE launch of the dominant sweep: recurrent flops 2 * T * (G H) * H per utterance, layer
+    # and direction; COMPULSORY HBM bytes per (utterance, step, layer, direction): the hidden sequence once -- written by the
+    # forward sweep, read by the backward sweep (8d: "hidden sequences written once in fwd and read once in bwd, nothing else,
+    # gates recomputed") = 4H bytes in fp32.  The DESIGN bytes count what this implementation chose to move instead (saved
+    # gate tensors, the materialised input projection and its gradient), DESIGN.md section 4.
+    sweep_flops = 2.0 * B * T * (G * H) * H * dirs * layers_per_launch
+    fused_gru = dom.startswith('gru') and layers_per_launch > 1.5
+    if fused_gru:
+        # a fused two-layer GRU launch carries a THIRD product of the same size beside the two recurrences: layer 1's input projection
+        # W_ih(l1) dropout(h0) in the forward, the gradient entering layer 0, dgi(l1) W_ih(l1), in the backward (the former projection / dX GEMMs)
+        sweep_flops *= 1.5
+    fusion = args.workload == 'fusion'
+    design_per_ut = ({'gru_fwd_sweep': 18 * H, 'lstm_fwd_sweep': 44 * H} if fusion else
+                     {'gru_fwd_sweep': 34 * H, 'gru_bwd_sweep': 32 * H, 'lstm_fwd_sweep': 84 * H, 'lstm_bwd_sweep': 88 * H})[dom]      # (round 4: GRU saved gates r, z, n are 2 bytes each: backward 38H -> 32H)
+    compulsory_per_ut = 4 * H * dirs
+    design_bytes = float(design_per_ut) * B * T * layers_per_launch
+    if dom == 'gru_fwd_sweep' and layers_per_launch > 1.5:
+        # the fused two-layer forward: layer 0's input projection in (12H), both layers' h (8H) and saved gates (2 x (6H + 4H)) out, the
+        # dropped copy of layer 0's h (4H); layer 1's projection never exists in HBM
+        design_bytes = float(44 * H) * B * T              # (round 4: 16-bit r, z, n: 56H -> 44H)
+    if dom == 'gru_bwd_sweep' and layers_per_launch > 1.5:
+        # the fused two-layer backward (round 5): per layer r, z, n (2 bytes each) + hn + h_{t-1} in (14H), the 4H-wide PK gate gradients out (16H);
+        # layer 1's dX / layer 0's dy never exist in HBM
+        design_bytes = float(60 * H) * B * T
+    compulsory_bytes = float(compulsory_per_ut) * B * T * layers_per_launch
+    split = L.get_gemm_mode() == 1                           # the cluster sweeps follow the GEMM precision mode
+    mfma_peak = PEAK_BF16_MFMA_TFLOPS / 3.0 if split else PEAK_F32_MFMA_TFLOPS
+    sec = dom_ms * 1e-3
+    tflops = sweep_flops / sec / 1e12
+    frac_mfma = tflops / mfma_peak
+    # serial floor (SURVEY 8d): the dependent recurrent steps of this launch at 1 us per hand-off
+    serial_steps = T + (layers_per_launch - 1)
+    serial_floor_ms = serial_steps * 1e-3
+    traffic, traffic_note = None, 'no PMC record for this workload / kernel'
+    tpath = os.path.join(ROOT, 'profiles', 'pmc_traffic.json')
+    try:
+        rec = json.load(open(tpath))
+        stamp = open(os.path.join(ROOT, 'icassp2022-depression_amd', 'libdep_rnn.so.stamp')).read().strip()
+        ent = rec.get('workloads', {}).get(args.workload, {}).get(dom)
+        if ent is not None and rec.get('kernel_digest') == stamp:
+            traffic, traffic_note = ent, f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes at commit {rec.get('commit')}, same kernel digest"
+        elif ent is not None:
+            traffic_note = 'PMC record is from other kernel sources (digest mismatch): refused'
+    except Exception:
+        pass
+    step_traffic = None
+    try:
+        step_traffic = rec.get('step_bytes', {}).get(args.workload) if rec.get('kernel_digest') == stamp else None
+    except Exception:
+        pass
+    # which roof is nearer, from SURVEY 8(d)'s algorithmic figures (flops; compulsory bytes): derived, not assumed.  Neither
+    # binds: the sweep is limited by the serial hand-off latency of its T dependent steps (serial_floor below).
+    frac_hbm_alg = compulsory_bytes / sec / 1e9 / PEAK_HBM_GBS
+    bound = 'mfma' if frac_mfma >= frac_hbm_alg else 'hbm'
+    roofline = {'bound': bound, 'kernel': dom,
+                'achieved': round(tflops, 3) if bound == 'mfma' else round(compulsory_bytes / sec / 1e9, 1),
+                'peak': round(mfma_peak, 1) if bound == 'mfma' else PEAK_HBM_GBS, 'unit': 'TFLOP/s' if bound == 'mfma' else 'GB/s',
+                'frac': round(frac_mfma if bound == 'mfma' else frac_hbm_alg, 4), 'traffic': traffic, 'traffic_note': traffic_note,
+                'limiter': 'serial hand-off latency of the recurrent steps (see serial_floor); sustained bf16 MFMA rate under the '
+                           'package power cap is 1.6-1.7 PFLOP/s (profiles/r03_micro_mfma_rate.txt), the guide peak is kept as `peak`',
+                'step_traffic': {'pmc_bytes_per_step': step_traffic, 'survey_8d_bytes_per_step': SURVEY_8D_BYTES_PER_STEP[args.workload],
+                                 'note': 'sum over all kernels of (2*FETCH_SIZE + WRITE_SIZE) per train step, rocprofv3 --pmc passes'},
+                'mfma_pipe': 'bf16 x3 split (peak = bf16 dense / 3)' if split else 'fp32',
+                'flops_per_launch': sweep_flops, 'avg_launch_ms': round(dom_ms, 4), 'launches_per_step': launches_per_step,
+                'achieved_mfma': {'tflops': round(tflops, 3), 'frac': round(frac_mfma, 4)},
+                'achieved_hbm': {'compulsory_bytes_per_launch': compulsory_bytes,
+                                 'compulsory_gbs': round(compulsory_bytes / sec / 1e9, 1),
+                                 'compulsory_frac': round(compulsory_bytes / sec / 1e9 / PEAK_HBM_GBS, 4),
+                                 'design_bytes_per_launch': design_bytes,
+                                 'design_gbs': round(design_bytes / sec / 1e9, 1),
+                                 'design_frac': round(design_bytes / sec / 1e9 / PEAK_HBM_GBS, 4),
+                                 'peak_gbs': PEAK_HBM_GBS},
+                'serial_floor': {'dependent_steps_per_launch': serial_steps, 'us_per_step': round(dom_ms * 1e3 / serial_steps, 3),
+                                 'floor_ms_at_1us': round(serial_floor_ms, 4), 'serial_floor_frac': round(serial_floor_ms / dom_ms, 4)},
+                'kernels_ms_per_step': {k: round(v[0] / args.steps, 4) for k, v in cats.items()}}
+    train_flops_per_utt = {'audio_gru': 1.4156e9, 'text_bilstm': 2.831e9,           # SURVEY 8(d); fusion = the two forwards
+                           'fusion': (1.4156e9 + 2.831e9) / 3.0}[args.workload]
+    step_tflops = train_flops_per_utt * value / 1e12 / world
+    roofline['step_tflops_fp32_equiv'] = round(step_tflops, 2)
+    roofline['families'] = kernel_families(cats, args.steps, args.workload, B, T, H, split, ms_per_step)
+    if step_traffic:
+        roofline['step_traffic']['wasted_traffic_ratio'] = round(step_traffic / SURVEY_8D_BYTES_PER_STEP[args.workload], 2)
+    return roofline
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -279,7 +413,12 @@ def main():
     ap.add_argument('--workload', default='audio_gru', choices=sorted(WORKLOADS))
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-other-workloads', action='store_true', help='skip extra.other_workloads (the other two BASELINE per-GPU workloads, a few steps each)')
-    ap.add_argument('--profile-run', action='store_true', help='warm-up + timed steps only (rocprofv3 passes: every launch belongs to a train step)')
+    ap.add_argument('--profile-run', action='store_true', help='warm-up + timed steps with per-launch event timing (roofline, kernels_ms_per_step) '
+                    'and none of the extra legs of --full (rocprofv3 passes: every launch belongs to a train step)')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: per-launch timing and roofline of the timed region, forward-only rate, the other precision '
+                         'modes, train() loop, the other workloads, CPU baseline, N-rank communication probes')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy (rank 0)')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='process-group backend (gloo: launch check on CPU, or a dry run of the N-rank bench with the ranks sharing one GPU)')
     ap.add_argument('--launch-check', action='store_true', help='only exercise the N-rank launch + one all-reduce')
@@ -313,16 +452,21 @@ def main():
     mod, model, optimizer, criterion, cfg, step = wl['mod'], wl['model'], wl['optimizer'], wl['criterion'], wl['cfg'], wl['step']
     x, xa, xt = wl.get('x'), wl.get('xa'), wl.get('xt')
 
+    # a plain run times the steps alone; --full / --profile-run also time every launch of them with HIP events (roofline)
+    timed_launches = args.full or args.profile_run
     for _ in range(args.warmup):
         step()
     parallel.barrier(); torch.cuda.synchronize()
-    L.profile_enable(True); L.profile_read()
+    if timed_launches:
+        L.profile_enable(True); L.profile_read()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = step()
     torch.cuda.synchronize(); parallel.barrier()
     dt = time.perf_counter() - t0
-    prof = L.profile_read(); L.profile_enable(False)
+    prof = None
+    if timed_launches:
+        prof = L.profile_read(); L.profile_enable(False)
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1:
         import torch.distributed as dist
@@ -356,7 +500,9 @@ def main():
         if any(r[1] for r in rows):
             raise SystemExit(f'bench.py: a recurrent sweep raised its status word on some rank {[r[1] for r in rows]}: refusing to report the step')
 
-    extras = not args.profile_run
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl, final_loss)       # before the legs of --full step the model further
+    extras = args.full and not args.profile_run
     # exposed communication per rank: the same step with the gradient exchange switched off, timed like the
     # headline region; exposed = step - step_without_comm.  The replicas drift apart without the exchange: parameters and optimizer
     # moments are snapshotted and restored around the leg.
@@ -540,100 +686,9 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = B * world * args.steps / dt
 
-    # ---- roofline of the dominant kernel ------------------------------------------------
-    cats = {k: v for k, v in prof.items() if v[1] > 0}
-    sweeps = {k: v for k, v in cats.items() if 'sweep' in k}
-    dom = max(sweeps, key=lambda k: sweeps[k][0])
-    dom_ms = sweeps[dom][0] / sweeps[dom][1]
     H_model = H
-    if dom.startswith('lstm'):
-        G, dirs, H = 4, 2, 128                                # the text encoder's hidden size in every workload
-    else:
-        G, dirs = 3, 1
-    launches_per_step = sweeps[dom][1] / args.steps          # 2 for per-layer sweeps, 1 for a launch that carries both layers
-    layers_per_launch = 2.0 / launches_per_step
-    # SURVEY 8(d) algorithmic work of ONE launch of the dominant sweep: recurrent flops 2 * T * (G H) * H per utterance, layer
-    # and direction; COMPULSORY HBM bytes per (utterance, step, layer, direction): the hidden sequence once -- written by the
-    # forward sweep, read by the backward sweep (8d: "hidden sequences written once in fwd and read once in bwd, nothing else,
-    # gates recomputed") = 4H bytes in fp32.  The DESIGN bytes count what this implementation chose to move instead (saved
-    # gate tensors, the materialised input projection and its gradient), DESIGN.md section 4.
-    sweep_flops = 2.0 * B * T * (G * H) * H * dirs * layers_per_launch
-    fused_gru = dom.startswith('gru') and layers_per_launch > 1.5
-    if fused_gru:
-        # a fused two-layer GRU launch carries a THIRD product of the same size beside the two recurrences: layer 1's input projection
-        # W_ih(l1) dropout(h0) in the forward, the gradient entering layer 0, dgi(l1) W_ih(l1), in the backward (the former projection / dX GEMMs)
-        sweep_flops *= 1.5
     fusion = args.workload == 'fusion'
-    design_per_ut = ({'gru_fwd_sweep': 18 * H, 'lstm_fwd_sweep': 44 * H} if fusion else
-                     {'gru_fwd_sweep': 34 * H, 'gru_bwd_sweep': 32 * H, 'lstm_fwd_sweep': 84 * H, 'lstm_bwd_sweep': 88 * H})[dom]      # (round 4: GRU saved gates r, z, n are 2 bytes each: backward 38H -> 32H)
-    compulsory_per_ut = 4 * H * dirs
-    design_bytes = float(design_per_ut) * B * T * layers_per_launch
-    if dom == 'gru_fwd_sweep' and layers_per_launch > 1.5:
-        # the fused two-layer forward: layer 0's input projection in (12H), both layers' h (8H) and saved gates (2 x (6H + 4H)) out, the
-        # dropped copy of layer 0's h (4H); layer 1's projection never exists in HBM
-        design_bytes = float(44 * H) * B * T              # (round 4: 16-bit r, z, n: 56H -> 44H)
-    if dom == 'gru_bwd_sweep' and layers_per_launch > 1.5:
-        # the fused two-layer backward (round 5): per layer r, z, n (2 bytes each) + hn + h_{t-1} in (14H), the 4H-wide PK gate gradients out (16H);
-        # layer 1's dX / layer 0's dy never exist in HBM
-        design_bytes = float(60 * H) * B * T
-    compulsory_bytes = float(compulsory_per_ut) * B * T * layers_per_launch
-    split = L.get_gemm_mode() == 1                           # the cluster sweeps follow the GEMM precision mode
-    mfma_peak = PEAK_BF16_MFMA_TFLOPS / 3.0 if split else PEAK_F32_MFMA_TFLOPS
-    sec = dom_ms * 1e-3
-    tflops = sweep_flops / sec / 1e12
-    frac_mfma = tflops / mfma_peak
-    # serial floor: the dependent recurrent steps of this launch at 1 us per hand-off
-    serial_steps = T + (layers_per_launch - 1)
-    serial_floor_ms = serial_steps * 1e-3
-    traffic, traffic_note = None, 'no PMC record for this workload / kernel'
-    tpath = os.path.join(ROOT, 'profiles', 'pmc_traffic.json')
-    try:
-        rec = json.load(open(tpath))
-        stamp = open(os.path.join(ROOT, 'icassp2022-depression_amd', 'libdep_rnn.so.stamp')).read().strip()
-        ent = rec.get('workloads', {}).get(args.workload, {}).get(dom)
-        if ent is not None and rec.get('kernel_digest') == stamp:
-            traffic, traffic_note = ent, f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes at commit {rec.get('commit')}, same kernel digest"
-        elif ent is not None:
-            traffic_note = 'PMC record is from other kernel sources (digest mismatch): refused'
-    except Exception:
-        pass
-    step_traffic = None
-    try:
-        step_traffic = rec.get('step_bytes', {}).get(args.workload) if rec.get('kernel_digest') == stamp else None
-    except Exception:
-        pass
-    # which roof is nearer, from SURVEY 8(d)'s algorithmic figures (flops; compulsory bytes): derived, not assumed.  Neither
-    # binds: the sweep is limited by the serial hand-off latency of its T dependent steps (serial_floor below).
-    frac_hbm_alg = compulsory_bytes / sec / 1e9 / PEAK_HBM_GBS
-    bound = 'mfma' if frac_mfma >= frac_hbm_alg else 'hbm'
-    roofline = {'bound': bound, 'kernel': dom,
-                'achieved': round(tflops, 3) if bound == 'mfma' else round(compulsory_bytes / sec / 1e9, 1),
-                'peak': round(mfma_peak, 1) if bound == 'mfma' else PEAK_HBM_GBS, 'unit': 'TFLOP/s' if bound == 'mfma' else 'GB/s',
-                'frac': round(frac_mfma if bound == 'mfma' else frac_hbm_alg, 4), 'traffic': traffic, 'traffic_note': traffic_note,
-                'limiter': 'serial hand-off latency of the recurrent steps (see serial_floor); sustained bf16 MFMA rate under the '
-                           'package power cap is 1.6-1.7 PFLOP/s (profiles/r03_micro_mfma_rate.txt), the guide peak is kept as `peak`',
-                'step_traffic': {'pmc_bytes_per_step': step_traffic, 'survey_8d_bytes_per_step': SURVEY_8D_BYTES_PER_STEP[args.workload],
-                                 'note': 'sum over all kernels of (2*FETCH_SIZE + WRITE_SIZE) per train step, rocprofv3 --pmc passes'},
-                'mfma_pipe': 'bf16 x3 split (peak = bf16 dense / 3)' if split else 'fp32',
-                'flops_per_launch': sweep_flops, 'avg_launch_ms': round(dom_ms, 4), 'launches_per_step': launches_per_step,
-                'achieved_mfma': {'tflops': round(tflops, 3), 'frac': round(frac_mfma, 4)},
-                'achieved_hbm': {'compulsory_bytes_per_launch': compulsory_bytes,
-                                 'compulsory_gbs': round(compulsory_bytes / sec / 1e9, 1),
-                                 'compulsory_frac': round(compulsory_bytes / sec / 1e9 / PEAK_HBM_GBS, 4),
-                                 'design_bytes_per_launch': design_bytes,
-                                 'design_gbs': round(design_bytes / sec / 1e9, 1),
-                                 'design_frac': round(design_bytes / sec / 1e9 / PEAK_HBM_GBS, 4),
-                                 'peak_gbs': PEAK_HBM_GBS},
-                'serial_floor': {'dependent_steps_per_launch': serial_steps, 'us_per_step': round(dom_ms * 1e3 / serial_steps, 3),
-                                 'floor_ms_at_1us': round(serial_floor_ms, 4), 'serial_floor_frac': round(serial_floor_ms / dom_ms, 4)},
-                'kernels_ms_per_step': {k: round(v[0] / args.steps, 4) for k, v in cats.items()}}
-    train_flops_per_utt = {'audio_gru': 1.4156e9, 'text_bilstm': 2.831e9,           # SURVEY 8(d); fusion = the two forwards
-                           'fusion': (1.4156e9 + 2.831e9) / 3.0}[args.workload]
-    step_tflops = train_flops_per_utt * value / 1e12 / world
-    roofline['step_tflops_fp32_equiv'] = round(step_tflops, 2)
-    roofline['families'] = kernel_families(cats, args.steps, args.workload, B, T, H, split, ms_per_step)
-    if step_traffic:
-        roofline['step_traffic']['wasted_traffic_ratio'] = round(step_traffic / SURVEY_8D_BYTES_PER_STEP[args.workload], 2)
+    roofline = roofline_figures(prof, args, L, B, T, H, value, world, ms_per_step) if prof is not None else None
 
     out = {'metric': {'audio_gru': 'utterances/sec (train step) for GRU-256 on (B,T,F)=(512,300,256)',
                       'text_bilstm': 'utterances/sec (train step) for BiLSTM-128x2 on (B,T,F)=(512,300,1024)',
@@ -647,8 +702,9 @@ def main():
                       'global_batch': B * world, 'parallelism': f'dp{world}', 'ranks': world,
                       'backend': comm_kind},
            'final_loss': round(final_loss, 6),
-           'gru_forward_path': fwd_path,
-           'roofline': roofline}
+           'gru_forward_path': fwd_path}
+    if roofline is not None:
+        out['roofline'] = roofline
     if world > 1:
         # top level, not only config.backend: which transport carried the gradients, and why if it is not the C-ABI's own communicator
         tr = parallel.transport()
@@ -661,10 +717,11 @@ def main():
     if eval_ms is not None:
         out['eval_forward'] = {'value': round(B / (eval_ms * 1e-3), 1), 'unit': 'utterances/s', 'ms_per_batch': round(eval_ms, 3),
                                'note': 'forward only (evaluate), rank 0, outside the headline region'}
-    out['extra'] = {'f32_exact': f32_exact, 'bf16_products': bf16_products, 'bf16_storage': bf16_storage, 'train_e2e': train_e2e, 'comm_alone_ms_per_step_by_rank': comm_alone, 'exposed_comm': exposed,
-                    'other_workloads': other,
-                    'precision_note': 'storage, state, accumulation and elementwise math fp32; products of the large contractions '
-                                      'and of the recurrent sweeps: 3-term bf16 split on the bf16 matrix cores (DEP_GEMM_MODE=f32 = exact)'}
+    if timed_launches:
+        out['extra'] = {'f32_exact': f32_exact, 'bf16_products': bf16_products, 'bf16_storage': bf16_storage, 'train_e2e': train_e2e,
+                        'comm_alone_ms_per_step_by_rank': comm_alone, 'exposed_comm': exposed, 'other_workloads': other,
+                        'precision_note': 'storage, state, accumulation and elementwise math fp32; products of the large contractions '
+                                          'and of the recurrent sweeps: 3-term bf16 split on the bf16 matrix cores (DEP_GEMM_MODE=f32 = exact)'}
 
     if world == 1 and not args.no_cpu_baseline and extras:
         import platform

@@ -303,7 +303,7 @@ def test_bench_two_rank_dry_run_on_one_gpu():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--steps', '3', '--warmup', '1',
-                        '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=600)
+                        '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     line = [l for l in r.stdout.splitlines() if l.startswith('{')][-1]
     d = json.loads(line)
@@ -319,3 +319,24 @@ def test_bench_two_rank_dry_run_on_one_gpu():
     assert len(rk['gru_forward_path_by_rank']) == 2 and rk['sweep_status_by_rank'] == [0, 0] and rk['native_rccl_by_rank'] == [False, False]
     assert d['comm_transport'] == 'torch.distributed' and d['comm_transport_is_native_rccl'] is False and 'gloo' in d['comm_transport_reason']
     assert 'rank' in d['gru_forward_path']              # "... (all 2 ranks)" or "MIXED over ranks: ..."
+
+
+@pytest.mark.skipif(not torch.cuda.is_available(), reason='needs a GPU')
+def test_bench_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run reports the headline of exactly --steps timed steps and nothing of --full; --dump-outputs
+    writes what the last timed step computed (probabilities, loss, updated parameters, gradients) as fp32 / fp64 .npy files."""
+    import json
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+                        '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+    assert d['steps'] == 2 and d['warmup'] == 1 and d['ms_per_step'] > 0 and d['higher_is_better'] is True and d['dtype'] == 'f32'
+    assert abs(d['value'] - 512 / (d['ms_per_step'] * 1e-3)) <= 1e-3 * d['value'] + 0.1
+    assert not {'roofline', 'extra', 'eval_forward', 'cpu_baseline'} & set(d)
+    files = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert all(f.endswith('.npy') for f in os.listdir(tmp_path)) and sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+    assert files['output'].shape == (512, 2) and np.allclose(files['output'].sum(1), 1.0, atol=1e-5)
+    assert abs(float(files['loss']) - d['final_loss']) < 1e-6
+    assert 'param.lstm_net_audio.weight_hh_l0' in files and 'grad.lstm_net_audio.weight_hh_l0' in files

@@ -14,9 +14,9 @@ find $out/stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/kern
 bash tools/prof_sq.sh $tag/sq python $PWD/bench.py --steps 3 --warmup 1 --profile-run --no-other-workloads > $out/sq.txt 2>&1
 python -m pytest tests/ -x -q -m gpu 2>&1 | grep -E "passed|failed|error" | tail -3
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_cfg2.json 2> $out/bench.err
-python bench.py --steps 20 --warmup 5 --no-other-workloads --workload text_bilstm > $out/bench_cfg3.json 2>> $out/bench.err
-python bench.py --steps 20 --warmup 5 --no-other-workloads --workload fusion > $out/bench_cfg4_fusion.json 2>> $out/bench.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_cfg2.json 2> $out/bench.err
+python bench.py --steps 20 --warmup 5 --full --no-other-workloads --workload text_bilstm > $out/bench_cfg3.json 2>> $out/bench.err
+python bench.py --steps 20 --warmup 5 --full --no-other-workloads --workload fusion > $out/bench_cfg4_fusion.json 2>> $out/bench.err
 python - "$out" <<'PY'
 import json, sys
 for f in ('bench_cfg2', 'bench_cfg3', 'bench_cfg4_fusion'):

@@ -9,9 +9,9 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 out=$PWD/gpurun_out/$tag
 mkdir -p $out
-python bench.py --steps 20 --warmup 5 > $out/bench_cfg2.json 2> $out/bench_cfg2.err
-python bench.py --steps 20 --warmup 5 --workload text_bilstm > $out/bench_cfg3.json 2> $out/bench_cfg3.err
-python bench.py --steps 20 --warmup 5 --workload fusion > $out/bench_cfg4_fusion.json 2> $out/bench_cfg4.err
+python bench.py --steps 20 --warmup 5 --full > $out/bench_cfg2.json 2> $out/bench_cfg2.err
+python bench.py --steps 20 --warmup 5 --full --workload text_bilstm > $out/bench_cfg3.json 2> $out/bench_cfg3.err
+python bench.py --steps 20 --warmup 5 --full --workload fusion > $out/bench_cfg4_fusion.json 2> $out/bench_cfg4.err
 ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o bench -- python $OLDPWD/bench.py --steps 10 --warmup 3 --profile-run ) > $out/stats.log 2>&1
 for wl in audio_gru text_bilstm fusion; do
   bash tools/prof_pmc.sh $tag/pmc_$wl python $PWD/bench.py --steps 3 --warmup 1 --profile-run --workload $wl > $out/pmc_$wl.txt 2>&1
