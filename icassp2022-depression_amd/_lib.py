@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get('DEP_LIB_PATH') or os.path.join(HERE, 'libdep_rnn.so')
 
 CELL_GRU, CELL_LSTM = 0, 1
 POOL_NONE, POOL_MEAN, POOL_SUM = 0, 1, 2
+# dep_rnn_desc.training (include/dep_rnn.h): no dropout / dropout + backward reserve / dropout, no backward reserve
+RUN_EVAL, RUN_TRAIN, RUN_DROPOUT_ONLY = 0, 1, 2
 LOSS_CE_ON_SOFTMAX, LOSS_L1_RELU, LOSS_SMOOTHL1_RELU, LOSS_CE_LOGITS, LOSS_SMOOTHL1 = 0, 1, 2, 3, 4
 LOSS_LABELS_I64 = 0x100                     # OR into a CE kind: int64 labels read in place
 SITE_FC0, SITE_FC1, SITE_FC2, SITE_FC3 = 1, 2, 3, 4
@@ -412,7 +414,8 @@ def note_fallback():
 
 
 class Rnn:
-    """One dep_rnn_desc + its reserve/workspace buffers (allocated once per shape, reused per step)."""
+    """One dep_rnn_desc + its reserve/workspace buffers (allocated once per shape, reused per step).
+    training: the run mode, RUN_EVAL / RUN_TRAIN / RUN_DROPOUT_ONLY (a bool is taken as RUN_EVAL / RUN_TRAIN)."""
 
     def __init__(self, cell, B, T, F, H, L, dirs, training, dropout_p, pool, device, impl=0):
         self.lib = load()
@@ -456,7 +459,10 @@ class Rnn:
         """Zero-copy view of a layer's output sequence (B,T,H*dirs) inside the reserve."""
         d = self.desc
         layer = d.L - 1 if layer is None else layer
-        off = self.lib.dep_rnn_reserve_y_offset(C.byref(d), layer) // 4
+        off = self.lib.dep_rnn_reserve_y_offset(C.byref(d), layer)
+        if off == C.c_size_t(-1).value:
+            raise DepError(f'layer {layer} output is not kept in the reserve (run mode {d.training}; pass y= to forward)')
+        off //= 4
         n = d.B * d.T * d.H * d.dirs
         return self.reserve[off:off + n].view(d.B, d.T, d.H * d.dirs)
 

@@ -141,6 +141,7 @@ extern "C" long dep_instance_log_read(char* buf, long cap, int reset) {
 namespace {
 
 constexpr int MAXL = 8;
+constexpr size_t NOT_KEPT = (size_t)-1;         // Layout offset of an array the run mode does not keep
 
 struct Layout {
     int G, D, L;
@@ -155,6 +156,8 @@ struct Layout {
     size_t gemm_bytes, xbuf_bytes, ws_floats;
     int nwg;
     bool drop;
+    bool keep;                       // DEP_RUN_TRAIN: the reserve holds everything the backward reads
+    bool donly;                      // DEP_RUN_DROPOUT_ONLY: dropout as in training, the reserve holds what the forward itself reads
     bool cluster;                    // cluster-parallel sweeps (rnn_cluster*.hip)
     bool cluster16;                  // forward with 16-unit members, two workgroups per CU (rnn_cluster16.hip)
     bool dg4;                        // GRU cluster backward: gate gradients as ONE (B*T, 4H) array [dr | dz | dn | dn*r] (dW_hh is then one contraction)
@@ -170,22 +173,30 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     else if (d->cell == DEP_CELL_LSTM) { if (d->dirs != 1 && d->dirs != 2) return false; }
     else return false;
     if (d->dropout_p < 0.f || d->dropout_p >= 1.f) return false;
+    if (d->training != DEP_RUN_EVAL && d->training != DEP_RUN_TRAIN && d->training != DEP_RUN_DROPOUT_ONLY) return false;
     lo.G = d->cell == DEP_CELL_GRU ? 3 : 4; lo.D = d->dirs; lo.L = d->L;
     lo.BT = (size_t)d->B * d->T;
-    lo.drop = d->training && d->dropout_p > 0.f;
+    lo.keep = d->training == DEP_RUN_TRAIN;
+    lo.donly = d->training == DEP_RUN_DROPOUT_ONLY;
+    lo.drop = d->training != DEP_RUN_EVAL && d->dropout_p > 0.f;
     const size_t H = d->H, D = d->dirs, G = lo.G;
     auto al = [](size_t f) { return (f + 63) / 64 * 64; };
     size_t off = 0;
     for (int l = 0; l < d->L; ++l) {
-        lo.y[l] = off; off += al(lo.BT * D * H);
+        // dropout-only: a lower layer keeps the copy the next layer's projection reads (dropout(y), or y when p = 0); the top layer
+        // keeps y (the caller's zero-copy view) unless it is a pooled GRU, whose pooled output is all that leaves the forward
+        const bool top = l == d->L - 1;
+        const bool ykept = !lo.donly || (top ? !(d->cell == DEP_CELL_GRU && d->pool != DEP_POOL_NONE) : !lo.drop);
+        lo.y[l] = NOT_KEPT; if (ykept) { lo.y[l] = off; off += al(lo.BT * D * H); }
         lo.ydrop[l] = off; if (lo.drop && l < d->L - 1) off += al(lo.BT * D * H);
-        if (d->training) {
+        for (int k = 0; k < 4; ++k) lo.sv[l][k] = NOT_KEPT;
+        if (lo.keep) {
             if (d->cell == DEP_CELL_GRU) { for (int k = 0; k < 4; ++k) { lo.sv[l][k] = off; off += al(lo.BT * H); } }
             else { lo.sv[l][0] = off; off += al(lo.BT * D * 4 * H); lo.sv[l][1] = off; off += al(lo.BT * D * H); lo.sv[l][2] = lo.sv[l][3] = 0; }
         }
         for (size_t dd = 0; dd < D; ++dd) {
             lo.wp[l][dd] = off; off += al(G * H * H);
-            lo.wpT[l][dd] = off; off += al(G * H * H);
+            lo.wpT[l][dd] = NOT_KEPT; if (!lo.donly) { lo.wpT[l][dd] = off; off += al(G * H * H); }
         }
     }
     // bidirectional stacks: the two directions share their input, so their input projections, dX and dW_ih are ONE contraction
@@ -205,7 +216,7 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     // the generic sweep.  (Sized for the larger; dep_finish_db sums the rows the sweep that ran has written: dbpart_rows.)
     lo.nwg = dep_sweep_num_wg(d->B, d->H, d->impl);
     size_t w = 0;
-    lo.gi = w; w += al(lo.BT * D * (G + (d->cell == DEP_CELL_GRU && d->training ? 1 : 0)) * H);     // GI (fwd) / dGI (bwd; GRU: room for the 4H-wide [dr|dz|dn|dn*r] rows)
+    lo.gi = w; w += al(lo.BT * D * (G + (d->cell == DEP_CELL_GRU && lo.keep ? 1 : 0)) * H);     // GI (fwd) / dGI (bwd; GRU: room for the 4H-wide [dr|dz|dn|dn*r] rows)
     lo.dghn = w; w += al(lo.BT * H);
     const size_t maxin = D * H > (size_t)d->F ? D * H : (size_t)d->F;
     lo.dx[0] = w; w += al(lo.BT * D * H);
@@ -213,7 +224,7 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     (void)maxin;
     lo.dbpart = w; w += al((size_t)D * lo.nwg * 4 * H);
     lo.biastmp = w; w += al(G * H);
-    lo.dwstack = w; if (d->dirs == 2 && d->training) { const size_t mx = D * H > (size_t)d->F ? D * H : (size_t)d->F; w += al(D * G * H * mx); }
+    lo.dwstack = w; if (d->dirs == 2 && lo.keep) { const size_t mx = D * H > (size_t)d->F ? D * H : (size_t)d->F; w += al(D * G * H * mx); }
     // split-K scratch: the largest weight-gradient contraction
     size_t gb = 0;
     {   // every (rows, cols) block dep_rnn_backward contracts over B*T: dW_ih (G H x F | D H), dW_hh whole or as the GRU's
@@ -226,7 +237,7 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
                 if (b1 > gb) gb = b1;
             }
     }
-    if (d->training && ((d->cell == DEP_CELL_GRU && d->dirs == 1) || (d->cell == DEP_CELL_LSTM && d->dirs == 2))) {
+    if (lo.keep && ((d->cell == DEP_CELL_GRU && d->dirs == 1) || (d->cell == DEP_CELL_LSTM && d->dirs == 2))) {
         // dW_ih + dW_hh of a GRU layer / dW_hh of both directions of a BiLSTM layer as one launch (dep_gemm_tn_pair): two sets of partials
         const size_t b2 = 2 * dep_gemm_workspace_bytes(1, 0, (int)(G * H), (int)H, (int)lo.BT);
         if (b2 > gb) gb = b2;
@@ -249,12 +260,12 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     lo.fused2 = lo.cluster && dep_fused2_ok(d->cell, d->H, d->L, d->dirs);
     if (lo.fused2) {
         size_t fb = dep_fused2_xbuf_bytes(d->B); if (fb > lo.xbuf_bytes) lo.xbuf_bytes = fb;
-        if (d->training) { fb = dep_fused2_bwd_xbuf_bytes(d->B); if (fb > lo.xbuf_bytes) lo.xbuf_bytes = fb; }
+        if (lo.keep) { fb = dep_fused2_bwd_xbuf_bytes(d->B); if (fb > lo.xbuf_bytes) lo.xbuf_bytes = fb; }
     }
     w += al(lo.xbuf_bytes / sizeof(float) + 64);
     lo.wih_img = w; if (lo.fused2) w += al(G * H * H);
     lo.gi2 = lo.dghn2 = lo.dbpart2 = 0;
-    if (lo.fused2 && d->training) {
+    if (lo.fused2 && lo.keep) {
         lo.gi2 = w; w += al(lo.BT * (G + 1) * H);      // (room for the 4H-wide [dr | dz | dn | dn*r] rows, like lo.gi)
         lo.dghn2 = w; w += al(lo.BT * H);
         lo.dbpart2 = w; w += al((size_t)lo.nwg * 4 * H);
@@ -265,12 +276,13 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     {
         static int sv_env = -1;
         if (sv_env < 0) { const char* e = getenv("DEP_SV16"); sv_env = (e && e[0] == '0') ? 0 : 1; }
-        lo.sv16 = sv_env && d->training && lo.cluster &&
+        // (an INSTANCE choice: a dropout-only forward launches the instance training launches, though it saves no gates)
+        lo.sv16 = sv_env && d->training != DEP_RUN_EVAL && lo.cluster &&
                   (d->cell == DEP_CELL_GRU ? (lo.fused2 || !lo.cluster16) : dep_cluster_lstm_sv16_ok());
         // bf16-STORAGE mode (dep_set_gemm_mode(3); a labelled throughput mode, never the parity path): only where every kernel of the
         // stack has the variant -- the fused 2-layer GRU forward and the burst backward with the 4H-wide gate-gradient rows.  Other
         // stacks run mode 3 exactly like mode 2 (single bf16 products, fp32 storage).
-        lo.bf16st = dep_get_gemm_mode() == 3 && lo.sv16 && lo.fused2 && lo.dg4 && d->cell == DEP_CELL_GRU && d->T % 2 == 0 &&
+        lo.bf16st = dep_get_gemm_mode() == 3 && lo.keep && lo.sv16 && lo.fused2 && lo.dg4 && d->cell == DEP_CELL_GRU && d->T % 2 == 0 &&
                     dep_cluster_bwd_pk_ok(d->H, d->T);
     }
     return true;
@@ -291,7 +303,7 @@ extern "C" size_t dep_rnn_workspace_bytes(const dep_rnn_desc* d) {
 // byte offset of layer l's output sequence (B,T,H*dirs) inside the reserve (zero-copy access for the caller)
 extern "C" size_t dep_rnn_reserve_y_offset(const dep_rnn_desc* d, int layer) {
     Layout lo;
-    if (!make_layout(d, lo) || layer < 0 || layer >= d->L) return (size_t)-1;
+    if (!make_layout(d, lo) || layer < 0 || layer >= d->L || lo.y[layer] == NOT_KEPT) return (size_t)-1;
     return lo.y[layer] * sizeof(float);
 }
 extern "C" size_t dep_rnn_reserve_ydrop_offset(const dep_rnn_desc* d, int layer) {
@@ -395,7 +407,18 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
                       "and has no fp32 copy of the output sequence (y must be NULL)");
         return DEP_ERR_ARG;
     }
-    record_reserve_mode(reserve, (sweep_split_mode() ? 1 : 0) | (sv16 ? 4 : 0) | (lo.bf16st ? 8 : 0));
+    // bit 4: a dropout-only forward wrote it -- no saved gates, no backward images: dep_rnn_backward refuses it
+    record_reserve_mode(reserve, (sweep_split_mode() ? 1 : 0) | (sv16 ? 4 : 0) | (lo.bf16st ? 8 : 0) | (lo.donly ? 16 : 0));
+    // Dropout-only: where a layer's output sequence goes when the reserve does not keep it.  The cluster BiLSTM sweep and the fused
+    // GRU forward take a null pointer (nothing written); the other sweeps read their own output back (h_{t-1}, the pool) and get the
+    // workspace's dX region, idle in a forward; the top layer of a pooled GRU writes straight into the caller's y when one is given.
+    float* const yscratch = W + lo.dx[0];
+    auto yout = [&](int l, bool null_ok) -> float* {
+        if (lo.y[l] != NOT_KEPT) return R + lo.y[l];
+        if (l == L - 1 && y) return y;
+        return null_ok ? nullptr : yscratch;
+    };
+    const bool ytop_kept = lo.y[L - 1] != NOT_KEPT;
     if (lo.fused2 && sweep_split_mode() && excl) {
         // both layers in one launch: layer 1 runs one step behind layer 0 and takes its input straight from the exchanged
         // h0_t (no layer-1 input-projection GEMM, no GI round trip through HBM for it)
@@ -405,7 +428,7 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
             const float* srcs[5] = {w0[1], w1[1], w1[0], w0[1], w1[1]};
             float* dsts[5] = {R + lo.wp[0][0], R + lo.wp[1][0], W + lo.wih_img, R + lo.wpT[0][0], R + lo.wpT[1][0]};
             const int kinds[5] = {0, 0, 0, 1, 1};
-            const bool bwd_multi = d->training != 0;
+            const bool bwd_multi = lo.keep;
             rc = dep_pack_cluster_split_multi(bwd_multi ? 5 : 3, srcs, dsts, kinds, H, s); if (rc) return rc;
         }
         float* gi = W + lo.gi;
@@ -416,11 +439,11 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
         f.wp0 = R + lo.wp[0][0]; f.wp1 = R + lo.wp[1][0]; f.wpi = W + lo.wih_img;
         f.b_hh0 = w0[3]; f.b_ih1 = w1[2]; f.b_hh1 = w1[3];
         f.ostride = (lo.BT * H + 63) / 64 * 64;
-        f.gi = gi; f.y0 = R + lo.y[0]; f.y0d = lo.drop ? R + lo.ydrop[0] : nullptr; f.y1 = R + lo.y[1];
+        f.gi = gi; f.y0 = lo.donly ? nullptr : R + lo.y[0]; f.y0d = (lo.drop && !lo.donly) ? R + lo.ydrop[0] : nullptr; f.y1 = yout(1, true);
         f.drop_p = lo.drop ? d->dropout_p : 0.f; f.seed = d->seed; f.site = DEP_SITE_RNN0;
         f.pooled = pooled; f.pool_scale = d->pool == DEP_POOL_MEAN ? 1.0f / (float)T : 1.0f;
         f.hn0 = h_n; f.hn1 = h_n ? h_n + (size_t)B * H : nullptr;
-        for (int l = 0; l < 2; ++l) for (int k = 0; k < 4; ++k) f.sv[l][k] = d->training ? R + lo.sv[l][k] : nullptr;
+        for (int l = 0; l < 2; ++l) for (int k = 0; k < 4; ++k) f.sv[l][k] = lo.keep ? R + lo.sv[l][k] : nullptr;
         f.stream = s;
         f.soft_fallback = lo.bf16st ? 0 : 1;           // (the tolerant per-layer kernels have no bf16-storage variant: a failed hello raises the status)
         f.sv16 = sv16 ? 1 : 0; f.bf16st = lo.bf16st ? 1 : 0;
@@ -444,18 +467,18 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
             dep_sweep_args a{};
             a.B = B; a.T = T; a.H = H; a.cell = d->cell; a.dirs = 1; a.training = d->training; a.impl = d->impl; a.split = 1;
             a.w_hh[0] = wl[1]; a.b_hh[0] = wl[3]; a.wp[0] = R + lo.wp[l][0];
-            a.gi = gi; a.y = R + lo.y[l]; a.ldy = H;
+            a.gi = gi; a.y = yout(l, false); a.ldy = H;
             const bool dropl = lo.drop && l == 0;
             a.ydrop = dropl ? R + lo.ydrop[0] : nullptr;
             a.drop_p = dropl ? d->dropout_p : 0.f; a.seed = d->seed; a.site = DEP_SITE_RNN0 + l;
             a.pooled = (l == 1 && pooled) ? pooled : nullptr; a.pool_scale = f.pool_scale;
             a.h_n = h_n ? h_n + (size_t)l * B * H : nullptr;
-            if (d->training) { a.sv0 = R + lo.sv[l][0]; a.sv1 = R + lo.sv[l][1]; a.sv2 = R + lo.sv[l][2]; a.sv3 = R + lo.sv[l][3]; }
+            if (lo.keep) { a.sv0 = R + lo.sv[l][0]; a.sv1 = R + lo.sv[l][1]; a.sv2 = R + lo.sv[l][2]; a.sv3 = R + lo.sv[l][3]; }
             a.only_if = soft; a.stream = s; a.sv16 = sv16 ? 1 : 0;
             a.hdr_slot = 1 + l; a.hdr_clean = 1;             // own header slots: still zero from the call's one memset
             rc = dep_launch_cluster_fwd(a, W + lo.xbuf, lo.xbuf_bytes); if (rc) return rc;
         }
-        if (y) { rc = dep_axpby(R + lo.y[1], y, (long)lo.BT * H, 1.f, 0.f, s); if (rc) return rc; }
+        if (y && ytop_kept) { rc = dep_axpby(R + lo.y[1], y, (long)lo.BT * H, 1.f, 0.f, s); if (rc) return rc; }
         return DEP_OK;
     }
     if (D == 2) {
@@ -483,16 +506,16 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
             DEP_CHECK_ARG(wl[0] && wl[1] && wl[2] && wl[3]);
             // recurrent weight images in MFMA fragment order (precision / clustering decide the format)
             if (split_lstm) {
-                rc = dep_pack_cluster_lstm_split(wl[1], R + lo.wp[l][dd], d->training ? R + lo.wpT[l][dd] : nullptr, H, s);
+                rc = dep_pack_cluster_lstm_split(wl[1], R + lo.wp[l][dd], lo.keep ? R + lo.wpT[l][dd] : nullptr, H, s);
                 if (rc) return rc;
             } else {
                 const bool split_bwd = lo.cluster && d->cell == DEP_CELL_GRU && sweep_split_mode();
                 // the fp32 fragment images are only needed by kernels that are not running on split-precision images
-                const bool need_f32 = mfma && !((split_fwd || split_fwd32) && (split_bwd || !d->training));
-                if (need_f32) { rc = dep_pack_whh(wl[1], R + lo.wp[l][dd], R + lo.wpT[l][dd], G, H, s); if (rc) return rc; }
+                const bool need_f32 = mfma && !((split_fwd || split_fwd32) && (split_bwd || !lo.keep));
+                if (need_f32) { rc = dep_pack_whh(wl[1], R + lo.wp[l][dd], lo.donly ? nullptr : R + lo.wpT[l][dd], G, H, s); if (rc) return rc; }
                 if (split_fwd) { rc = dep_pack_cluster16_fwd_split(wl[1], R + lo.wp[l][dd], H, s); if (rc) return rc; }
                 if (split_fwd32) { rc = dep_pack_cluster_fwd_split(wl[1], R + lo.wp[l][dd], H, s); if (rc) return rc; }
-                if (lo.cluster && d->training) {     // the cluster backward wants its own member-sliced image
+                if (lo.cluster && lo.keep) {         // the cluster backward wants its own member-sliced image
                     rc = split_bwd ? dep_pack_cluster_bwd_split(wl[1], R + lo.wpT[l][dd], H, s)
                                    : dep_pack_cluster_bwd(wl[1], R + lo.wpT[l][dd], G, H, s);
                     if (rc) return rc;
@@ -523,15 +546,15 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
             const float* const* wl = weights + (size_t)(l * D + dd) * 4;
             a.w_hh[dd] = wl[1]; a.b_hh[dd] = wl[3]; a.wp[dd] = R + lo.wp[l][dd];
         }
-        a.gi = gi; a.y = R + lo.y[l]; a.ldy = D * H;
         const bool dropl = lo.drop && l < L - 1;
+        a.gi = gi; a.y = yout(l, lo.cluster && d->cell == DEP_CELL_LSTM && dropl && !use16); a.ldy = D * H;
         a.ydrop = dropl ? R + lo.ydrop[l] : nullptr;
         a.drop_p = dropl ? d->dropout_p : 0.f; a.seed = d->seed; a.site = DEP_SITE_RNN0 + l;
         const bool top = l == L - 1;
         a.pooled = (top && pooled) ? pooled : nullptr;
         a.pool_scale = d->pool == DEP_POOL_MEAN ? 1.0f / (float)T : 1.0f;
         a.h_n = h_n ? h_n + (size_t)l * D * B * H : nullptr;
-        if (d->training) { a.sv0 = R + lo.sv[l][0]; a.sv1 = R + lo.sv[l][1]; a.sv2 = R + lo.sv[l][2]; a.sv3 = R + lo.sv[l][3]; }
+        if (lo.keep) { a.sv0 = R + lo.sv[l][0]; a.sv1 = R + lo.sv[l][1]; a.sv2 = R + lo.sv[l][2]; a.sv3 = R + lo.sv[l][3]; }
         a.stream = s;
         a.sv16 = (sv16 && lo.cluster && (d->cell == DEP_CELL_LSTM || !use16)) ? 1 : 0;
         a.hdr_slot = l < DEP_HDR_SLOTS ? l : 0; a.hdr_clean = l < DEP_HDR_SLOTS;      // one header slot per layer, zeroed once per call
@@ -540,7 +563,7 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
            : lo.cluster ? dep_launch_cluster_fwd(a, W + lo.xbuf, lo.xbuf_bytes) : dep_launch_sweep_fwd(a);
         if (rc) return rc;
     }
-    if (y) {
+    if (y && ytop_kept) {
         rc = dep_axpby(R + lo.y[L - 1], y, (long)lo.BT * D * H, 1.f, 0.f, s);
         if (rc) return rc;
     }
@@ -561,7 +584,19 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float*
                              void* stream, const dep_grad_sync* gs) {
     Layout lo;
     DEP_CHECK_ARG(make_layout(d, lo));
-    DEP_CHECK_ARG(d->training);
+    if (d->training != DEP_RUN_TRAIN) {
+        dep_set_error("dep_rnn_backward: the descriptor's run mode is %d; a backward needs a DEP_RUN_TRAIN (1) forward's reserve%s", d->training,
+                      d->training == DEP_RUN_DROPOUT_ONLY ? " (DEP_RUN_DROPOUT_ONLY keeps no saved gates)" : "");
+        return DEP_ERR_ARG;
+    }
+    {
+        const int fm = lookup_reserve_mode(reserve);
+        if (fm >= 0 && (fm & 16)) {
+            dep_set_error("dep_rnn_backward: the reserve was last written by a DEP_RUN_DROPOUT_ONLY forward, which keeps no saved gates; "
+                          "run the forward with DEP_RUN_TRAIN before a backward");
+            return DEP_ERR_ARG;
+        }
+    }
     DEP_CHECK_ARG(x && weights && dweights && reserve && workspace);
     DEP_CHECK_ARG(dy || dpooled || dh_n);
     DEP_CHECK_ARG(!(dpooled && (d->cell != DEP_CELL_GRU || d->pool == DEP_POOL_NONE)));

@@ -535,7 +535,7 @@ __global__ __launch_bounds__(KB ? CT + L_SVC : CT) void lstm_fwd_cluster(LF p) {
             if (p.svg) { st2(ob + 2 * LARR, ig); st2(ob + 3 * LARR, fg); st2(ob + 4 * LARR, gg); st2(ob + 5 * LARR, og); st2(ob + 6 * LARR, cst); }
         } else if (valid) {
             const size_t o = row * p.ldy + dir * H + col;
-            st2(p.y + o, h);
+            if (p.y) st2(p.y + o, h);
             if (p.ydrop) {
                 const f32x4 m = dep_dropmask4(p.seed, p.site, o >> 2, p.drop_p, p.drop_scale);
                 st2(p.ydrop + o, f2(h.x * (kh ? m[2] : m[0]), h.y * (kh ? m[3] : m[1])));

@@ -45,6 +45,7 @@ struct FF {
     const float* gi; int ldgi;                                    // layer-0 input projection incl. b_ih (B*T, 3H)
     float* y0; float* y1;                                         // (B,T,H) outputs; the other per-layer arrays follow each at
     unsigned ostride; int training;                               // +k*ostride floats: [y0, dropout(y0) (DROP only), r, z, n, hn] / [y1, r, z, n, hn]
+    unsigned wmask;                                               // write-set: bit a = obuf array a (0..5 layer 0 h, r, z, n, hn, dropout(h); 6..10 layer 1 h, r, z, n, hn)
     float drop_p, drop_scale; uint64_t seed; uint32_t site;
     float* pooled; float pool_scale; float* hn0; float* hn1;
     unsigned* status; unsigned* flags; unsigned* hello; float* payload; unsigned payload_bytes; int nofast;
@@ -186,6 +187,12 @@ __global__ __launch_bounds__(FTHREADS) void gru2_fwd_fused(FF p) {
         // wait for at barrier #1.
         const bool steady = s >= 2 && s < T && p.training != 0 && !p.ntstore;
         if (!steady && part == 1) return;                 // (outside the steady state slot Z writes everything)
+        if (steady && p.training == DEP_RUN_DROPOUT_ONLY) {
+            // dropout-only forward (no backward reads the reserve): layer 1 takes dropout(h0) from the exchange and the fallback
+            // kernels redo the whole forward, so the only array left is the top sequence -- when the caller asked for it
+            if (shalf == 0 && part != 2 && (p.wmask & (1u << 6))) *reinterpret_cast<f32x4*>(p.y1 + so + (unsigned)(s - 2) * FH) = ld4(obuf + 6 * OARR + su * OROW + sqd * 4);
+            return;
+        }
         if (steady) {
             const float* ob = obuf + su * OROW;
             const unsigned e0 = so + (unsigned)s * FH, e1 = so + (unsigned)(s - 2) * FH;
@@ -215,7 +222,7 @@ __global__ __launch_bounds__(FTHREADS) void gru2_fwd_fused(FF p) {
             const int a = pr * 2 + shalf;             // obuf array (wave-uniform): 0..5 layer 0, 6..10 layer 1
             const bool l0 = a < 6;
             const int k = l0 ? a : a - 6;
-            const bool on = (l0 ? (s < T) : (s >= 2)) && a < 11 && (k == 0 || (k == 5 ? DROP : p.training != 0));
+            const bool on = (l0 ? (s < T) : (s >= 2)) && a < 11 && ((p.wmask >> a) & 1u);
             const int t = l0 ? s : s - 2;
             float* base = l0 ? p.y0 : p.y1;
             const unsigned slot = l0 ? dslot0[k] : k;
@@ -551,21 +558,27 @@ int dep_launch_fused2_fwd(const dep_fused2_args& a, void* xbuf, size_t xbuf_byte
     p.gi = a.gi; p.ldgi = 3 * FH;
     const bool drop = a.drop_p > 0.f;
     p.y0 = a.y0; p.y1 = a.y1; p.ostride = (unsigned)a.ostride; p.training = a.training;
+    const bool donly = a.training == DEP_RUN_DROPOUT_ONLY;
+    // write-set (run time, no template parameter): every array in training; h0, h1 (and dropout(h0)) in eval; in dropout-only mode
+    // the top sequence when a.y1 is set -- layer 1 reads dropout(h0) from the exchange, the fallback kernels rewrite layer 0 themselves
+    p.wmask = donly ? (a.y1 ? 1u << 6 : 0u) : (1u | (1u << 6) | (drop ? 1u << 5 : 0u) | (a.training ? 0x79eu : 0u));
     p.drop_p = a.drop_p; p.drop_scale = drop ? 1.0f / (1.0f - a.drop_p) : 1.0f; p.seed = a.seed; p.site = a.site;
     p.pooled = a.pooled; p.pool_scale = a.pool_scale; p.hn0 = a.hn0; p.hn1 = a.hn1;
     // the kernel addresses every per-layer output array as y_l + k * ostride: check the caller's layout really is that
-    DEP_CHECK_ARG(!drop || a.y0d == a.y0 + a.ostride);
-    if (a.training) for (int k = 0; k < 4; ++k)
+    DEP_CHECK_ARG(donly || !drop || a.y0d == a.y0 + a.ostride);
+    DEP_CHECK_ARG(donly || a.y0);
+    if (a.training == DEP_RUN_TRAIN) for (int k = 0; k < 4; ++k)
         DEP_CHECK_ARG(a.sv[0][k] == a.y0 + (size_t)(k + (drop ? 2 : 1)) * a.ostride && a.sv[1][k] == a.y1 + (size_t)(k + 1) * a.ostride);
     const size_t pay = (size_t)4 * nbtp_max * 3 * F_REGION * sizeof(float);      // four sentinel-armed slots
     DEP_CHECK_ARG(xbuf && PAYLOAD_OFF + pay <= xbuf_bytes && (size_t)nbtp_max * FNC <= 256);
-    DEP_CHECK_ARG(!drop || a.y0d);
+    DEP_CHECK_ARG(donly || !drop || a.y0d);
     p.status = (unsigned*)xbuf; p.flags = (unsigned*)(hdr_base(xbuf, 0) + FLAG_OFF); p.hello = (unsigned*)(hdr_base(xbuf, 0) + HELLO_OFF);
     p.payload = (float*)((char*)xbuf + PAYLOAD_OFF); p.payload_bytes = (unsigned)pay; p.nofast = nofast_env();
     p.trace = trace_env() ? (long long*)(hdr_base(xbuf, 0) + TRACE_OFF) : nullptr;
     p.soft = a.soft_fallback ? (unsigned*)xbuf + 1 : nullptr;
-    const bool sv16 = a.training && a.sv16;
-    const bool bf = a.training && a.bf16st;
+    // instance choice: dropout-only picks the one training picks (a.sv16 is the caller's instance decision; nothing is saved)
+    const bool sv16 = a.training != DEP_RUN_EVAL && a.sv16;
+    const bool bf = a.training == DEP_RUN_TRAIN && a.bf16st;
     DEP_CHECK_ARG(!bf || sv16);
     p.ntstore = 0;                                    // (non-temporal write-out measured: no effect on this launch -- its payload, 0.4 MB per XCD, survives anyway)
     { static int fs = -1; if (fs < 0) { const char* e = getenv("DEP_FORCE_SOFT_FALLBACK"); fs = (e && e[0] >= '1' && e[0] <= '3') ? e[0] - '0' : 0; } p.force_soft = fs; }

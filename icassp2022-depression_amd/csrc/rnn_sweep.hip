@@ -592,7 +592,7 @@ __global__ void pack_whh_kernel(const float* __restrict__ W, float* __restrict__
         const int g = tg % G; const int jt = tg / G;
         wp[idx] = W[(size_t)(g * H + jt * 16 + (l & 15)) * H + kc * 16 + (l >> 4) * 4 + e];
     }
-    {
+    if (wpT) {                                        // (null: no backward reads this reserve, DEP_RUN_DROPOUT_ONLY)
         const int KC2 = G * H / 16;
         const int kc = blk % KC2; const int jt = blk / KC2;
         wpT[idx] = W[(size_t)(kc * 16 + (l >> 4) * 4 + e) * H + jt * 16 + (l & 15)];

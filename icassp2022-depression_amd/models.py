@@ -32,14 +32,16 @@ def _rnn_names(prefix, F, H, Lyr, dirs, G):
 
 
 class _RnnCache:
-    """dep_rnn descriptors + reserve/workspace per (B,T,training) so steady-state steps never allocate."""
+    """dep_rnn descriptors + reserve/workspace per (B,T,run mode) so steady-state steps never allocate."""
 
     def __init__(self, cell, F, H, Lyr, dirs, p, pool, device):
         self.args = (cell, F, H, Lyr, dirs, p, pool, device)
         self.cache = {}
 
     def get(self, B, T, training):
-        key = (B, T, bool(training))
+        """training: a run mode (L.RUN_*); a bool means RUN_TRAIN / RUN_EVAL."""
+        training = int(training)
+        key = (B, T, training)
         r = self.cache.get(key)
         if r is None:
             cell, F, H, Lyr, dirs, p, pool, device = self.args
@@ -432,8 +434,10 @@ class FusionNet(nn.Module):
         p = self.dropout if training else 0.0
         P = self._params
         B, T, _ = xt.shape
-        # text encoder (inference-mode kernels; dropout sites drawn when training)
-        rnn = self._rnn_t.get(B, T, training)
+        # frozen encoders: dropout drawn as in training, but no backward follows -- the dropout-only run mode keeps no saved gates
+        mode = L.RUN_DROPOUT_ONLY if training else L.RUN_EVAL
+        # text encoder
+        rnn = self._rnn_t.get(B, T, mode)
         h_n = torch.empty(2 * self.rnn_layers, B, self.text_hidden_dims, dtype=torch.float32, device=self.device)
         rnn.forward(xt, self._wt, seed=seed, h_n=h_n)
         ctx, _ = L.attn_fwd(rnn.layer_output(), h_n, P['attention_layer.0.weight'].data, P['attention_layer.0.bias'].data)
@@ -444,7 +448,7 @@ class FusionNet(nn.Module):
             xn, _ = L.layernorm_fwd(xa.view(Ba * Ta, Fa), P['ln.weight'].data, P['ln.bias'].data, save=False)
         else:
             xn = xa.view(Ba * Ta, Fa)
-        rna = self._rnn_a.get(Ba, Ta, training)
+        rna = self._rnn_a.get(Ba, Ta, mode)
         pooled = torch.empty(Ba, self.audio_hidden_dims, dtype=torch.float32, device=self.device)
         rna.forward(xn, self._wa, seed=seed + 1, pooled=pooled)
         af = _mlp_feature(pooled, P['fc_audio.1.weight'].data, P['fc_audio.1.bias'].data, p, seed, (L.SITE_FC2, L.SITE_FC3))

@@ -46,6 +46,24 @@ const char* dep_arch(void);
 /* ------------------------------------------------------------------ descriptors ---- */
 enum { DEP_POOL_NONE = 0, DEP_POOL_MEAN = 1, DEP_POOL_SUM = 2 };
 enum { DEP_CELL_GRU = 0, DEP_CELL_LSTM = 1 };
+/* Run modes (dep_rnn_desc.training):
+ *   DEP_RUN_EVAL          no dropout; the reserve is scratch for the forward (output sequences, weight images).
+ *   DEP_RUN_TRAIN         inter-layer dropout, and the reserve keeps everything dep_rnn_backward reads.
+ *   DEP_RUN_DROPOUT_ONLY  inter-layer dropout drawn exactly as in DEP_RUN_TRAIN (same Philox key, sites and masks: y, pooled and
+ *                         h_n are bit-identical to a DEP_RUN_TRAIN forward with the same seed), but no backward follows -- a frozen
+ *                         encoder run under torch.no_grad() in train() mode (Classification/fuse_net_whole.py:336-366,
+ *                         fusion_net.pretrained_feature).  The reserve keeps only what the forward itself reads: the packed
+ *                         forward W_hh images, the direction-stacked W_ih / bias of a bidirectional stack, the copy of layer l
+ *                         that feeds layer l+1 (dropout(y), or y when dropout_p = 0) and the top layer's output sequence -- except
+ *                         for a GRU with pool != DEP_POOL_NONE, whose top sequence is not kept and is written only into the
+ *                         caller's y, if one is given.  Not kept: saved gates / c, the backward W_hh images, the undropped outputs
+ *                         of the lower layers; dep_rnn_reserve_y_offset / _ydrop_offset return (size_t)-1 for every array not
+ *                         kept.  The workspace drops its backward-only parts (the 4H-wide gate-gradient room, the second set of
+ *                         gate-gradient buffers, the dW_ih scratch of a bidirectional stack, the fused backward's exchange
+ *                         room).  dep_rnn_backward / _overlapped refuse (DEP_ERR_ARG) a descriptor in this mode and a reserve
+ *                         whose last forward ran in it.
+ * Any other value is a bad descriptor (the size queries return 0, the entry points DEP_ERR_ARG). */
+enum { DEP_RUN_EVAL = 0, DEP_RUN_TRAIN = 1, DEP_RUN_DROPOUT_ONLY = 2 };
 
 /* One stacked recurrent network: torch.nn.GRU(F,H,num_layers=L,dropout=p,batch_first=True)
  * (Classification/audio_gru_whole.py:59-60) or torch.nn.LSTM(F,H,num_layers=L,dropout=p,
@@ -55,7 +73,7 @@ typedef struct {
     int32_t B, T, F, H;  /* batch, steps, input features, hidden units */
     int32_t L;           /* stacked layers (>=1) */
     int32_t dirs;        /* 1 (GRU, unidirectional) or 2 (bidirectional LSTM) */
-    int32_t training;    /* 1: keep the reserve for backward and apply inter-layer dropout */
+    int32_t training;    /* run mode: DEP_RUN_EVAL | DEP_RUN_TRAIN | DEP_RUN_DROPOUT_ONLY (see above) */
     float   dropout_p;   /* inter-layer dropout probability (applied to layers 0..L-2 outputs) */
     uint64_t seed;       /* Philox key for this call's dropout masks */
     int32_t pool;        /* GRU only: DEP_POOL_* over T of the top layer (fused in the sweep) */
@@ -69,7 +87,7 @@ size_t dep_rnn_workspace_bytes(const dep_rnn_desc* d);   /* scratch, either dire
 /* Byte offset, inside the reserve, of layer `layer`'s output sequence (B,T,H*dirs) -- zero-copy
  * access to `output` for the caller (attention reads it in place); (size_t)-1 on bad arguments. */
 size_t dep_rnn_reserve_y_offset(const dep_rnn_desc* d, int layer);
-/* Same for the dropped-out copy that feeds layer+1 (training && dropout_p > 0 only). */
+/* Same for the dropped-out copy that feeds layer+1 (DEP_RUN_TRAIN / DEP_RUN_DROPOUT_ONLY with dropout_p > 0 only). */
 size_t dep_rnn_reserve_ydrop_offset(const dep_rnn_desc* d, int layer);
 
 /* Health of the cluster-parallel sweeps that ran on `workspace` since the last dep_rnn_forward (desc.impl 0/3 with a
