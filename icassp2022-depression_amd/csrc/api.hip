@@ -390,7 +390,7 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
     const int B = d->B, T = d->T, H = d->H, D = d->dirs, G = lo.G, L = d->L;
     const int BTr = (int)lo.BT;
     // the unsplit projections' scratch (the weight's stage image of gemm_bf16x3_nt_dma): the split-K region, idle during the forward
-    struct ScratchGuard { ScratchGuard(void* q, size_t n) { dep_gemm_set_scratch(q, n); } ~ScratchGuard() { dep_gemm_set_scratch(nullptr, 0); } } scratch_guard(W + lo.gemm, lo.gemm_bytes);
+    DepGemmOpts proj; proj.scratch = W + lo.gemm; proj.scratch_bytes = lo.gemm_bytes;
     const bool mfma = lo.cluster || dep_sweep_use_mfma(H, d->impl);
     const bool excl = dep_exclusive_on();
     const bool use16 = lo.cluster16 && excl;                        // the 16-unit-member forward fills the CUs: not on a shared GPU
@@ -432,7 +432,7 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
             rc = dep_pack_cluster_split_multi(bwd_multi ? 5 : 3, srcs, dsts, kinds, H, s); if (rc) return rc;
         }
         float* gi = W + lo.gi;
-        rc = dep_gemm_internal(0, 1, BTr, G * H, d->F, x, d->F, w0[0], d->F, gi, G * H, w0[2], 0.f, 0, 0, nullptr, 0, s);
+        rc = dep_gemm_internal(0, 1, BTr, G * H, d->F, x, d->F, w0[0], d->F, gi, G * H, w0[2], 0.f, 0, 0, nullptr, 0, proj, s);
         if (rc) return rc;
         dep_fused2_args f{};
         f.B = B; f.T = T; f.training = d->training;
@@ -459,9 +459,8 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
             const float* const* wl = l == 0 ? w0 : w1;
             if (l == 1) {
                 const float* in = lo.drop ? R + lo.ydrop[0] : R + lo.y[0];
-                dep_gemm_set_predicate(soft);
-                rc = dep_gemm_internal(0, 1, BTr, G * H, H, in, H, wl[0], H, gi, G * H, wl[2], 0.f, 0, 0, nullptr, 0, s);
-                dep_gemm_set_predicate(nullptr);
+                DepGemmOpts fallback = proj; fallback.only_if = soft;
+                rc = dep_gemm_internal(0, 1, BTr, G * H, H, in, H, wl[0], H, gi, G * H, wl[2], 0.f, 0, 0, nullptr, 0, fallback, s);
                 if (rc) return rc;
             }
             dep_sweep_args a{};
@@ -530,13 +529,13 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
                 bias = tb;
             }
             rc = dep_gemm_internal(0, 1, BTr, G * H, Kl, in, Kl, wl[0], Kl, gi + (size_t)dd * G * H, D * G * H, bias,
-                                   0.f, 0, 0, nullptr, 0, s);
+                                   0.f, 0, 0, nullptr, 0, proj, s);
             if (rc) return rc;
             // the bias scratch is reused by the next direction: stream order keeps this safe
         }
         if (stacked) {
             rc = dep_gemm_internal(0, 1, BTr, D * G * H, Kl, in, Kl, R + lo.wstack[l], Kl, gi, D * G * H, R + lo.bstack[l],
-                                   0.f, 0, 0, nullptr, 0, s);
+                                   0.f, 0, 0, nullptr, 0, proj, s);
             if (rc) return rc;
         }
         dep_sweep_args a{};
@@ -628,7 +627,6 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float*
     const int BTr = (int)lo.BT;
     void* gws = W + lo.gemm; const size_t gwsb = lo.gemm_bytes;
     // (dX's weight image shares the region with the split-K partials of the contractions enqueued behind it: stream order keeps them apart)
-    struct ScratchGuard { ScratchGuard(void* q, size_t n) { dep_gemm_set_scratch(q, n); } ~ScratchGuard() { dep_gemm_set_scratch(nullptr, 0); } } scratch_guard(gws, gwsb);
     int rc;
     // The fused two-layer backward (rnn_fused2_bwd.hip; round 5: all-gather form): both layers' BPTT in ONE launch, layer 1's dX -- the gradient
     // entering layer 0 -- formed in-kernel.  It writes the same gate-gradient arrays as the per-layer sweeps (4H-wide rows, PK image when the
@@ -724,12 +722,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float*
             return DEP_ERR_ARG;
         }
         a.bf16st = lo.bf16st ? 1 : 0;
-        // FMT_PKH / FMT_PK (gemm_bf16x3.hip).  Round 6: the single-product modes (dep_set_gemm_mode(2 / 3)) read the sweep's PK image through its hi rows
-        // on every stack (the same bf16 values their on-the-fly conversion formed: bit-identical, without the fp32 staging path that made
-        // cfg3's weight gradients slower in that mode than with three products)
-        const int fmt_a = (lo.bf16st || dep_get_gemm_mode() >= 2) ? 2 : 1;
         a.sv16 = (lo.sv16 && sweep_split_mode() && lo.cluster) ? 1 : 0;
-        struct FmtGuard { bool on; ~FmtGuard() { if (on) dep_gemm_set_operand_formats(0, 0); } } fmt_guard{pk};
         if (!fused) {
             rc = (lo.cluster && d->cell == DEP_CELL_LSTM) ? dep_launch_cluster_lstm_bwd(a, W + lo.xbuf, lo.xbuf_bytes)
                : lo.cluster ? dep_launch_cluster_bwd(a, W + lo.xbuf, lo.xbuf_bytes) : dep_launch_sweep_bwd(a);
@@ -752,27 +745,31 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float*
         }
         rc = dep_finish_db(a, dbi, dbh);
         if (rc) return rc;
-        if (pk) dep_gemm_set_operand_formats(fmt_a, 0);           // A = the PK gate gradients in dX, dW_ih and dW_hh below (reset by fmt_guard)
+        // A = the PK gate gradients in dX, dW_ih and dW_hh below.  Round 6: the single-product modes (dep_set_gemm_mode(2 / 3)) read the sweep's PK
+        // image through its hi rows (FMT_PKH) on every stack (the same bf16 values their on-the-fly conversion formed: bit-identical, without the fp32
+        // staging path that made cfg3's weight gradients slower in that mode than with three products)
+        DepGemmOpts go; go.scratch = gws; go.scratch_bytes = gwsb;
+        if (pk) go.fmt_a = (lo.bf16st || dep_get_gemm_mode() >= 2) ? FMT_PKH : FMT_PK;
         float* dxl = l == 0 ? dx : (fused ? nullptr : W + lo.dx[l & 1]);      // (fused: the gradient entering layer 0 never left the chip)
         // dX (B*T, Kl) (+)= dG * W_ih first: it is the only product the next layer's sweep waits for
         const bool stacked = D == 2 && lo.wstack[l] != 0;
         if (dxl && stacked) {
             // dX = [dG_fwd | dG_bwd] [W_ih(fwd); W_ih(bwd)]: one contraction over K = 2 G H (the forward left the stacked copy in
             // the reserve) instead of two with a read-modify-write of dX in between
-            rc = dep_gemm_internal(0, 0, BTr, Kl, D * G * H, dgi, ldg, R + lo.wstack[l], Kl, dxl, Kl, nullptr, 0.f, 0, 0, nullptr, 0, s);
+            rc = dep_gemm_internal(0, 0, BTr, Kl, D * G * H, dgi, ldg, R + lo.wstack[l], Kl, dxl, Kl, nullptr, 0.f, 0, 0, nullptr, 0, go, s);
             if (rc) return rc;
         } else if (dxl) {
             for (int dd = 0; dd < D; ++dd) {
                 const float* const* wl = weights + (size_t)(l * D + dd) * 4;
                 rc = dep_gemm_internal(0, 0, BTr, Kl, G * H, dgi + (size_t)dd * G * H, ldg, wl[0], Kl, dxl, Kl, nullptr,
-                                       dd == 0 ? 0.f : 1.f, 0, 0, nullptr, 0, s);
+                                       dd == 0 ? 0.f : 1.f, 0, 0, nullptr, 0, go, s);
                 if (rc) return rc;
             }
         }
         if (stacked) {
             // dW_ih of both directions: (2 G H x Kl) = dG^T in, the input read once; rows [0, G H) / [G H, 2 G H) are the two tensors
             float* dws = W + lo.dwstack;
-            rc = dep_gemm_internal(1, 0, D * G * H, Kl, BTr, dgi, ldg, in, Kl, dws, Kl, nullptr, 0.f, 0, 0, gws, gwsb, s);
+            rc = dep_gemm_internal(1, 0, D * G * H, Kl, BTr, dgi, ldg, in, Kl, dws, Kl, nullptr, 0.f, 0, 0, gws, gwsb, go, s);
             if (rc) return rc;
             const float* src[2]; float* dst[2]; long cnt[2];
             for (int dd = 0; dd < D; ++dd) {
@@ -785,12 +782,13 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float*
         // (DEP_DW_PAIR=0) must keep summing in the same order as the pair -- tests/test_presplit_gpu.py holds them bit-identical)
         const bool pair_layer = d->cell == DEP_CELL_GRU && lo.dg4 && !stacked && D == 1 && Kl == H && dep_get_gemm_mode() == 1 && sweep_split_mode();      // (the other precision modes never pair: they keep the single launches' target)
         const bool pair_shape = pair_layer && pk_gru && !lo.bf16st;
-        struct SplitGuard { bool on; SplitGuard(bool o) : on(o) { if (on) dep_gemm_set_split_target(512); } ~SplitGuard() { if (on) dep_gemm_set_split_target(0); } } split_guard(pair_layer);
+        DepGemmOpts dwo = go; dwo.split_target = pair_layer ? 512 : 0;       // the weight gradients below
         if (pair_shape) {
             // Round 5: dW_ih and dW_hh of this layer in ONE launch -- both read the PK gate gradients, [dr | dz] are the same bytes
             // (gemm_bf16x3_tn_pair; bit-identical to the two calls below, which remain the path for every other configuration)
             float* const* gl = dweights + (size_t)l * 4;
-            const int pr = dep_gemm_tn_pair(G * H, H, BTr, dgi, dgi, ldg, 2 * H, H, in, Kl, 0, 0, R + lo.y[l], H, T, -1, gl[0], Kl, gl[1], H, gws, gwsb, s);
+            DepGemmOpts po = dwo; po.skip_at = 2 * H; po.skip_by = H;       // problem 1 (dW_hh) reads [dr | dz] and [dn*r]
+            const int pr = dep_gemm_tn_pair(G * H, H, BTr, dgi, dgi, ldg, in, Kl, 0, 0, R + lo.y[l], H, T, -1, gl[0], Kl, gl[1], H, po, gws, gwsb, s);
             if (pr < 0) return pr;
             paired = pr == 1;
         }
@@ -799,8 +797,8 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float*
             // Round 5: dW_hh of the two directions of a BiLSTM layer (4H x H each: 254 tile-jobs, half of the persistent grid) as ONE paired launch;
             // tiles, K chunks and split-K order per direction are those of the single launches (bit-identical)
             float* const* gf = dweights + (size_t)(l * D) * 4; float* const* gb = dweights + (size_t)(l * D + 1) * 4;
-            const int pr = dep_gemm_tn_pair(G * H, H, BTr, dgi, dgi + (size_t)G * H, ldg, 0, 0, R + lo.y[l], D * H, T, -1, R + lo.y[l] + H, D * H, T, 1,
-                                            gf[1], H, gb[1], H, gws, gwsb, s);
+            const int pr = dep_gemm_tn_pair(G * H, H, BTr, dgi, dgi + (size_t)G * H, ldg, R + lo.y[l], D * H, T, -1, R + lo.y[l] + H, D * H, T, 1,
+                                            gf[1], H, gb[1], H, dwo, gws, gwsb, s);
             if (pr < 0) return pr;
             paired_hh = pr == 1;
         }
@@ -809,29 +807,28 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float*
             const float* dg = dgi + (size_t)dd * G * H;
             // dW_ih (G*H, Kl) = dG^T * in
             if (!stacked) {
-                if (lo.bf16st && l > 0) dep_gemm_set_operand_formats(fmt_a, 3);          // the layer below's (dropped) output is a bf16 array
-                rc = dep_gemm_internal(1, 0, G * H, Kl, BTr, dg, ldg, in, Kl, gl[0], Kl, nullptr, 0.f, 0, 0, gws, gwsb, s);
+                DepGemmOpts io = dwo; io.fmt_b = (lo.bf16st && l > 0) ? FMT_BF16 : FMT_F32;       // the layer below's (dropped) output is a bf16 array
+                rc = dep_gemm_internal(1, 0, G * H, Kl, BTr, dg, ldg, in, Kl, gl[0], Kl, nullptr, 0.f, 0, 0, gws, gwsb, io, s);
                 if (rc) return rc;
             }
-            if (lo.bf16st) dep_gemm_set_operand_formats(fmt_a, 3);                       // dW_hh: B = this layer's bf16 output, shifted one step
+            DepGemmOpts ho = dwo; ho.fmt_b = lo.bf16st ? FMT_BF16 : FMT_F32;          // dW_hh: B = this layer's bf16 output, shifted one step
             // dW_hh (G*H, H) = dGH^T * h_prev   (h_prev = layer output shifted by one step along the sweep)
             const float* yl = R + lo.y[l] + (size_t)dd * H;
             const int shift = dd == 0 ? -1 : 1;
             if (d->cell == DEP_CELL_GRU && lo.dg4 && dep_gemm_uses_bf16x3(3 * H, H, BTr, T)) {
                 // ONE contraction over the 4H-wide rows: op(A) columns [dr | dz] and [dn*r] (the dn block in between is skipped by
                 // the loader).  The separate (H x H) call for the n rows cost 100 us for a third of the (2H x H) call's 165 us work.
-                dep_gemm_set_a_colskip(2 * H, H);
-                rc = dep_gemm_internal(1, 0, 3 * H, H, BTr, dg, ldg, yl, D * H, gl[1], H, nullptr, 0.f, T, shift, gws, gwsb, s);
-                dep_gemm_set_a_colskip(0, 0);
+                DepGemmOpts so = ho; so.skip_at = 2 * H; so.skip_by = H;
+                rc = dep_gemm_internal(1, 0, 3 * H, H, BTr, dg, ldg, yl, D * H, gl[1], H, nullptr, 0.f, T, shift, gws, gwsb, so, s);
                 if (rc) return rc;
             } else if (d->cell == DEP_CELL_GRU) {
-                rc = dep_gemm_internal(1, 0, 2 * H, H, BTr, dg, ldg, yl, D * H, gl[1], H, nullptr, 0.f, T, shift, gws, gwsb, s);
+                rc = dep_gemm_internal(1, 0, 2 * H, H, BTr, dg, ldg, yl, D * H, gl[1], H, nullptr, 0.f, T, shift, gws, gwsb, ho, s);
                 if (rc) return rc;
                 rc = dep_gemm_internal(1, 0, H, H, BTr, dghn, lo.dg4 ? ldg : H, yl, D * H, gl[1] + (size_t)2 * H * H, H, nullptr,
-                                       0.f, T, shift, gws, gwsb, s);
+                                       0.f, T, shift, gws, gwsb, ho, s);
                 if (rc) return rc;
             } else {
-                rc = dep_gemm_internal(1, 0, 4 * H, H, BTr, dg, ldg, yl, D * H, gl[1], H, nullptr, 0.f, T, shift, gws, gwsb, s);
+                rc = dep_gemm_internal(1, 0, 4 * H, H, BTr, dg, ldg, yl, D * H, gl[1], H, nullptr, 0.f, T, shift, gws, gwsb, ho, s);
                 if (rc) return rc;
             }
         }

@@ -84,7 +84,7 @@ __device__ __forceinline__ void dep_xcd_tile(int gx, int gy, int gz, int& bx, in
 // ---- launch-instance log (dep_instance_log_*, include/dep_rnn.h) ------------------------------------
 // Every kernel launch of the library goes through DEP_LAUNCH: while the log is on it records the kernel expression as written at the
 // launch site plus the enclosing function's signature (which carries the template arguments of templated launchers), once per distinct
-// pair.  tests/test_instance_coverage_gpu.py uses it to tie the template instances a bench.py step launches to the ones the
+// pair.  tests/test_step_coverage_gpu.py uses it to tie the template instances a bench.py step launches to the ones the
 // oracle-comparing tests launched.  Off (the default): one relaxed atomic load per launch.
 bool dep_ilog_on();
 void dep_ilog_note(const char* kern, const char* where);
@@ -99,30 +99,38 @@ void dep_olog_add(char kind, const char* text, long n);
 // ---- optional per-kernel timing with HIP events on the launch stream (bench.py roofline leg) ----
 enum { DEP_PROF_GRU_FWD = 0, DEP_PROF_GRU_BWD = 1, DEP_PROF_LSTM_FWD = 2, DEP_PROF_LSTM_BWD = 3,
        DEP_PROF_GEMM_NT = 4, DEP_PROF_GEMM_NN = 5, DEP_PROF_GEMM_TN = 6, DEP_PROF_NCAT = 7 };
-// GEMM predicate of the calling thread: launches of dep_gemm_internal made while it is set return at kernel entry unless the
-// device word is non-zero (the conditional fallback of dep_rnn_forward).  nullptr = unconditional.
-void dep_gemm_set_predicate(const unsigned* only_if);
-const unsigned* dep_gemm_predicate();
-// A-operand column skip of the calling thread's next TN contractions (bf16x3 kernel only): logical column m of op(A) is stored
-// column m + (m >= at ? by : 0).  dW_hh of a GRU reads [dr | dz] and [dn*r] out of [dr | dz | dn | dn*r] with (2H, H).  (0, 0) = off.
-void dep_gemm_set_a_colskip(int at, int by);
-// Storage format of the calling thread's next contractions' operands (gemm_bf16x3.hip): 0 = fp32, 1 = PK, the pre-split row-pair
-// (hi, lo) bf16 image a producer kernel wrote in place of the fp32 array.  Only the bf16x3 kernel reads PK; dep_gemm_internal
-// refuses (DEP_ERR_ARG) a PK operand on any other path.  Reset to (0, 0) after the calls.
-void dep_gemm_set_operand_formats(int fmt_a, int fmt_b);
-void dep_gemm_set_scratch(void* p, size_t bytes);      // per calling thread: scratch of its unsplit contractions (gemm.hip)
-bool dep_gemm_pk_pending();
+// ---- GEMM call options (gemm.hip, gemm_bf16x3.hip) ----------------------------------------------------------------
+// Operand storage formats of the split-precision kernel (gemm_bf16x3.hip describes them); its FMT template parameters take these values.
+enum { FMT_F32 = 0, FMT_PK = 1, FMT_PKH = 2, FMT_BF16 = 3 };
+enum { DEP_PREC_MODE = 0, DEP_PREC_EXACT = 1, DEP_PREC_X3 = 2 };
+// Everything a contraction takes besides its operands.  The default value is the plain call: fp32 operands, precision by dep_set_gemm_mode.
+struct DepGemmOpts {
+    int prec = DEP_PREC_MODE;            // follow the mode | exact fp32 | three-term bf16x3 whatever the mode
+    int fmt_a = FMT_F32, fmt_b = FMT_F32;    // anything but FMT_F32 needs the split kernel: dep_gemm_internal refuses it elsewhere
+    int skip_at = 0, skip_by = 0;        // TN A operand (split kernel only): logical column m is stored at m + (m >= skip_at ? skip_by : 0)
+    long split_target = 0;               // split-K target in 128x128 tile-chunks (0 = DEP_GEMM_SPLIT_TARGET, default 1024)
+    const unsigned* only_if = nullptr;   // the launches return at kernel entry unless this device word is non-zero
+    void* scratch = nullptr; size_t scratch_bytes = 0;      // unsplit calls without a workspace: room for the DMA kernels' weight image
+};
+// The DEP_GEMM_* / DEP_DW_PAIR switches, read once per process.
+struct DepGemmSwitches {
+    int mode;                 // DEP_GEMM_MODE: initial precision mode (dep_set_gemm_mode changes it)
+    bool naive, pair, tn_dma, nt_dma, bm256, nt256;
+    long split_target;
+    int ablate, persist;
+};
+const DepGemmSwitches& dep_gemm_switches();
 bool dep_gemm_bf16x3_pair_ok();
-// true when dep_gemm_internal would run the bf16x3 kernel for a contraction of this size (it is the one that honours the skip)
+// true when dep_gemm_internal would run the split kernel for a plain contraction of this size (the one that reads PK and honours the skip)
 bool dep_gemm_uses_bf16x3(int M, int N, int K, int seq_T);
-void dep_gemm_set_split_target(long target);      // split-K target of this thread's next contractions (0 = default); gemm.hip
-// two TN contractions of equal shape over PK A operands in one launch (gemm.hip): 1 = enqueued, 0 = not covered, < 0 = error
-int dep_gemm_tn_pair(int M, int N, int K, const float* A0, const float* A1, int lda, int skip_at1, int skip_by1,
+// two TN contractions of equal shape over PK A operands in one launch (gemm.hip), the column skip on problem 1: 1 = enqueued, 0 = not covered, < 0 = error
+int dep_gemm_tn_pair(int M, int N, int K, const float* A0, const float* A1, int lda,
                      const float* B0, int ldb0, int seq_T0, int shift0, const float* B1, int ldb1, int seq_T1, int shift1,
-                     float* C0, int ldc0, float* C1, int ldc1, void* ws, size_t ws_bytes, hipStream_t s);
-int dep_gemm_bf16x3_tn_pair_launch(int M, int N, int K, const float* A0, const float* A1, int lda, int skip_at1, int skip_by1,
+                     float* C0, int ldc0, float* C1, int ldc1, const DepGemmOpts& o, void* ws, size_t ws_bytes, hipStream_t s);
+int dep_gemm_bf16x3_tn_pair_launch(int M, int N, int K, const float* A0, const float* A1, int lda,
                                    const float* B0, int ldb0, int seq_T0, int shift0, const float* B1, int ldb1, int seq_T1, int shift1,
-                                   float* C0, int ldc0, float* C1, int ldc1, int splits, int kchunk, float* part0, float* part1, hipStream_t s);
+                                   float* C0, int ldc0, float* C1, int ldc1, const DepGemmOpts& o, int splits, int kchunk, float* part0, float* part1,
+                                   hipStream_t s);
 // process-wide: may dep_rnn_forward use kernels that need every CU to themselves (dep_rnn_set_exclusive, include/dep_rnn.h)
 bool dep_exclusive_on();
 bool dep_prof_on();
@@ -271,4 +279,4 @@ int dep_launch_cluster16_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf_by
 
 int dep_gemm_internal(int transA, int transB, int M, int N, int K, const float* A, int lda,
                       const float* B, int ldb, float* C, int ldc, const float* bias, float beta,
-                      int seq_T, int shiftB, void* ws, size_t ws_bytes, hipStream_t s);
+                      int seq_T, int shiftB, void* ws, size_t ws_bytes, const DepGemmOpts& o, hipStream_t s);

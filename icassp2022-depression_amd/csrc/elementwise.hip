@@ -677,7 +677,7 @@ extern "C" int dep_attn_fwd(const float* out, const float* h_n, int K, const flo
     const long BH = (long)B * H;
     DEP_LAUNCH(attn_hsum_kernel, dim3(nblk(BH)), dim3(256), 0, S_, h_n, K, BH, hsum);
     DEP_CHECK_LAUNCH();
-    int rc = dep_gemm_internal(0, 1, B, H, H, hsum, H, Wa, H, pre, H, ba, 0.f, 0, 0, nullptr, 0, S_);
+    int rc = dep_gemm_internal(0, 1, B, H, H, hsum, H, Wa, H, pre, H, ba, 0.f, 0, 0, nullptr, 0, DepGemmOpts{}, S_);
     if (rc) return rc;
     if (!dep_attn2_fwd(out, pre, ctx, alpha, B, T, H, S_)) {
         const size_t lds = (size_t)(H + T + 16) * sizeof(float);
@@ -709,11 +709,11 @@ extern "C" int dep_attn_bwd(const float* dctx, const float* out, const float* Wa
     }
     DEP_CHECK_LAUNCH();
     // dWa (H,H) = dpre^T (H,B) * hsum (B,H) ; dba = colsum(dpre) ; dhsum = dpre * Wa
-    int rc = dep_gemm_internal(1, 0, H, H, B, dpre, H, hsum, H, dWa, H, nullptr, 0.f, 0, 0, gws, gws_bytes, S_);
+    int rc = dep_gemm_internal(1, 0, H, H, B, dpre, H, hsum, H, dWa, H, nullptr, 0.f, 0, 0, gws, gws_bytes, DepGemmOpts{}, S_);
     if (rc) return rc;
     rc = dep_colsum(dpre, B, H, H, dba, stream);
     if (rc) return rc;
-    rc = dep_gemm_internal(0, 0, B, H, H, dpre, H, Wa, H, dhs, H, nullptr, 0.f, 0, 0, nullptr, 0, S_);
+    rc = dep_gemm_internal(0, 0, B, H, H, dpre, H, Wa, H, dhs, H, nullptr, 0.f, 0, 0, nullptr, 0, DepGemmOpts{}, S_);
     if (rc) return rc;
     const long BH = (long)B * H;
     DEP_LAUNCH(attn_bcast_kernel, dim3(nblk(BH)), dim3(256), 0, S_, dhs, K, BH, dh_n);

@@ -27,7 +27,7 @@ struct GemmP {
     int kchunk, splits;
     float* part;
     int gx, gy;             // tile grid (x: N tiles, y: M tiles); the launch is 1-D, see dep_xcd_tile            // split-K partials [splits][M][N] or nullptr
-    const unsigned* only_if;    // run only if this device word is non-zero (dep_gemm_set_predicate), or nullptr
+    const unsigned* only_if;    // run only if this device word is non-zero (DepGemmOpts::only_if), or nullptr
 };
 
 // Load one (128 x 32) operand tile into registers.  TR = operand stored MN-contiguous.
@@ -286,34 +286,28 @@ __global__ __launch_bounds__(256) void gemm_small(SmallP p) {
     }
 }
 
-thread_local long g_split_target_override = 0;      // dep_gemm_set_split_target: per calling thread, 0 = the default / DEP_GEMM_SPLIT_TARGET
-int choose_splits(int M, int N, int K) {
+int choose_splits(int M, int N, int K, long target) {
     const long tiles = (long)dep_cdiv(M, BM) * dep_cdiv(N, BN);
     if (tiles >= 256 || K < 1024) return 1;
     // fill the persistent bf16x3 grid without spilling into a second round: its 256x128 tiles run two per CU (512 slots),
     // i.e. 1024 tile-chunks counted in 128x128 tiles, rounded DOWN (measured on dW at cfg2: 504 workgroup-tiles 0.271 ms,
-    // 384 -> 0.306 ms, 516 -> 0.366 ms)
-    static long target = -1;
-    if (target < 0) { const char* e = getenv("DEP_GEMM_SPLIT_TARGET"); target = e ? atol(e) : 1024; }
-    long s = (g_split_target_override > 0 ? g_split_target_override : target) / tiles;
+    // 384 -> 0.306 ms, 516 -> 0.366 ms).  Round 5: a layer whose dW_ih and dW_hh run as ONE paired launch asks for 512 (DepGemmOpts::split_target):
+    // the pair then fills the grid in one round (2 x 252 tile-jobs on 512 slots) with half the partial-sum traffic.  Asked for on both paths of such
+    // a layer, so that DEP_DW_PAIR=0 stays bit-identical to the pair.
+    long s = (target > 0 ? target : dep_gemm_switches().split_target) / tiles;
     const long maxs = K / 256;
     if (s > maxs) s = maxs;
     if (s > 128) s = 128;
     return s < 1 ? 1 : (int)s;
 }
 
-}  // namespace
-// Split-K target of the calling thread's next contractions, in 128x128 tile-chunks (0 = default).  Round 5: a layer whose dW_ih and dW_hh run as
-// ONE paired launch asks for 512: the pair then fills the persistent grid in one round (2 x 252 tile-jobs on 512 slots) with half the partial-sum
-// traffic; the single launches want 1024.  Set for both paths of such a layer, so that DEP_DW_PAIR=0 stays bit-identical to the pair.
-void dep_gemm_set_split_target(long target) { g_split_target_override = target; }
-namespace {
-
-bool naive_forced() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("DEP_GEMM_NAIVE"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v == 1;
-}
+enum { GEMM_NAIVE, GEMM_SMALL, GEMM_F32, GEMM_SPLIT };
+struct GemmPlan {
+    int path;               // reference kernel (DEP_GEMM_NAIVE=1) | gemm_small | exact fp32 MFMA | split-precision kernel (gemm_bf16x3.hip)
+    int terms;              // GEMM_SPLIT: 3 (bf16x3) or 1 (single bf16 products)
+    int want;               // split-K count the shape asks for: dep_gemm_workspace_bytes sizes the partials for it
+    int splits, kchunk;     // what runs (fewer splits when the workspace holds fewer partials)
+};
 
 }  // namespace
 
@@ -323,20 +317,30 @@ bool naive_forced() {
 // always exact.  Default: DEP_GEMM_MODE env ("f32" -> 0), else 1.
 int dep_gemm_bf16x3_launch(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B,
                            int ldb, float* C, int ldc, const float* bias, float beta, int seq_T, int shiftB,
-                           int splits, int kchunk, float* part, bool vec, hipStream_t s, int terms, void* ws, size_t ws_bytes);
-static std::atomic<int> g_split_mode{-1};            // process-global (documented in dep_rnn.h)
+                           int splits, int kchunk, float* part, bool vec, int terms, const DepGemmOpts& o, void* ws, size_t ws_bytes,
+                           hipStream_t s);
+static std::atomic<int> g_split_mode{-1};            // process-global (documented in dep_rnn.h); -1 = not set: DEP_GEMM_MODE
 static std::atomic<long> g_split_min_macs{1L << 28};
-static thread_local const unsigned* g_only_if = nullptr;
-// Scratch of the calling thread's UNSPLIT contractions (gemm_bf16x3_nt_dma's weight image).  Not the `ws` argument: a workspace turns split-K on for
-// small problems, and the RNN calls' projections must keep summing as they always did (tests/golden/device_bits.json).
-static thread_local void* g_scratch = nullptr;
-static thread_local size_t g_scratch_bytes = 0;
-void dep_gemm_set_scratch(void* p, size_t bytes) { g_scratch = p; g_scratch_bytes = bytes; }
-void dep_gemm_set_predicate(const unsigned* only_if) { g_only_if = only_if; }
-const unsigned* dep_gemm_predicate() { return g_only_if; }
-static thread_local int g_force_exact = 0;       // per calling thread: 1 = this call is exact fp32, 2 = this call is bf16x3 whatever the global mode
-static void init_split_mode() {
-    if (g_split_mode < 0) { const char* e = getenv("DEP_GEMM_MODE"); g_split_mode = (e && e[0] == 'f') ? 0 : ((e && !strcmp(e, "bf16")) ? 2 : ((e && !strcmp(e, "bf16s")) ? 3 : 1)); }   // "f32" | "bf16" | "bf16s" | default ("bf16x3")
+
+const DepGemmSwitches& dep_gemm_switches() {
+    static const DepGemmSwitches sw = [] {
+        DepGemmSwitches w;
+        const char* e = getenv("DEP_GEMM_MODE");        // "f32" | "bf16" | "bf16s" | default ("bf16x3")
+        w.mode = (e && e[0] == 'f') ? 0 : ((e && !strcmp(e, "bf16")) ? 2 : ((e && !strcmp(e, "bf16s")) ? 3 : 1));
+        e = getenv("DEP_GEMM_NAIVE"); w.naive = e && e[0] == '1';
+        e = getenv("DEP_GEMM_SPLIT_TARGET"); w.split_target = e ? atol(e) : 1024;
+        e = getenv("DEP_DW_PAIR"); w.pair = !(e && e[0] == '0');
+        e = getenv("DEP_GEMM_TN_DMA"); w.tn_dma = !(e && e[0] == '0');
+        e = getenv("DEP_GEMM_NT_DMA"); w.nt_dma = !(e && e[0] == '0');
+        e = getenv("DEP_GEMM_BM"); w.bm256 = !(e && atoi(e) == 128);
+        e = getenv("DEP_GEMM_NT256"); w.nt256 = !(e && e[0] == '0');
+        e = getenv("DEP_GEMM_PERSIST"); w.persist = e ? atoi(e) : 768; if (w.persist < 8) w.persist = 8; w.persist = w.persist / 8 * 8;
+        e = getenv("DEP_GEMM_ABLATE"); w.ablate = e ? atoi(e) : 0;
+        if (w.ablate)      // measurement hook (profiles/r06_gemm_clock_ablation.txt): the results are garbage, and the process says so once
+            fprintf(stderr, "libdep_rnn: DEP_GEMM_ABLATE=%d -- parts of the split-precision GEMM are compiled out of the loop, RESULTS ARE GARBAGE (timing only)\n", w.ablate);
+        return w;
+    }();
+    return sw;
 }
 extern "C" int dep_set_gemm_mode(int mode, long min_macs) {
     if (mode < 0 || mode > 3) { dep_set_error("dep_set_gemm_mode: mode must be 0 (f32), 1 (bf16x3 split), 2 (bf16 products) or 3 (bf16 products + bf16 storage)"); return DEP_ERR_ARG; }
@@ -344,75 +348,76 @@ extern "C" int dep_set_gemm_mode(int mode, long min_macs) {
     if (min_macs >= 0) g_split_min_macs = min_macs;
     return DEP_OK;
 }
-extern "C" int dep_get_gemm_mode(void) { init_split_mode(); return g_split_mode; }
-bool dep_gemm_uses_bf16x3(int M, int N, int K, int seq_T) {
-    init_split_mode();
-    // same branch order as dep_gemm_internal
-    if (naive_forced()) return false;
-    if (seq_T <= 0 && (long)dep_cdiv(M, BM) * dep_cdiv(N, BN) < 32 && K <= 8192 && (long)M * N * K <= (1L << 27)) return false;    // gemm_small
-    if (g_force_exact == 2) return true;
-    return g_force_exact == 0 && g_split_mode >= 1 && (long)M * N * K >= g_split_min_macs;
+extern "C" int dep_get_gemm_mode(void) { const int m = g_split_mode; return m >= 0 ? m : dep_gemm_switches().mode; }
+
+// How a contraction runs: the one place that decides it.
+static GemmPlan gemm_plan(int M, int N, int K, int seq_T, const DepGemmOpts& o, const void* ws, size_t ws_bytes) {
+    GemmPlan g{GEMM_F32, 3, choose_splits(M, N, K, o.split_target), 1, K};
+    const long macs = (long)M * N * K;
+    const int mode = dep_get_gemm_mode();
+    if (dep_gemm_switches().naive) g.path = GEMM_NAIVE;
+    else if (seq_T <= 0 && (long)dep_cdiv(M, BM) * dep_cdiv(N, BN) < 32 && K <= 8192 && macs <= (1L << 27)) g.path = GEMM_SMALL;
+    else if (o.prec == DEP_PREC_X3 || (o.prec == DEP_PREC_MODE && mode >= 1 && macs >= g_split_min_macs)) {
+        g.path = GEMM_SPLIT;
+        g.terms = (o.prec == DEP_PREC_MODE && mode >= 2) ? 1 : 3;        // the public bf16x3 entry is always 3 terms
+    }
+    if (g.path == GEMM_NAIVE || g.path == GEMM_SMALL || g.want == 1) return g;
+    // a smaller workspace than dep_gemm_workspace_bytes asked for lowers the split count, it does not drop it
+    const size_t fit = ws ? ws_bytes / ((size_t)M * N * sizeof(float)) : 0;
+    g.splits = fit < (size_t)g.want ? (fit < 1 ? 1 : (int)fit) : g.want;
+    if (g.splits > 1) {
+        g.kchunk = dep_cdiv(dep_cdiv(K, g.splits), BK) * BK;
+        g.splits = dep_cdiv(K, g.kchunk);
+    }
+    return g;
 }
+
+bool dep_gemm_uses_bf16x3(int M, int N, int K, int seq_T) { return gemm_plan(M, N, K, seq_T, DepGemmOpts{}, nullptr, 0).path == GEMM_SPLIT; }
 
 extern "C" size_t dep_gemm_workspace_bytes(int transA, int transB, int M, int N, int K) {
     (void)transA; (void)transB;
-    const int s = choose_splits(M, N, K);
+    const int s = gemm_plan(M, N, K, 0, DepGemmOpts{}, nullptr, 0).want;
     return s > 1 ? dep_align((size_t)s * M * N * sizeof(float)) : 0;
 }
 
 int dep_gemm_internal(int transA, int transB, int M, int N, int K, const float* A, int lda,
                       const float* B, int ldb, float* C, int ldc, const float* bias, float beta,
-                      int seq_T, int shiftB, void* ws, size_t ws_bytes, hipStream_t s) {
+                      int seq_T, int shiftB, void* ws, size_t ws_bytes, const DepGemmOpts& o, hipStream_t s) {
     DEP_CHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && C);
     DEP_CHECK_ARG(!(transA && transB));
     DEP_CHECK_ARG(!(seq_T > 0 && transB));
-    GemmP p{M, N, K, A, lda, B, ldb, C, ldc, bias, beta, seq_T, shiftB, K, 1, nullptr, 1, 1, dep_gemm_predicate()};
-    init_split_mode();
-    const bool to_split = !naive_forced() && (g_force_exact == 2 || (g_force_exact == 0 && g_split_mode >= 1 && (long)M * N * K >= g_split_min_macs)) &&
-                          !(seq_T <= 0 && (long)dep_cdiv(M, BM) * dep_cdiv(N, BN) < 32 && K <= 8192 && (long)M * N * K <= (1L << 27));
-    if (dep_gemm_pk_pending() && !to_split) {      // (the launcher checks that the format matches the term count)
+    const GemmPlan plan = gemm_plan(M, N, K, seq_T, o, ws, ws_bytes);
+    if ((o.fmt_a != FMT_F32 || o.fmt_b != FMT_F32) && plan.path != GEMM_SPLIT) {      // (the launcher checks that the format matches the term count)
         dep_set_error("dep_gemm: a pre-split (PK) operand reached a contraction that does not run the three-term bf16x3 kernel");
         return DEP_ERR_ARG;
     }
-    if (naive_forced()) {
+    GemmP p{M, N, K, A, lda, B, ldb, C, ldc, bias, beta, seq_T, shiftB, plan.kchunk, plan.splits, plan.splits > 1 ? (float*)ws : nullptr, 1, 1, o.only_if};
+    if (plan.path == GEMM_NAIVE) {
         dim3 g(dep_cdiv(N, 128), M);
         DEP_LAUNCH(gemm_naive, g, dim3(128), 0, s, p, transA, transB);
         DEP_CHECK_LAUNCH();
         return DEP_OK;
     }
-    if (seq_T <= 0 && (long)dep_cdiv(M, BM) * dep_cdiv(N, BN) < 32 && K <= 8192 && (long)M * N * K <= (1L << 27)) {
+    DepProfScope prof(transA ? DEP_PROF_GEMM_TN : (transB ? DEP_PROF_GEMM_NT : DEP_PROF_GEMM_NN), s, o.only_if == nullptr);
+    if (plan.path == GEMM_SMALL) {
         SmallP q{M, N, K, A, transA ? 1L : (long)lda, transA ? (long)lda : 1L, B, transB ? 1L : (long)ldb,
-                 transB ? (long)ldb : 1L, C, ldc, bias, beta, dep_gemm_predicate()};
-        DepProfScope prof(transA ? DEP_PROF_GEMM_TN : (transB ? DEP_PROF_GEMM_NT : DEP_PROF_GEMM_NN), s, dep_gemm_predicate() == nullptr);
+                 transB ? (long)ldb : 1L, C, ldc, bias, beta, o.only_if};
         DEP_LAUNCH(gemm_small, dim3(dep_cdiv(N, 32), dep_cdiv(M, 32)), dim3(256), 0, s, q);
         DEP_CHECK_LAUNCH();
         return DEP_OK;
     }
-    int splits = choose_splits(M, N, K);
-    if (splits > 1) {       // a smaller workspace than dep_gemm_workspace_bytes asked for lowers the split count, it does not drop it
-        const size_t fit = ws ? ws_bytes / ((size_t)M * N * sizeof(float)) : 0;
-        if (fit < (size_t)splits) splits = fit < 1 ? 1 : (int)fit;
-    }
-    int kchunk = K;
-    if (splits > 1) {
-        kchunk = dep_cdiv(dep_cdiv(K, splits), BK) * BK;
-        splits = dep_cdiv(K, kchunk);
-    }
-    p.kchunk = kchunk; p.splits = splits; p.part = splits > 1 ? (float*)ws : nullptr;
+    const int splits = plan.splits;
     const bool a16 = ((uintptr_t)A % 16 == 0) && (lda % 4 == 0);
     const bool b16 = ((uintptr_t)B % 16 == 0) && (ldb % 4 == 0);
     // contiguous-dimension divisibility: K for K-contiguous operands, M/N for MN-contiguous ones
     const bool adim = transA ? (M % 4 == 0) : (K % 4 == 0);
     const bool bdim = transB ? (K % 4 == 0) : (N % 4 == 0);
     const bool vec = a16 && b16 && adim && bdim;
+    if (plan.path == GEMM_SPLIT)       // an unsplit call may use its workspace as scratch
+        return dep_gemm_bf16x3_launch(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, beta, seq_T, shiftB, splits, plan.kchunk, p.part, vec,
+                                      plan.terms, o, (splits == 1 && ws) ? ws : o.scratch, (splits == 1 && ws) ? ws_bytes : o.scratch_bytes, s);
     p.gx = dep_cdiv(N, BN); p.gy = dep_cdiv(M, BM);
     dim3 g(p.gx * p.gy * splits);
-    DepProfScope prof(transA ? DEP_PROF_GEMM_TN : (transB ? DEP_PROF_GEMM_NT : DEP_PROF_GEMM_NN), s, dep_gemm_predicate() == nullptr);
-    init_split_mode();
-    if (g_force_exact == 2 || (g_force_exact == 0 && g_split_mode >= 1 && (long)M * N * K >= g_split_min_macs))
-        return dep_gemm_bf16x3_launch(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, beta, seq_T, shiftB,
-                                      splits, kchunk, p.part, vec, s, (g_force_exact != 2 && g_split_mode >= 2) ? 1 : 3,
-                                      (splits == 1 && ws) ? ws : g_scratch, (splits == 1 && ws) ? ws_bytes : g_scratch_bytes);      // an unsplit call may use its workspace as scratch     // the public bf16x3 entry is always 3 terms
 #define LAUNCH(TA, TB)                                                                    \
     do {                                                                                   \
         if (vec) DEP_LAUNCH((gemm_mfma<TA, TB, true>), g, dim3(NT), 0, s, p);      \
@@ -438,36 +443,30 @@ int dep_gemm_internal(int transA, int transB, int M, int N, int K, const float* 
 // only half of the persistent grid).
 // Returns 1 when the pair was enqueued, 0 when this configuration is not covered (the caller then issues the two calls itself), < 0 on error.
 // Split count, K chunks and summation order per problem are those dep_gemm_internal would use: bit-identical results.
-int dep_gemm_tn_pair(int M, int N, int K, const float* A0, const float* A1, int lda, int skip_at1, int skip_by1,
+int dep_gemm_tn_pair(int M, int N, int K, const float* A0, const float* A1, int lda,
                      const float* B0, int ldb0, int seq_T0, int shift0, const float* B1, int ldb1, int seq_T1, int shift1,
-                     float* C0, int ldc0, float* C1, int ldc1, void* ws, size_t ws_bytes, hipStream_t s) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("DEP_DW_PAIR"); on = (e && e[0] == '0') ? 0 : 1; }
-    init_split_mode();
-    if (!on || naive_forced() || g_force_exact != 0 || g_split_mode != 1 || (long)M * N * K < g_split_min_macs || M < 512 || dep_gemm_predicate()) return 0;
-    if (!dep_gemm_pk_pending() || !dep_gemm_bf16x3_pair_ok()) return 0;
+                     float* C0, int ldc0, float* C1, int ldc1, const DepGemmOpts& o, void* ws, size_t ws_bytes, hipStream_t s) {
+    const GemmPlan plan = gemm_plan(M, N, K, seq_T0 < seq_T1 ? seq_T0 : seq_T1, o, ws, ws_bytes);
+    if (!dep_gemm_switches().pair || plan.path != GEMM_SPLIT || plan.terms != 3 || o.fmt_a != FMT_PK || o.fmt_b != FMT_F32 || o.only_if ||
+        M < 512 || !dep_gemm_bf16x3_pair_ok())
+        return 0;
     auto a16 = [](const void* q, int ld) { return ((uintptr_t)q % 16 == 0) && (ld % 4 == 0); };
     if (!(a16(A0, lda) && a16(A1, lda) && a16(B0, ldb0) && a16(B1, ldb1) && M % 4 == 0 && N % 4 == 0)) return 0;
-    int splits = choose_splits(M, N, K);
-    if (splits <= 1 || !ws) return 0;
-    const size_t one = dep_align((size_t)splits * M * N * sizeof(float));
-    if (ws_bytes < 2 * one) return 0;                 // (a smaller workspace would change the split count of one problem: not bit-identical any more)
-    const int kchunk = dep_cdiv(dep_cdiv(K, splits), BK) * BK;
-    splits = dep_cdiv(K, kchunk);
+    // both sets of partials must fit at the split count the single calls would use (fewer would change one problem's summation order)
+    const size_t one = dep_align((size_t)plan.want * M * N * sizeof(float));
+    if (plan.want <= 1 || !ws || ws_bytes < 2 * one) return 0;
     DepProfScope prof(DEP_PROF_GEMM_TN, s, true);
-    const int rc = dep_gemm_bf16x3_tn_pair_launch(M, N, K, A0, A1, lda, skip_at1, skip_by1, B0, ldb0, seq_T0, shift0, B1, ldb1, seq_T1, shift1,
-                                                  C0, ldc0, C1, ldc1, splits, kchunk, (float*)ws, (float*)((char*)ws + one), s);
+    const int rc = dep_gemm_bf16x3_tn_pair_launch(M, N, K, A0, A1, lda, B0, ldb0, seq_T0, shift0, B1, ldb1, seq_T1, shift1,
+                                                  C0, ldc0, C1, ldc1, o, plan.splits, plan.kchunk, (float*)ws, (float*)((char*)ws + one), s);
     return rc == DEP_OK ? 1 : rc;
 }
 
+// the public fp32 entry is always exact
 extern "C" int dep_gemm_f32(int transA, int transB, int M, int N, int K, const float* A, int lda,
                             const float* B, int ldb, float* C, int ldc, const float* bias, float beta,
                             int seq_T, int shiftB, void* workspace, size_t workspace_bytes, void* stream) {
-    g_force_exact = 1;                  // the public fp32 entry is always exact
-    const int rc = dep_gemm_internal(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, beta, seq_T, shiftB,
-                                     workspace, workspace_bytes, (hipStream_t)stream);
-    g_force_exact = 0;
-    return rc;
+    DepGemmOpts o; o.prec = DEP_PREC_EXACT;
+    return dep_gemm_internal(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, beta, seq_T, shiftB, workspace, workspace_bytes, o, (hipStream_t)stream);
 }
 
 // Same contract, precision as dep_rnn_forward / _backward would choose for a contraction of this size under the current
@@ -475,17 +474,14 @@ extern "C" int dep_gemm_f32(int transA, int transB, int M, int N, int K, const f
 extern "C" int dep_gemm(int transA, int transB, int M, int N, int K, const float* A, int lda,
                         const float* B, int ldb, float* C, int ldc, const float* bias, float beta,
                         int seq_T, int shiftB, void* workspace, size_t workspace_bytes, void* stream) {
-    return dep_gemm_internal(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, beta, seq_T, shiftB,
-                             workspace, workspace_bytes, (hipStream_t)stream);
+    return dep_gemm_internal(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, beta, seq_T, shiftB, workspace, workspace_bytes, DepGemmOpts{},
+                             (hipStream_t)stream);
 }
 
-// Same contract, 3-term bf16 split products (fp32 operands and accumulation): see gemm_bf16x3.hip.
+// Same contract, 3-term bf16 split products (fp32 operands and accumulation): see gemm_bf16x3.hip.  Per call: the process-global mode is not touched.
 extern "C" int dep_gemm_bf16x3(int transA, int transB, int M, int N, int K, const float* A, int lda,
                                const float* B, int ldb, float* C, int ldc, const float* bias, float beta,
                                int seq_T, int shiftB, void* workspace, size_t workspace_bytes, void* stream) {
-    g_force_exact = 2;                  // thread-local: the process-global mode is not touched (reentrancy)
-    const int rc = dep_gemm_internal(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, beta, seq_T, shiftB,
-                                     workspace, workspace_bytes, (hipStream_t)stream);
-    g_force_exact = 0;
-    return rc;
+    DepGemmOpts o; o.prec = DEP_PREC_X3;
+    return dep_gemm_internal(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, beta, seq_T, shiftB, workspace, workspace_bytes, o, (hipStream_t)stream);
 }

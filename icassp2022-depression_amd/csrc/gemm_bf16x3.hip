@@ -30,7 +30,7 @@ struct GemmP {
     float* part;
     int gx, gy;             // tile grid (x: N tiles, y: M tiles); the launch is 1-D, see dep_xcd_tile
     int ablate;             // debug (DEP_GEMM_ABLATE): 1 no epilogue stores, 2 no MFMA, 4 no tile reloads, 8 no LDS staging
-    const unsigned* only_if;    // run only if this device word is non-zero (dep_gemm_set_predicate), or nullptr
+    const unsigned* only_if;    // run only if this device word is non-zero (DepGemmOpts::only_if), or nullptr
     int xcd_lo, xcd_n;          // experiment (dep_gemm_set_xcds): only the workgroups of XCDs [xcd_lo, xcd_lo + xcd_n) work; 0, 8 = all
     int skip_at, skip_by;       // A stored MN-contiguous (transA): logical column m lives at m + (m >= skip_at ? skip_by : 0); 0, 0 = off
 };
@@ -47,7 +47,7 @@ struct GemmP {
 //             gradients as bf16 with the k-pairs already packed: half the operand bytes, nothing to convert
 //   FMT_BF16: a plain row-major bf16 array (ld counted in bf16 elements) -- the hidden sequences y / dropout(y) as the B operand of
 //             the TN contractions (rows may be shifted: dW_hh)
-enum { FMT_F32 = 0, FMT_PK = 1, FMT_PKH = 2, FMT_BF16 = 3 };
+// (FMT_F32 / FMT_PK / FMT_PKH / FMT_BF16: dep_common.h, the values of DepGemmOpts::fmt_a / fmt_b)
 
 
 // Operand tile of ROWS (128 or 256) rows x 32 k, NTH threads (256; 512 in the 256 x 256-tile kernel): a = tid&7, bq = tid>>3, RPI = NTH / 8 rows
@@ -841,26 +841,45 @@ __global__ void splitk_reduce2(const unsigned* only_if, const float* __restrict_
 
 // experiment hook: confine the persistent kernel's working workgroups to a range of XCDs (per calling thread)
 static thread_local int g_xcd_lo = 0, g_xcd_n = 8;
-static thread_local int g_skip_at = 0, g_skip_by = 0;
-void dep_gemm_set_a_colskip(int at, int by) { g_skip_at = at; g_skip_by = by; }
-static thread_local int g_fmt_a = FMT_F32, g_fmt_b = FMT_F32;
-void dep_gemm_set_operand_formats(int fmt_a, int fmt_b) { g_fmt_a = fmt_a; g_fmt_b = fmt_b; }
-bool dep_gemm_pk_pending() { return g_fmt_a != FMT_F32 || g_fmt_b != FMT_F32; }
+extern "C" int dep_gemm_set_xcds(int lo, int n) { if (lo < 0 || n < 1 || lo + n > 8) return DEP_ERR_ARG; g_xcd_lo = lo; g_xcd_n = n; return DEP_OK; }
 // can the paired launch run in this thread's / process's configuration?  (An XCD restriction, an ablation setting or DEP_GEMM_BM=128 apply to the
-// single launches only: dep_gemm_tn_pair then reports "not covered" and the caller issues the two contractions itself -- ADVICE r5.)
+// single launches only: dep_gemm_tn_pair then reports "not covered" and the caller issues the two contractions itself -- ADVICE r5.)  The DMA
+// kernels want the same.
 bool dep_gemm_bf16x3_pair_ok() {
-    static int plain = -1;
-    if (plain < 0) { const char* a = getenv("DEP_GEMM_ABLATE"); const char* b = getenv("DEP_GEMM_BM"); plain = ((a && atoi(a) != 0) || (b && atoi(b) == 128)) ? 0 : 1; }
-    return plain && g_xcd_lo == 0 && g_xcd_n == 8;
+    const DepGemmSwitches& sw = dep_gemm_switches();
+    return !sw.ablate && sw.bm256 && g_xcd_lo == 0 && g_xcd_n == 8;
 }
-// may this TN contraction (A = PK image, B = fp32 rows, split-K) take the LDS-DMA kernel?  DEP_GEMM_TN_DMA=0: the register-staged kernel everywhere.
-static bool tn_dma_ok(int M, int N, int K, int lda, int ldb, int splits, int kchunk, const float* part, int skip_at, int skip_by) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("DEP_GEMM_TN_DMA"); off = (e && e[0] == '0') ? 1 : 0; }
-    return !off && dep_gemm_bf16x3_pair_ok() && M % DM_BM == 0 && N % 128 == 0 && splits > 1 && part && kchunk % DM_SK == 0 && K % DM_SK == 0 &&
-           lda % 4 == 0 && ldb % 4 == 0 && (skip_by == 0 || skip_at % DM_BM == 0);
+
+namespace {
+
+enum { FORM_STAGED, FORM_NT_DMA, FORM_NN_DMA, FORM_TN_DMA };
+struct Form { int kind, bm; };      // bm: row tile of the register-staged kernel (also the tile grid's M step in GemmP)
+// Which form of the split kernel runs problem p: the LDS-DMA kernels where the shape fits (round 6), else the register-staged one.  Input projections
+// (NT) and dX = dG W over the PK gate gradients (NN) take gemm_bf16x3_nt_dma, which needs `ws` for the weight's stage image; the weight gradients (TN,
+// A = PK gate gradients, split-K) take gemm_bf16x3_tn_dma.  Both address their operands with 32-bit buffer offsets: every span they read or write
+// stays below 4 GiB, else the register-staged kernel (64-bit pointers) runs.  DEP_GEMM_NT_DMA=0 / DEP_GEMM_TN_DMA=0: register-staged everywhere.
+Form split_form(bool ta, bool tb, const GemmP& p, int fa, int fb, int terms, bool vec, const void* ws, size_t ws_bytes) {
+    const DepGemmSwitches& sw = dep_gemm_switches();
+    const bool nt = !ta && tb;
+    // measured at cfg2: 256-row tiles win 8-10 % on the NN (dX) and TN (dW) forms, lose 6 % on the short-K NT projection (round 4: long-K
+    // projections -- cfg3's F = 1024 layer -- take the 256-row tile too; DEP_GEMM_NT256=0 restores 128 rows for every NT call).  A pre-split A
+    // operand in the NT form has only the 128-row instantiation.
+    const bool big = sw.bm256 && p.M >= 512 && (!nt || (sw.nt256 && p.K >= 512)) && !(nt && fa != FMT_F32);
+    const Form staged{FORM_STAGED, big ? 256 : 128};
+    if (terms != 3 || !vec || fb != FMT_F32 || !dep_gemm_bf16x3_pair_ok() || p.lda % 4 != 0 || p.ldb % 4 != 0) return staged;
+    const size_t lim = 0xfffffff0ull;
+    if (ta) {
+        const bool ok = sw.tn_dma && fa == FMT_PK && p.M % DM_BM == 0 && p.N % 128 == 0 && p.splits > 1 && p.part && p.kchunk % DM_SK == 0 &&
+                        p.K % DM_SK == 0 && (p.skip_by == 0 || p.skip_at % DM_BM == 0) && (size_t)p.K * p.lda * 4 < lim && (size_t)p.K * p.ldb * 4 < lim;
+        return ok ? Form{FORM_TN_DMA, staged.bm} : staged;
+    }
+    auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    const bool ok = sw.nt_dma && fa == (tb ? FMT_F32 : FMT_PK) && p.seqT <= 0 && p.M % NTD_BM == 0 && p.N % NTD_BN == 0 && p.N <= NTD_MAXN &&
+                    p.K % NTD_SK == 0 && p.K >= 3 * NTD_SK && p.splits == 1 && p.beta == 0.f && a16(p.A) && a16(p.B) && p.C && ws && a16(ws) &&
+                    ws_bytes >= (size_t)p.N * p.K * 4 && !p.only_if && (size_t)p.M * p.lda * 4 < lim && (size_t)p.M * p.ldc * 4 < lim;
+    return ok ? Form{tb ? FORM_NT_DMA : FORM_NN_DMA, staged.bm} : staged;
 }
-static int tn_dma_launch(const GemmP& p0, const GemmP& p1, int np, hipStream_t s) {
+int tn_dma_launch(const GemmP& p0, const GemmP& p1, int np, hipStream_t s) {
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute((const void*)gemm_bf16x3_tn_dma<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dm_lds_bytes(256));
@@ -875,17 +894,7 @@ static int tn_dma_launch(const GemmP& p0, const GemmP& p1, int np, hipStream_t s
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }
-// may this NT projection take the LDS-DMA kernel?  `ws` holds the weight's stage image.  DEP_GEMM_NT_DMA=0: the register-staged kernel everywhere.
-static bool nt_dma_ok(int M, int N, int K, int lda, int ldb, int ldc, const float* A, const float* B, const float* C, const float* bias, float beta, int splits,
-                      void* ws, size_t ws_bytes) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("DEP_GEMM_NT_DMA"); off = (e && e[0] == '0') ? 1 : 0; }
-    auto a16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-    return !off && dep_gemm_bf16x3_pair_ok() && M % NTD_BM == 0 && N % NTD_BN == 0 && N <= NTD_MAXN && K % NTD_SK == 0 && K >= 3 * NTD_SK && splits == 1 && beta == 0.f &&
-           lda % 4 == 0 && ldb % 4 == 0 && a16(A) && a16(B) && C && ws && a16(ws) && ws_bytes >= (size_t)N * K * 4 && dep_gemm_predicate() == nullptr &&
-           (size_t)M * lda * 4 < 0xfffffff0ull && (size_t)M * ldc * 4 < 0xfffffff0ull;
-}
-static int nt_dma_launch(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc, const float* bias, void* ws, hipStream_t s, bool nn_pk = false) {
+int nt_dma_launch(int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc, const float* bias, void* ws, hipStream_t s, bool nn_pk = false) {
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute((const void*)gemm_bf16x3_nt_dma<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTD_LDS_BYTES);
@@ -895,7 +904,7 @@ static int nt_dma_launch(int M, int N, int K, const float* A, int lda, const flo
     if (nn_pk) DEP_LAUNCH(pack_w_stage_image_kn, dim3((unsigned)dep_cdiv((long)N * (K / 8), 256)), dim3(256), 0, s, B, ldb, N, K, (unsigned*)ws);
     else DEP_LAUNCH(pack_w_stage_image, dim3((unsigned)dep_cdiv((long)N * (K / 8), 256)), dim3(256), 0, s, B, ldb, N, K, (unsigned*)ws);
     DEP_CHECK_LAUNCH();
-    NtdP p{A, lda, (const unsigned*)ws, bias, C, ldc, M, N, K, N / NTD_BN, dep_gemm_predicate()};
+    NtdP p{A, lda, (const unsigned*)ws, bias, C, ldc, M, N, K, N / NTD_BN, nullptr};        // (split_form: never predicated)
     const int per_xcd = dep_cdiv((M / NTD_BM) * p.gx, 8);
     const dim3 g((unsigned)((per_xcd < 64 ? per_xcd : 64) * 8));      // two resident workgroups per CU, 32 CUs per XCD
     if (nn_pk) DEP_LAUNCH(gemm_bf16x3_nt_dma<true>, g, dim3(NTD_TH), NTD_LDS_BYTES, s, p);
@@ -903,16 +912,15 @@ static int nt_dma_launch(int M, int N, int K, const float* A, int lda, const flo
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }
-extern "C" int dep_gemm_set_xcds(int lo, int n) { if (lo < 0 || n < 1 || lo + n > 8) return DEP_ERR_ARG; g_xcd_lo = lo; g_xcd_n = n; return DEP_OK; }
 
-// Same contract as dep_gemm_internal (gemm.hip); `splits` is decided by the caller's shared heuristic.
+}  // namespace
+
+// Same contract as dep_gemm_internal (gemm.hip); `splits` is decided by the caller's plan.  `ws`: scratch of an unsplit call.
 int dep_gemm_bf16x3_launch(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B,
                            int ldb, float* C, int ldc, const float* bias, float beta, int seq_T, int shiftB,
-                           int splits, int kchunk, float* part, bool vec, hipStream_t s, int terms, void* ws, size_t ws_bytes) {
-    static int abl = -1, persist = -1, bm256 = -1;
-    // (32-bit lane offsets: every operand must span less than 4 GB)
-    const size_t spanA = (size_t)(transA ? K : M) * lda * 4, spanB = (size_t)(transB ? N : K) * ldb * 4;
-    const int fa = g_fmt_a, fb = g_fmt_b;
+                           int splits, int kchunk, float* part, bool vec, int terms, const DepGemmOpts& o, void* ws, size_t ws_bytes,
+                           hipStream_t s) {
+    const int fa = o.fmt_a, fb = o.fmt_b;
     if (fa != FMT_F32 || fb != FMT_F32) {
         // pre-split operands: vector loads, three-term products; a PK operand pairs ROWS, so its row count must be even, the
         // contraction index (TN) must start on even rows (k-chunks are multiples of 32) and a row-shifted operand cannot be PK
@@ -924,39 +932,16 @@ int dep_gemm_bf16x3_launch(int transA, int transB, int M, int N, int K, const fl
         }
         DEP_CHECK_ARG(transA ? (K % 2 == 0 && kchunk % 2 == 0) : (M % 2 == 0));
     }
-    if (abl < 0) {      // measurement hook (profiles/r06_gemm_clock_ablation.txt): the results are garbage, and the process says so once
-        const char* e = getenv("DEP_GEMM_ABLATE"); abl = e ? atoi(e) : 0;
-        if (abl) fprintf(stderr, "libdep_rnn: DEP_GEMM_ABLATE=%d -- parts of the split-precision GEMM are compiled out of the loop, RESULTS ARE GARBAGE (timing only)\n", abl);
-    }
-    if (persist < 0) { const char* e = getenv("DEP_GEMM_PERSIST"); persist = e ? atoi(e) : 768; if (persist < 8) persist = 8; persist = persist / 8 * 8; }
-    if (bm256 < 0) { const char* e = getenv("DEP_GEMM_BM"); bm256 = (e && atoi(e) == 128) ? 0 : 1; }
-    // measured at cfg2: 256-row tiles win 8-10 % on the NN (dX) and TN (dW) forms, lose 6 % on the short-K NT projection
-    // (round 4: long-K projections -- cfg3's F = 1024 layer -- take the 256-row tile too; DEP_GEMM_NT256=0 restores 128 rows for every NT call)
-    static int nt256 = -1;
-    if (nt256 < 0) { const char* e = getenv("DEP_GEMM_NT256"); nt256 = (e && e[0] == '0') ? 0 : 1; }
-    // (a pre-split A operand in the NT form has only the 128-row instantiation: the tile grid must follow -- ADVICE r4)
-    const bool big = bm256 && M >= 512 && (!(!transA && transB) || (nt256 && K >= 512)) && !(fa != FMT_F32 && !transA && transB);
-    const int BMT = big ? 256 : 128;
-    GemmP p{M, N, K, A, lda, B, ldb, C, ldc, bias, beta, seq_T, shiftB, kchunk, splits, part, dep_cdiv(N, BN), dep_cdiv(M, BMT), abl, dep_gemm_predicate(), g_xcd_lo, g_xcd_n, transA ? g_skip_at : 0, transA ? g_skip_by : 0};
-    if (!transA && transB && fa == FMT_F32 && fb == FMT_F32 && terms == 3 && vec && !abl && seq_T <= 0 &&
-        nt_dma_ok(M, N, K, lda, ldb, ldc, A, B, C, bias, beta, splits, ws, ws_bytes))
-        return nt_dma_launch(M, N, K, A, lda, B, ldb, C, ldc, bias, ws, s);      // Round 6: the input projections whose shape fits take the LDS-DMA kernel
-    // ... and so does dX = dG W (NN) over the PK gate-gradient image: the same kernel with the row operand's fragments read, not converted
-    if (!transA && !transB && fa == FMT_PK && fb == FMT_F32 && terms == 3 && vec && !abl && seq_T <= 0 && ldb % 4 == 0 &&
-        nt_dma_ok(M, N, K, lda, ldb, ldc, A, B, C, bias, beta, splits, ws, ws_bytes))
-        return nt_dma_launch(M, N, K, A, lda, B, ldb, C, ldc, bias, ws, s, true);
-    if (transA && !transB && fa == FMT_PK && fb == FMT_F32 && terms == 3 && vec && !abl && tn_dma_ok(M, N, K, lda, ldb, splits, kchunk, part, p.skip_at, p.skip_by)) {
-        // Round 6: the weight-gradient contractions whose shape fits take the LDS-DMA kernel (bit-identical partial sums); the reduce below is shared
-        const int rc = tn_dma_launch(p, p, 1, s);
-        if (rc) return rc;
-        const long n = (long)M * N;
-        DEP_LAUNCH(splitk_reduce2, dim3(dep_cdiv(n, 256)), dim3(256), 0, s, dep_gemm_predicate(), part, splits, M, N, C, ldc, bias, beta);
-        DEP_CHECK_LAUNCH();
-        return DEP_OK;
-    }
+    const DepGemmSwitches& sw = dep_gemm_switches();
+    GemmP p{M, N, K, A, lda, B, ldb, C, ldc, bias, beta, seq_T, shiftB, kchunk, splits, part, dep_cdiv(N, BN), 0, sw.ablate, o.only_if, g_xcd_lo, g_xcd_n,
+            transA ? o.skip_at : 0, transA ? o.skip_by : 0};
+    const Form f = split_form(transA, transB, p, fa, fb, terms, vec, ws, ws_bytes);
+    const bool big = f.bm == 256;
+    p.gy = dep_cdiv(M, f.bm);
+    if (f.kind == FORM_NT_DMA || f.kind == FORM_NN_DMA) return nt_dma_launch(M, N, K, A, lda, B, ldb, C, ldc, bias, ws, s, f.kind == FORM_NN_DMA);
     // persistent launch: at most `persist` workgroups (a multiple of 8: one share per XCD), each walks a list of tiles
     const int ntiles = p.gx * p.gy * splits;
-    const int cap = big ? persist * 2 / 3 : persist;              // 2 resident workgroups per CU with 256-row tiles, 3 otherwise
+    const int cap = big ? sw.persist * 2 / 3 : sw.persist;        // 2 resident workgroups per CU with 256-row tiles, 3 otherwise
     const int per_xcd = (ntiles + g_xcd_n - 1) / g_xcd_n;
     dim3 g((per_xcd < cap / 8 ? per_xcd : cap / 8) * 8);
 #define LAUNCH1(TA, TB, TERMS)                                                                       \
@@ -969,7 +954,11 @@ int dep_gemm_bf16x3_launch(int transA, int transB, int M, int N, int K, const fl
 #define LAUNCH(TA, TB) do { if (terms == 1) LAUNCH1(TA, TB, 1); else LAUNCH1(TA, TB, 3); } while (0)
 #define LAUNCH_PK(TA, TB, BM, FA_, FB_) DEP_LAUNCH((gemm_bf16x3<TA, TB, true, BM, 3, FA_, FB_>), g, dim3(NT), 0, s, p)
 #define LAUNCH_H(TA, TB, BM, FB_) DEP_LAUNCH((gemm_bf16x3<TA, TB, true, BM, 1, FMT_PKH, FB_>), g, dim3(NT), 0, s, p)
-    if (fa == FMT_PKH) {
+    if (f.kind == FORM_TN_DMA) {        // bit-identical partial sums; the reduce below is shared
+        const int rc = tn_dma_launch(p, p, 1, s);
+        if (rc) return rc;
+    }
+    else if (fa == FMT_PKH) {
         if (transA) {
             if (big) { if (fb == FMT_BF16) LAUNCH_H(true, false, 256, FMT_BF16); else LAUNCH_H(true, false, 256, FMT_F32); }
             else     { if (fb == FMT_BF16) LAUNCH_H(true, false, 128, FMT_BF16); else LAUNCH_H(true, false, 128, FMT_F32); }
@@ -997,7 +986,7 @@ int dep_gemm_bf16x3_launch(int transA, int transB, int M, int N, int K, const fl
     DEP_CHECK_LAUNCH();
     if (splits > 1) {
         const long n = (long)M * N;
-        DEP_LAUNCH(splitk_reduce2, dim3(dep_cdiv(n, 256)), dim3(256), 0, s, dep_gemm_predicate(), part, splits, M, N, C, ldc, bias, beta);
+        DEP_LAUNCH(splitk_reduce2, dim3(dep_cdiv(n, 256)), dim3(256), 0, s, o.only_if, part, splits, M, N, C, ldc, bias, beta);
         DEP_CHECK_LAUNCH();
     }
     return DEP_OK;
@@ -1006,17 +995,17 @@ int dep_gemm_bf16x3_launch(int transA, int transB, int M, int N, int K, const fl
 // dW_ih + dW_hh of one GRU layer in one launch (gemm_bf16x3_tn_pair above).  A = the sweep's PK gate-gradient image for both (problem 1
 // reads it through the column skip), B0 = the layer's input, B1 = the layer's own output shifted one step; same (M, N, K, splits, kchunk).
 // The caller (dep_gemm_tn_pair, gemm.hip) has checked formats / alignment / sizes; returns DEP_OK after enqueueing both the walk and the reduce.
-int dep_gemm_bf16x3_tn_pair_launch(int M, int N, int K, const float* A0, const float* A1, int lda, int skip_at1, int skip_by1,
+int dep_gemm_bf16x3_tn_pair_launch(int M, int N, int K, const float* A0, const float* A1, int lda,
                                    const float* B0, int ldb0, int seq_T0, int shift0, const float* B1, int ldb1, int seq_T1, int shift1,
-                                   float* C0, int ldc0, float* C1, int ldc1, int splits, int kchunk, float* part0, float* part1, hipStream_t s) {
-    DEP_CHECK_ARG(g_fmt_a == FMT_PK && g_fmt_b == FMT_F32 && M >= 512 && splits > 1 && part0 && part1);
-    DEP_CHECK_ARG(K % 2 == 0 && kchunk % 2 == 0 && dep_gemm_predicate() == nullptr && g_xcd_lo == 0 && g_xcd_n == 8);
-    static int persist = -1;
-    if (persist < 0) { const char* e = getenv("DEP_GEMM_PERSIST"); persist = e ? atoi(e) : 768; if (persist < 8) persist = 8; persist = persist / 8 * 8; }
+                                   float* C0, int ldc0, float* C1, int ldc1, const DepGemmOpts& o, int splits, int kchunk, float* part0, float* part1,
+                                   hipStream_t s) {
+    DEP_CHECK_ARG(o.fmt_a == FMT_PK && o.fmt_b == FMT_F32 && M >= 512 && splits > 1 && part0 && part1);
+    DEP_CHECK_ARG(K % 2 == 0 && kchunk % 2 == 0 && o.only_if == nullptr && g_xcd_lo == 0 && g_xcd_n == 8);
     GemmP p0{M, N, K, A0, lda, B0, ldb0, C0, ldc0, nullptr, 0.f, seq_T0, shift0, kchunk, splits, part0, dep_cdiv(N, BN), dep_cdiv(M, 256), 0, nullptr, 0, 8, 0, 0};
     GemmP p1 = p0;
-    p1.A = A1; p1.B = B1; p1.ldb = ldb1; p1.C = C1; p1.ldc = ldc1; p1.seqT = seq_T1; p1.shiftB = shift1; p1.part = part1; p1.skip_at = skip_at1; p1.skip_by = skip_by1;
-    if (tn_dma_ok(M, N, K, lda, ldb0, splits, kchunk, part0, skip_at1, skip_by1) && ldb1 % 4 == 0) {
+    p1.A = A1; p1.B = B1; p1.ldb = ldb1; p1.C = C1; p1.ldc = ldc1; p1.seqT = seq_T1; p1.shiftB = shift1; p1.part = part1; p1.skip_at = o.skip_at; p1.skip_by = o.skip_by;
+    if (split_form(true, false, p0, FMT_PK, FMT_F32, 3, true, nullptr, 0).kind == FORM_TN_DMA &&
+        split_form(true, false, p1, FMT_PK, FMT_F32, 3, true, nullptr, 0).kind == FORM_TN_DMA) {
         const int rc = tn_dma_launch(p0, p1, 2, s);
         if (rc) return rc;
         const long n = (long)M * N;
@@ -1025,7 +1014,7 @@ int dep_gemm_bf16x3_tn_pair_launch(int M, int N, int K, const float* A0, const f
         return DEP_OK;
     }
     const int ntiles = p0.gx * p0.gy * splits;
-    const int cap = persist * 2 / 3 / 2;                          // two resident workgroups per CU with 256-row tiles, half of the slots per problem
+    const int cap = dep_gemm_switches().persist * 2 / 3 / 2;     // two resident workgroups per CU with 256-row tiles, half of the slots per problem
     const int per_xcd = (ntiles + 7) / 8;
     dim3 g((per_xcd < cap / 8 ? per_xcd : cap / 8) * 8 * 2);
     DEP_LAUNCH((gemm_bf16x3_tn_pair<true, 256, FMT_PK, FMT_F32>), g, dim3(NT), 0, s, p0, p1);

@@ -207,7 +207,8 @@ int dep_rnn_backward_overlapped(const dep_rnn_desc* d, const float* x, const flo
  * input-projection / weight-gradient contractions inside nn.GRU / nn.LSTM.
  * seq_T/shiftB: when seq_T > 0 and transB == 0, row r of B is read from row r+shiftB and is taken
  * as zero when (r % seq_T)+shiftB falls outside [0,seq_T)  (h_{t-1} operand of dW_hh).
- * workspace is needed for split-K (dep_gemm_workspace_bytes), may be NULL otherwise. */
+ * workspace is needed for split-K (dep_gemm_workspace_bytes), may be NULL otherwise.  A call that does not split may
+ * still use a workspace it is given as scratch: calls that may run concurrently need one workspace each (one per stream). */
 size_t dep_gemm_workspace_bytes(int transA, int transB, int M, int N, int K);
 int dep_gemm_f32(int transA, int transB, int M, int N, int K,
                  const float* A, int lda, const float* B, int ldb, float* C, int ldc,
@@ -369,7 +370,7 @@ int dep_vlad_normalize(const float* vkf, const float* a_sum, const float* w2, fl
 int dep_profile_enable(int on);
 int dep_profile_read(double* total_ms, int* counts, int ncat);
 
-/* Launch-instance log (test infrastructure of the parity suite, tests/test_instance_coverage_gpu.py): while enabled, every
+/* Launch-instance log (test infrastructure of the parity suite, tests/test_step_coverage_gpu.py): while enabled, every
  * kernel launch of the library records its template instance (kernel expression + launcher signature), once per distinct
  * instance.  dep_instance_log_enable(1) clears and starts, (0) stops.  dep_instance_log_read copies the newline-separated
  * list into buf (NUL-terminated, truncated to cap; buf may be NULL) and returns the bytes the full list needs; reset != 0

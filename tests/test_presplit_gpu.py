@@ -63,14 +63,18 @@ def test_pk_gate_gradients_of_the_bilstm_stack_are_bit_identical_too(tmp_path, B
 # fits (256 x 256 / 128 x 256 tiles, K chunks of 16 rows).  Same K chunks, same order of k, same three products per 16 k in the same order: every output
 # and every gradient bit-identical to the register-staged kernels (DEP_GEMM_TN_DMA=0 DEP_GEMM_NT_DMA=0) -- and the DMA kernels must really have run.
 # (the projection kernel wants B T % 128 == 0 and an unsplit contraction, the weight-gradient kernel a split-K one with chunks of 16 rows)
+# Both address their operands with 32-bit buffer offsets.  Past B T = 2^20 rows the BiLSTM stack's 4H-wide gate gradients and its projections' output
+# span more than 4 GiB: neither DMA kernel may run there, the register-staged kernels (64-bit pointers) take every contraction.
 @pytest.mark.parametrize('B,T,F,dx,nody,lstm,tn', [(512, 300, 256, False, True, False, True), (384, 24, 256, True, False, False, True), (64, 32, 256, False, True, False, True),
-                                                   (512, 300, 1024, False, False, True, True), (128, 32, 1024, True, False, True, True)])
+                                                   (512, 300, 1024, False, False, True, True), (128, 32, 1024, True, False, True, True),
+                                                   (4096, 258, 64, False, False, True, False)])
 def test_dma_fed_contractions_leave_every_output_and_gradient_bit_identical(tmp_path, B, T, F, dx, nody, lstm, tn):
+    nt = B * T <= 1 << 20
     a = _run(tmp_path, 'a', 1, B, T, F, dx, lstm=lstm, env={'DEP_GEMM_TN_DMA': '0', 'DEP_GEMM_NT_DMA': '0', 'PROBE_INSTANCES': '1'}, nody=nody)
     b = _run(tmp_path, 'b', 1, B, T, F, dx, lstm=lstm, env={'PROBE_INSTANCES': '1'}, nody=nody)
     ia, ib = ' '.join(a['instances']), ' '.join(b['instances'])
     assert 'nt_dma' not in ia and 'tn_dma' not in ia
-    assert 'gemm_bf16x3_nt_dma' in ib and ('gemm_bf16x3_tn_dma' in ib) == tn, ib
+    assert ('gemm_bf16x3_nt_dma' in ib) == nt and ('gemm_bf16x3_tn_dma' in ib) == tn, ib
     for k in a.files:
         if k == 'instances':
             continue
