@@ -143,6 +143,8 @@ namespace {
 constexpr int MAXL = 8;
 constexpr size_t NOT_KEPT = (size_t)-1;         // Layout offset of an array the run mode does not keep
 
+// Sizes and offsets of a descriptor's reserve and workspace.  A function of the descriptor and the switches alone: the size queries
+// answer the same whatever precision mode or exclusivity the calls run under (what a call runs is its RnnPlan, below).
 struct Layout {
     int G, D, L;
     size_t BT;                       // B*T rows
@@ -158,13 +160,9 @@ struct Layout {
     bool drop;
     bool keep;                       // DEP_RUN_TRAIN: the reserve holds everything the backward reads
     bool donly;                      // DEP_RUN_DROPOUT_ONLY: dropout as in training, the reserve holds what the forward itself reads
-    bool cluster;                    // cluster-parallel sweeps (rnn_cluster*.hip)
-    bool cluster16;                  // forward with 16-unit members, two workgroups per CU (rnn_cluster16.hip)
-    bool dg4;                        // GRU cluster backward: gate gradients as ONE (B*T, 4H) array [dr | dz | dn | dn*r] (dW_hh is then one contraction)
-    bool bf16st;                     // dep_set_gemm_mode(3) on a stack whose kernels have the bf16-storage variants (2-layer GRU, H = 256, fused forward): y, hn as bf16, gate gradients as PKH
-    bool sv16;                       // GRU cluster sweeps: saved gates r, z, n as 16-bit fixed point (split-precision mode only; decided per call)
-    bool fused2;                     // 2-layer GRU, H = 256: both layers in one launch (rnn_fused2.hip), split-precision mode only
-    size_t wih_img;                  // workspace: packed W_ih of layer 1 for the fused forward
+    bool cluster;                    // cluster-parallel sweeps (rnn_cluster*.hip): the workspace has their exchange buffer
+    bool fused2;                     // 2-layer GRU, H = 256: both layers in one launch (rnn_fused2*.hip) where the call's plan allows it
+    size_t wih_img;                  // workspace: packed W_ih of layer 1 for the fused launches
 };
 
 bool make_layout(const dep_rnn_desc* d, Layout& lo) {
@@ -180,6 +178,7 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     lo.donly = d->training == DEP_RUN_DROPOUT_ONLY;
     lo.drop = d->training != DEP_RUN_EVAL && d->dropout_p > 0.f;
     const size_t H = d->H, D = d->dirs, G = lo.G;
+    const size_t maxin = D * H > (size_t)d->F ? D * H : (size_t)d->F;      // the widest layer input
     auto al = [](size_t f) { return (f + 63) / 64 * 64; };
     size_t off = 0;
     for (int l = 0; l < d->L; ++l) {
@@ -218,13 +217,11 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     size_t w = 0;
     lo.gi = w; w += al(lo.BT * D * (G + (d->cell == DEP_CELL_GRU && lo.keep ? 1 : 0)) * H);     // GI (fwd) / dGI (bwd; GRU: room for the 4H-wide [dr|dz|dn|dn*r] rows)
     lo.dghn = w; w += al(lo.BT * H);
-    const size_t maxin = D * H > (size_t)d->F ? D * H : (size_t)d->F;
     lo.dx[0] = w; w += al(lo.BT * D * H);
     lo.dx[1] = w; w += al(lo.BT * D * H);
-    (void)maxin;
     lo.dbpart = w; w += al((size_t)D * lo.nwg * 4 * H);
     lo.biastmp = w; w += al(G * H);
-    lo.dwstack = w; if (d->dirs == 2 && lo.keep) { const size_t mx = D * H > (size_t)d->F ? D * H : (size_t)d->F; w += al(D * G * H * mx); }
+    lo.dwstack = w; if (d->dirs == 2 && lo.keep) w += al(D * G * H * maxin);
     // split-K scratch: the largest weight-gradient contraction
     size_t gb = 0;
     {   // every (rows, cols) block dep_rnn_backward contracts over B*T: dW_ih (G H x F | D H), dW_hh whole or as the GRU's
@@ -243,8 +240,7 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
         if (b2 > gb) gb = b2;
     }
     {   // ... and the forward's use of the same scratch: the stage image of a layer's (direction-stacked) W_ih (gemm_bf16x3_nt_dma)
-        const size_t mx = D * H > (size_t)d->F ? D * H : (size_t)d->F;
-        const size_t b3 = (size_t)D * G * H * mx * sizeof(float);
+        const size_t b3 = (size_t)D * G * H * maxin * sizeof(float);
         if (b3 > gb) gb = b3;
     }
     lo.gemm = w; lo.gemm_bytes = gb; w += al(gb / sizeof(float) + 64);
@@ -252,8 +248,6 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     const bool cok = d->cell == DEP_CELL_GRU ? dep_cluster_ok(d->cell, d->H, d->B, d->dirs) : dep_cluster_lstm_ok(d->H, d->B, d->dirs);
     if (d->impl == 3 && !cok) return false;
     lo.cluster = cok && (d->impl == 0 || d->impl == 3);
-    lo.cluster16 = lo.cluster && dep_cluster16_ok(d->cell, d->H, d->B);
-    lo.dg4 = lo.cluster && d->cell == DEP_CELL_GRU && d->dirs == 1;
     lo.xbuf = w; lo.xbuf_bytes = !lo.cluster ? 0 : (d->cell == DEP_CELL_GRU ? dep_cluster_xbuf_bytes(d->cell, d->H, d->B, d->dirs)
                                                                 : dep_cluster_lstm_xbuf_bytes(d->H, d->B, d->dirs));
     if (lo.cluster) lo.nwg = dep_cdiv(d->B, 16);      // the cluster sweeps write one row per tile whatever the tile-MFMA sweep could do at this H
@@ -271,20 +265,6 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
         lo.dbpart2 = w; w += al((size_t)lo.nwg * 4 * H);
     }
     lo.ws_floats = w;
-    // 16-bit saved gates: the kernels that implement them are the fused forward, the 32-unit-member forward and the 32-unit-member
-    // backward (burst or not); the 16-unit-member kernels and the opt-in fused backward read / write fp32 gates
-    {
-        static int sv_env = -1;
-        if (sv_env < 0) { const char* e = getenv("DEP_SV16"); sv_env = (e && e[0] == '0') ? 0 : 1; }
-        // (an INSTANCE choice: a dropout-only forward launches the instance training launches, though it saves no gates)
-        lo.sv16 = sv_env && d->training != DEP_RUN_EVAL && lo.cluster &&
-                  (d->cell == DEP_CELL_GRU ? (lo.fused2 || !lo.cluster16) : dep_cluster_lstm_sv16_ok());
-        // bf16-STORAGE mode (dep_set_gemm_mode(3); a labelled throughput mode, never the parity path): only where every kernel of the
-        // stack has the variant -- the fused 2-layer GRU forward and the burst backward with the 4H-wide gate-gradient rows.  Other
-        // stacks run mode 3 exactly like mode 2 (single bf16 products, fp32 storage).
-        lo.bf16st = dep_get_gemm_mode() == 3 && lo.keep && lo.sv16 && lo.fused2 && lo.dg4 && d->cell == DEP_CELL_GRU && d->T % 2 == 0 &&
-                    dep_cluster_bwd_pk_ok(d->H, d->T);
-    }
     return true;
 }
 
@@ -334,43 +314,143 @@ extern "C" int dep_rnn_status(const dep_rnn_desc* d, void* workspace, void* stre
     return DEP_OK;
 }
 
+const RnnSwitches& dep_rnn_switches() {
+    static const RnnSwitches sw = [] {
+        RnnSwitches w;
+        const char* e = getenv("DEP_SV16"); w.sv16 = !(e && e[0] == '0');
+        e = getenv("DEP_LSTM_SV16"); w.lstm_sv16 = e && e[0] == '1';
+        e = getenv("DEP_FUSED2"); w.fused2 = !(e && e[0] == '0');
+        e = getenv("DEP_FUSED2_BWD"); w.fused2_bwd = e ? e[0] == '1' : DEP_FUSED2_BWD_DEFAULT != 0;
+        e = getenv("DEP_CLUSTER16"); w.cluster16 = !(e && e[0] == '0');
+        e = getenv("DEP_CLUSTER_LSTM"); w.cluster_lstm = !(e && e[0] == '0');
+        e = getenv("DEP_DGI_PK"); w.dgi_pk = !(e && e[0] == '0');
+        e = getenv("DEP_COMM_OVERLAP"); w.comm_beside_sweeps = e && e[0] == 's';
+        e = getenv("DEP_EXCLUSIVE"); w.exclusive = !(e && e[0] == '0');
+        return w;
+    }();
+    return sw;
+}
+
 // Kernels that need every CU to themselves (the fused two-layer GRU forward, the 16-unit-member forward): allowed unless the
 // process said otherwise (DEP_EXCLUSIVE=0 / dep_rnn_set_exclusive(0): the GPU is shared with other streams or processes).
-static std::atomic<int> g_exclusive{-1};
-bool dep_exclusive_on() {
-    int v = g_exclusive.load(std::memory_order_relaxed);
-    if (v < 0) { const char* e = getenv("DEP_EXCLUSIVE"); v = (e && e[0] == '0') ? 0 : 1; g_exclusive.store(v); }
-    return v == 1;
-}
+static std::atomic<int> g_exclusive{-1};             // -1 = not set: DEP_EXCLUSIVE
+static bool dep_exclusive_on() { const int v = g_exclusive.load(std::memory_order_relaxed); return v >= 0 ? v == 1 : dep_rnn_switches().exclusive; }
 extern "C" int dep_rnn_set_exclusive(int on) { g_exclusive.store(on ? 1 : 0); return DEP_OK; }
 extern "C" int dep_rnn_get_exclusive(void) { return dep_exclusive_on() ? 1 : 0; }
 
-// Precision of the recurrent products inside the cluster sweeps: follows the GEMM mode (include/dep_rnn.h,
-// dep_set_gemm_mode): 1 = 3-term bf16 split on the bf16 matrix cores, 0 = exact fp32 MFMA.
-static bool sweep_split_mode() {
-    return dep_get_gemm_mode() >= 1;                // mode 2 (single bf16 products in the GEMMs) keeps the split sweeps
+namespace {
+
+// ---- the plan of one call ----------------------------------------------------------------------------------------------------
+// Which kernels a dep_rnn_forward / dep_rnn_backward call runs and on which weight images, decided once from the descriptor, the
+// switches and the call's snapshot of the two process-wide settings (dep_set_gemm_mode, dep_rnn_set_exclusive): the entry points
+// take the snapshot at entry and read neither again, so another thread changing them mid-call cannot mix two modes in one call.
+// (The GEMM layer follows the mode on its own -- its documented contract.)
+enum FwdKernel { FWD_FUSED2,          // both GRU layers in one launch, the per-layer cluster kernels enqueued behind it as its on-device fallback
+                 FWD_CLUSTER16,       // GRU, 16-unit members (rnn_cluster16.hip)
+                 FWD_CLUSTER_GRU,     // GRU, 32-unit members (rnn_cluster.hip)
+                 FWD_CLUSTER_LSTM,    // (Bi)LSTM cluster (rnn_cluster_lstm.hip)
+                 FWD_TILE };          // tile-MFMA / generic sweep (rnn_sweep.hip picks by impl and H)
+enum BwdKernel { BWD_FUSED2, BWD_CLUSTER_GRU, BWD_CLUSTER_LSTM, BWD_TILE };
+// the split-precision recurrent-weight images (the fp32 fragment images of dep_pack_whh are RnnPlan::whh_f32)
+enum WhhImage { WHH_NONE, WHH_SPLIT16, WHH_SPLIT32, WHH_LSTM_PAIR /* forward and backward image in one launch */, WHH_BWD_SPLIT, WHH_BWD_F32 /* fp32, member-sliced */ };
+// What a forward leaves behind in its reserve: dep_rnn_backward must run kernels of the same kind (reserve_tag_refusal).
+enum ReserveTag { TAG_SPLIT = 1, TAG_SV16 = 4, TAG_BF16ST = 8, TAG_DONLY = 16 };
+
+struct RnnPlan {
+    bool excl;                       // the snapshot of dep_rnn_set_exclusive (the mode's is in the fields below)
+    bool split;                      // recurrent products of the cluster sweeps: 3-term bf16 split on the bf16 matrix cores (mode >= 1; mode 2 / 3 keep it), else exact fp32 MFMA
+    FwdKernel fwd; BwdKernel bwd;
+    bool whh_f32;                    // a layer packs the fp32 fragment images (kernels that are not running on split-precision images)
+    WhhImage whh_fwd, whh_bwd;       // ... and these (FWD_FUSED2 packs the same two kinds for both layers in one launch)
+    bool sv16;                       // saved gates r, z, n as 16-bit fixed point: reserve tag, fused launches, backward sweeps
+    bool sv16_fwd;                   // ... and the per-layer forward launches: the 16-unit-member kernel has no 16-bit path
+    bool dg4;                        // GRU cluster backward: gate gradients as ONE (B*T, 4H) array [dr | dz | dn | dn*r] (dW_hh is then one contraction)
+    bool bf16st;                     // dep_set_gemm_mode(3) on a stack whose kernels have the bf16-storage variants (2-layer GRU, H = 256, fused forward): y, hn as bf16, gate gradients as PKH
+    bool pk;                         // gate gradients may be the PK image of gemm_bf16x3.hip: what the descriptor decides of it (operand alignment and GEMM paths are checked per layer)
+    int pk_fmt;                      // ... read by the contractions as FMT_PK, or through its hi rows (FMT_PKH) in the single-product modes
+    bool dw_pair;                    // layers with H inputs ask split-K target 512 for their weight gradients (the dW_ih + dW_hh pair's; bf16x3 mode only)
+    int tag;                         // ReserveTag bits
+};
+
+RnnPlan make_plan(const dep_rnn_desc* d, const Layout& lo, int mode, bool excl) {
+    const RnnSwitches& sw = dep_rnn_switches();
+    const bool gru = d->cell == DEP_CELL_GRU;
+    RnnPlan p{};
+    p.excl = excl; p.split = mode >= 1;
+    const bool csplit = lo.cluster && p.split;
+    // the kernels that fill every CU (fused forward, 16-unit members) are not for a shared GPU; the fused BACKWARD does not care
+    const bool cluster16 = lo.cluster && dep_cluster16_ok(d->cell, d->H, d->B);
+    p.fwd = (lo.fused2 && p.split && excl) ? FWD_FUSED2 : (cluster16 && excl) ? FWD_CLUSTER16
+          : !lo.cluster ? FWD_TILE : gru ? FWD_CLUSTER_GRU : FWD_CLUSTER_LSTM;
+    p.bwd = (lo.fused2 && sw.fused2_bwd && p.split && dep_fused2_bwd_fits(d->B, d->T)) ? BWD_FUSED2
+          : !lo.cluster ? BWD_TILE : gru ? BWD_CLUSTER_GRU : BWD_CLUSTER_LSTM;
+    p.whh_f32 = lo.cluster ? !p.split : dep_sweep_use_mfma(d->H, d->impl);
+    p.whh_fwd = !csplit ? WHH_NONE : !gru ? WHH_LSTM_PAIR : p.fwd == FWD_CLUSTER16 ? WHH_SPLIT16 : WHH_SPLIT32;
+    p.whh_bwd = (!lo.cluster || !lo.keep || p.whh_fwd == WHH_LSTM_PAIR) ? WHH_NONE : p.split ? WHH_BWD_SPLIT : WHH_BWD_F32;
+    // 16-bit saved gates: the kernels that implement them are the fused forward, the 32-unit-member forward and the 32-unit-member
+    // backward (burst or not); the 16-unit-member kernels and exact-fp32 mode read / write fp32 gates.  Follows the DESCRIPTOR's
+    // cluster16, not whether this call may run that kernel.  An INSTANCE choice: a dropout-only forward launches the instance
+    // training launches, though it saves no gates.
+    p.sv16 = p.split && sw.sv16 && d->training != DEP_RUN_EVAL && lo.cluster && (gru ? (lo.fused2 || !cluster16) : dep_cluster_lstm_sv16_ok());
+    p.sv16_fwd = p.sv16 && p.fwd != FWD_CLUSTER16;
+    p.dg4 = lo.cluster && gru && d->dirs == 1;
+    // bf16-STORAGE mode (dep_set_gemm_mode(3); a labelled throughput mode, never the parity path): only where every kernel of the
+    // stack has the variant -- the fused 2-layer GRU forward and the burst backward with the 4H-wide gate-gradient rows.  Other
+    // stacks run mode 3 exactly like mode 2 (single bf16 products, fp32 storage).
+    p.bf16st = mode == 3 && lo.keep && p.sv16 && lo.fused2 && p.dg4 && d->T % 2 == 0 && dep_cluster_bwd_pk_ok(d->H, d->T);
+    p.pk = sw.dgi_pk && csplit && lo.BT % 2 == 0 &&
+           (gru ? p.dg4 && d->T % 2 == 0 && (p.bwd == BWD_FUSED2 || dep_cluster_bwd_pk_ok(d->H, d->T)) : d->dirs == 2 && dep_cluster_lstm_bwd_pk_ok(d->T));
+    p.pk_fmt = (p.bf16st || mode >= 2) ? FMT_PKH : FMT_PK;
+    p.dw_pair = p.dg4 && mode == 1;      // (the other precision modes never pair: they keep the single launches' target)
+    p.tag = (p.split ? TAG_SPLIT : 0) | (p.sv16 ? TAG_SV16 : 0) | (p.bf16st ? TAG_BF16ST : 0) | (lo.donly ? TAG_DONLY : 0);
+    return p;
 }
 
-// Precision mode of the packed recurrent-weight images a reserve holds (host-side record, no device traffic): the
-// backward must run the kernels of the SAME mode, so dep_rnn_backward refuses a reserve whose forward ran in the other
-// mode (a caller flipping dep_set_gemm_mode in between would otherwise get silently wrong gradients).  Small ring: the
-// newest record of a pointer wins; a reserve with no record (evicted after 256 other forwards) is trusted.
-namespace {
-struct ModeRec { const void* p; int mode; };
-ModeRec g_modes[256];
-int g_mode_next = 0;
-std::mutex g_mode_mu;
-void record_reserve_mode(const void* reserve, int mode) {
-    std::lock_guard<std::mutex> lk(g_mode_mu);
-    for (auto& r : g_modes) if (r.p == reserve) { r.mode = mode; return; }
-    g_modes[g_mode_next] = {reserve, mode};
-    g_mode_next = (g_mode_next + 1) % 256;
+// what layer l's input projection (and its dW_ih) reads: x, or the layer below's (dropped) output in the reserve; K = its width
+struct LayerIn { const float* p; int K; };
+LayerIn layer_input(const dep_rnn_desc* d, const Layout& lo, const float* x, const float* R, int l) {
+    if (l == 0) return {x, d->F};
+    return {R + (lo.drop ? lo.ydrop[l - 1] : lo.y[l - 1]), d->dirs * d->H};
 }
-int lookup_reserve_mode(const void* reserve) {
-    std::lock_guard<std::mutex> lk(g_mode_mu);
-    for (auto& r : g_modes) if (r.p == reserve) return r.mode;
-    return -1;
+
+// The tag of the plan whose forward wrote a reserve (host-side record, no device traffic): the recurrent-weight images and saved
+// gates in it are precision-mode specific, and a caller flipping dep_set_gemm_mode between a forward and its backward would
+// otherwise get silently wrong gradients.  Small ring: the newest record of a pointer wins; a reserve with no record (evicted
+// after 256 other forwards) is trusted.
+struct TagRec { const void* p; int tag; };
+TagRec g_tags[256];
+int g_tag_next = 0;
+std::mutex g_tag_mu;
+void record_reserve_tag(const void* reserve, int tag) {
+    std::lock_guard<std::mutex> lk(g_tag_mu);
+    for (auto& r : g_tags) if (r.p == reserve) { r.tag = tag; return; }
+    g_tags[g_tag_next] = {reserve, tag};
+    g_tag_next = (g_tag_next + 1) % 256;
 }
+// dep_rnn_backward: DEP_OK unless the reserve's recorded tag and this call's differ in one of `bits`
+int reserve_tag_refusal(const void* reserve, int want, int bits) {
+    int have = -1;
+    {
+        std::lock_guard<std::mutex> lk(g_tag_mu);
+        for (auto& r : g_tags) if (r.p == reserve) { have = r.tag; break; }
+    }
+    if (have < 0) return DEP_OK;
+    const int diff = (have ^ want) & bits;
+    if (diff & TAG_DONLY)
+        dep_set_error("dep_rnn_backward: the reserve was last written by a DEP_RUN_DROPOUT_ONLY forward, which keeps no saved gates; "
+                      "run the forward with DEP_RUN_TRAIN before a backward");
+    else if (diff & TAG_SPLIT)
+        dep_set_error("dep_rnn_backward: the reserve was produced by a forward in %s mode, the current mode is %s "
+                      "(dep_set_gemm_mode must not change between a forward and its backward)",
+                      (have & TAG_SPLIT) ? "bf16x3" : "f32", (have & TAG_SPLIT) ? "f32" : "bf16x3");
+    else if (diff & TAG_BF16ST)
+        dep_set_error("dep_rnn_backward: the reserve was %swritten in bf16-storage mode (dep_set_gemm_mode(3)), this call runs in the other", (have & TAG_BF16ST) ? "" : "not ");
+    else if (diff & TAG_SV16)
+        dep_set_error("dep_rnn_backward: the reserve holds %s saved gates, this call expects the other format (DEP_SV16 / DEP_EXCLUSIVE changed?)",
+                      (have & TAG_SV16) ? "16-bit" : "fp32");
+    return diff ? DEP_ERR_ARG : DEP_OK;
+}
+
 }  // namespace
 
 extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const float* const* weights, float* y,
@@ -378,6 +458,7 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
                                size_t workspace_bytes, void* stream) {
     Layout lo;
     DEP_CHECK_ARG(make_layout(d, lo));
+    const RnnPlan p = make_plan(d, lo, dep_get_gemm_mode(), dep_exclusive_on());
     DEP_CHECK_ARG(x && weights && reserve && workspace);
     DEP_CHECK_ARG(!(pooled && (d->cell != DEP_CELL_GRU || d->pool == DEP_POOL_NONE)));
     if (reserve_bytes < lo.reserve_floats * sizeof(float) || workspace_bytes < lo.ws_floats * sizeof(float)) {
@@ -391,35 +472,48 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
     const int BTr = (int)lo.BT;
     // the unsplit projections' scratch (the weight's stage image of gemm_bf16x3_nt_dma): the split-K region, idle during the forward
     DepGemmOpts proj; proj.scratch = W + lo.gemm; proj.scratch_bytes = lo.gemm_bytes;
-    const bool mfma = lo.cluster || dep_sweep_use_mfma(H, d->impl);
-    const bool excl = dep_exclusive_on();
-    const bool use16 = lo.cluster16 && excl;                        // the 16-unit-member forward fills the CUs: not on a shared GPU
-    const bool split_fwd = use16 && sweep_split_mode();
-    const bool split_fwd32 = lo.cluster && !use16 && d->cell == DEP_CELL_GRU && sweep_split_mode();     // 32-unit members
-    const bool split_lstm = lo.cluster && d->cell == DEP_CELL_LSTM && sweep_split_mode();
+    float* const gi = W + lo.gi;
     int rc;
     if (lo.cluster) { rc = dep_cluster_reset_status(W + lo.xbuf, s); if (rc) return rc; }
-    // the recurrent-weight images packed below are precision-mode specific: remember which mode this reserve holds
-    // bit 0: precision mode; bit 1: the backward image is the 16-unit-member one (a caller flipping DEP_CLUSTER16_BWD is refused too)
-    const bool sv16 = lo.sv16 && sweep_split_mode();      // (exact-fp32 mode keeps fp32 gates: its 16-unit-member forward has no 16-bit path)
-    if (lo.bf16st && (!excl || y)) {
+    if (p.bf16st && (!p.excl || y)) {
         dep_set_error("dep_rnn_forward: bf16-storage mode (dep_set_gemm_mode(3)) runs the exclusive fused forward only (dep_rnn_set_exclusive(1)) "
                       "and has no fp32 copy of the output sequence (y must be NULL)");
         return DEP_ERR_ARG;
     }
-    // bit 4: a dropout-only forward wrote it -- no saved gates, no backward images: dep_rnn_backward refuses it
-    record_reserve_mode(reserve, (sweep_split_mode() ? 1 : 0) | (sv16 ? 4 : 0) | (lo.bf16st ? 8 : 0) | (lo.donly ? 16 : 0));
+    record_reserve_tag(reserve, p.tag);
     // Dropout-only: where a layer's output sequence goes when the reserve does not keep it.  The cluster BiLSTM sweep and the fused
     // GRU forward take a null pointer (nothing written); the other sweeps read their own output back (h_{t-1}, the pool) and get the
     // workspace's dX region, idle in a forward; the top layer of a pooled GRU writes straight into the caller's y when one is given.
-    float* const yscratch = W + lo.dx[0];
     auto yout = [&](int l, bool null_ok) -> float* {
         if (lo.y[l] != NOT_KEPT) return R + lo.y[l];
         if (l == L - 1 && y) return y;
-        return null_ok ? nullptr : yscratch;
+        return null_ok ? nullptr : W + lo.dx[0];
     };
     const bool ytop_kept = lo.y[L - 1] != NOT_KEPT;
-    if (lo.fused2 && sweep_split_mode() && excl) {
+    const float pool_scale = d->pool == DEP_POOL_MEAN ? 1.0f / (float)T : 1.0f;
+    // layer l's sweep; only_if: as a fallback launch behind the fused one, which runs only when that device word is set
+    auto sweep_args = [&](int l, const unsigned* only_if) {
+        dep_sweep_args a{};
+        a.B = B; a.T = T; a.H = H; a.cell = d->cell; a.dirs = D; a.training = d->training; a.impl = d->impl;
+        a.split = (lo.cluster && p.split) ? 1 : 0;
+        for (int dd = 0; dd < D; ++dd) {
+            const float* const* wl = weights + (size_t)(l * D + dd) * 4;
+            a.w_hh[dd] = wl[1]; a.b_hh[dd] = wl[3]; a.wp[dd] = R + lo.wp[l][dd];
+        }
+        const bool dropl = lo.drop && l < L - 1;
+        a.gi = gi; a.y = yout(l, p.fwd == FWD_CLUSTER_LSTM && dropl); a.ldy = D * H;
+        a.ydrop = dropl ? R + lo.ydrop[l] : nullptr;
+        a.drop_p = dropl ? d->dropout_p : 0.f; a.seed = d->seed; a.site = DEP_SITE_RNN0 + l;
+        a.pooled = l == L - 1 ? pooled : nullptr;
+        a.pool_scale = pool_scale;
+        a.h_n = h_n ? h_n + (size_t)l * D * B * H : nullptr;
+        if (lo.keep) { a.sv0 = R + lo.sv[l][0]; a.sv1 = R + lo.sv[l][1]; a.sv2 = R + lo.sv[l][2]; a.sv3 = R + lo.sv[l][3]; }
+        a.only_if = only_if; a.stream = s; a.sv16 = p.sv16_fwd ? 1 : 0;
+        // one exchange-header slot per layer, all zeroed by the call's one memset; the fused launch has slot 0, its fallbacks 1 + l
+        a.hdr_slot = only_if ? 1 + l : (l < DEP_HDR_SLOTS ? l : 0); a.hdr_clean = only_if || l < DEP_HDR_SLOTS;
+        return a;
+    };
+    if (p.fwd == FWD_FUSED2) {
         // both layers in one launch: layer 1 runs one step behind layer 0 and takes its input straight from the exchanged
         // h0_t (no layer-1 input-projection GEMM, no GI round trip through HBM for it)
         const float* const* w0 = weights; const float* const* w1 = weights + 4;
@@ -428,10 +522,8 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
             const float* srcs[5] = {w0[1], w1[1], w1[0], w0[1], w1[1]};
             float* dsts[5] = {R + lo.wp[0][0], R + lo.wp[1][0], W + lo.wih_img, R + lo.wpT[0][0], R + lo.wpT[1][0]};
             const int kinds[5] = {0, 0, 0, 1, 1};
-            const bool bwd_multi = lo.keep;
-            rc = dep_pack_cluster_split_multi(bwd_multi ? 5 : 3, srcs, dsts, kinds, H, s); if (rc) return rc;
+            rc = dep_pack_cluster_split_multi(p.whh_bwd == WHH_BWD_SPLIT ? 5 : 3, srcs, dsts, kinds, H, s); if (rc) return rc;
         }
-        float* gi = W + lo.gi;
         rc = dep_gemm_internal(0, 1, BTr, G * H, d->F, x, d->F, w0[0], d->F, gi, G * H, w0[2], 0.f, 0, 0, nullptr, 0, proj, s);
         if (rc) return rc;
         dep_fused2_args f{};
@@ -441,12 +533,12 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
         f.ostride = (lo.BT * H + 63) / 64 * 64;
         f.gi = gi; f.y0 = lo.donly ? nullptr : R + lo.y[0]; f.y0d = (lo.drop && !lo.donly) ? R + lo.ydrop[0] : nullptr; f.y1 = yout(1, true);
         f.drop_p = lo.drop ? d->dropout_p : 0.f; f.seed = d->seed; f.site = DEP_SITE_RNN0;
-        f.pooled = pooled; f.pool_scale = d->pool == DEP_POOL_MEAN ? 1.0f / (float)T : 1.0f;
+        f.pooled = pooled; f.pool_scale = pool_scale;
         f.hn0 = h_n; f.hn1 = h_n ? h_n + (size_t)B * H : nullptr;
         for (int l = 0; l < 2; ++l) for (int k = 0; k < 4; ++k) f.sv[l][k] = lo.keep ? R + lo.sv[l][k] : nullptr;
         f.stream = s;
-        f.soft_fallback = lo.bf16st ? 0 : 1;           // (the tolerant per-layer kernels have no bf16-storage variant: a failed hello raises the status)
-        f.sv16 = sv16 ? 1 : 0; f.bf16st = lo.bf16st ? 1 : 0;
+        f.soft_fallback = p.bf16st ? 0 : 1;           // (the tolerant per-layer kernels have no bf16-storage variant: a failed hello raises the status)
+        f.sv16 = p.sv16 ? 1 : 0; f.bf16st = p.bf16st ? 1 : 0;
         f.hdr_clean = 1;                                   // dep_cluster_reset_status above zeroed every header slot
         rc = dep_launch_fused2_fwd(f, W + lo.xbuf, lo.xbuf_bytes); if (rc) return rc;
         // Fallback, decided ON THE DEVICE (no host synchronisation, identical on every data-parallel rank): the launch above
@@ -455,27 +547,14 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
         // at entry unless the flag is set (3 near-empty launches per forward, ~10 us); they write the same reserve layout, so
         // the backward does not care which of the two produced it.
         const unsigned* soft = reinterpret_cast<const unsigned*>(W + lo.xbuf) + 1;
-        for (int l = 0; l < 2 && !lo.bf16st; ++l) {
-            const float* const* wl = l == 0 ? w0 : w1;
+        for (int l = 0; l < 2 && !p.bf16st; ++l) {
             if (l == 1) {
-                const float* in = lo.drop ? R + lo.ydrop[0] : R + lo.y[0];
+                const LayerIn in = layer_input(d, lo, x, R, 1);
                 DepGemmOpts fallback = proj; fallback.only_if = soft;
-                rc = dep_gemm_internal(0, 1, BTr, G * H, H, in, H, wl[0], H, gi, G * H, wl[2], 0.f, 0, 0, nullptr, 0, fallback, s);
+                rc = dep_gemm_internal(0, 1, BTr, G * H, in.K, in.p, in.K, w1[0], in.K, gi, G * H, w1[2], 0.f, 0, 0, nullptr, 0, fallback, s);
                 if (rc) return rc;
             }
-            dep_sweep_args a{};
-            a.B = B; a.T = T; a.H = H; a.cell = d->cell; a.dirs = 1; a.training = d->training; a.impl = d->impl; a.split = 1;
-            a.w_hh[0] = wl[1]; a.b_hh[0] = wl[3]; a.wp[0] = R + lo.wp[l][0];
-            a.gi = gi; a.y = yout(l, false); a.ldy = H;
-            const bool dropl = lo.drop && l == 0;
-            a.ydrop = dropl ? R + lo.ydrop[0] : nullptr;
-            a.drop_p = dropl ? d->dropout_p : 0.f; a.seed = d->seed; a.site = DEP_SITE_RNN0 + l;
-            a.pooled = (l == 1 && pooled) ? pooled : nullptr; a.pool_scale = f.pool_scale;
-            a.h_n = h_n ? h_n + (size_t)l * B * H : nullptr;
-            if (lo.keep) { a.sv0 = R + lo.sv[l][0]; a.sv1 = R + lo.sv[l][1]; a.sv2 = R + lo.sv[l][2]; a.sv3 = R + lo.sv[l][3]; }
-            a.only_if = soft; a.stream = s; a.sv16 = sv16 ? 1 : 0;
-            a.hdr_slot = 1 + l; a.hdr_clean = 1;             // own header slots: still zero from the call's one memset
-            rc = dep_launch_cluster_fwd(a, W + lo.xbuf, lo.xbuf_bytes); if (rc) return rc;
+            rc = dep_launch_cluster_fwd(sweep_args(l, soft), W + lo.xbuf, lo.xbuf_bytes); if (rc) return rc;
         }
         if (y && ytop_kept) { rc = dep_axpby(R + lo.y[1], y, (long)lo.BT * H, 1.f, 0.f, s); if (rc) return rc; }
         return DEP_OK;
@@ -484,7 +563,7 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
         // gather every layer's direction-stacked W_ih and folded bias (b_ih [+ b_hh]) in one launch (16 jobs at a time)
         const float* src[16]; const float* add[16]; float* dst[16]; long cnt[16]; int nj = 0;
         for (int l = 0; l < L; ++l) {
-            const int Kl = l == 0 ? d->F : D * H;
+            const int Kl = layer_input(d, lo, x, R, l).K;
             for (int dd = 0; dd < D; ++dd) {
                 const float* const* wl = weights + (size_t)(l * D + dd) * 4;
                 DEP_CHECK_ARG(wl[0] && wl[1] && wl[2] && wl[3]);
@@ -496,30 +575,23 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
         if (nj) { rc = dep_multi_copy(nj, src, add, dst, cnt, s); if (rc) return rc; }
     }
     for (int l = 0; l < L; ++l) {
-        const float* in = l == 0 ? x : (lo.drop ? R + lo.ydrop[l - 1] : R + lo.y[l - 1]);
-        const int Kl = l == 0 ? d->F : D * H;
-        float* gi = W + lo.gi;
+        const LayerIn in = layer_input(d, lo, x, R, l);
+        const int Kl = in.K;
         const bool stacked = D == 2;                   // both directions' projections as one GEMM over stacked weights
         for (int dd = 0; dd < D; ++dd) {
             const float* const* wl = weights + (size_t)(l * D + dd) * 4;
             DEP_CHECK_ARG(wl[0] && wl[1] && wl[2] && wl[3]);
-            // recurrent weight images in MFMA fragment order (precision / clustering decide the format)
-            if (split_lstm) {
-                rc = dep_pack_cluster_lstm_split(wl[1], R + lo.wp[l][dd], lo.keep ? R + lo.wpT[l][dd] : nullptr, H, s);
-                if (rc) return rc;
-            } else {
-                const bool split_bwd = lo.cluster && d->cell == DEP_CELL_GRU && sweep_split_mode();
-                // the fp32 fragment images are only needed by kernels that are not running on split-precision images
-                const bool need_f32 = mfma && !((split_fwd || split_fwd32) && (split_bwd || !lo.keep));
-                if (need_f32) { rc = dep_pack_whh(wl[1], R + lo.wp[l][dd], lo.donly ? nullptr : R + lo.wpT[l][dd], G, H, s); if (rc) return rc; }
-                if (split_fwd) { rc = dep_pack_cluster16_fwd_split(wl[1], R + lo.wp[l][dd], H, s); if (rc) return rc; }
-                if (split_fwd32) { rc = dep_pack_cluster_fwd_split(wl[1], R + lo.wp[l][dd], H, s); if (rc) return rc; }
-                if (lo.cluster && lo.keep) {         // the cluster backward wants its own member-sliced image
-                    rc = split_bwd ? dep_pack_cluster_bwd_split(wl[1], R + lo.wpT[l][dd], H, s)
-                                   : dep_pack_cluster_bwd(wl[1], R + lo.wpT[l][dd], G, H, s);
-                    if (rc) return rc;
-                }
-            }
+            // recurrent weight images in MFMA fragment order (precision / clustering decide the format: RnnPlan)
+            float* const wp = R + lo.wp[l][dd]; float* const wpT = lo.wpT[l][dd] == NOT_KEPT ? nullptr : R + lo.wpT[l][dd];
+            if (p.whh_f32) { rc = dep_pack_whh(wl[1], wp, wpT, G, H, s); if (rc) return rc; }
+            rc = p.whh_fwd == WHH_LSTM_PAIR ? dep_pack_cluster_lstm_split(wl[1], wp, lo.keep ? wpT : nullptr, H, s)
+               : p.whh_fwd == WHH_SPLIT16 ? dep_pack_cluster16_fwd_split(wl[1], wp, H, s)
+               : p.whh_fwd == WHH_SPLIT32 ? dep_pack_cluster_fwd_split(wl[1], wp, H, s) : DEP_OK;
+            if (rc) return rc;
+            // the cluster backward wants its own member-sliced image
+            rc = p.whh_bwd == WHH_BWD_SPLIT ? dep_pack_cluster_bwd_split(wl[1], wpT, H, s)
+               : p.whh_bwd == WHH_BWD_F32 ? dep_pack_cluster_bwd(wl[1], wpT, G, H, s) : DEP_OK;
+            if (rc) return rc;
             const float* bias = wl[2];
             if (stacked) continue;                     // weights and biases were stacked above; the GEMM follows the loop
             if (d->cell == DEP_CELL_LSTM) {          // both biases fold into the projection
@@ -528,38 +600,20 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
                 rc = dep_axpby(wl[3], tb, (long)G * H, 1.f, 1.f, s); if (rc) return rc;
                 bias = tb;
             }
-            rc = dep_gemm_internal(0, 1, BTr, G * H, Kl, in, Kl, wl[0], Kl, gi + (size_t)dd * G * H, D * G * H, bias,
+            rc = dep_gemm_internal(0, 1, BTr, G * H, Kl, in.p, Kl, wl[0], Kl, gi + (size_t)dd * G * H, D * G * H, bias,
                                    0.f, 0, 0, nullptr, 0, proj, s);
             if (rc) return rc;
             // the bias scratch is reused by the next direction: stream order keeps this safe
         }
         if (stacked) {
-            rc = dep_gemm_internal(0, 1, BTr, D * G * H, Kl, in, Kl, R + lo.wstack[l], Kl, gi, D * G * H, R + lo.bstack[l],
+            rc = dep_gemm_internal(0, 1, BTr, D * G * H, Kl, in.p, Kl, R + lo.wstack[l], Kl, gi, D * G * H, R + lo.bstack[l],
                                    0.f, 0, 0, nullptr, 0, proj, s);
             if (rc) return rc;
         }
-        dep_sweep_args a{};
-        a.B = B; a.T = T; a.H = H; a.cell = d->cell; a.dirs = D; a.training = d->training; a.impl = d->impl;
-        a.split = (split_fwd || split_fwd32 || split_lstm) ? 1 : 0;
-        for (int dd = 0; dd < D; ++dd) {
-            const float* const* wl = weights + (size_t)(l * D + dd) * 4;
-            a.w_hh[dd] = wl[1]; a.b_hh[dd] = wl[3]; a.wp[dd] = R + lo.wp[l][dd];
-        }
-        const bool dropl = lo.drop && l < L - 1;
-        a.gi = gi; a.y = yout(l, lo.cluster && d->cell == DEP_CELL_LSTM && dropl && !use16); a.ldy = D * H;
-        a.ydrop = dropl ? R + lo.ydrop[l] : nullptr;
-        a.drop_p = dropl ? d->dropout_p : 0.f; a.seed = d->seed; a.site = DEP_SITE_RNN0 + l;
-        const bool top = l == L - 1;
-        a.pooled = (top && pooled) ? pooled : nullptr;
-        a.pool_scale = d->pool == DEP_POOL_MEAN ? 1.0f / (float)T : 1.0f;
-        a.h_n = h_n ? h_n + (size_t)l * D * B * H : nullptr;
-        if (lo.keep) { a.sv0 = R + lo.sv[l][0]; a.sv1 = R + lo.sv[l][1]; a.sv2 = R + lo.sv[l][2]; a.sv3 = R + lo.sv[l][3]; }
-        a.stream = s;
-        a.sv16 = (sv16 && lo.cluster && (d->cell == DEP_CELL_LSTM || !use16)) ? 1 : 0;
-        a.hdr_slot = l < DEP_HDR_SLOTS ? l : 0; a.hdr_clean = l < DEP_HDR_SLOTS;      // one header slot per layer, zeroed once per call
-        rc = use16 ? dep_launch_cluster16_fwd(a, W + lo.xbuf, lo.xbuf_bytes)
-           : (lo.cluster && d->cell == DEP_CELL_LSTM) ? dep_launch_cluster_lstm_fwd(a, W + lo.xbuf, lo.xbuf_bytes)
-           : lo.cluster ? dep_launch_cluster_fwd(a, W + lo.xbuf, lo.xbuf_bytes) : dep_launch_sweep_fwd(a);
+        const dep_sweep_args a = sweep_args(l, nullptr);
+        rc = p.fwd == FWD_CLUSTER16 ? dep_launch_cluster16_fwd(a, W + lo.xbuf, lo.xbuf_bytes)
+           : p.fwd == FWD_CLUSTER_LSTM ? dep_launch_cluster_lstm_fwd(a, W + lo.xbuf, lo.xbuf_bytes)
+           : p.fwd == FWD_CLUSTER_GRU ? dep_launch_cluster_fwd(a, W + lo.xbuf, lo.xbuf_bytes) : dep_launch_sweep_fwd(a);
         if (rc) return rc;
     }
     if (y && ytop_kept) {
@@ -569,33 +623,19 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
     return DEP_OK;
 }
 
-// DEP_COMM_OVERLAP=sweep: enqueue a layer's gradient all-reduce as soon as its GEMMs are enqueued (it may then run beside the
-// next layer's backward sweep); default: behind that sweep, beside its GEMMs.
-static bool comm_beside_sweeps() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("DEP_COMM_OVERLAP"); v = (e && e[0] == 's') ? 1 : 0; }
-    return v != 0;
-}
-
 static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float* const* weights, const float* dy,
                              const float* dpooled, const float* dh_n, float* const* dweights, float* dx,
                              void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
                              void* stream, const dep_grad_sync* gs) {
     Layout lo;
     DEP_CHECK_ARG(make_layout(d, lo));
+    const RnnPlan p = make_plan(d, lo, dep_get_gemm_mode(), dep_exclusive_on());
     if (d->training != DEP_RUN_TRAIN) {
         dep_set_error("dep_rnn_backward: the descriptor's run mode is %d; a backward needs a DEP_RUN_TRAIN (1) forward's reserve%s", d->training,
                       d->training == DEP_RUN_DROPOUT_ONLY ? " (DEP_RUN_DROPOUT_ONLY keeps no saved gates)" : "");
         return DEP_ERR_ARG;
     }
-    {
-        const int fm = lookup_reserve_mode(reserve);
-        if (fm >= 0 && (fm & 16)) {
-            dep_set_error("dep_rnn_backward: the reserve was last written by a DEP_RUN_DROPOUT_ONLY forward, which keeps no saved gates; "
-                          "run the forward with DEP_RUN_TRAIN before a backward");
-            return DEP_ERR_ARG;
-        }
-    }
+    int rc = reserve_tag_refusal(reserve, p.tag, TAG_DONLY); if (rc) return rc;
     DEP_CHECK_ARG(x && weights && dweights && reserve && workspace);
     DEP_CHECK_ARG(dy || dpooled || dh_n);
     DEP_CHECK_ARG(!(dpooled && (d->cell != DEP_CELL_GRU || d->pool == DEP_POOL_NONE)));
@@ -603,89 +643,68 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float*
         dep_set_error("dep_rnn_backward: reserve/workspace too small");
         return DEP_ERR_WORKSPACE;
     }
-    if (lo.cluster) {
-        const int fm = lookup_reserve_mode(reserve);
-        if (fm >= 0 && (fm & 1) != (sweep_split_mode() ? 1 : 0)) {
-            dep_set_error("dep_rnn_backward: the reserve was produced by a forward in %s mode, the current mode is %s "
-                          "(dep_set_gemm_mode must not change between a forward and its backward)",
-                          (fm & 1) ? "bf16x3" : "f32", (fm & 1) ? "f32" : "bf16x3");
-            return DEP_ERR_ARG;
-        }
-        if (fm >= 0 && ((fm >> 3) & 1) != (lo.bf16st ? 1 : 0)) {
-            dep_set_error("dep_rnn_backward: the reserve was %swritten in bf16-storage mode (dep_set_gemm_mode(3)), this call runs in the other", (fm & 8) ? "" : "not ");
-            return DEP_ERR_ARG;
-        }
-        if (fm >= 0 && ((fm >> 2) & 1) != ((lo.sv16 && sweep_split_mode()) ? 1 : 0)) {
-            dep_set_error("dep_rnn_backward: the reserve holds %s saved gates, this call expects the other format (DEP_SV16 / DEP_EXCLUSIVE changed?)",
-                          (fm & 4) ? "16-bit" : "fp32");
-            return DEP_ERR_ARG;
-        }
-    }
+    // the cluster kernels must match the images and saved gates dep_rnn_forward left
+    if (lo.cluster) { rc = reserve_tag_refusal(reserve, p.tag, TAG_SPLIT | TAG_BF16ST | TAG_SV16); if (rc) return rc; }
     hipStream_t s = (hipStream_t)stream;
     float* R = (float*)reserve; float* W = (float*)workspace;
     const int B = d->B, T = d->T, H = d->H, D = d->dirs, G = lo.G, L = d->L;
     const int BTr = (int)lo.BT;
+    const bool gru = d->cell == DEP_CELL_GRU;
     void* gws = W + lo.gemm; const size_t gwsb = lo.gemm_bytes;
     // (dX's weight image shares the region with the split-K partials of the contractions enqueued behind it: stream order keeps them apart)
-    int rc;
+    const float pool_scale = d->pool == DEP_POOL_MEAN ? 1.0f / (float)T : 1.0f;
+    const int ldg = p.dg4 ? 4 * H : D * G * H;                  // row stride of the gate-gradient arrays
+    const char* const no_pk = "dep_rnn_backward: bf16-storage mode needs the pre-split gate-gradient path (aligned operands, DEP_DGI_PK not 0, contractions above the split threshold)";
     // The fused two-layer backward (rnn_fused2_bwd.hip; round 5: all-gather form): both layers' BPTT in ONE launch, layer 1's dX -- the gradient
     // entering layer 0 -- formed in-kernel.  It writes the same gate-gradient arrays as the per-layer sweeps (4H-wide rows, PK image when the
     // contractions take it), so everything behind the sweeps -- bias finish, dW GEMMs (paired), layer 0's dX, the gradient ranges -- is the
     // per-layer loop below with the sweep launches and layer 1's dX GEMM left out.  DEP_FUSED2_BWD=1 / 0.
-    static int fused_bwd_on = -1;
-    if (fused_bwd_on < 0) { const char* e = getenv("DEP_FUSED2_BWD"); fused_bwd_on = e ? ((e[0] == '1') ? 1 : 0) : DEP_FUSED2_BWD_DEFAULT; }
-    const bool fused = lo.fused2 && fused_bwd_on && sweep_split_mode() && d->cell == DEP_CELL_GRU && L == 2 && D == 1 && dep_fused2_bwd_fits(B, T);
-    static int pk_env = -1;
-    if (pk_env < 0) { const char* e = getenv("DEP_DGI_PK"); pk_env = (e && e[0] == '0') ? 0 : 1; }
+    const bool fused = p.bwd == BWD_FUSED2;
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    // may layer l's gate gradients be the PK image?  Only when all contractions that read them really run the three-term kernel on its vector path.
-    auto pk_gru_ok = [&](int l, bool has_dxl, const float* dxl_probe) {
-        const float* in = l == 0 ? x : (lo.drop ? R + lo.ydrop[l - 1] : R + lo.y[l - 1]);
-        const int Kl = l == 0 ? d->F : D * H;
-        return pk_env && lo.dg4 && lo.cluster && d->cell == DEP_CELL_GRU && sweep_split_mode() && dep_get_gemm_mode() >= 1 &&
-               (fused || dep_cluster_bwd_pk_ok(H, T)) && (T % 2 == 0) && (BTr % 2 == 0) && (Kl % 4 == 0) && al16(in) && al16(weights[(size_t)l * 4]) &&
-               al16(dweights[(size_t)l * 4]) && al16(dweights[(size_t)l * 4 + 1]) &&
-               dep_gemm_uses_bf16x3(G * H, Kl, BTr, 0) && dep_gemm_uses_bf16x3(3 * H, H, BTr, T) &&
-               (!has_dxl || (dep_gemm_uses_bf16x3(BTr, Kl, G * H, 0) && al16(dxl_probe)));
+    // Round 4: the sweep writes the gate gradients as the PK image (rows (t even, t + 1) = (hi, lo) bf16 pairs of both steps,
+    // gemm_bf16x3.hip) -- the three contractions that read them (dX, dW_ih, dW_hh) then stage them without converting; same
+    // bytes, same bits.  Only when all three really run the three-term kernel on its vector path: may layer l's be?  (dxl: its dX,
+    // if formed.  The BiLSTM cluster sweep -- both directions in one launch, direction-stacked contractions -- takes the same image.)
+    auto pk_ok = [&](int l, const float* dxl) {
+        const LayerIn in = layer_input(d, lo, x, R, l);
+        const int M = D * G * H;
+        bool ok = p.pk && (in.K % 4 == 0) && al16(in.p) &&
+                  (gru ? al16(weights[(size_t)l * 4]) && al16(dweights[(size_t)l * 4]) : lo.wstack[l] != 0 && al16(W + lo.dwstack)) &&
+                  dep_gemm_uses_bf16x3(M, in.K, BTr, 0) && dep_gemm_uses_bf16x3(G * H, H, BTr, T) &&
+                  (!dxl || (dep_gemm_uses_bf16x3(BTr, in.K, M, 0) && al16(dxl)));
+        for (int dd = 0; dd < D && ok; ++dd) ok = al16(dweights[(size_t)(l * D + dd) * 4 + 1]);
+        return ok;
     };
     bool fused_pk = false;
     if (fused) {
         const float* const* w0 = weights; const float* const* w1 = weights + 4;
         float* const* g0 = dweights; float* const* g1 = dweights + 4;
         for (int k = 0; k < 4; ++k) DEP_CHECK_ARG(w0[k] && w1[k] && g0[k] && g1[k]);
-        const bool sv16 = lo.sv16 && sweep_split_mode();
-        fused_pk = sv16 && pk_gru_ok(1, false, nullptr) && pk_gru_ok(0, dx != nullptr, dx);      // one kernel writes both layers: both or neither
+        fused_pk = p.sv16 && pk_ok(1, nullptr) && pk_ok(0, dx);      // one kernel writes both layers: both or neither
         rc = dep_pack_cluster_bwd_split(w1[0], W + lo.wih_img, H, s); if (rc) return rc;
         dep_fused2_bwd_args f{};
         f.B = B; f.T = T;
         f.wh1 = R + lo.wpT[1][0]; f.wi1 = W + lo.wih_img; f.wh0 = R + lo.wpT[0][0];
         f.y1 = R + lo.y[1]; f.y0 = R + lo.y[0]; f.sv1 = R + lo.sv[1][0]; f.sv0 = R + lo.sv[0][0];
         f.svstride = (lo.BT * H + 63) / 64 * 64;
-        f.dy = dy; f.dpooled = dpooled; f.pool_scale = d->pool == DEP_POOL_MEAN ? 1.0f / (float)T : 1.0f;
+        f.dy = dy; f.dpooled = dpooled; f.pool_scale = pool_scale;
         f.dhn1 = dh_n ? dh_n + (size_t)B * H : nullptr; f.dhn0 = dh_n;
         f.drop_p = lo.drop ? d->dropout_p : 0.f; f.seed = d->seed; f.site = DEP_SITE_RNN0;
         f.dgi1 = W + lo.gi; f.dgi0 = W + lo.gi2;
-        f.dghn1 = lo.dg4 ? f.dgi1 + 3 * H : W + lo.dghn; f.dghn0 = lo.dg4 ? f.dgi0 + 3 * H : W + lo.dghn2;
-        f.lddg = lo.dg4 ? 4 * H : 3 * H; f.lddghn = lo.dg4 ? 4 * H : H;
+        f.dghn1 = p.dg4 ? f.dgi1 + 3 * H : W + lo.dghn; f.dghn0 = p.dg4 ? f.dgi0 + 3 * H : W + lo.dghn2;
+        f.lddg = ldg; f.lddghn = p.dg4 ? ldg : H;
         f.dbpart1 = W + lo.dbpart; f.dbpart0 = W + lo.dbpart2; f.dbpart_rows = lo.nwg; f.stream = s;
-        if (lo.bf16st && !fused_pk) {
-            dep_set_error("dep_rnn_backward: bf16-storage mode needs the pre-split gate-gradient path (aligned operands, DEP_DGI_PK not 0, contractions above the split threshold)");
-            return DEP_ERR_ARG;
-        }
-        f.sv16 = sv16 ? 1 : 0; f.dg_pk = fused_pk ? 1 : 0; f.bf16st = lo.bf16st ? 1 : 0;
+        if (p.bf16st && !fused_pk) { dep_set_error(no_pk); return DEP_ERR_ARG; }
+        f.sv16 = p.sv16 ? 1 : 0; f.dg_pk = fused_pk ? 1 : 0; f.bf16st = p.bf16st ? 1 : 0;
         rc = dep_launch_fused2_bwd(f, W + lo.xbuf, lo.xbuf_bytes); if (rc) return rc;
     }
-    float* pending_ptr = nullptr; long pending_n = 0;      // data parallel: a finished layer's gradient range waiting for the next sweep to be enqueued
-    if (lo.cluster && !fused) { rc = dep_cluster_reset_flags(W + lo.xbuf, s); if (rc) return rc; }      // every layer's header slot in one memset (the status words stay)
-    for (int l = L - 1; l >= 0; --l) {
+    // layer l's sweep (fused: not launched, but dep_finish_db and the contractions read where its gate gradients are from the same struct)
+    auto sweep_args = [&](int l, bool pk) {
         const bool top = l == L - 1;
-        const float* in = l == 0 ? x : (lo.drop ? R + lo.ydrop[l - 1] : R + lo.y[l - 1]);
-        const int Kl = l == 0 ? d->F : D * H;
-        float* dgi = (fused && l == 0) ? W + lo.gi2 : W + lo.gi;       // (the fused launch left both layers' gate gradients behind)
+        const bool second = fused && l == 0;                  // (the fused launch left both layers' gate gradients behind)
         dep_sweep_bwd_args a{};
         a.B = B; a.T = T; a.H = H; a.cell = d->cell; a.dirs = D; a.impl = d->impl;
-        // must match the image dep_rnn_forward packed: the precision mode may not change between a forward and its backward
-        a.split = (lo.cluster && sweep_split_mode()) ? 1 : 0;
+        a.split = (lo.cluster && p.split) ? 1 : 0;
         for (int dd = 0; dd < D; ++dd) {
             const float* const* wl = weights + (size_t)(l * D + dd) * 4;
             a.w_hh[dd] = wl[1]; a.wpT[dd] = R + lo.wpT[l][dd];
@@ -695,37 +714,30 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float*
         else { a.dy = W + lo.dx[(l + 1) & 1]; a.drop_p = lo.drop ? d->dropout_p : 0.f; }
         a.lddy = D * H; a.seed = d->seed; a.site = DEP_SITE_RNN0 + l;
         a.dpooled = top ? dpooled : nullptr;
-        a.pool_scale = d->pool == DEP_POOL_MEAN ? 1.0f / (float)T : 1.0f;
+        a.pool_scale = pool_scale;
         a.dh_n = dh_n ? dh_n + (size_t)l * D * B * H : nullptr;
         a.sv0 = R + lo.sv[l][0]; a.sv1 = R + lo.sv[l][1]; a.sv2 = R + lo.sv[l][2]; a.sv3 = R + lo.sv[l][3];
-        const int ldg = lo.dg4 ? 4 * H : D * G * H;                  // row stride of the gate-gradient array
-        float* dghn = lo.dg4 ? dgi + 3 * H : ((fused && l == 0) ? W + lo.dghn2 : W + lo.dghn);
-        a.dgi = dgi; a.dghn = dghn; a.lddg = lo.dg4 ? ldg : 0; a.lddghn = lo.dg4 ? ldg : 0;
-        a.dbpart = (fused && l == 0) ? W + lo.dbpart2 : W + lo.dbpart; a.dbpart_rows = D * lo.nwg; a.stream = s;
+        a.dgi = W + (second ? lo.gi2 : lo.gi);
+        a.dghn = p.dg4 ? a.dgi + 3 * H : W + (second ? lo.dghn2 : lo.dghn);
+        a.lddg = p.dg4 ? ldg : 0; a.lddghn = p.dg4 ? ldg : 0;
+        a.dbpart = W + (second ? lo.dbpart2 : lo.dbpart); a.dbpart_rows = D * lo.nwg; a.stream = s;
         a.hdr_slot = l < DEP_HDR_SLOTS ? l : 0; a.hdr_clean = l < DEP_HDR_SLOTS;
-        // Round 4: the sweep writes the gate gradients as the PK image (rows (t even, t + 1) = (hi, lo) bf16 pairs of both steps,
-        // gemm_bf16x3.hip) -- the three contractions that read them (dX, dW_ih, dW_hh) then stage them without converting; same
-        // bytes, same bits.  Only when all three really run the three-term kernel on its vector path.
-        a.split = (lo.cluster && sweep_split_mode()) ? 1 : 0;
-        float* dxl_probe = l == 0 ? dx : (fused ? nullptr : W + lo.dx[l & 1]);
-        const bool pk_gru = fused ? fused_pk : (a.split && pk_gru_ok(l, dxl_probe != nullptr, dxl_probe));
-        // the BiLSTM cluster sweep (both directions in one launch, direction-stacked contractions): same image, same conditions
-        bool pk_lstm = pk_env && lo.cluster && d->cell == DEP_CELL_LSTM && D == 2 && lo.wstack[l] != 0 && a.split && dep_get_gemm_mode() >= 1 &&
-                       dep_cluster_lstm_bwd_pk_ok(T) && (BTr % 2 == 0) && (Kl % 4 == 0) && al16(in) && al16(W + lo.dwstack) &&
-                       dep_gemm_uses_bf16x3(D * G * H, Kl, BTr, 0) && dep_gemm_uses_bf16x3(4 * H, H, BTr, T) &&
-                       (!dxl_probe || (dep_gemm_uses_bf16x3(BTr, Kl, D * G * H, 0) && al16(dxl_probe)));
-        for (int dd = 0; dd < D && pk_lstm; ++dd) pk_lstm = al16(dweights[(size_t)(l * D + dd) * 4 + 1]);
-        const bool pk = pk_gru || pk_lstm;
-        a.dg_pk = pk ? 1 : 0;
-        if (lo.bf16st && !pk) {
-            dep_set_error("dep_rnn_backward: bf16-storage mode needs the pre-split gate-gradient path (aligned operands, DEP_DGI_PK not 0, contractions above the split threshold)");
-            return DEP_ERR_ARG;
-        }
-        a.bf16st = lo.bf16st ? 1 : 0;
-        a.sv16 = (lo.sv16 && sweep_split_mode() && lo.cluster) ? 1 : 0;
+        a.dg_pk = pk ? 1 : 0; a.bf16st = p.bf16st ? 1 : 0; a.sv16 = p.sv16 ? 1 : 0;
+        return a;
+    };
+    float* pending_ptr = nullptr; long pending_n = 0;      // data parallel: a finished layer's gradient range waiting for the next sweep to be enqueued
+    if (lo.cluster && !fused) { rc = dep_cluster_reset_flags(W + lo.xbuf, s); if (rc) return rc; }      // every layer's header slot in one memset (the status words stay)
+    for (int l = L - 1; l >= 0; --l) {
+        const LayerIn lin = layer_input(d, lo, x, R, l);
+        const float* const in = lin.p; const int Kl = lin.K;
+        float* dxl = l == 0 ? dx : (fused ? nullptr : W + lo.dx[l & 1]);      // (fused: the gradient entering layer 0 never left the chip)
+        const bool pk = fused ? fused_pk : pk_ok(l, dxl);
+        if (p.bf16st && !pk) { dep_set_error(no_pk); return DEP_ERR_ARG; }
+        const dep_sweep_bwd_args a = sweep_args(l, pk);
+        float* const dgi = a.dgi; float* const dghn = a.dghn;
         if (!fused) {
-            rc = (lo.cluster && d->cell == DEP_CELL_LSTM) ? dep_launch_cluster_lstm_bwd(a, W + lo.xbuf, lo.xbuf_bytes)
-               : lo.cluster ? dep_launch_cluster_bwd(a, W + lo.xbuf, lo.xbuf_bytes) : dep_launch_sweep_bwd(a);
+            rc = p.bwd == BWD_CLUSTER_LSTM ? dep_launch_cluster_lstm_bwd(a, W + lo.xbuf, lo.xbuf_bytes)
+               : p.bwd == BWD_CLUSTER_GRU ? dep_launch_cluster_bwd(a, W + lo.xbuf, lo.xbuf_bytes) : dep_launch_sweep_bwd(a);
             if (rc) return rc;
         }
         if (pending_ptr) {
@@ -749,8 +761,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float*
         // image through its hi rows (FMT_PKH) on every stack (the same bf16 values their on-the-fly conversion formed: bit-identical, without the fp32
         // staging path that made cfg3's weight gradients slower in that mode than with three products)
         DepGemmOpts go; go.scratch = gws; go.scratch_bytes = gwsb;
-        if (pk) go.fmt_a = (lo.bf16st || dep_get_gemm_mode() >= 2) ? FMT_PKH : FMT_PK;
-        float* dxl = l == 0 ? dx : (fused ? nullptr : W + lo.dx[l & 1]);      // (fused: the gradient entering layer 0 never left the chip)
+        if (pk) go.fmt_a = p.pk_fmt;
         // dX (B*T, Kl) (+)= dG * W_ih first: it is the only product the next layer's sweep waits for
         const bool stacked = D == 2 && lo.wstack[l] != 0;
         if (dxl && stacked) {
@@ -780,8 +791,8 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float*
         bool paired = false;
         // (the split-K target follows the layer's SHAPE, not whether the pair really runs: the fp32-row path (DEP_DGI_PK=0) and the unpaired path
         // (DEP_DW_PAIR=0) must keep summing in the same order as the pair -- tests/test_presplit_gpu.py holds them bit-identical)
-        const bool pair_layer = d->cell == DEP_CELL_GRU && lo.dg4 && !stacked && D == 1 && Kl == H && dep_get_gemm_mode() == 1 && sweep_split_mode();      // (the other precision modes never pair: they keep the single launches' target)
-        const bool pair_shape = pair_layer && pk_gru && !lo.bf16st;
+        const bool pair_layer = p.dw_pair && Kl == H;
+        const bool pair_shape = pair_layer && pk && !p.bf16st;
         DepGemmOpts dwo = go; dwo.split_target = pair_layer ? 512 : 0;       // the weight gradients below
         if (pair_shape) {
             // Round 5: dW_ih and dW_hh of this layer in ONE launch -- both read the PK gate gradients, [dr | dz] are the same bytes
@@ -793,7 +804,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float*
             paired = pr == 1;
         }
         bool paired_hh = false;
-        if (pk_lstm && stacked && D == 2) {
+        if (pk && !gru) {
             // Round 5: dW_hh of the two directions of a BiLSTM layer (4H x H each: 254 tile-jobs, half of the persistent grid) as ONE paired launch;
             // tiles, K chunks and split-K order per direction are those of the single launches (bit-identical)
             float* const* gf = dweights + (size_t)(l * D) * 4; float* const* gb = dweights + (size_t)(l * D + 1) * 4;
@@ -807,24 +818,24 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float*
             const float* dg = dgi + (size_t)dd * G * H;
             // dW_ih (G*H, Kl) = dG^T * in
             if (!stacked) {
-                DepGemmOpts io = dwo; io.fmt_b = (lo.bf16st && l > 0) ? FMT_BF16 : FMT_F32;       // the layer below's (dropped) output is a bf16 array
+                DepGemmOpts io = dwo; io.fmt_b = (p.bf16st && l > 0) ? FMT_BF16 : FMT_F32;       // the layer below's (dropped) output is a bf16 array
                 rc = dep_gemm_internal(1, 0, G * H, Kl, BTr, dg, ldg, in, Kl, gl[0], Kl, nullptr, 0.f, 0, 0, gws, gwsb, io, s);
                 if (rc) return rc;
             }
-            DepGemmOpts ho = dwo; ho.fmt_b = lo.bf16st ? FMT_BF16 : FMT_F32;          // dW_hh: B = this layer's bf16 output, shifted one step
+            DepGemmOpts ho = dwo; ho.fmt_b = p.bf16st ? FMT_BF16 : FMT_F32;          // dW_hh: B = this layer's bf16 output, shifted one step
             // dW_hh (G*H, H) = dGH^T * h_prev   (h_prev = layer output shifted by one step along the sweep)
             const float* yl = R + lo.y[l] + (size_t)dd * H;
             const int shift = dd == 0 ? -1 : 1;
-            if (d->cell == DEP_CELL_GRU && lo.dg4 && dep_gemm_uses_bf16x3(3 * H, H, BTr, T)) {
+            if (p.dg4 && dep_gemm_uses_bf16x3(3 * H, H, BTr, T)) {
                 // ONE contraction over the 4H-wide rows: op(A) columns [dr | dz] and [dn*r] (the dn block in between is skipped by
                 // the loader).  The separate (H x H) call for the n rows cost 100 us for a third of the (2H x H) call's 165 us work.
                 DepGemmOpts so = ho; so.skip_at = 2 * H; so.skip_by = H;
                 rc = dep_gemm_internal(1, 0, 3 * H, H, BTr, dg, ldg, yl, D * H, gl[1], H, nullptr, 0.f, T, shift, gws, gwsb, so, s);
                 if (rc) return rc;
-            } else if (d->cell == DEP_CELL_GRU) {
+            } else if (gru) {
                 rc = dep_gemm_internal(1, 0, 2 * H, H, BTr, dg, ldg, yl, D * H, gl[1], H, nullptr, 0.f, T, shift, gws, gwsb, ho, s);
                 if (rc) return rc;
-                rc = dep_gemm_internal(1, 0, H, H, BTr, dghn, lo.dg4 ? ldg : H, yl, D * H, gl[1] + (size_t)2 * H * H, H, nullptr,
+                rc = dep_gemm_internal(1, 0, H, H, BTr, dghn, p.dg4 ? ldg : H, yl, D * H, gl[1] + (size_t)2 * H * H, H, nullptr,
                                        0.f, T, shift, gws, gwsb, ho, s);
                 if (rc) return rc;
             } else {
@@ -837,7 +848,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float*
         // so that it travels over xGMI beside that layer's weight-gradient GEMMs and never beside a sweep.  The bottom layer's
         // range has nothing left to hide behind and goes out at once.
         if (gs && gs->comm && gs->range_ptr[l] && gs->range_count[l] > 0) {
-            if (l > 0 && !comm_beside_sweeps() && !fused) { pending_ptr = gs->range_ptr[l]; pending_n = gs->range_count[l]; }
+            if (l > 0 && !dep_rnn_switches().comm_beside_sweeps && !fused) { pending_ptr = gs->range_ptr[l]; pending_n = gs->range_count[l]; }
             else {
                 rc = dep_comm_enqueue_after((dep_comm*)gs->comm, gs->range_ptr[l], gs->range_count[l], s, (hipStream_t)gs->comm_stream);
                 if (rc) return rc;

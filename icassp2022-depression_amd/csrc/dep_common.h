@@ -131,8 +131,16 @@ int dep_gemm_bf16x3_tn_pair_launch(int M, int N, int K, const float* A0, const f
                                    const float* B0, int ldb0, int seq_T0, int shift0, const float* B1, int ldb1, int seq_T1, int shift1,
                                    float* C0, int ldc0, float* C1, int ldc1, const DepGemmOpts& o, int splits, int kchunk, float* part0, float* part1,
                                    hipStream_t s);
-// process-wide: may dep_rnn_forward use kernels that need every CU to themselves (dep_rnn_set_exclusive, include/dep_rnn.h)
-bool dep_exclusive_on();
+// The switches of the RNN call path, read once per process.
+struct RnnSwitches {
+    bool sv16, lstm_sv16;             // DEP_SV16 (default on), DEP_LSTM_SV16 (opt-in, rnn_cluster_lstm.hip): 16-bit saved gates
+    bool fused2, fused2_bwd;          // DEP_FUSED2, DEP_FUSED2_BWD ("1" on, anything else off, unset: DEP_FUSED2_BWD_DEFAULT)
+    bool cluster16, cluster_lstm;     // DEP_CLUSTER16, DEP_CLUSTER_LSTM
+    bool dgi_pk;                      // DEP_DGI_PK: gate gradients as the PK image where the contractions take it
+    bool comm_beside_sweeps;          // DEP_COMM_OVERLAP=sweep
+    bool exclusive;                   // DEP_EXCLUSIVE: initial value (dep_rnn_set_exclusive changes it)
+};
+const RnnSwitches& dep_rnn_switches();
 bool dep_prof_on();
 void dep_prof_begin(int cat, hipStream_t s);
 void dep_prof_end(hipStream_t s);

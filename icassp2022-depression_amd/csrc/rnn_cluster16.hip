@@ -306,9 +306,7 @@ int dep_pack_cluster16_fwd_split(const float* w_hh, float* out, int H, hipStream
 
 // 16-unit members are used when they fit two per CU and the 32-unit clustering would leave CUs sharing nothing:
 bool dep_cluster16_ok(int cell, int H, int B) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("DEP_CLUSTER16"); off = (e && e[0] == '0') ? 1 : 0; }
-    if (off || cell != DEP_CELL_GRU || H != 256) return false;
+    if (!dep_rnn_switches().cluster16 || cell != DEP_CELL_GRU || H != 256) return false;
     (void)B;                                          // any batch: launches cover chunks of at most 512 utterances
     return true;
 }

@@ -1008,10 +1008,8 @@ int dep_pack_cluster_lstm_split(const float* w_hh, float* wp, float* wpT, int H,
 }
 
 bool dep_cluster_lstm_ok(int H, int B, int dirs) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("DEP_CLUSTER_LSTM"); off = (e && e[0] == '0') ? 1 : 0; }
     (void)B; (void)dirs;                               // any batch: the launchers chunk it
-    return !off && H == 128;                           // KCH = 4, NTW = 2, NC = 4 (backward gathers exactly 4 partials)
+    return dep_rnn_switches().cluster_lstm && H == 128;                           // KCH = 4, NTW = 2, NC = 4 (backward gathers exactly 4 partials)
 }
 
 size_t dep_cluster_lstm_xbuf_bytes(int H, int B, int dirs) {
@@ -1067,11 +1065,7 @@ int dep_launch_cluster_lstm_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf
 // OPT-IN (DEP_LSTM_SV16=1): measured at cfg3 it buys 1.5 % on each sweep (1.18 -> 1.16, 1.35 -> 1.33 ms; the BiLSTM sweeps are less
 // byte-bound than the GRU backward), and it moves the text model's parameters after two AdamW steps by up to 8.6e-5 from the reference
 // fixture -- inside the path's 1e-4 bar but outside tests/test_scripts_gpu.py's tighter 7.1e-5 -- so the default keeps fp32 gates.
-bool dep_cluster_lstm_sv16_ok() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("DEP_LSTM_SV16"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v != 0;
-}
+bool dep_cluster_lstm_sv16_ok() { return dep_rnn_switches().lstm_sv16; }
 
 bool dep_cluster_lstm_bwd_pk_ok(int T) { return T % 2 == 0; }
 

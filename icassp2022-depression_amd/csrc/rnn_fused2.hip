@@ -537,9 +537,7 @@ __global__ __launch_bounds__(FTHREADS) void gru2_fwd_fused(FF p) {
 }  // namespace
 
 bool dep_fused2_ok(int cell, int H, int L, int dirs) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("DEP_FUSED2"); off = (e && e[0] == '0') ? 1 : 0; }
-    return !off && cell == DEP_CELL_GRU && H == FH && L == 2 && dirs == 1;
+    return dep_rnn_switches().fused2 && cell == DEP_CELL_GRU && H == FH && L == 2 && dirs == 1;
 }
 
 size_t dep_fused2_xbuf_bytes(int B) {
