@@ -13,9 +13,10 @@
 // bounds it to 256 (one per CU) or 512 (two per CU) workgroups; larger batches run as consecutive chunks of the batch.
 // (The first version of the exchange, 8-byte {epoch, value} granules polled by the consumers, was 2-3x slower than the
 // flag-published payload for the 4096-value reduce-scatter and is no longer kept.)
-#include "rnn_cluster_common.h"
+#include <algorithm>
+#include "rnn_cluster_launch.h"
 
-using depc::BT; using depc::FLAG_OFF; using depc::PAYLOAD_OFF;
+using namespace depc;
 
 namespace {
 
@@ -41,20 +42,24 @@ __global__ void pack_cluster_bwd_kernel(const float* __restrict__ W, float* __re
 // Every member of every cluster of a launch must be resident at the same time (they wait for each other inside the launch),
 // so the number of tiles per launch follows the number of CUs actually present (a partitioned or harvested device has fewer
 // than 256); larger batches run as consecutive chunks.
-static int num_cus() {
-    static int n = -1;
-    if (n < 0) {
-        const char* e = getenv("DEP_NUM_CUS");
+const ClusterSwitches& depc::cluster_switches() {
+    static const ClusterSwitches sw = [] {
+        ClusterSwitches w;
+        const char* e = getenv("DEP_CLUSTER_NOFAST"); w.nofast = (e && e[0] == '1') ? 1 : 0;
+        e = getenv("DEP_TRACE"); w.trace = e && e[0] == '1';
+        e = getenv("DEP_NUM_CUS");
         int dev = 0, v = 0;
-        if (e && atoi(e) > 0) n = atoi(e);
-        else if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
+        if (e && atoi(e) > 0) w.num_cus = atoi(e);
+        else if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) w.num_cus = v;
+        else w.num_cus = 256;
+        e = getenv("DEP_FORCE_SOFT_FALLBACK"); w.force_soft = (e && e[0] >= '1' && e[0] <= '3') ? e[0] - '0' : 0;
+        return w;
+    }();
+    return sw;
 }
 
 int dep_cluster_chunk(int members, int per_cu, int max_wgs) {
-    long wgs = (long)num_cus() * per_cu;
+    long wgs = (long)cluster_switches().num_cus * per_cu;
     if (wgs > max_wgs) wgs = max_wgs;
     long tiles = wgs / members;
     if (tiles >= 8) tiles = tiles / 8 * 8;             // whole groups of 8 tiles: block id -> XCD stays member-invariant
@@ -62,17 +67,20 @@ int dep_cluster_chunk(int members, int per_cu, int max_wgs) {
     return (int)tiles * BT;
 }
 
-bool dep_cluster_ok(int cell, int H, int B, int dirs) {
-    (void)B; (void)dirs;                              // any batch: the launchers chunk it
+bool dep_cluster_ok(int cell, int H, int, int) {      // any batch: the launchers chunk it
     return cell == DEP_CELL_GRU && (H == 64 || H == 128 || H == 256 || H == 512);     // KCH = H/32 in {2,4,8,16}; NTW = H/64 in {1,2,4,8}
 }
 
-// header + the largest (backward) exchange of one launch chunk
+// headers + the exchange of one launch chunk, for the three launchers that use the buffer.  What is returned is 8192 bytes plus TWICE
+// the backward's payload: the 8192 are left from the 16 KiB the function put in front of the payload before the header slots came, and
+// no launcher uses the factor 2 -- both are slack, kept because the number is visible through dep_rnn_workspace_bytes.  The max with
+// the forwards' payloads never binds (both member sizes cut the batch into the same chunks, and the doubled backward payload is
+// 2 * NC times a forward's); it is there to show that the buffer covers the 16-unit-member forward too.
 size_t dep_cluster_xbuf_bytes(int cell, int H, int B, int dirs) {
     if (!dep_cluster_ok(cell, H, B, dirs)) return 0;
-    const int NC = H / 32, CH = dep_cluster_chunk(NC, 1, 256);
-    const int nbtp = (dep_cdiv(B < CH ? B : CH, BT) + 7) / 8 * 8;
-    return PAYLOAD_OFF + 8192 + (size_t)2 * nbtp * NC * BT * H * sizeof(float) * 2;
+    const ChunkGeometry g32 = gru32_geometry(H, B), g16 = gru16_geometry(H, B);
+    const size_t fwd = std::max(gru_fwd_payload_bytes(g32, H), gru_fwd_payload_bytes(g16, H));
+    return PAYLOAD_OFF + std::max(fwd, 8192 + 2 * gru_bwd_payload_bytes(g32, H));
 }
 
 // The status word (first 256 bytes of the exchange buffer header, see rnn_cluster_common.h) is raised by any sweep whose

@@ -9,7 +9,7 @@
 //   backward: K = 48 (the member's 3x16 gate rows) x all H output columns (4 tiles per wave), partial dh published
 //             in fragment order (16 KB), each thread sums its column over the NC partials in member order.
 // Exchange protocol, same-XCD fast path, parity double-buffering, bounded spins: identical to rnn_cluster_bwd.hip.
-#include "rnn_cluster_common.h"
+#include "rnn_cluster_launch.h"
 
 namespace {
 using namespace depc;
@@ -274,9 +274,10 @@ __global__ __launch_bounds__(CT + 64, 4) void gru_fwd_cluster16(F16 p) {
 // split-precision forward image (see gru_fwd_cluster16<., true>): 16-byte piece
 //   [((((c*3 + g)*4 + w)*KS2 + ks)*2 + plane)*64 + lane]  =  bf16 plane (0 hi, 1 lo) of
 //   W[(g*H + 16c + (lane&15)) * H + 64w + 32ks + 8(lane>>4) + 0..7]          (KS2 = H/128 k-steps of 32 per wave)
+__host__ __device__ inline long pack16_fwd_pieces(int H) { const int KS2 = H / 128; return (long)(H / 16) * 3 * 4 * KS2 * 64; }
 __global__ void pack_cluster16_fwd_split_kernel(const float* __restrict__ W, u32x4* __restrict__ out, int H) {
     const int KS2 = H / 128;
-    const long n = (long)(H / 16) * 3 * 4 * KS2 * 64;
+    const long n = pack16_fwd_pieces(H);
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
     const int lane = idx & 63; long r = idx >> 6;
@@ -295,27 +296,32 @@ __global__ void pack_cluster16_fwd_split_kernel(const float* __restrict__ W, u32
     out[(idx - lane) * 2 + 64 + lane] = lo;
 }
 
+// the launchable instances (H = 256: KCQ = 4); below the default dynamic-LDS limit, so no attribute is asked for
+Instance<F16>& fwd16_instance(bool split) {
+    constexpr size_t LDS = (size_t)(BT * (256 + 8) + 4 * 3 * RED_BLK + 2 * 768 + 2 * 1280 + 64) * sizeof(float);
+    static_assert(LDS <= DEFAULT_DYNAMIC_LDS, "two members per CU: each well below half of the CU's LDS");
+    static Instance<F16> split3 DEP_INSTANCE((gru_fwd_cluster16<4, true>), LDS), exact DEP_INSTANCE((gru_fwd_cluster16<4, false>), LDS);
+    return split ? split3 : exact;
+}
+
 }  // namespace
 
 int dep_pack_cluster16_fwd_split(const float* w_hh, float* out, int H, hipStream_t s) {
-    const long n = (long)(H / 16) * 3 * 4 * (H / 128) * 64;
-    DEP_LAUNCH(pack_cluster16_fwd_split_kernel, dim3(dep_cdiv(n, 256)), dim3(256), 0, s, w_hh, (u32x4*)out, H);
+    DEP_LAUNCH(pack_cluster16_fwd_split_kernel, dim3(dep_cdiv(pack16_fwd_pieces(H), 256)), dim3(256), 0, s, w_hh, (u32x4*)out, H);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }
 
 // 16-unit members are used when they fit two per CU and the 32-unit clustering would leave CUs sharing nothing:
-bool dep_cluster16_ok(int cell, int H, int B) {
-    if (!dep_rnn_switches().cluster16 || cell != DEP_CELL_GRU || H != 256) return false;
-    (void)B;                                          // any batch: launches cover chunks of at most 512 utterances
-    return true;
+bool dep_cluster16_ok(int cell, int H, int) {      // any batch: launches cover chunks of at most 512 utterances
+    return dep_rnn_switches().cluster16 && cell == DEP_CELL_GRU && H == 256;
 }
 
 int dep_launch_cluster16_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf_bytes) {
     // co-residency bounds a launch to two workgroups per CU (512 = 32 tiles = 512 utterances on a full MI355X); larger
     // batches run chunk after chunk
-    const int NC = a.H / 16, CH = dep_cluster_chunk(NC, 2, 512);
-    const int nbtp_max = (dep_cdiv(a.B < CH ? a.B : CH, BT) + 7) / 8 * 8;
+    DEP_CHECK_ARG(a.H == 256);
+    const ChunkGeometry g = gru16_geometry(a.H, a.B);
     F16 p{};
     p.B = a.B; p.T = a.T; p.H = a.H;
     p.wp = (const f32x4*)a.wp[0]; p.b_hh = a.b_hh[0];
@@ -324,21 +330,10 @@ int dep_launch_cluster16_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf_by
     p.drop_p = a.drop_p; p.drop_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f; p.seed = a.seed; p.site = a.site;
     p.pooled = a.pooled; p.pool_scale = a.pool_scale; p.h_n = a.h_n;
     p.sv0 = a.training ? a.sv0 : nullptr; p.sv1 = a.sv1; p.sv2 = a.sv2; p.sv3 = a.sv3;
-    const size_t pay = (size_t)2 * nbtp_max * BT * a.H * sizeof(float);
-    DEP_CHECK_ARG(xbuf && PAYLOAD_OFF + pay <= xbuf_bytes && (size_t)nbtp_max * NC <= 512);
-    p.status = (unsigned*)xbuf; p.flags = (unsigned*)(hdr_base(xbuf, 0) + FLAG_OFF); p.hello = (unsigned*)(hdr_base(xbuf, 0) + HELLO_OFF);
-    p.payload = (float*)((char*)xbuf + PAYLOAD_OFF); p.payload_bytes = (unsigned)pay; p.nofast = nofast_env();
-    p.trace = trace_env() ? (long long*)(hdr_base(xbuf, 0) + TRACE_OFF) : nullptr;
+    const size_t pay = gru_fwd_payload_bytes(g, a.H);
+    DEP_CHECK_ARG(xbuf && PAYLOAD_OFF + pay <= xbuf_bytes && g.resident());
+    p.flags = bind_exchange(p, xbuf, 0, pay);
     DepProfScope prof(DEP_PROF_GRU_FWD, a.stream);
-    const size_t lds = (size_t)(BT * (a.H + 8) + 4 * 3 * RED_BLK + 2 * 768 + 2 * 1280 + 64) * sizeof(float);
-    for (int b0 = 0; b0 < a.B; b0 += CH) {
-        const int cb = a.B - b0 < CH ? a.B - b0 : CH;
-        p.b0 = b0; p.nbtp = (dep_cdiv(cb, BT) + 7) / 8 * 8;
-        // flags / hello words only: the status word is sticky over every sweep of a step (cleared by dep_rnn_forward)
-        { const int rc_h = hdr_prepare(xbuf, 0, false, a.stream); if (rc_h) return rc_h; }
-        if (a.split) DEP_LAUNCH((gru_fwd_cluster16<4, true>), dim3(NC * p.nbtp), dim3(CT + 64), lds, a.stream, p);
-        else DEP_LAUNCH((gru_fwd_cluster16<4, false>), dim3(NC * p.nbtp), dim3(CT + 64), lds, a.stream, p);
-        DEP_CHECK_LAUNCH();
-    }
-    return DEP_OK;
+    return launch_chunks(fwd16_instance(a.split), g, dim3(CT + 64), p, a.stream, __PRETTY_FUNCTION__,
+                         [&](int) { return hdr_prepare(xbuf, 0, false, a.stream); });
 }

@@ -9,7 +9,7 @@
 // member's flag word; consumers poll the NC flags with relaxed agent-scope loads (>= epoch: flags only grow)
 // and then read their two columns of every member's partial with sc1 loads, summing in member order
 // (deterministic).  Payload buffers alternate by step parity; only the status/flag words are zeroed per launch.
-#include "rnn_cluster_common.h"
+#include "rnn_cluster_launch.h"
 
 namespace {
 using namespace depc;
@@ -858,45 +858,18 @@ __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
     }
 }
 
-// split-precision backward image (gru_bwd_cluster_r1<., true>): 16-byte piece
-//   [(((c*(H/16) + jt)*3 + ks)*2 + plane)*64 + lane] = bf16 plane (0 hi, 1 lo) of
-//   W[(ks*H + 32c + 8(lane>>4) + e) * H + jt*16 + (lane&15)],  e = 0..7     (k-step ks = gate, 32 units of member c)
+// split-precision images (rnn_cluster_common.h), G = 3
 __global__ void pack_cluster_bwd_split_kernel(const float* __restrict__ W, u32x4* __restrict__ out, int H) {
-    const long n = (long)(H / 32) * (H / 16) * 3 * 64;
+    const long n = pack_bwd_split_pieces(3, H);
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
-    const int lane = idx & 63; long r = idx >> 6;
-    const int ks = r % 3; r /= 3;
-    const int jt = r % (H / 16); const int c = r / (H / 16);
-    const float* src = W + (size_t)(ks * H + 32 * c + 8 * (lane >> 4)) * H + jt * 16 + (lane & 15);
-    u32x4 hi, lo;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        unsigned h, l;
-        split_pair(src[(size_t)(2 * e) * H], src[(size_t)(2 * e + 1) * H], h, l);
-        hi[e] = h; lo[e] = l;
-    }
-    out[(idx - lane) * 2 + lane] = hi;
-    out[(idx - lane) * 2 + 64 + lane] = lo;
+    pack_bwd_split_piece<3>(W, out, H, idx);
 }
-
-// split-precision forward image of the 32-unit-member kernel (gru_fwd_cluster_r1<., true>): 16-byte piece
-//   [((((jt*3 + g)*2 + kh)*KS2 + ks)*2 + plane)*64 + lane] = bf16 plane of W[(g*H + jt*16 + (lane&15))*H + kh*(H/2) + 32ks + 8(lane>>4) + 0..7]
 __global__ void pack_cluster_fwd_split_kernel(const float* __restrict__ W, u32x4* __restrict__ out, int H) {
-    const int KS2 = H / 64;
-    const long n = (long)(H / 16) * 3 * 2 * KS2 * 64;
+    const long n = pack_fwd_split_pieces(3, H);
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
-    const int lane = idx & 63; long r = idx >> 6;
-    const int ks = r % KS2; r /= KS2;
-    const int kh = r % 2; r /= 2;
-    const int g = r % 3; const int jt = r / 3;
-    const float* src = W + (size_t)(g * H + jt * 16 + (lane & 15)) * H + kh * (H / 2) + 32 * ks + 8 * (lane >> 4);
-    u32x4 hi, lo;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { unsigned h, l; split_pair(src[2 * e], src[2 * e + 1], h, l); hi[e] = h; lo[e] = l; }
-    out[(idx - lane) * 2 + lane] = hi;
-    out[(idx - lane) * 2 + 64 + lane] = lo;
+    pack_fwd_split_piece<3>(W, out, H, idx);
 }
 
 // all split-precision images of a step in ONE launch (blockIdx.y = job): five ~4.5 us launches per training step otherwise
@@ -907,34 +880,52 @@ __global__ void pack_cluster_split_multi_kernel(PackJobs j, int H) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const float* W = j.src[k]; u32x4* out = j.dst[k];
     if (j.bwd[k]) {
-        const long n = (long)(H / 32) * (H / 16) * 3 * 64;
-        if (idx >= n) return;
-        const int lane = idx & 63; long r = idx >> 6;
-        const int ks = r % 3; r /= 3;
-        const int jt = r % (H / 16); const int c = r / (H / 16);
-        const float* src = W + (size_t)(ks * H + 32 * c + 8 * (lane >> 4)) * H + jt * 16 + (lane & 15);
-        u32x4 hi, lo;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { unsigned h, l; split_pair(src[(size_t)(2 * e) * H], src[(size_t)(2 * e + 1) * H], h, l); hi[e] = h; lo[e] = l; }
-        out[(idx - lane) * 2 + lane] = hi;
-        out[(idx - lane) * 2 + 64 + lane] = lo;
+        if (idx >= pack_bwd_split_pieces(3, H)) return;
+        pack_bwd_split_piece<3>(W, out, H, idx);
     } else {
-        const int KS2 = H / 64;
-        const long n = (long)(H / 16) * 3 * 2 * KS2 * 64;
-        if (idx >= n) return;
-        const int lane = idx & 63; long r = idx >> 6;
-        const int ks = r % KS2; r /= KS2;
-        const int kh = r % 2; r /= 2;
-        const int g = r % 3; const int jt = r / 3;
-        const float* src = W + (size_t)(g * H + jt * 16 + (lane & 15)) * H + kh * (H / 2) + 32 * ks + 8 * (lane >> 4);
-        u32x4 hi, lo;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { unsigned h, l; split_pair(src[2 * e], src[2 * e + 1], h, l); hi[e] = h; lo[e] = l; }
-        out[(idx - lane) * 2 + lane] = hi;
-        out[(idx - lane) * 2 + 64 + lane] = lo;
+        if (idx >= pack_fwd_split_pieces(3, H)) return;
+        pack_fwd_split_piece<3>(W, out, H, idx);
     }
 }
 
+// ---- the launchable instances.  Every one asks for more than half of the CU's 160 KiB LDS: the dispatcher can then never co-locate
+// two members on one CU (they would share the four matrix pipes and stretch every step of BOTH clusters).
+Instance<F2>& fwd_instance(int H, bool split) {      // KCH = H / 32; exact fp32 | split products
+    static Instance<F2> rows[4][2] = {
+        { DEP_INSTANCE((gru_fwd_cluster_r1<2, false>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<2, true>), EXCLUSIVE_LDS) },
+        { DEP_INSTANCE((gru_fwd_cluster_r1<4, false>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<4, true>), EXCLUSIVE_LDS) },
+        { DEP_INSTANCE((gru_fwd_cluster_r1<8, false>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<8, true>), EXCLUSIVE_LDS) },
+        { DEP_INSTANCE((gru_fwd_cluster_r1<16, false>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<16, true>), EXCLUSIVE_LDS) } };
+    return rows[H == 64 ? 0 : H == 128 ? 1 : H == 256 ? 2 : 3][split];
+}
+
+// NTW = H / 64.  Burst length 4 up to H = 256; H = 512 keeps the round-1 schedule (KB = 0): 192 weight registers per
+// compute wave leave no room for a second wave per SIMD.  H = 256 with split products: the all-gather exchange of the members' gate
+// gradients (round 5); every other shape / the exact-fp32 mode: the reduce-scatter of fp32 partial dh.  The last 2048 bytes of a
+// launch's LDS hold the trace stamps.
+constexpr int bwd_burst(int H) { return H >= 512 ? 0 : 4; }
+Instance<P2>& bwd_instance(int H, bool split, bool sv16, bool bf16st) {
+    constexpr size_t R1 = EXCLUSIVE_LDS + 2048, AG = burst_lds_bytes_ag(4) + 2048;
+    constexpr size_t BURST = (burst_lds_bytes(4) > EXCLUSIVE_LDS ? burst_lds_bytes(4) : EXCLUSIVE_LDS) + 2048;
+    // per H: exact fp32 | split products, 16-bit saved gates | split products
+    static Instance<P2> h64[3] = { DEP_INSTANCE((gru_bwd_cluster_r1<1, false, 4, false>), BURST), DEP_INSTANCE((gru_bwd_cluster_r1<1, true, 4, true>), BURST),
+                                   DEP_INSTANCE((gru_bwd_cluster_r1<1, true, 4, false>), BURST) };
+    static Instance<P2> h128[3] = { DEP_INSTANCE((gru_bwd_cluster_r1<2, false, 4, false>), BURST), DEP_INSTANCE((gru_bwd_cluster_r1<2, true, 4, true>), BURST),
+                                    DEP_INSTANCE((gru_bwd_cluster_r1<2, true, 4, false>), BURST) };
+    static Instance<P2> h256_exact DEP_INSTANCE((gru_bwd_cluster_r1<4, false, 4, false>), BURST);
+    static Instance<P2> h512[3] = { DEP_INSTANCE((gru_bwd_cluster_r1<8, false, 0>), R1), DEP_INSTANCE((gru_bwd_cluster_r1<8, true, 0, true>), R1),
+                                    DEP_INSTANCE((gru_bwd_cluster_r1<8, true, 0>), R1) };
+    // H = 256, split products (all-gather): fp32 saved gates | 16-bit saved gates | 16-bit saved gates and bf16 storage
+    static Instance<P2> h256_ag[3] = { DEP_INSTANCE((gru_bwd_cluster_r1<4, true, 4, false, false, true>), AG), DEP_INSTANCE((gru_bwd_cluster_r1<4, true, 4, true, false, true>), AG),
+                                       DEP_INSTANCE((gru_bwd_cluster_r1<4, true, 4, true, true, true>), AG) };
+    const int form = !split ? 0 : sv16 ? 1 : 2;
+    switch (H) {
+        case 64: return h64[form];
+        case 128: return h128[form];
+        case 256: return !split ? h256_exact : h256_ag[bf16st ? 2 : sv16 ? 1 : 0];
+        default: return h512[form];
+    }
+}
 }  // namespace
 
 // (H x 3H recurrent / input weight) -> forward (bwd[k] = 0) or backward (1) split image, up to 8 jobs in one launch
@@ -943,30 +934,27 @@ int dep_pack_cluster_split_multi(int n, const float* const* src, float* const* d
     PackJobs j{};
     j.n = n;
     for (int k = 0; k < n; ++k) { DEP_CHECK_ARG(src[k] && dst[k]); j.src[k] = src[k]; j.dst[k] = (u32x4*)dst[k]; j.bwd[k] = bwd[k]; }
-    const long nf = (long)(H / 16) * 3 * 2 * (H / 64) * 64, nb = (long)(H / 32) * (H / 16) * 3 * 64;
+    const long nf = pack_fwd_split_pieces(3, H), nb = pack_bwd_split_pieces(3, H);
     DEP_LAUNCH(pack_cluster_split_multi_kernel, dim3(dep_cdiv(nf > nb ? nf : nb, 256), n), dim3(256), 0, s, j, H);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }
 
 int dep_pack_cluster_fwd_split(const float* w_hh, float* out, int H, hipStream_t s) {
-    const long n = (long)(H / 16) * 3 * 2 * (H / 64) * 64;
-    DEP_LAUNCH(pack_cluster_fwd_split_kernel, dim3(dep_cdiv(n, 256)), dim3(256), 0, s, w_hh, (u32x4*)out, H);
+    DEP_LAUNCH(pack_cluster_fwd_split_kernel, dim3(dep_cdiv(pack_fwd_split_pieces(3, H), 256)), dim3(256), 0, s, w_hh, (u32x4*)out, H);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }
 
 int dep_pack_cluster_bwd_split(const float* w_hh, float* out, int H, hipStream_t s) {
-    const long n = (long)(H / 32) * (H / 16) * 3 * 64;
-    DEP_LAUNCH(pack_cluster_bwd_split_kernel, dim3(dep_cdiv(n, 256)), dim3(256), 0, s, w_hh, (u32x4*)out, H);
+    DEP_LAUNCH(pack_cluster_bwd_split_kernel, dim3(dep_cdiv(pack_bwd_split_pieces(3, H), 256)), dim3(256), 0, s, w_hh, (u32x4*)out, H);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }
 
 int dep_launch_cluster_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf_bytes) {
     DEP_CHECK_ARG(dep_cluster_ok(a.cell, a.H, a.B, a.dirs) && xbuf && xbuf_bytes >= dep_cluster_xbuf_bytes(a.cell, a.H, a.B, a.dirs));
-    const int NC = a.H / 32, CH = dep_cluster_chunk(NC, 1, 256);      // one workgroup per CU: 256 / NC tiles per launch, larger batches in chunks
-    const int nbtp_max = (dep_cdiv(a.B < CH ? a.B : CH, BT) + 7) / 8 * 8;
+    const ChunkGeometry g = gru32_geometry(a.H, a.B);      // one workgroup per CU: 256 / NC tiles per launch, larger batches in chunks
     F2 p{};
     p.B = a.B; p.T = a.T; p.H = a.H;
     p.wp = (const f32x4*)a.wp[0]; p.b_hh = a.b_hh[0];
@@ -975,54 +963,23 @@ int dep_launch_cluster_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf_byte
     p.drop_p = a.drop_p; p.drop_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f; p.seed = a.seed; p.site = a.site;
     p.pooled = a.pooled; p.pool_scale = a.pool_scale; p.h_n = a.h_n;
     p.sv0 = a.training ? a.sv0 : nullptr; p.sv1 = a.sv1; p.sv2 = a.sv2; p.sv3 = a.sv3;
-    const size_t pay = (size_t)2 * nbtp_max * BT * a.H * sizeof(float);
-    DEP_CHECK_ARG(PAYLOAD_OFF + pay <= xbuf_bytes && (size_t)nbtp_max * NC <= 256);
-    p.status = (unsigned*)xbuf; p.flags = (unsigned*)(hdr_base(xbuf, a.hdr_slot) + FLAG_OFF); p.hello = (unsigned*)(hdr_base(xbuf, a.hdr_slot) + HELLO_OFF);
-    p.nofast = nofast_env();
-    p.payload = (float*)((char*)xbuf + PAYLOAD_OFF); p.payload_bytes = (unsigned)pay;
-    p.trace = trace_env() ? (long long*)(hdr_base(xbuf, a.hdr_slot) + TRACE_OFF) : nullptr;
+    const size_t pay = gru_fwd_payload_bytes(g, a.H);
+    DEP_CHECK_ARG(PAYLOAD_OFF + pay <= xbuf_bytes && g.resident());
+    p.flags = bind_exchange(p, xbuf, a.hdr_slot, pay);
     p.only_if = a.only_if; p.sv16 = a.training ? a.sv16 : 0;
     DepProfScope prof(DEP_PROF_GRU_FWD, a.stream, a.only_if == nullptr);      // a conditional fallback launch is not a sweep of the step
-    // Ask for more than half of the CU's 160 KiB LDS: the dispatcher can then never co-locate two members on one
-    // CU (they would share the four matrix pipes and stretch every step of BOTH clusters).
-    const size_t lds = EXCLUSIVE_LDS;
-    static bool attr_f = false;
-    if (!attr_f) {
-#define DEP_FWD_ATTR(K) (void)hipFuncSetAttribute((const void*)gru_fwd_cluster_r1<K, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                        (void)hipFuncSetAttribute((const void*)gru_fwd_cluster_r1<K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-        DEP_FWD_ATTR(2); DEP_FWD_ATTR(4); DEP_FWD_ATTR(8); DEP_FWD_ATTR(16);
-#undef DEP_FWD_ATTR
-        attr_f = true;
-    }
-    for (int b0 = 0; b0 < a.B; b0 += CH) {
-        const int cb = a.B - b0 < CH ? a.B - b0 : CH;
-        p.b0 = b0; p.nbtp = (dep_cdiv(cb, BT) + 7) / 8 * 8;
-        // flags / hello words only: the status word is sticky over every sweep of a step (cleared by dep_rnn_forward)
-        { const int rc_h = hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); if (rc_h) return rc_h; }
-        dim3 grid(NC * p.nbtp);
-#define DEP_FWD_LAUNCH(K)                                                                                                 \
-        do { if (a.split) DEP_LAUNCH((gru_fwd_cluster_r1<K, true>), grid, dim3(CT), lds, a.stream, p);            \
-             else DEP_LAUNCH((gru_fwd_cluster_r1<K, false>), grid, dim3(CT), lds, a.stream, p); } while (0)
-        switch (a.H) {                                // KCH = H / 32
-            case 64: DEP_FWD_LAUNCH(2); break;
-            case 128: DEP_FWD_LAUNCH(4); break;
-            case 256: DEP_FWD_LAUNCH(8); break;
-            default: DEP_FWD_LAUNCH(16); break;       // 512
-        }
-#undef DEP_FWD_LAUNCH
-        DEP_CHECK_LAUNCH();
-    }
-    return DEP_OK;
+    return launch_chunks(fwd_instance(a.H, a.split), g, dim3(CT), p, a.stream, __PRETTY_FUNCTION__,
+                         [&](int b0) { return hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); });
 }
 
 // May dep_launch_cluster_bwd write the gate gradients as the PK image (dep_sweep_bwd_args.dg_pk)?  Needs the burst-stream kernel
-// (its service waves' flush forms the pairs): H <= 256, bursts not switched off, not the two-per-CU placement experiment.
+// (its service waves' flush forms the pairs), i.e. H <= 256, and whole step pairs.
 bool dep_cluster_bwd_pk_ok(int H, int T) { return H <= 256 && T % 2 == 0; }
 
 int dep_launch_cluster_bwd(const dep_sweep_bwd_args& a, void* xbuf, size_t xbuf_bytes) {
     DEP_CHECK_ARG(dep_cluster_ok(a.cell, a.H, a.B, a.dirs) && xbuf && xbuf_bytes >= dep_cluster_xbuf_bytes(a.cell, a.H, a.B, a.dirs));
-    const int NC = a.H / 32, CH = dep_cluster_chunk(NC, 1, 256), nbt = dep_cdiv(a.B, BT);
-    const int nbtp_max = (dep_cdiv(a.B < CH ? a.B : CH, BT) + 7) / 8 * 8;
+    const ChunkGeometry g = gru32_geometry(a.H, a.B);
+    const int nbt = dep_cdiv(a.B, BT);
     P2 p{};
     p.B = a.B; p.T = a.T; p.H = a.H;
     p.wp = (const f32x4*)a.wpT[0];
@@ -1036,69 +993,21 @@ int dep_launch_cluster_bwd(const dep_sweep_bwd_args& a, void* xbuf, size_t xbuf_
     DEP_CHECK_ARG(!a.sv16 || a.split);               // the 16-bit saved gates exist in split-precision mode only
     DEP_CHECK_ARG(!a.bf16st || (a.H == 256 && a.split && a.sv16 && a.dg_pk));      // bf16-storage mode: H = 256, burst kernel (checked below via dg_pk)
     DEP_CHECK_ARG(a.dbpart_rows >= nbt);
-    const size_t pay = (size_t)2 * nbtp_max * NC * BT * a.H * sizeof(float);
-    DEP_CHECK_ARG(PAYLOAD_OFF + pay <= xbuf_bytes && (size_t)nbtp_max * NC <= 256);
-    p.status = (unsigned*)xbuf; p.flags = (unsigned*)(hdr_base(xbuf, a.hdr_slot) + FLAG_OFF); p.hello = (unsigned*)(hdr_base(xbuf, a.hdr_slot) + HELLO_OFF);
-    p.nofast = nofast_env();
-    p.payload = (float*)((char*)xbuf + PAYLOAD_OFF); p.payload_bytes = (unsigned)pay;
-    p.trace = trace_env() ? (long long*)(hdr_base(xbuf, a.hdr_slot) + TRACE_OFF) : nullptr;
+    const size_t pay = gru_bwd_payload_bytes(g, a.H);
+    DEP_CHECK_ARG(PAYLOAD_OFF + pay <= xbuf_bytes && g.resident());
+    p.flags = bind_exchange(p, xbuf, a.hdr_slot, pay);
     DepProfScope prof(DEP_PROF_GRU_BWD, a.stream);
-    // burst length 4 (the round-1 schedule KB = 0 serves H = 512 only), per-wave epoch flags, non-temporal one-touch streams:
-    // the measured winners of rounds 2-5 (profiles/r04_ab_pairs.txt, r05_final_ab_switches.txt); the losers live in the git history
+    // per-wave epoch flags, non-temporal one-touch streams: the measured winners of rounds 2-5 (profiles/r04_ab_pairs.txt,
+    // r05_final_ab_switches.txt); the losers live in the git history
     p.wflags = 1; p.ntstream = 1; p.ntload = 1;
     // (one tile's rows of the widest array must fit a 32-bit buffer offset)
     { const int mxl = p.lddg > p.lddy ? p.lddg : p.lddy; DEP_CHECK_ARG((size_t)(BT * a.T + 1) * (mxl > p.ldy ? mxl : p.ldy) * 4 < 0xffffffffull); }
-    const int kb = a.H >= 512 ? 0 : 4;                // H = 512: 192 weight registers per compute wave leave no room for a second wave per SIMD
-    // H = 256, split products: the all-gather exchange of the members' gate gradients (round 5); every other shape / the exact-fp32 mode: the
-    // reduce-scatter of fp32 partial dh
-    const bool ag = a.H == 256 && a.split && kb == 4;
-    const size_t lds = ag ? burst_lds_bytes_ag(4) + 2048
-                          : (kb ? (burst_lds_bytes(kb) > EXCLUSIVE_LDS ? burst_lds_bytes(kb) : EXCLUSIVE_LDS) : EXCLUSIVE_LDS) + 2048;
-    p.trall_off = (int)((lds - 2048) / 4);
-    static bool attr_b = false;
-    if (!attr_b) {
-#define DEP_BWD_ATTR1(N, S, V, X) (void)hipFuncSetAttribute((const void*)gru_bwd_cluster_r1<N, S, V, X>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((V ? burst_lds_bytes(V) > EXCLUSIVE_LDS ? burst_lds_bytes(V) : EXCLUSIVE_LDS : EXCLUSIVE_LDS) + 2048))
-#define DEP_BWD_ATTR(N, S, V) do { DEP_BWD_ATTR1(N, S, V, false); if (S) DEP_BWD_ATTR1(N, true, V, true); } while (0)
-        DEP_BWD_ATTR(1, false, 4); DEP_BWD_ATTR(1, true, 4);
-        DEP_BWD_ATTR(2, false, 4); DEP_BWD_ATTR(2, true, 4); DEP_BWD_ATTR1(4, false, 4, false);
-        DEP_BWD_ATTR(8, false, 0); DEP_BWD_ATTR(8, true, 0);
-        (void)hipFuncSetAttribute((const void*)gru_bwd_cluster_r1<4, true, 4, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(burst_lds_bytes_ag(4) + 2048));
-        (void)hipFuncSetAttribute((const void*)gru_bwd_cluster_r1<4, true, 4, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(burst_lds_bytes_ag(4) + 2048));
-        (void)hipFuncSetAttribute((const void*)gru_bwd_cluster_r1<4, true, 4, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(burst_lds_bytes_ag(4) + 2048));
-#undef DEP_BWD_ATTR1
-#undef DEP_BWD_ATTR
-        attr_b = true;
-    }
+    const int kb = bwd_burst(a.H);
+    Instance<P2>& k = bwd_instance(a.H, a.split, a.sv16, a.bf16st);
+    p.trall_off = (int)((k.lds - 2048) / 4);
     if (p.dgpk) {       // the PK image needs the burst kernel's flush, the 4H-wide rows and whole step pairs (dep_cluster_bwd_pk_ok)
         DEP_CHECK_ARG(kb == 4 && a.split && a.T % 2 == 0 && a.lddg == 4 * a.H && a.lddghn == 4 * a.H && a.dghn == a.dgi + 3 * a.H);
     }
-    for (int b0 = 0; b0 < a.B; b0 += CH) {
-        const int cb = a.B - b0 < CH ? a.B - b0 : CH;
-        p.b0 = b0; p.nbtp = (dep_cdiv(cb, BT) + 7) / 8 * 8;
-        // flags / hello words only: the status word is sticky over every sweep of a step (cleared by dep_rnn_forward)
-        { const int rc_h = hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); if (rc_h) return rc_h; }
-        dim3 grid(NC * p.nbtp);
-        const dim3 block(kb ? CT + SVC_THREADS : CT);
-#define DEP_BWD_LAUNCH1(N, S, X) DEP_LAUNCH((gru_bwd_cluster_r1<N, S, 4, X>), grid, block, lds, a.stream, p)
-#define DEP_BWD_LAUNCH(N, S) do { if (S && a.sv16) DEP_BWD_LAUNCH1(N, true, true); else DEP_BWD_LAUNCH1(N, S, false); } while (0)
-        switch (a.H) {                                // NTW = H / 64
-            case 64: if (a.split) DEP_BWD_LAUNCH(1, true); else DEP_BWD_LAUNCH(1, false); break;
-            case 128: if (a.split) DEP_BWD_LAUNCH(2, true); else DEP_BWD_LAUNCH(2, false); break;
-            case 256:
-                if (ag && a.bf16st) DEP_LAUNCH((gru_bwd_cluster_r1<4, true, 4, true, true, true>), grid, block, lds, a.stream, p);
-                else if (ag && a.sv16) DEP_LAUNCH((gru_bwd_cluster_r1<4, true, 4, true, false, true>), grid, block, lds, a.stream, p);
-                else if (ag) DEP_LAUNCH((gru_bwd_cluster_r1<4, true, 4, false, false, true>), grid, block, lds, a.stream, p);
-                else DEP_BWD_LAUNCH(4, false);        // exact-fp32 mode
-                break;
-            default:                                  // 512: round-1 schedule only (kb == 0)
-                if (a.split && a.sv16) DEP_LAUNCH((gru_bwd_cluster_r1<8, true, 0, true>), grid, block, lds, a.stream, p);
-                else if (a.split) DEP_LAUNCH((gru_bwd_cluster_r1<8, true, 0>), grid, block, lds, a.stream, p);
-                else DEP_LAUNCH((gru_bwd_cluster_r1<8, false, 0>), grid, block, lds, a.stream, p);
-                break;
-        }
-#undef DEP_BWD_LAUNCH1
-#undef DEP_BWD_LAUNCH
-        DEP_CHECK_LAUNCH();
-    }
-    return DEP_OK;
+    return launch_chunks(k, g, dim3(kb ? CT + SVC_THREADS : CT), p, a.stream, __PRETTY_FUNCTION__,
+                         [&](int b0) { return hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); });
 }

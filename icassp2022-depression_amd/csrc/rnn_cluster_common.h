@@ -102,6 +102,39 @@ __device__ __forceinline__ void split_pair(float x0, float x1, unsigned& hi, uns
     lo = __builtin_bit_cast(unsigned, __builtin_convertvector(d, b2v));
 }
 
+// Split-precision weight images of the 32-unit-member sweeps (G gates: 3 GRU, 4 LSTM; W is (G*H, H) row-major).  A piece is 16 bytes
+// = 8 bf16 of one plane (0 hi, 1 lo); `idx` counts (piece, lane) pairs of one plane, one thread writes both planes.
+//   forward  (gru_fwd_cluster_r1<., true>, gru2_fwd_fused, lstm_fwd_cluster):  [((((jt*G + g)*2 + kh)*KS2 + ks)*2 + plane)*64 + lane]
+//            = W[(g*H + jt*16 + (lane&15))*H + kh*(H/2) + 32ks + 8(lane>>4) + 0..7]                       (KS2 = H/64 k-steps of 32 per K half)
+//   backward (gru_bwd_cluster_r1<., true>, gru2_bwd_fused, lstm_bwd_cluster):  [(((c*(H/16) + jt)*G + ks)*2 + plane)*64 + lane]
+//            = W[(ks*H + 32c + 8(lane>>4) + e)*H + jt*16 + (lane&15)], e = 0..7                           (k-step ks = gate, 32 units of member c)
+__host__ __device__ inline long pack_fwd_split_pieces(int G, int H) { const int KS2 = H / 64; return (long)(H / 16) * G * 2 * KS2 * 64; }
+__host__ __device__ inline long pack_bwd_split_pieces(int G, int H) { return (long)(H / 32) * (H / 16) * G * 64; }
+template <int G> __device__ __forceinline__ void pack_fwd_split_piece(const float* __restrict__ W, u32x4* __restrict__ out, int H, long idx) {
+    const int KS2 = H / 64;
+    const int lane = idx & 63; long r = idx >> 6;
+    const int ks = r % KS2; r /= KS2;
+    const int kh = r % 2; r /= 2;
+    const int g = r % G; const int jt = r / G;
+    const float* src = W + (size_t)(g * H + jt * 16 + (lane & 15)) * H + kh * (H / 2) + 32 * ks + 8 * (lane >> 4);
+    u32x4 hi, lo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { unsigned h, l; split_pair(src[2 * e], src[2 * e + 1], h, l); hi[e] = h; lo[e] = l; }
+    out[(idx - lane) * 2 + lane] = hi;
+    out[(idx - lane) * 2 + 64 + lane] = lo;
+}
+template <int G> __device__ __forceinline__ void pack_bwd_split_piece(const float* __restrict__ W, u32x4* __restrict__ out, int H, long idx) {
+    const int lane = idx & 63; long r = idx >> 6;
+    const int ks = r % G; r /= G;
+    const int jt = r % (H / 16); const int c = r / (H / 16);
+    const float* src = W + (size_t)(ks * H + 32 * c + 8 * (lane >> 4)) * H + jt * 16 + (lane & 15);
+    u32x4 hi, lo;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { unsigned h, l; split_pair(src[(size_t)(2 * e) * H], src[(size_t)(2 * e + 1) * H], h, l); hi[e] = h; lo[e] = l; }
+    out[(idx - lane) * 2 + lane] = hi;
+    out[(idx - lane) * 2 + 64 + lane] = lo;
+}
+
 // Same-XCD fast path.  Correctness never depends on placement: every member announces the XCD it runs on through the
 // placement-independent protocol (sc1 store / sc1 polls); only if ALL members of the cluster report the same XCD do the
 // per-step payload and flag stores drop the write-through bit -- that XCD's L2 is then the coherence point for writers
@@ -189,17 +222,6 @@ __device__ __forceinline__ void nt_st2w(const NtArr& a, void* q, unsigned w0, un
 }
 __device__ __forceinline__ void nt_st4(const NtArr& a, float* q, f32x4 v) {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), a.rs, (unsigned)(reinterpret_cast<const char*>(q) - a.base), 0, 2 /* nt */);
-}
-
-inline int nofast_env() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("DEP_CLUSTER_NOFAST"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v;
-}
-inline int trace_env() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("DEP_TRACE"); v = (e && e[0] == '1') ? 1 : 0; }
-    return v;
 }
 
 }  // namespace depc

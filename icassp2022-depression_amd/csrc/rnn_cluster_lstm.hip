@@ -5,7 +5,7 @@
 // through flag-published fp32 payloads with the same-XCD fast path, parity double-buffering and bounded spins.
 // Both directions run in the same launch: at H = 128, B = 512 that is 2 x 32 tiles x 4 members = 256 workgroups.
 // Both biases are folded into the input projection by the caller (dep_rnn_forward), as in rnn_sweep.hip.
-#include "rnn_cluster_common.h"
+#include "rnn_cluster_launch.h"
 
 namespace {
 using namespace depc;
@@ -967,60 +967,58 @@ __global__ __launch_bounds__(KB ? CT + L_SVC : CT) void lstm_bwd_cluster(LB p) {
     }
 }
 
-// split-precision weight images (16-byte pieces of 8 bf16):
-//   forward : [((((jt*4 + g)*2 + kh)*KS2 + ks)*2 + plane)*64 + lane] = W[(g*H + jt*16 + (lane&15))*H + kh*(H/2) + 32ks + 8(lane>>4) + 0..7]
-//   backward: [(((c*(H/16) + jt)*4 + ks)*2 + plane)*64 + lane]        = W[(ks*H + 32c + 8(lane>>4) + e)*H + jt*16 + (lane&15)], e = 0..7
+// split-precision weight images (rnn_cluster_common.h, G = 4): the forward's, and the backward's when `bwd` is set -- equally many pieces
 __global__ void pack_lstm_split_kernel(const float* __restrict__ W, u32x4* __restrict__ fwd, u32x4* __restrict__ bwd, int H) {
-    const int KS2 = H / 64;
-    const long n = (long)(H / 16) * 4 * 2 * KS2 * 64;          // == (H/32) * (H/16) * 4 * 64 pieces in either image
+    const long n = pack_fwd_split_pieces(4, H);
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
-    const int lane = idx & 63;
-    u32x4 hi, lo;
-    {
-        long r = idx >> 6;
-        const int ks = r % KS2; r /= KS2;
-        const int kh = r % 2; r /= 2;
-        const int g = r % 4; const int jt = r / 4;
-        const float* src = W + (size_t)(g * H + jt * 16 + (lane & 15)) * H + kh * (H / 2) + 32 * ks + 8 * (lane >> 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { unsigned h, l; split_pair(src[2 * e], src[2 * e + 1], h, l); hi[e] = h; lo[e] = l; }
-        fwd[(idx - lane) * 2 + lane] = hi; fwd[(idx - lane) * 2 + 64 + lane] = lo;
-    }
-    if (bwd) {
-        long r = idx >> 6;
-        const int ks = r % 4; r /= 4;
-        const int jt = r % (H / 16); const int c = r / (H / 16);
-        const float* src = W + (size_t)(ks * H + 32 * c + 8 * (lane >> 4)) * H + jt * 16 + (lane & 15);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { unsigned h, l; split_pair(src[(size_t)(2 * e) * H], src[(size_t)(2 * e + 1) * H], h, l); hi[e] = h; lo[e] = l; }
-        bwd[(idx - lane) * 2 + lane] = hi; bwd[(idx - lane) * 2 + 64 + lane] = lo;
-    }
+    pack_fwd_split_piece<4>(W, fwd, H, idx);
+    if (bwd) pack_bwd_split_piece<4>(W, bwd, H, idx);
 }
+
+// ---- the launchable instances (H = 128: KCH = 4, NTW = 2; burst length 4, the service waves own the HBM streams -- DESIGN 4.1c)
+// exact-fp32 mode: h_t through LDS planes (DF = 0); split products: the direct-fragment exchange with sentinel slots (DF = 3, round 5)
+Instance<LF>& fwd_instance(bool split, bool sv16) {
+    constexpr size_t PLANES = lstm_fwd_lds_floats(128, 4) * sizeof(float), DIRECT = lstm_fwd_lds_floats(128, 4, true) * sizeof(float);
+    static Instance<LF> exact DEP_INSTANCE((lstm_fwd_cluster<4, false, 4>), PLANES);
+    static Instance<LF> df3[2] = { DEP_INSTANCE((lstm_fwd_cluster<4, true, 4, false, 3>), DIRECT), DEP_INSTANCE((lstm_fwd_cluster<4, true, 4, true, 3>), DIRECT) };
+    return split ? df3[sv16] : exact;
+}
+// exact-fp32 mode: burst streams, one flag per member behind a drain barrier; split products: per-step streams + per-wave flags (SE, round 5)
+Instance<LB>& bwd_instance(bool split, bool sv16) {
+    constexpr size_t LDS = lstm_bwd_lds_floats(4) * sizeof(float);
+    static Instance<LB> exact DEP_INSTANCE((lstm_bwd_cluster<2, false, 4>), LDS);
+    static Instance<LB> se[2] = { DEP_INSTANCE((lstm_bwd_cluster<2, true, 4, false, true>), LDS), DEP_INSTANCE((lstm_bwd_cluster<2, true, 4, true, true>), LDS) };
+    return split ? se[sv16] : exact;
+}
+
+// the backward's two parities of NC x 16 x H fp32 per cluster; the forward's four slots of 16 x H (DF = 3; the other forms use two)
+ChunkGeometry lstm_geometry(int H, int dirs, int B) { return chunk_geometry(dirs * (H / 32), 1, 256, B); }      // one workgroup per CU per launch
+size_t lstm_bwd_payload_bytes(const ChunkGeometry& g, int H) { return (size_t)2 * g.nbtp_max * g.members * BT * H * sizeof(float); }
+size_t lstm_fwd_payload_bytes(const ChunkGeometry& g, int H, int dirs) { return (size_t)4 * dirs * g.nbtp_max * BT * H * sizeof(float); }
 
 }  // namespace
 
 int dep_pack_cluster_lstm_split(const float* w_hh, float* wp, float* wpT, int H, hipStream_t s) {
-    const long n = (long)(H / 16) * 4 * 2 * (H / 64) * 64;
-    DEP_LAUNCH(pack_lstm_split_kernel, dim3(dep_cdiv(n, 256)), dim3(256), 0, s, w_hh, (u32x4*)wp, (u32x4*)wpT, H);
+    DEP_LAUNCH(pack_lstm_split_kernel, dim3(dep_cdiv(pack_fwd_split_pieces(4, H), 256)), dim3(256), 0, s, w_hh, (u32x4*)wp, (u32x4*)wpT, H);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }
 
-bool dep_cluster_lstm_ok(int H, int B, int dirs) {
-    (void)B; (void)dirs;                               // any batch: the launchers chunk it
+bool dep_cluster_lstm_ok(int H, int, int) {      // any batch: the launchers chunk it
     return dep_rnn_switches().cluster_lstm && H == 128;                           // KCH = 4, NTW = 2, NC = 4 (backward gathers exactly 4 partials)
 }
 
+// the larger of the two sweeps' payloads (the backward's from two members per direction on); the 256 bytes on top are slack
 size_t dep_cluster_lstm_xbuf_bytes(int H, int B, int dirs) {
-    const int NC = H / 32, CH = dep_cluster_chunk(dirs * NC, 1, 256);
-    const int nbtp = (dep_cdiv(B < CH ? B : CH, BT) + 7) / 8 * 8;
-    return PAYLOAD_OFF + (size_t)2 * dirs * nbtp * NC * BT * H * sizeof(float) + 256;      // the backward's two parities of NC x 16 x H fp32 per cluster (NC >= 2: covers the forward's four slots of 16 x H)
+    const ChunkGeometry g = lstm_geometry(H, dirs, B);
+    const size_t fwd = lstm_fwd_payload_bytes(g, H, dirs), bwd = lstm_bwd_payload_bytes(g, H);
+    return PAYLOAD_OFF + (fwd > bwd ? fwd : bwd) + 256;
 }
 
 int dep_launch_cluster_lstm_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf_bytes) {
-    const int NC = a.H / 32, CH = dep_cluster_chunk(a.dirs * NC, 1, 256);      // one workgroup per CU per launch; larger batches in chunks
-    const int nbtp_max = (dep_cdiv(a.B < CH ? a.B : CH, BT) + 7) / 8 * 8;
+    DEP_CHECK_ARG(a.H == 128);
+    const ChunkGeometry g = lstm_geometry(a.H, a.dirs, a.B);      // larger batches in chunks
     LF p{};
     p.B = a.B; p.T = a.T; p.H = a.H; p.dirs = a.dirs;
     for (int d = 0; d < a.dirs; ++d) p.wp[d] = (const f32x4*)a.wp[d];
@@ -1029,36 +1027,12 @@ int dep_launch_cluster_lstm_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf
     p.drop_p = a.drop_p; p.drop_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f; p.seed = a.seed; p.site = a.site;
     p.h_n = a.h_n;
     p.svg = a.training ? a.sv0 : nullptr; p.svc = a.sv1;
-    const size_t pay = (size_t)4 * a.dirs * nbtp_max * BT * a.H * sizeof(float);      // four slots (DF = 3; the other forms use two)
-    DEP_CHECK_ARG(xbuf && PAYLOAD_OFF + pay <= xbuf_bytes && (size_t)a.dirs * nbtp_max * NC <= 256);
-    p.status = (unsigned*)xbuf; p.flags = (unsigned*)(hdr_base(xbuf, a.hdr_slot) + FLAG_OFF); p.hello = (unsigned*)(hdr_base(xbuf, a.hdr_slot) + HELLO_OFF);
-    p.payload = (float*)((char*)xbuf + PAYLOAD_OFF); p.payload_bytes = (unsigned)pay; p.nofast = nofast_env();
+    const size_t pay = lstm_fwd_payload_bytes(g, a.H, a.dirs);
+    DEP_CHECK_ARG(xbuf && PAYLOAD_OFF + pay <= xbuf_bytes && g.resident());
+    p.flags = bind_exchange(p, xbuf, a.hdr_slot, pay);
     DepProfScope prof(DEP_PROF_LSTM_FWD, a.stream);
-    const int kb = 4;                                 // service waves own the HBM streams
-    // split products: the direct-fragment exchange with sentinel slots (DF = 3, round 5); exact-fp32 mode: h_t through LDS planes (DF = 0)
-    const int df = (a.split && a.H == 128) ? 3 : 0;
-    p.trace = (kb && trace_env()) ? (long long*)(hdr_base(xbuf, a.hdr_slot) + TRACE_OFF) : nullptr;
-    const size_t lds = lstm_fwd_lds_floats(a.H, kb, df != 0) * sizeof(float);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)lstm_fwd_cluster<4, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lstm_fwd_lds_floats(128, 4) * sizeof(float)));
-        (void)hipFuncSetAttribute((const void*)lstm_fwd_cluster<4, true, 4, false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lstm_fwd_lds_floats(128, 4, true) * sizeof(float)));
-        (void)hipFuncSetAttribute((const void*)lstm_fwd_cluster<4, true, 4, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lstm_fwd_lds_floats(128, 4, true) * sizeof(float)));
-        attr = true;
-    }
-    for (int b0 = 0; b0 < a.B; b0 += CH) {
-        const int cb = a.B - b0 < CH ? a.B - b0 : CH;
-        p.b0 = b0; p.nbtp = (dep_cdiv(cb, BT) + 7) / 8 * 8;
-        // flags / hello words only: the status word is sticky over every sweep of a step (cleared by dep_rnn_forward)
-        { const int rc_h = hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); if (rc_h) return rc_h; }
-        const dim3 grid(a.dirs * NC * p.nbtp), block(kb ? CT + L_SVC : CT);
-        const bool sv16 = kb && a.split && a.sv16 && a.training;
-        if (df == 3) { if (sv16) DEP_LAUNCH((lstm_fwd_cluster<4, true, 4, true, 3>), grid, block, lds, a.stream, p);
-                       else DEP_LAUNCH((lstm_fwd_cluster<4, true, 4, false, 3>), grid, block, lds, a.stream, p); }
-        else DEP_LAUNCH((lstm_fwd_cluster<4, false, 4>), grid, block, lds, a.stream, p);
-        DEP_CHECK_LAUNCH();
-    }
-    return DEP_OK;
+    return launch_chunks(fwd_instance(a.split, a.sv16 && a.training), g, dim3(CT + L_SVC), p, a.stream, __PRETTY_FUNCTION__,
+                         [&](int b0) { return hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); });
 }
 
 // both LSTM sweeps must be the burst kernels for the 16-bit saved gates (dep_sweep_args.sv16)
@@ -1070,8 +1044,9 @@ bool dep_cluster_lstm_sv16_ok() { return dep_rnn_switches().lstm_sv16; }
 bool dep_cluster_lstm_bwd_pk_ok(int T) { return T % 2 == 0; }
 
 int dep_launch_cluster_lstm_bwd(const dep_sweep_bwd_args& a, void* xbuf, size_t xbuf_bytes) {
-    const int NC = a.H / 32, CH = dep_cluster_chunk(a.dirs * NC, 1, 256), nbt = dep_cdiv(a.B, BT);
-    const int nbtp_max = (dep_cdiv(a.B < CH ? a.B : CH, BT) + 7) / 8 * 8;
+    DEP_CHECK_ARG(a.H == 128);
+    const ChunkGeometry g = lstm_geometry(a.H, a.dirs, a.B);
+    const int nbt = dep_cdiv(a.B, BT);
     LB p{};
     p.B = a.B; p.T = a.T; p.H = a.H; p.dirs = a.dirs;
     for (int d = 0; d < a.dirs; ++d) p.wp[d] = (const f32x4*)a.wpT[d];
@@ -1081,35 +1056,12 @@ int dep_launch_cluster_lstm_bwd(const dep_sweep_bwd_args& a, void* xbuf, size_t 
     p.dh_n = a.dh_n; p.svg = a.sv0; p.svc = a.sv1;
     p.dgi = a.dgi; p.lddg = a.dirs * 4 * a.H; p.dbpart = a.dbpart; p.nwg = nbt; p.dgpk = a.dg_pk;
     DEP_CHECK_ARG(a.dbpart_rows >= nbt * a.dirs);
-    const size_t pay = (size_t)2 * a.dirs * nbtp_max * NC * BT * a.H * sizeof(float);
-    DEP_CHECK_ARG(xbuf && PAYLOAD_OFF + pay <= xbuf_bytes && (size_t)a.dirs * nbtp_max * NC <= 256);
-    p.status = (unsigned*)xbuf; p.flags = (unsigned*)(hdr_base(xbuf, a.hdr_slot) + FLAG_OFF); p.hello = (unsigned*)(hdr_base(xbuf, a.hdr_slot) + HELLO_OFF);
-    p.payload = (float*)((char*)xbuf + PAYLOAD_OFF); p.payload_bytes = (unsigned)pay; p.nofast = nofast_env();
+    const size_t pay = lstm_bwd_payload_bytes(g, a.H);
+    DEP_CHECK_ARG(xbuf && PAYLOAD_OFF + pay <= xbuf_bytes && g.resident());
+    p.flags = bind_exchange(p, xbuf, a.hdr_slot, pay);
     DepProfScope prof(DEP_PROF_LSTM_BWD, a.stream);
-    const int kb = 4;
-    DEP_CHECK_ARG(!a.dg_pk || (kb == 4 && a.T % 2 == 0));
-    DEP_CHECK_ARG(!a.sv16 || (kb == 4 && a.split));           // 16-bit saved gates: burst kernel, split-precision mode      // the PK image comes out of the burst kernel's flush (dep_cluster_lstm_bwd_pk_ok)
-    // split products: per-step streams + per-wave flags (SE, round 5); exact-fp32 mode: burst streams, one flag per member behind a drain barrier
-    const bool se = a.split;
-    p.trace = (kb && trace_env()) ? (long long*)(hdr_base(xbuf, a.hdr_slot) + TRACE_OFF) : nullptr;
-    const size_t lds = lstm_bwd_lds_floats(kb) * sizeof(float);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)lstm_bwd_cluster<2, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lstm_bwd_lds_floats(4) * sizeof(float)));
-        (void)hipFuncSetAttribute((const void*)lstm_bwd_cluster<2, true, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lstm_bwd_lds_floats(4) * sizeof(float)));
-        (void)hipFuncSetAttribute((const void*)lstm_bwd_cluster<2, true, 4, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lstm_bwd_lds_floats(4) * sizeof(float)));
-        attr = true;
-    }
-    for (int b0 = 0; b0 < a.B; b0 += CH) {
-        const int cb = a.B - b0 < CH ? a.B - b0 : CH;
-        p.b0 = b0; p.nbtp = (dep_cdiv(cb, BT) + 7) / 8 * 8;
-        // flags / hello words only: the status word is sticky over every sweep of a step (cleared by dep_rnn_forward)
-        { const int rc_h = hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); if (rc_h) return rc_h; }
-        const dim3 grid(a.dirs * NC * p.nbtp), block(kb ? CT + L_SVC : CT);
-        if (se) { if (a.sv16) DEP_LAUNCH((lstm_bwd_cluster<2, true, 4, true, true>), grid, block, lds, a.stream, p);
-                  else DEP_LAUNCH((lstm_bwd_cluster<2, true, 4, false, true>), grid, block, lds, a.stream, p); }
-        else DEP_LAUNCH((lstm_bwd_cluster<2, false, 4>), grid, block, lds, a.stream, p);
-        DEP_CHECK_LAUNCH();
-    }
-    return DEP_OK;
+    DEP_CHECK_ARG(!a.dg_pk || a.T % 2 == 0);         // the PK image comes out of the burst kernel's flush in whole step pairs (dep_cluster_lstm_bwd_pk_ok)
+    DEP_CHECK_ARG(!a.sv16 || a.split);               // 16-bit saved gates: split-precision mode
+    return launch_chunks(bwd_instance(a.split, a.sv16), g, dim3(CT + L_SVC), p, a.stream, __PRETTY_FUNCTION__,
+                         [&](int b0) { return hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); });
 }

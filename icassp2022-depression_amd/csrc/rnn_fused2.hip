@@ -17,7 +17,7 @@
 // double-buffered payload, bounded spins and sticky status: rnn_cluster_common.h.  Products use the 3-term bf16 split
 // (w_hi h_lo + w_lo h_hi + w_hi h_hi, fp32 accumulate), everything elementwise is fp32.
 // Matrix-pipe time per step and SIMD: 2 x 36 v_mfma_f32_16x16x32_bf16 on the critical path (1152 cycles) + 36 beside the gate math.
-#include "rnn_cluster_common.h"
+#include "rnn_cluster_launch.h"
 
 namespace {
 using namespace depc;
@@ -533,6 +533,21 @@ __global__ __launch_bounds__(FTHREADS) void gru2_fwd_fused(FF p) {
 }
 
 
+// ---- the launchable instances: the bf16-storage mode (16-bit saved gates, never traced), then
+// [16-bit saved gates][DEP_TRACE=1: the stamped variant (tools/trace_fused.py)][dropout between the layers | none]
+Instance<FF>& fwd_instance(bool drop, bool trace, bool sv16, bool bf) {
+    static Instance<FF> bf16st[2] = { DEP_INSTANCE((gru2_fwd_fused<true, false, true, true>), F_LDS_BYTES), DEP_INSTANCE((gru2_fwd_fused<false, false, true, true>), F_LDS_BYTES) };
+    static Instance<FF> rows[2][2][2] = {
+        { { DEP_INSTANCE((gru2_fwd_fused<true, false, false>), F_LDS_BYTES), DEP_INSTANCE((gru2_fwd_fused<false, false, false>), F_LDS_BYTES) },
+          { DEP_INSTANCE((gru2_fwd_fused<true, true, false>), F_LDS_BYTES), DEP_INSTANCE((gru2_fwd_fused<false, true, false>), F_LDS_BYTES) } },
+        { { DEP_INSTANCE((gru2_fwd_fused<true, false, true>), F_LDS_BYTES), DEP_INSTANCE((gru2_fwd_fused<false, false, true>), F_LDS_BYTES) },
+          { DEP_INSTANCE((gru2_fwd_fused<true, true, true>), F_LDS_BYTES), DEP_INSTANCE((gru2_fwd_fused<false, true, true>), F_LDS_BYTES) } } };
+    return bf ? bf16st[!drop] : rows[sv16][trace][!drop];
+}
+
+ChunkGeometry fused2_geometry(int B) { return chunk_geometry(FNC, 1, 256, B); }
+size_t fused2_payload_bytes(const ChunkGeometry& g) { return (size_t)4 * g.nbtp_max * 3 * F_REGION * sizeof(float); }      // four sentinel-armed slots
+
 // =====================================================================================================================================
 }  // namespace
 
@@ -540,15 +555,10 @@ bool dep_fused2_ok(int cell, int H, int L, int dirs) {
     return dep_rnn_switches().fused2 && cell == DEP_CELL_GRU && H == FH && L == 2 && dirs == 1;
 }
 
-size_t dep_fused2_xbuf_bytes(int B) {
-    const int CH = dep_cluster_chunk(FNC, 1, 256);
-    const int nbtp = (dep_cdiv(B < CH ? B : CH, BT) + 7) / 8 * 8;
-    return PAYLOAD_OFF + (size_t)4 * nbtp * 3 * F_REGION * sizeof(float) + 4096;      // four sentinel-armed slots
-}
+size_t dep_fused2_xbuf_bytes(int B) { return PAYLOAD_OFF + fused2_payload_bytes(fused2_geometry(B)) + 4096; }      // (4096: slack)
 
 int dep_launch_fused2_fwd(const dep_fused2_args& a, void* xbuf, size_t xbuf_bytes) {
-    const int CH = dep_cluster_chunk(FNC, 1, 256);
-    const int nbtp_max = (dep_cdiv(a.B < CH ? a.B : CH, BT) + 7) / 8 * 8;
+    const ChunkGeometry g = fused2_geometry(a.B);
     FF p{};
     p.B = a.B; p.T = a.T;
     p.wp0 = (const u32x4*)a.wp0; p.wp1 = (const u32x4*)a.wp1; p.wpi = (const u32x4*)a.wpi;
@@ -567,48 +577,18 @@ int dep_launch_fused2_fwd(const dep_fused2_args& a, void* xbuf, size_t xbuf_byte
     DEP_CHECK_ARG(donly || a.y0);
     if (a.training == DEP_RUN_TRAIN) for (int k = 0; k < 4; ++k)
         DEP_CHECK_ARG(a.sv[0][k] == a.y0 + (size_t)(k + (drop ? 2 : 1)) * a.ostride && a.sv[1][k] == a.y1 + (size_t)(k + 1) * a.ostride);
-    const size_t pay = (size_t)4 * nbtp_max * 3 * F_REGION * sizeof(float);      // four sentinel-armed slots
-    DEP_CHECK_ARG(xbuf && PAYLOAD_OFF + pay <= xbuf_bytes && (size_t)nbtp_max * FNC <= 256);
+    const size_t pay = fused2_payload_bytes(g);
+    DEP_CHECK_ARG(xbuf && PAYLOAD_OFF + pay <= xbuf_bytes && g.resident());
     DEP_CHECK_ARG(donly || !drop || a.y0d);
-    p.status = (unsigned*)xbuf; p.flags = (unsigned*)(hdr_base(xbuf, 0) + FLAG_OFF); p.hello = (unsigned*)(hdr_base(xbuf, 0) + HELLO_OFF);
-    p.payload = (float*)((char*)xbuf + PAYLOAD_OFF); p.payload_bytes = (unsigned)pay; p.nofast = nofast_env();
-    p.trace = trace_env() ? (long long*)(hdr_base(xbuf, 0) + TRACE_OFF) : nullptr;
+    p.flags = bind_exchange(p, xbuf, 0, pay);
     p.soft = a.soft_fallback ? (unsigned*)xbuf + 1 : nullptr;
     // instance choice: dropout-only picks the one training picks (a.sv16 is the caller's instance decision; nothing is saved)
     const bool sv16 = a.training != DEP_RUN_EVAL && a.sv16;
     const bool bf = a.training == DEP_RUN_TRAIN && a.bf16st;
     DEP_CHECK_ARG(!bf || sv16);
     p.ntstore = 0;                                    // (non-temporal write-out measured: no effect on this launch -- its payload, 0.4 MB per XCD, survives anyway)
-    { static int fs = -1; if (fs < 0) { const char* e = getenv("DEP_FORCE_SOFT_FALLBACK"); fs = (e && e[0] >= '1' && e[0] <= '3') ? e[0] - '0' : 0; } p.force_soft = fs; }
-    static bool attr = false;
-    if (!attr) {
-#define F2_ATTR(D, TR, X) (void)hipFuncSetAttribute((const void*)gru2_fwd_fused<D, TR, X, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES)
-        (void)hipFuncSetAttribute((const void*)gru2_fwd_fused<true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES);
-        (void)hipFuncSetAttribute((const void*)gru2_fwd_fused<false, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_BYTES);
-        F2_ATTR(true, false, false); F2_ATTR(false, false, false); F2_ATTR(true, true, false); F2_ATTR(false, true, false);
-        F2_ATTR(true, false, true); F2_ATTR(false, false, true); F2_ATTR(true, true, true); F2_ATTR(false, true, true);
-#undef F2_ATTR
-        attr = true;
-    }
+    p.force_soft = cluster_switches().force_soft;
     DepProfScope prof(DEP_PROF_GRU_FWD, a.stream);
-    for (int b0 = 0; b0 < a.B; b0 += CH) {
-        const int cb = a.B - b0 < CH ? a.B - b0 : CH;
-        p.b0 = b0; p.nbtp = (dep_cdiv(cb, BT) + 7) / 8 * 8;
-        // flags / hello words only: the status word is sticky over every sweep of a step (cleared by dep_rnn_forward)
-        { const int rc_h = hdr_prepare(xbuf, 0, a.hdr_clean && b0 == 0, a.stream); if (rc_h) return rc_h; }
-        const dim3 grid(FNC * p.nbtp), blk(FTHREADS);
-#define F2_LAUNCH(D, TR) do { if (sv16) DEP_LAUNCH((gru2_fwd_fused<D, TR, true>), grid, blk, F_LDS_BYTES, a.stream, p); \
-                              else DEP_LAUNCH((gru2_fwd_fused<D, TR, false>), grid, blk, F_LDS_BYTES, a.stream, p); } while (0)
-        if (bf) {                                         // bf16-storage mode (never traced)
-            if (drop) DEP_LAUNCH((gru2_fwd_fused<true, false, true, true>), grid, blk, F_LDS_BYTES, a.stream, p);
-            else DEP_LAUNCH((gru2_fwd_fused<false, false, true, true>), grid, blk, F_LDS_BYTES, a.stream, p);
-        } else if (p.trace) {                             // DEP_TRACE=1: the stamped variant (tools/trace_fused.py)
-            if (drop) F2_LAUNCH(true, true); else F2_LAUNCH(false, true);
-        } else {
-            if (drop) F2_LAUNCH(true, false); else F2_LAUNCH(false, false);
-        }
-#undef F2_LAUNCH
-        DEP_CHECK_LAUNCH();
-    }
-    return DEP_OK;
+    return launch_chunks(fwd_instance(drop, p.trace != nullptr, sv16, bf), g, dim3(FTHREADS), p, a.stream, __PRETTY_FUNCTION__,
+                         [&](int b0) { return hdr_prepare(xbuf, 0, a.hdr_clean && b0 == 0, a.stream); });
 }

@@ -21,7 +21,7 @@
 //   -> ONE barrier -> [K-quarter sums: dh1_rec (group 0), dh0_rec and the masked dy0 (group 2)].
 // Layer 1's exchange buffer is triple-buffered (group 1 reads step v-1 while step v+1 may already be written by a fast member), layer
 // 0's double-buffered.  Exchange protocol, same-XCD fast path, bounded spins, sticky status: rnn_cluster_common.h.
-#include "rnn_cluster_common.h"
+#include "rnn_cluster_launch.h"
 
 namespace {
 using namespace depc;
@@ -482,21 +482,39 @@ __global__ __launch_bounds__(BTHREADS) void gru2_bwd_fused(FB p) {
     }
 }
 
+// ---- the launchable instances: [fp32 saved gates | 16-bit saved gates | 16-bit gates and the PK gradient image][dropout on dy | none][dy given | not],
+// the bf16-storage mode (16-bit gates, PKH image; never traced) and the stamped variant of the model form (DEP_TRACE=1, tools/trace_fbwd.py)
+#define FB_ROW(D, Y, S, P) DEP_INSTANCE((gru2_bwd_fused<D, Y, S, P>), fb_lds_bytes(S, Y, P))
+#define FB_ROWS(S, P) { { FB_ROW(true, true, S, P), FB_ROW(true, false, S, P) }, { FB_ROW(false, true, S, P), FB_ROW(false, false, S, P) } }
+#define FB_ROW_BF(D, Y) DEP_INSTANCE((gru2_bwd_fused<D, Y, true, true, false, true>), fb_lds_bytes(true, Y, true, true))
+Instance<FB>& bwd_instance(bool drop, bool hasdy, bool sv16, bool pk, bool bf, bool trace) {
+    static Instance<FB> rows[3][2][2] = { FB_ROWS(false, false), FB_ROWS(true, false), FB_ROWS(true, true) };
+    static Instance<FB> bf16st[2][2] = { { FB_ROW_BF(true, true), FB_ROW_BF(true, false) }, { FB_ROW_BF(false, true), FB_ROW_BF(false, false) } };
+    static Instance<FB> stamped[2] = { DEP_INSTANCE((gru2_bwd_fused<true, false, true, true, true>), fb_lds_bytes(true, false, true)),
+                                       DEP_INSTANCE((gru2_bwd_fused<false, false, true, true, true>), fb_lds_bytes(true, false, true)) };
+    if (bf) return bf16st[!drop][!hasdy];
+    if (trace && pk && !hasdy) return stamped[!drop];
+    return rows[pk ? 2 : sv16 ? 1 : 0][!drop][!hasdy];
+}
+#undef FB_ROW_BF
+#undef FB_ROWS
+#undef FB_ROW
+
+ChunkGeometry fused2_bwd_geometry(int B) { return chunk_geometry(BNC, 1, 256, B); }
+// layer 1's three buffers, then layer 0's two, of a launch of nbtp tiles
+size_t fused2_bwd_payload_bytes(int nbtp) { return (size_t)nbtp * BNC * (3 * L1_MEMBER + 2 * L0_MEMBER); }
+
 }  // namespace
 
 // The fused backward addresses a layer's input arrays (y, dropped y, r, z, n, hn: one stride apart in the reserve) and its 4H-wide gate-gradient image
 // through 32-bit buffer offsets: larger batches take the per-layer sweeps (tile-relative resources) instead.
 bool dep_fused2_bwd_fits(int B, int T) { return (size_t)B * T * BH * sizeof(float) * 8 < 0xfffffff0ull; }
 
-size_t dep_fused2_bwd_xbuf_bytes(int B) {
-    const int CH = dep_cluster_chunk(BNC, 1, 256);
-    const int nbtp = (dep_cdiv(B < CH ? B : CH, BT) + 7) / 8 * 8;
-    return PAYLOAD_OFF + (size_t)nbtp * BNC * (3 * L1_MEMBER + 2 * L0_MEMBER) + 4096;
-}
+size_t dep_fused2_bwd_xbuf_bytes(int B) { return PAYLOAD_OFF + fused2_bwd_payload_bytes(fused2_bwd_geometry(B).nbtp_max) + 4096; }      // (4096: slack)
 
 int dep_launch_fused2_bwd(const dep_fused2_bwd_args& a, void* xbuf, size_t xbuf_bytes) {
-    const int CH = dep_cluster_chunk(BNC, 1, 256), nbt = dep_cdiv(a.B, BT);
-    const int nbtp_max = (dep_cdiv(a.B < CH ? a.B : CH, BT) + 7) / 8 * 8;
+    const ChunkGeometry g = fused2_bwd_geometry(a.B);
+    const int nbt = dep_cdiv(a.B, BT);
     FB p{};
     p.B = a.B; p.T = a.T;
     p.wh1 = (const u32x4*)a.wh1; p.wi1 = (const u32x4*)a.wi1; p.wh0 = (const u32x4*)a.wh0;
@@ -509,10 +527,8 @@ int dep_launch_fused2_bwd(const dep_fused2_bwd_args& a, void* xbuf, size_t xbuf_
     DEP_CHECK_ARG(!a.dg_pk || (p.lddg == 4 * BH && a.dghn1 == a.dgi1 + 3 * BH && a.dghn0 == a.dgi0 + 3 * BH));
     DEP_CHECK_ARG(a.dbpart_rows >= nbt && a.wh1 && a.wi1 && a.wh0 && a.dgi1 && a.dgi0 && a.dghn1 && a.dghn0);
     static_assert(DEP_HDR_SLOTS >= 2, "the fused backward keeps layer 0's flags in header slot 1");
-    p.status = (unsigned*)xbuf; p.flags1 = (unsigned*)(hdr_base(xbuf, 0) + FLAG_OFF); p.flags0 = (unsigned*)(hdr_base(xbuf, 1) + FLAG_OFF);
-    p.hello = (unsigned*)(hdr_base(xbuf, 0) + HELLO_OFF);
-    p.payload = (float*)((char*)xbuf + PAYLOAD_OFF); p.nofast = nofast_env();
-    p.trace = trace_env() ? (long long*)(hdr_base(xbuf, 0) + TRACE_OFF) : nullptr;
+    p.flags1 = bind_exchange(p, xbuf, 0, 0);     // (payload_bytes: per chunk, below)
+    p.flags0 = hdr_words(xbuf, 1, FLAG_OFF);
     {   // the input streams' buffer resources: per layer one base below its arrays, 32-bit offsets
         const size_t arr = (size_t)a.B * a.T * BH * sizeof(float);
         auto span = [&](const float* y, const float* sv, const char*& base, unsigned& bytes, unsigned& oy, unsigned& osv) {
@@ -529,47 +545,13 @@ int dep_launch_fused2_bwd(const dep_fused2_bwd_args& a, void* xbuf, size_t xbuf_
     const bool sv16 = a.sv16 != 0, pk = a.dg_pk != 0, bf = a.bf16st != 0;
     DEP_CHECK_ARG(!bf || (sv16 && pk));               // bf16-storage mode: 16-bit gates, PKH image
     DEP_CHECK_ARG(!pk || (sv16 && a.T % 2 == 0 && (size_t)a.B * a.T * 4 * BH * 4 < 0xfffffff0ull));      // PK: 16-bit gates (LDS), whole step pairs, 32-bit offsets into the image
-    static bool attr = false;
-    if (!attr) {
-#define FB_ATTR(D, Y, S, P) (void)hipFuncSetAttribute((const void*)gru2_bwd_fused<D, Y, S, P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fb_lds_bytes(S, Y, P))
-#define FB_ATTR4(S, P) FB_ATTR(true, true, S, P); FB_ATTR(true, false, S, P); FB_ATTR(false, true, S, P); FB_ATTR(false, false, S, P)
-        FB_ATTR4(false, false); FB_ATTR4(true, false); FB_ATTR4(true, true);
-#define FB_ATTRB(D, Y) (void)hipFuncSetAttribute((const void*)gru2_bwd_fused<D, Y, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fb_lds_bytes(true, Y, true, true))
-        FB_ATTRB(true, true); FB_ATTRB(true, false); FB_ATTRB(false, true); FB_ATTRB(false, false);
-#undef FB_ATTRB
-        (void)hipFuncSetAttribute((const void*)gru2_bwd_fused<true, false, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fb_lds_bytes(true, false, true));
-        (void)hipFuncSetAttribute((const void*)gru2_bwd_fused<false, false, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fb_lds_bytes(true, false, true));
-#undef FB_ATTR4
-#undef FB_ATTR
-        attr = true;
-    }
     DepProfScope prof(DEP_PROF_GRU_BWD, a.stream);
-    for (int b0 = 0; b0 < a.B; b0 += CH) {
-        const int cb = a.B - b0 < CH ? a.B - b0 : CH;
-        p.b0 = b0; p.nbtp = (dep_cdiv(cb, BT) + 7) / 8 * 8;
-        const size_t pay = (size_t)p.nbtp * BNC * (3 * L1_MEMBER + 2 * L0_MEMBER);
-        DEP_CHECK_ARG(xbuf && PAYLOAD_OFF + pay <= xbuf_bytes && (size_t)nbtp_max * BNC <= 256 && pay < (1ull << 32));
+    return launch_chunks(bwd_instance(drop, a.dy != nullptr, sv16, pk, bf, p.trace != nullptr), g, dim3(BTHREADS), p, a.stream, __PRETTY_FUNCTION__, [&](int) -> int {
+        const size_t pay = fused2_bwd_payload_bytes(p.nbtp);
+        DEP_CHECK_ARG(xbuf && PAYLOAD_OFF + pay <= xbuf_bytes && g.resident() && pay < (1ull << 32));
         p.payload_bytes = (unsigned)pay; p.l0_off = (unsigned)((size_t)3 * p.nbtp * BNC * L1_MEMBER);
-        // flags / hello words only (both layers' slots): the status word is sticky over every sweep of a step (cleared by dep_rnn_forward)
-        { const int rc_h = hdr_prepare(xbuf, 0, false, a.stream); if (rc_h) return rc_h; }
-        { const int rc_h = hdr_prepare(xbuf, 1, false, a.stream); if (rc_h) return rc_h; }
-        const dim3 grid(BNC * p.nbtp), blk(BTHREADS);
-#define FB_GO(D, Y, S, P) DEP_LAUNCH((gru2_bwd_fused<D, Y, S, P>), grid, blk, fb_lds_bytes(S, Y, P), a.stream, p)
-#define FB_GO4(S, P) do { if (drop) { if (a.dy) FB_GO(true, true, S, P); else FB_GO(true, false, S, P); } \
-                          else      { if (a.dy) FB_GO(false, true, S, P); else FB_GO(false, false, S, P); } } while (0)
-        if (bf) {                                     // bf16-storage mode (never traced)
-#define FB_GOB(D, Y) DEP_LAUNCH((gru2_bwd_fused<D, Y, true, true, false, true>), grid, blk, fb_lds_bytes(true, Y, true, true), a.stream, p)
-            if (drop) { if (a.dy) FB_GOB(true, true); else FB_GOB(true, false); } else { if (a.dy) FB_GOB(false, true); else FB_GOB(false, false); }
-#undef FB_GOB
-        }
-        else if (p.trace && pk && !a.dy) {            // DEP_TRACE=1: the stamped variant (tools/trace_fbwd.py)
-            if (drop) DEP_LAUNCH((gru2_bwd_fused<true, false, true, true, true>), grid, blk, fb_lds_bytes(true, false, true), a.stream, p);
-            else DEP_LAUNCH((gru2_bwd_fused<false, false, true, true, true>), grid, blk, fb_lds_bytes(true, false, true), a.stream, p);
-        }
-        else if (pk) FB_GO4(true, true); else if (sv16) FB_GO4(true, false); else FB_GO4(false, false);
-#undef FB_GO4
-#undef FB_GO
-        DEP_CHECK_LAUNCH();
-    }
-    return DEP_OK;
+        // both layers' slots, always cleared here
+        if (const int rc = hdr_prepare(xbuf, 0, false, a.stream)) return rc;
+        return hdr_prepare(xbuf, 1, false, a.stream);
+    });
 }
