@@ -264,14 +264,43 @@ def device_features(arr, device, role='x'):
     return t
 
 
+def pad_ragged(seqs):
+    """A ragged corpus -> (x, lengths): `seqs` is a list of (T_i, F) arrays, or the object array a ragged Python list becomes in
+    `np.savez` (load it with `np.load(path, allow_pickle=True)`: numpy refuses object arrays otherwise) -- e.g. one NetVLAD vector
+    per interview topic, DAICFeatureExtarction/feature_extraction.py:31-64 of the reference.  x is the zero-padded float32
+    (N, max T_i, F) array, lengths the int32 (N,) vector the models' `lengths=` argument takes.  The padding is zeros: the ragged
+    entry points need it finite (include/dep_rnn.h).  An empty sequence (T_i = 0) needs an explicit (0, F) shape."""
+    items = [np.asarray(s, dtype=np.float32) for s in seqs]
+    if not items:
+        raise ValueError('pad_ragged: no sequences')
+    for i, a in enumerate(items):
+        if a.ndim != 2:
+            raise ValueError(f'pad_ragged: sequence {i} has shape {a.shape}, expected (T_i, F)')
+    F = items[0].shape[1]
+    if any(a.shape[1] != F for a in items):
+        raise ValueError('pad_ragged: the sequences differ in their feature width')
+    lengths = np.asarray([a.shape[0] for a in items], dtype=np.int32)
+    x = np.zeros((len(items), max(1, int(lengths.max())), F), dtype=np.float32)
+    for i, a in enumerate(items):
+        x[i, :a.shape[0]] = a
+    return x, lengths
+
+
 class FeatureFeeder:
     """Mini-batch inputs of one epoch, already on the device.  rows(a, b) = fp32 features of idxs[a:b] -- the rows the
-    reference slices out of `features[idxs]` -- as a (b-a, T, F) device tensor."""
+    reference slices out of `features[idxs]` -- as a (b-a, T, F) device tensor.
+    lengths: the int32 lengths of a padded ragged corpus (pad_ragged), one per row of `features`; the lengths of `idxs` are kept on
+    the device and lengths_rows(a, b) is the slice that belongs to rows(a, b)."""
 
-    def __init__(self, features, idxs, device, role='x'):
+    def __init__(self, features, idxs, device, role='x', lengths=None):
         self.idxs = np.asarray(idxs, dtype=np.int64).reshape(-1)
         self.device = device
         n_rows = len(features)
+        self.len_dev = None
+        if lengths is not None:
+            ln = np.asarray(lengths)
+            if ln.shape != (n_rows,) or not np.issubdtype(ln.dtype, np.integer):
+                raise ValueError(f'lengths: expected {n_rows} integers, one per feature row, got {ln.shape} {ln.dtype}')
         if self.idxs.size and (self.idxs.min() < 0 or self.idxs.max() >= n_rows):      # the device gather does not range-check (index_select did)
             bad = int(self.idxs.min()) if self.idxs.min() < 0 else int(self.idxs.max())
             raise IndexError(f'index {bad} is out of bounds for a feature array of {n_rows} rows')
@@ -283,6 +312,12 @@ class FeatureFeeder:
             self.host = torch.from_numpy(np.ascontiguousarray(np.asarray(features)[self.idxs], dtype=np.float32)).pin_memory()
             self.copy_stream = torch.cuda.Stream(device=device)
             self.inflight = {}
+        if lengths is not None:                       # gathered once, on the host: lengths_rows is then always a view
+            self.len_dev = torch.as_tensor(np.ascontiguousarray(ln[self.idxs], dtype=np.int32), device=device)
+
+    def lengths_rows(self, a, b):
+        """int32 device lengths of rows(a, b) (a view: no gather, no host synchronisation); None for a dense corpus."""
+        return None if self.len_dev is None else self.len_dev[a:b]
 
     def _start(self, a, b):
         if (a, b) in self.inflight or b <= a:

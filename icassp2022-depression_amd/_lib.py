@@ -39,6 +39,7 @@ class GradSync(C.Structure):
 
 
 _BWD_ARGS = [C.POINTER(RnnDesc), _P, C.POINTER(_P), _P, _P, _P, C.POINTER(_P), _P, _P, C.c_size_t, _P, C.c_size_t, _P]
+_BWD_VARLEN_ARGS = _BWD_ARGS[:2] + [_P] + _BWD_ARGS[2:]          # lengths (device int32) follow x
 _SIGS = {
     'dep_last_error': (C.c_char_p, []),
     'dep_version': (C.c_int, []),
@@ -54,6 +55,9 @@ _SIGS = {
     'dep_rnn_forward': (C.c_int, [C.POINTER(RnnDesc), _P, C.POINTER(_P), _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, _P]),
     'dep_rnn_backward': (C.c_int, _BWD_ARGS),
     'dep_rnn_backward_overlapped': (C.c_int, _BWD_ARGS + [C.POINTER(GradSync)]),
+    'dep_rnn_forward_varlen': (C.c_int, [C.POINTER(RnnDesc), _P, _P, C.POINTER(_P), _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, _P]),
+    'dep_rnn_backward_varlen': (C.c_int, _BWD_VARLEN_ARGS),
+    'dep_rnn_backward_overlapped_varlen': (C.c_int, _BWD_VARLEN_ARGS + [C.POINTER(GradSync)]),
     'dep_comm_available': (C.c_int, []),
     'dep_comm_unique_id': (C.c_int, [_P, C.c_size_t]),
     'dep_comm_init': (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, _P, C.c_size_t, C.c_int]),
@@ -80,6 +84,9 @@ _SIGS = {
     'dep_attn_bwd_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'dep_attn_bwd': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P,
                                C.c_size_t, _P]),
+    'dep_attn_fwd_varlen': (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    'dep_attn_bwd_varlen': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P,
+                                      C.c_size_t, _P]),
     'dep_dropout': (C.c_int, [_P, _P, C.c_long, C.c_float, C.c_uint64, C.c_uint32, _P]),
     'dep_dropout_mask': (C.c_int, [_P, C.c_long, C.c_float, C.c_uint64, C.c_uint32, _P]),
     'dep_relu_dropout_fwd': (C.c_int, [_P, _P, C.c_long, C.c_float, C.c_uint64, C.c_uint32, _P]),
@@ -118,8 +125,10 @@ EXPORTS = tuple(_SIGS)
 _lib = None
 
 
-def load():
-    """Load the shared library (once).  Raises DepError loudly if it is absent -- no CPU fallback."""
+def load(optional=()):
+    """Load the shared library (once).  Raises DepError loudly if it is absent -- no CPU fallback.
+    optional: names of EXPORTS the build may lack (an older build of the same ABI loaded through DEP_LIB_PATH for an A/B run,
+    tools/bench_ragged.py --lib); calling one of those afterwards is an AttributeError.  Every other symbol must resolve."""
     global _lib
     if _lib is not None:
         return _lib
@@ -128,6 +137,8 @@ def load():
                        '(hipcc --offload-arch=gfx950). The HIP path has no fallback.')
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in _SIGS.items():
+        if name in optional and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)       # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -369,7 +380,20 @@ def argmax_count(probs, labels=None, count=None, want_pred=False):
     return pred
 
 
-def attn_fwd(out, h_n, Wa, ba):
+def check_lengths(lengths, B, device):
+    """A ragged call's `lengths`: B int32 values on the call's device (checked on the host: dtype, device, size; the VALUES are
+    clamped to [0, T] by the kernels -- reading them here would cost a synchronisation)."""
+    if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32:
+        raise DepError(f'lengths must be an int32 tensor, got {getattr(lengths, "dtype", type(lengths))}')
+    dev = torch.device(device)
+    if not lengths.is_cuda or (dev.index is not None and lengths.device != dev):
+        raise DepError(f'lengths must live on {device}, got {lengths.device}')
+    if lengths.dim() != 1 or lengths.numel() != B or not lengths.is_contiguous():
+        raise DepError(f'lengths must be a contiguous vector of B = {B} elements, got shape {tuple(lengths.shape)}')
+    return lengths
+
+
+def attn_fwd(out, h_n, Wa, ba, lengths=None):
     B, T, H2 = out.shape
     H = H2 // 2
     K = h_n.shape[0]
@@ -378,12 +402,16 @@ def attn_fwd(out, h_n, Wa, ba):
     alpha = torch.empty(B, T, dtype=torch.float32, device=dev)
     pre = torch.empty(B, H, dtype=torch.float32, device=dev)
     hsum = torch.empty(B, H, dtype=torch.float32, device=dev)
+    if lengths is not None:
+        check(load().dep_attn_fwd_varlen(_ptr(out), _ptr(check_lengths(lengths, B, dev)), _ptr(h_n), K, _ptr(Wa), _ptr(ba), _ptr(ctx),
+                                         _ptr(alpha), _ptr(pre), _ptr(hsum), B, T, H, stream()), 'dep_attn_fwd_varlen')
+        return ctx, (alpha, pre, hsum)
     check(load().dep_attn_fwd(_ptr(out), _ptr(h_n), K, _ptr(Wa), _ptr(ba), _ptr(ctx), _ptr(alpha), _ptr(pre),
                               _ptr(hsum), B, T, H, stream()), 'dep_attn_fwd')
     return ctx, (alpha, pre, hsum)
 
 
-def attn_bwd(dctx, out, Wa, saved, K, dWa, dba):
+def attn_bwd(dctx, out, Wa, saved, K, dWa, dba, lengths=None):
     alpha, pre, hsum = saved
     B, T, H2 = out.shape
     H = H2 // 2
@@ -392,6 +420,11 @@ def attn_bwd(dctx, out, Wa, saved, K, dWa, dba):
     dout = torch.empty_like(out)
     dh_n = torch.empty(K, B, H, dtype=torch.float32, device=dev)
     ws = torch.empty(lib.dep_attn_bwd_workspace_bytes(B, T, H) // 4 + 64, dtype=torch.float32, device=dev)
+    if lengths is not None:
+        check(lib.dep_attn_bwd_varlen(_ptr(dctx), _ptr(out), _ptr(check_lengths(lengths, B, dev)), _ptr(Wa), _ptr(alpha), _ptr(pre),
+                                      _ptr(hsum), K, _ptr(dout), _ptr(dh_n), _ptr(dWa), _ptr(dba), B, T, H, _ptr(ws),
+                                      ws.numel() * 4, stream()), 'dep_attn_bwd_varlen')
+        return dout, dh_n
     check(lib.dep_attn_bwd(_ptr(dctx), _ptr(out), _ptr(Wa), _ptr(alpha), _ptr(pre), _ptr(hsum), K, _ptr(dout),
                            _ptr(dh_n), _ptr(dWa), _ptr(dba), B, T, H, _ptr(ws), ws.numel() * 4, stream()),
           'dep_attn_bwd')
@@ -475,23 +508,38 @@ class Rnn:
         n = d.B * d.T * d.H * d.dirs
         return self.reserve[off:off + n].view(d.B, d.T, d.H * d.dirs)
 
-    def forward(self, x, weights, seed=0, pooled=None, h_n=None, y=None):
+    def forward(self, x, weights, seed=0, pooled=None, h_n=None, y=None, lengths=None):
+        """lengths: int32 device tensor of B elements -> the ragged call (dep_rnn_forward_varlen: x is padded to T, row b is
+        lengths[b] steps long; padded positions of x must be finite)."""
         for i, w in enumerate(weights):
             self._warr[i] = w.data_ptr()
         self.desc.seed = seed
+        if lengths is not None:
+            check(self.lib.dep_rnn_forward_varlen(C.byref(self.desc), _ptr(x), _ptr(check_lengths(lengths, self.desc.B, self.device)),
+                                                  self._warr, _ptr(y), _ptr(pooled), _ptr(h_n), _ptr(self.reserve),
+                                                  self.reserve.numel() * 4, _ptr(self.workspace), self.workspace.numel() * 4,
+                                                  stream()), 'dep_rnn_forward_varlen')
+            return
         check(self.lib.dep_rnn_forward(C.byref(self.desc), _ptr(x), self._warr, _ptr(y), _ptr(pooled), _ptr(h_n),
                                        _ptr(self.reserve), self.reserve.numel() * 4, _ptr(self.workspace),
                                        self.workspace.numel() * 4, stream()), 'dep_rnn_forward')
 
-    def backward(self, x, weights, dweights, dy=None, dpooled=None, dh_n=None, dx=None, grad_sync=None):
+    def backward(self, x, weights, dweights, dy=None, dpooled=None, dh_n=None, dx=None, grad_sync=None, lengths=None):
         """grad_sync: a GradSync (data parallel) -> dep_rnn_backward_overlapped: layer l's range of the flat gradient
-        buffer is all-reduced on the communication stream beside the weight-gradient GEMMs of the layer below."""
+        buffer is all-reduced on the communication stream beside the weight-gradient GEMMs of the layer below.
+        lengths: the lengths of the ragged forward that wrote the reserve (the *_varlen entry points)."""
         for i, (w, g) in enumerate(zip(weights, dweights)):
             self._warr[i] = w.data_ptr()
             self._garr[i] = g.data_ptr()
         args = (C.byref(self.desc), _ptr(x), self._warr, _ptr(dy), _ptr(dpooled), _ptr(dh_n), self._garr, _ptr(dx),
                 _ptr(self.reserve), self.reserve.numel() * 4, _ptr(self.workspace), self.workspace.numel() * 4, stream())
-        if grad_sync is None:
+        if lengths is not None:
+            args = args[:2] + (_ptr(check_lengths(lengths, self.desc.B, self.device)),) + args[2:]
+            if grad_sync is None:
+                check(self.lib.dep_rnn_backward_varlen(*args), 'dep_rnn_backward_varlen')
+            else:
+                check(self.lib.dep_rnn_backward_overlapped_varlen(*args, C.byref(grad_sync)), 'dep_rnn_backward_overlapped_varlen')
+        elif grad_sync is None:
             check(self.lib.dep_rnn_backward(*args), 'dep_rnn_backward')
         else:
             check(self.lib.dep_rnn_backward_overlapped(*args, C.byref(grad_sync)), 'dep_rnn_backward_overlapped')

@@ -372,7 +372,11 @@ struct RnnPlan {
     int tag;                         // ReserveTag bits
 };
 
-RnnPlan make_plan(const dep_rnn_desc* d, const Layout& lo, int mode, bool excl) {
+// ragged: the call has a lengths array (dep_rnn_*_varlen).  It is planned only onto kernels that implement the per-row predicate -- the
+// tile / generic sweeps, the per-layer cluster GRU sweeps and the cluster BiLSTM sweeps, each of which launches its RAG instance when
+// the sweep arguments carry lengths -- never onto the fused two-layer launches or the 16-unit-member forward (so it enqueues no
+// soft-fallback launches either).  Everything else (images, saved-gate format, PK gate gradients) is decided as for a dense call.
+RnnPlan make_plan(const dep_rnn_desc* d, const Layout& lo, int mode, bool excl, bool ragged) {
     const RnnSwitches& sw = dep_rnn_switches();
     const bool gru = d->cell == DEP_CELL_GRU;
     RnnPlan p{};
@@ -380,9 +384,9 @@ RnnPlan make_plan(const dep_rnn_desc* d, const Layout& lo, int mode, bool excl) 
     const bool csplit = lo.cluster && p.split;
     // the kernels that fill every CU (fused forward, 16-unit members) are not for a shared GPU; the fused BACKWARD does not care
     const bool cluster16 = lo.cluster && dep_cluster16_ok(d->cell, d->H, d->B);
-    p.fwd = (lo.fused2 && p.split && excl) ? FWD_FUSED2 : (cluster16 && excl) ? FWD_CLUSTER16
+    p.fwd = (lo.fused2 && p.split && excl && !ragged) ? FWD_FUSED2 : (cluster16 && excl && !ragged) ? FWD_CLUSTER16
           : !lo.cluster ? FWD_TILE : gru ? FWD_CLUSTER_GRU : FWD_CLUSTER_LSTM;
-    p.bwd = (lo.fused2 && sw.fused2_bwd && p.split && dep_fused2_bwd_fits(d->B, d->T)) ? BWD_FUSED2
+    p.bwd = (lo.fused2 && sw.fused2_bwd && p.split && dep_fused2_bwd_fits(d->B, d->T) && !ragged) ? BWD_FUSED2
           : !lo.cluster ? BWD_TILE : gru ? BWD_CLUSTER_GRU : BWD_CLUSTER_LSTM;
     p.whh_f32 = lo.cluster ? !p.split : dep_sweep_use_mfma(d->H, d->impl);
     p.whh_fwd = !csplit ? WHH_NONE : !gru ? WHH_LSTM_PAIR : p.fwd == FWD_CLUSTER16 ? WHH_SPLIT16 : WHH_SPLIT32;
@@ -451,14 +455,23 @@ int reserve_tag_refusal(const void* reserve, int want, int bits) {
     return diff ? DEP_ERR_ARG : DEP_OK;
 }
 
+// ragged calls run in the parity modes only: the single-product modes' storage variants have no ragged instances
+int ragged_mode_refusal(const char* who, const int32_t* lengths, int mode) {
+    if (!lengths || mode <= 1) return DEP_OK;
+    dep_set_error("%s: a ragged call (lengths given) runs in GEMM modes 0 and 1 only; the current mode is %d (dep_set_gemm_mode)", who, mode);
+    return DEP_ERR_ARG;
+}
+
 }  // namespace
 
-extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const float* const* weights, float* y,
-                               float* pooled, float* h_n, void* reserve, size_t reserve_bytes, void* workspace,
-                               size_t workspace_bytes, void* stream) {
+static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights, float* y,
+                            float* pooled, float* h_n, void* reserve, size_t reserve_bytes, void* workspace,
+                            size_t workspace_bytes, void* stream) {
     Layout lo;
     DEP_CHECK_ARG(make_layout(d, lo));
-    const RnnPlan p = make_plan(d, lo, dep_get_gemm_mode(), dep_exclusive_on());
+    const int mode = dep_get_gemm_mode();
+    if (const int rf = ragged_mode_refusal("dep_rnn_forward_varlen", lengths, mode)) return rf;
+    const RnnPlan p = make_plan(d, lo, mode, dep_exclusive_on(), lengths != nullptr);
     DEP_CHECK_ARG(x && weights && reserve && workspace);
     DEP_CHECK_ARG(!(pooled && (d->cell != DEP_CELL_GRU || d->pool == DEP_POOL_NONE)));
     if (reserve_bytes < lo.reserve_floats * sizeof(float) || workspace_bytes < lo.ws_floats * sizeof(float)) {
@@ -509,6 +522,7 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
         a.h_n = h_n ? h_n + (size_t)l * D * B * H : nullptr;
         if (lo.keep) { a.sv0 = R + lo.sv[l][0]; a.sv1 = R + lo.sv[l][1]; a.sv2 = R + lo.sv[l][2]; a.sv3 = R + lo.sv[l][3]; }
         a.only_if = only_if; a.stream = s; a.sv16 = p.sv16_fwd ? 1 : 0;
+        a.lengths = lengths; a.pool_mean = d->pool == DEP_POOL_MEAN ? 1 : 0;
         // one exchange-header slot per layer, all zeroed by the call's one memset; the fused launch has slot 0, its fallbacks 1 + l
         a.hdr_slot = only_if ? 1 + l : (l < DEP_HDR_SLOTS ? l : 0); a.hdr_clean = only_if || l < DEP_HDR_SLOTS;
         return a;
@@ -623,13 +637,28 @@ extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const floa
     return DEP_OK;
 }
 
-static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float* const* weights, const float* dy,
+extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const float* const* weights, float* y,
+                               float* pooled, float* h_n, void* reserve, size_t reserve_bytes, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    return rnn_forward_impl(d, x, nullptr, weights, y, pooled, h_n, reserve, reserve_bytes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dep_rnn_forward_varlen(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights,
+                                      float* y, float* pooled, float* h_n, void* reserve, size_t reserve_bytes, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    DEP_CHECK_ARG(lengths);
+    return rnn_forward_impl(d, x, lengths, weights, y, pooled, h_n, reserve, reserve_bytes, workspace, workspace_bytes, stream);
+}
+
+static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights, const float* dy,
                              const float* dpooled, const float* dh_n, float* const* dweights, float* dx,
                              void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
                              void* stream, const dep_grad_sync* gs) {
     Layout lo;
     DEP_CHECK_ARG(make_layout(d, lo));
-    const RnnPlan p = make_plan(d, lo, dep_get_gemm_mode(), dep_exclusive_on());
+    const int mode = dep_get_gemm_mode();
+    if (const int rf = ragged_mode_refusal("dep_rnn_backward_varlen", lengths, mode)) return rf;
+    const RnnPlan p = make_plan(d, lo, mode, dep_exclusive_on(), lengths != nullptr);
     if (d->training != DEP_RUN_TRAIN) {
         dep_set_error("dep_rnn_backward: the descriptor's run mode is %d; a backward needs a DEP_RUN_TRAIN (1) forward's reserve%s", d->training,
                       d->training == DEP_RUN_DROPOUT_ONLY ? " (DEP_RUN_DROPOUT_ONLY keeps no saved gates)" : "");
@@ -723,6 +752,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const float*
         a.dbpart = W + (second ? lo.dbpart2 : lo.dbpart); a.dbpart_rows = D * lo.nwg; a.stream = s;
         a.hdr_slot = l < DEP_HDR_SLOTS ? l : 0; a.hdr_clean = l < DEP_HDR_SLOTS;
         a.dg_pk = pk ? 1 : 0; a.bf16st = p.bf16st ? 1 : 0; a.sv16 = p.sv16 ? 1 : 0;
+        a.lengths = lengths; a.pool_mean = d->pool == DEP_POOL_MEAN ? 1 : 0;
         return a;
     };
     float* pending_ptr = nullptr; long pending_n = 0;      // data parallel: a finished layer's gradient range waiting for the next sweep to be enqueued
@@ -862,7 +892,15 @@ extern "C" int dep_rnn_backward(const dep_rnn_desc* d, const float* x, const flo
                                 const float* dpooled, const float* dh_n, float* const* dweights, float* dx,
                                 void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
                                 void* stream) {
-    return rnn_backward_impl(d, x, weights, dy, dpooled, dh_n, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
+    return rnn_backward_impl(d, x, nullptr, weights, dy, dpooled, dh_n, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
+                             stream, nullptr);
+}
+
+extern "C" int dep_rnn_backward_varlen(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights,
+                                       const float* dy, const float* dpooled, const float* dh_n, float* const* dweights, float* dx,
+                                       void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    DEP_CHECK_ARG(lengths);
+    return rnn_backward_impl(d, x, lengths, weights, dy, dpooled, dh_n, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
                              stream, nullptr);
 }
 
@@ -871,6 +909,16 @@ extern "C" int dep_rnn_backward_overlapped(const dep_rnn_desc* d, const float* x
                                            void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
                                            void* stream, const dep_grad_sync* gs) {
     DEP_CHECK_ARG(gs && gs->comm && gs->comm_stream && gs->comm_stream != stream);
-    return rnn_backward_impl(d, x, weights, dy, dpooled, dh_n, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
+    return rnn_backward_impl(d, x, nullptr, weights, dy, dpooled, dh_n, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
+                             stream, gs);
+}
+
+extern "C" int dep_rnn_backward_overlapped_varlen(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights,
+                                                  const float* dy, const float* dpooled, const float* dh_n, float* const* dweights,
+                                                  float* dx, void* reserve, size_t reserve_bytes, void* workspace,
+                                                  size_t workspace_bytes, void* stream, const dep_grad_sync* gs) {
+    DEP_CHECK_ARG(lengths);
+    DEP_CHECK_ARG(gs && gs->comm && gs->comm_stream && gs->comm_stream != stream);
+    return rnn_backward_impl(d, x, lengths, weights, dy, dpooled, dh_n, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
                              stream, gs);
 }

@@ -50,25 +50,30 @@ __device__ __forceinline__ f32x4 tanh4(f32x4 v) { return f32x4{tanhf(v[0]), tanh
 __device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return fmaf(a[3], b[3], fmaf(a[2], b[2], fmaf(a[1], b[1], a[0] * b[0]))); }
 
 // HQ = H / 4 lanes per row; a wave covers 64 / HQ rows, the workgroup R = 8 * 64 / HQ rows per pass
-template <int HQ, bool CACHE>
+// RAG: ragged batches (dep_attn_fwd_varlen / dep_attn_bwd_varlen).  TS is the row stride of the padded arrays, T the utterance's own
+// length lengths[b] clamped to [0, TS]: the softmax runs over t < T, alpha and dout are exactly 0 behind it, an empty row gives ctx = 0.
+template <int HQ, bool CACHE, bool RAG = false>
 __global__ __launch_bounds__(AT) void attn_fwd2_kernel(const float* __restrict__ out, const float* __restrict__ pre,
-                                                       float* __restrict__ ctx, float* __restrict__ alpha, int T) {
+                                                       float* __restrict__ ctx, float* __restrict__ alpha, int TS,
+                                                       const int* __restrict__ lengths) {
     constexpr int H = HQ * 4, RPW = 64 / HQ, R = (AT / 64) * RPW;
+    const int T = RAG ? dep_row_len(lengths, blockIdx.x, TS) : TS;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* sc = smem;                                  // [T], padded to 4
-    float* red = sc + ((T + 3) & ~3);                  // [32]
+    float* sc = smem;                                  // [TS], padded to 4
+    float* red = sc + ((TS + 3) & ~3);                 // [32]
     float* vs = red + 32;                              // CACHE: h_t for the whole utterance; afterwards the R partial rows
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int jc = lane % HQ, g = w * RPW + lane / HQ;
-    const float* ob = out + (size_t)b * T * 2 * H + 4 * jc;
+    const float* ob = out + (size_t)b * TS * 2 * H + 4 * jc;
     f32x4 q4 = *reinterpret_cast<const f32x4*>(pre + (size_t)b * H + 4 * jc);
 #pragma unroll
     for (int e = 0; e < 4; ++e) q4[e] = fmaxf(q4[e], 0.f);
+    const int tlast = T > 0 ? T - 1 : 0;               // (T = 0: a ragged empty row; nothing below loops)
     for (int t0 = 0; t0 < T; t0 += R * AU) {
         f32x4 a[AU], c[AU];
 #pragma unroll
         for (int u = 0; u < AU; ++u) {                 // clamped, unconditional: 2 AU loads in flight
-            const int t = t0 + u * R + g, tc = t < T ? t : T - 1;
+            const int t = t0 + u * R + g, tc = t < T ? t : tlast;
             a[u] = *reinterpret_cast<const f32x4*>(ob + (size_t)tc * 2 * H);
             c[u] = *reinterpret_cast<const f32x4*>(ob + (size_t)tc * 2 * H + H);
         }
@@ -90,7 +95,8 @@ __global__ __launch_bounds__(AT) void attn_fwd2_kernel(const float* __restrict__
     float se = 0.f;
     for (int t = tid; t < T; t += AT) { const float e = expf(sc[t] - mx); sc[t] = e; se += e; }
     se = bsum(se, red);
-    for (int t = tid; t < T; t += AT) { const float al = sc[t] / se; sc[t] = al; alpha[(size_t)b * T + t] = al; }
+    for (int t = tid; t < T; t += AT) { const float al = sc[t] / se; sc[t] = al; alpha[(size_t)b * TS + t] = al; }
+    if constexpr (RAG) for (int t = T + tid; t < TS; t += AT) alpha[(size_t)b * TS + t] = 0.f;
     __syncthreads();
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int t0 = 0; t0 < T; t0 += R * AU) {
@@ -98,7 +104,7 @@ __global__ __launch_bounds__(AT) void attn_fwd2_kernel(const float* __restrict__
         if (!CACHE) {
 #pragma unroll
             for (int u = 0; u < AU; ++u) {
-                const int t = t0 + u * R + g, tc = t < T ? t : T - 1;
+                const int t = t0 + u * R + g, tc = t < T ? t : tlast;
                 a[u] = *reinterpret_cast<const f32x4*>(ob + (size_t)tc * 2 * H);
                 c[u] = *reinterpret_cast<const f32x4*>(ob + (size_t)tc * 2 * H + H);
             }
@@ -124,31 +130,41 @@ __global__ __launch_bounds__(AT) void attn_fwd2_kernel(const float* __restrict__
     }
 }
 
-template <int HQ, bool CACHE>
+template <int HQ, bool CACHE, bool RAG = false>
 __global__ __launch_bounds__(AT) void attn_bwd2_kernel(const float* __restrict__ dctx, const float* __restrict__ out,
                                                        const float* __restrict__ alpha, const float* __restrict__ pre,
-                                                       float* __restrict__ dout, float* __restrict__ dpre, int T) {
+                                                       float* __restrict__ dout, float* __restrict__ dpre, int TS,
+                                                       const int* __restrict__ lengths) {
     constexpr int H = HQ * 4, RPW = 64 / HQ, R = (AT / 64) * RPW;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int Tp = (T + 3) & ~3;
+    const int T = RAG ? dep_row_len(lengths, blockIdx.x, TS) : TS;
+    const int tlast = T > 0 ? T - 1 : 0;
+    const int Tp = (TS + 3) & ~3;
     float* al = smem;                                  // [Tp]
     float* ds = al + Tp;                               // [Tp]
     float* red = ds + Tp;                              // [32]
     float* vs = red + 32;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int jc = lane % HQ, g = w * RPW + lane / HQ;
-    const float* ob = out + (size_t)b * T * 2 * H + 4 * jc;
-    float* dob = dout + (size_t)b * T * 2 * H + 4 * jc;
+    const float* ob = out + (size_t)b * TS * 2 * H + 4 * jc;
+    float* dob = dout + (size_t)b * TS * 2 * H + 4 * jc;
     f32x4 q4 = *reinterpret_cast<const f32x4*>(pre + (size_t)b * H + 4 * jc);
 #pragma unroll
     for (int e = 0; e < 4; ++e) q4[e] = fmaxf(q4[e], 0.f);
     const f32x4 dc4 = *reinterpret_cast<const f32x4*>(dctx + (size_t)b * H + 4 * jc);
-    for (int t = tid; t < T; t += AT) al[t] = alpha[(size_t)b * T + t];
+    for (int t = tid; t < T; t += AT) al[t] = alpha[(size_t)b * TS + t];
+    if constexpr (RAG) {                               // dout is exactly 0 behind the utterance's last step
+        const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int t = T + g; t < TS; t += R) {
+            *reinterpret_cast<f32x4*>(dob + (size_t)t * 2 * H) = z;
+            *reinterpret_cast<f32x4*>(dob + (size_t)t * 2 * H + H) = z;
+        }
+    }
     for (int t0 = 0; t0 < T; t0 += R * AU) {
         f32x4 a[AU], c[AU];
 #pragma unroll
         for (int u = 0; u < AU; ++u) {
-            const int t = t0 + u * R + g, tc = t < T ? t : T - 1;
+            const int t = t0 + u * R + g, tc = t < T ? t : tlast;
             a[u] = *reinterpret_cast<const f32x4*>(ob + (size_t)tc * 2 * H);
             c[u] = *reinterpret_cast<const f32x4*>(ob + (size_t)tc * 2 * H + H);
         }
@@ -175,7 +191,7 @@ __global__ __launch_bounds__(AT) void attn_bwd2_kernel(const float* __restrict__
         if (!CACHE) {
 #pragma unroll
             for (int u = 0; u < AU; ++u) {
-                const int t = t0 + u * R + g, tc = t < T ? t : T - 1;
+                const int t = t0 + u * R + g, tc = t < T ? t : tlast;
                 a[u] = *reinterpret_cast<const f32x4*>(ob + (size_t)tc * 2 * H);
                 c[u] = *reinterpret_cast<const f32x4*>(ob + (size_t)tc * 2 * H + H);
             }
@@ -224,7 +240,7 @@ bool v1_forced() {
 }  // namespace
 
 // Both return 1 when they launched, 0 when the shape is left to the first-generation kernels (elementwise.hip).
-int dep_attn2_fwd(const float* out, const float* pre, float* ctx, float* alpha, int B, int T, int H, hipStream_t s) {
+int dep_attn2_fwd(const float* out, const float* pre, float* ctx, float* alpha, int B, int T, int H, const int* lengths, hipStream_t s) {
     if (v1_forced() || !(H == 64 || H == 128 || H == 256) || !al16(out) || !al16(pre)) return 0;
     const int R = (AT / 64) * (64 / (H / 4));
     const size_t fixed = (size_t)(((T + 3) & ~3) + 32) * 4;
@@ -234,10 +250,16 @@ int dep_attn2_fwd(const float* out, const float* pre, float* ctx, float* alpha, 
     if (lds > (size_t)LDS_MAX) return 0;
 #define GO(HQ)                                                                                                   \
     do {                                                                                                         \
+        if (lengths) {                                                                                           \
+            if (cache) { allow_lds(attn_fwd2_kernel<HQ, true, true>, lds);                                       \
+                         DEP_LAUNCH((attn_fwd2_kernel<HQ, true, true>), dim3(B), dim3(AT), lds, s, out, pre, ctx, alpha, T, lengths); } \
+            else { allow_lds(attn_fwd2_kernel<HQ, false, true>, lds);                                            \
+                   DEP_LAUNCH((attn_fwd2_kernel<HQ, false, true>), dim3(B), dim3(AT), lds, s, out, pre, ctx, alpha, T, lengths); } \
+        } else                                                                                                   \
         if (cache) { allow_lds(attn_fwd2_kernel<HQ, true>, lds);                                                 \
-                     DEP_LAUNCH((attn_fwd2_kernel<HQ, true>), dim3(B), dim3(AT), lds, s, out, pre, ctx, alpha, T); } \
+                     DEP_LAUNCH((attn_fwd2_kernel<HQ, true>), dim3(B), dim3(AT), lds, s, out, pre, ctx, alpha, T, lengths); } \
         else { allow_lds(attn_fwd2_kernel<HQ, false>, lds);                                                      \
-               DEP_LAUNCH((attn_fwd2_kernel<HQ, false>), dim3(B), dim3(AT), lds, s, out, pre, ctx, alpha, T); }      \
+               DEP_LAUNCH((attn_fwd2_kernel<HQ, false>), dim3(B), dim3(AT), lds, s, out, pre, ctx, alpha, T, lengths); }      \
     } while (0)
     if (H == 64) GO(16); else if (H == 128) GO(32); else GO(64);
 #undef GO
@@ -245,7 +267,7 @@ int dep_attn2_fwd(const float* out, const float* pre, float* ctx, float* alpha, 
 }
 
 int dep_attn2_bwd(const float* dctx, const float* out, const float* alpha, const float* pre, float* dout, float* dpre, int B,
-                  int T, int H, hipStream_t s) {
+                  int T, int H, const int* lengths, hipStream_t s) {
     if (v1_forced() || !(H == 64 || H == 128 || H == 256) || !al16(out) || !al16(pre) || !al16(dctx) || !al16(dout)) return 0;
     const int R = (AT / 64) * (64 / (H / 4));
     const size_t fixed = (size_t)(2 * ((T + 3) & ~3) + 32) * 4;
@@ -255,10 +277,16 @@ int dep_attn2_bwd(const float* dctx, const float* out, const float* alpha, const
     if (lds > (size_t)LDS_MAX) return 0;
 #define GO(HQ)                                                                                                   \
     do {                                                                                                         \
+        if (lengths) {                                                                                           \
+            if (cache) { allow_lds(attn_bwd2_kernel<HQ, true, true>, lds);                                       \
+                         DEP_LAUNCH((attn_bwd2_kernel<HQ, true, true>), dim3(B), dim3(AT), lds, s, dctx, out, alpha, pre, dout, dpre, T, lengths); } \
+            else { allow_lds(attn_bwd2_kernel<HQ, false, true>, lds);                                            \
+                   DEP_LAUNCH((attn_bwd2_kernel<HQ, false, true>), dim3(B), dim3(AT), lds, s, dctx, out, alpha, pre, dout, dpre, T, lengths); } \
+        } else                                                                                                   \
         if (cache) { allow_lds(attn_bwd2_kernel<HQ, true>, lds);                                                 \
-                     DEP_LAUNCH((attn_bwd2_kernel<HQ, true>), dim3(B), dim3(AT), lds, s, dctx, out, alpha, pre, dout, dpre, T); } \
+                     DEP_LAUNCH((attn_bwd2_kernel<HQ, true>), dim3(B), dim3(AT), lds, s, dctx, out, alpha, pre, dout, dpre, T, lengths); } \
         else { allow_lds(attn_bwd2_kernel<HQ, false>, lds);                                                      \
-               DEP_LAUNCH((attn_bwd2_kernel<HQ, false>), dim3(B), dim3(AT), lds, s, dctx, out, alpha, pre, dout, dpre, T); }      \
+               DEP_LAUNCH((attn_bwd2_kernel<HQ, false>), dim3(B), dim3(AT), lds, s, dctx, out, alpha, pre, dout, dpre, T, lengths); }      \
     } while (0)
     if (H == 64) GO(16); else if (H == 128) GO(32); else GO(64);
 #undef GO

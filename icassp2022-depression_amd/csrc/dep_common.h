@@ -66,6 +66,29 @@ __device__ __forceinline__ float dep_dropmask1(uint64_t seed, uint32_t site, uin
     return m[idx & 3];
 }
 
+// ---- ragged batches (dep_rnn_*_varlen, include/dep_rnn.h) ---------------------------------------------
+// Row b's length as the kernels use it: clamped to [0, T] on the device (the host never sees the values).
+__device__ __forceinline__ int dep_row_len(const int* lengths, int b, int T) { const int n = lengths[b]; return n < 0 ? 0 : (n > T ? T : n); }
+// Pool scale of a ragged row: 1 / len for the mean (the dense call's own 1 / T when len == T, so that a ragged call with
+// every length T reproduces the dense call's bits; 0 for an empty row, which divides by nothing), 1 for the sum.
+__device__ __forceinline__ float dep_ragged_pool_scale(int pool_mean, int len, int T, float dense_scale) {
+    return !pool_mean ? 1.0f : len == T ? dense_scale : len > 0 ? 1.0f / (float)len : 0.f;
+}
+__device__ __forceinline__ float2 dep_sel2(bool c, float2 a, float2 b) { return make_float2(c ? a.x : b.x, c ? a.y : b.y); }
+__device__ __forceinline__ f32x4 dep_sel4(bool c, f32x4 a, f32x4 b) { f32x4 r = {c ? a[0] : b[0], c ? a[1] : b[1], c ? a[2] : b[2], c ? a[3] : b[3]}; return r; }
+
+// DEP_FP_CONTRACT_NOTE.  The forward sweeps that have a ragged instance (gru_fwd_mfma, lstm_fwd_mfma, gru_fwd_generic, gru_fwd_cluster_r1,
+// lstm_fwd_cluster) open with `#pragma clang fp contract(on)`: a * b + c written in ONE expression is one fma (the product on the left
+// of the sum is the fused one) and nothing else is fused.  Under the default (contract = fast) the backend decides, and its choice
+// depends on what surrounds the expression -- the selects of a ragged instance, or a neighbouring product the vectoriser pairs it
+// with -- so the dense and the ragged instance of one kernel rounded differently; a ragged call whose lengths all equal T must reproduce
+// the dense call's bits (tests/test_varlen_gpu.py).  The expressions are written so that the dense instances keep the operations the
+// backend chose before (h = z * h_prev + (1 - z) * n: the fused product first).  To re-verify after a compiler change: compile the
+// file at the commit before the pragma and now with `hipcc --offload-arch=gfx950 -O3 --cuda-device-only -S`, and compare the dense
+// instances' v_fma / v_mul / v_add / v_pk_* instructions (same multiset; operands of a product may swap); tests/golden/device_bits.json
+// (tests/test_presplit_gpu.py) anchors the results on the device.  The backward sweeps keep the default: there the ragged instances
+// select on final results only (the split words, the summed dh), which leaves the arithmetic of a live step as the dense instance has it.
+
 // dropout sites (Philox counter word 2): distinct per place a mask is drawn in one step
 enum { DEP_SITE_RNN0 = 16 /* + layer */, DEP_SITE_USER = 0 };
 
@@ -173,6 +196,8 @@ struct dep_sweep_args {
     const unsigned* only_if;  // cluster forward: run only when this device word is non-zero (fallback behind an exclusive kernel), or NULL
     int sv16;                 // GRU cluster sweeps: sv0..sv2 (r, z, n) are 16-bit fixed point (rnn_cluster_common.h), sv3 (hn) stays fp32
     int hdr_slot, hdr_clean;  // cluster sweeps: exchange-header slot of this launch; clean = the caller zeroed it (rnn_cluster_common.h)
+    const int* lengths;       // ragged call: (B) int32 device array, row b is live for t < lengths[b]; NULL = dense (the dense instances)
+    int pool_mean;            // ragged call: the pool is a mean (scale 1 / lengths[b]), not a sum
     hipStream_t stream;
 };
 int dep_launch_sweep_fwd(const dep_sweep_args& a);
@@ -200,6 +225,8 @@ struct dep_sweep_bwd_args {
     int sv16;                // saved gates r, z, n are 16-bit fixed point (must match the forward that wrote them)
     int dg_pk;               // GRU cluster sweep (burst kernel, 4H-wide rows): dgi / dghn as the PK image of gemm_bf16x3.hip instead of fp32
     int bf16st;              // bf16-storage mode (dep_set_gemm_mode(3)): y and hn are bf16 arrays, the gate gradients the PKH image (hi rows only)
+    const int* lengths;      // ragged call (the lengths of the forward that wrote the reserve), or NULL
+    int pool_mean;           // ragged call: dpooled is the gradient of a mean (scaled by 1 / lengths[b])
     hipStream_t stream;
 };
 bool dep_cluster_bwd_pk_ok(int H, int T);
@@ -278,9 +305,9 @@ int dep_pack_cluster_bwd_split(const float* w_hh, float* out, int H, hipStream_t
 int dep_pack_cluster_split_multi(int n, const float* const* src, float* const* dst, const int* bwd, int H, hipStream_t s);
 int dep_multi_copy(int count, const float* const* src, const float* const* add, float* const* dst, const long* n, hipStream_t s);
 // attention.hip: the loads-in-flight attention kernels (H in {64,128,256}); 1 = launched, 0 = shape left to elementwise.hip's
-int dep_attn2_fwd(const float* out, const float* pre, float* ctx, float* alpha, int B, int T, int H, hipStream_t s);
+int dep_attn2_fwd(const float* out, const float* pre, float* ctx, float* alpha, int B, int T, int H, const int* lengths, hipStream_t s);
 int dep_attn2_bwd(const float* dctx, const float* out, const float* alpha, const float* pre, float* dout, float* dpre, int B,
-                  int T, int H, hipStream_t s);
+                  int T, int H, const int* lengths, hipStream_t s);
 int dep_pack_cluster_fwd_split(const float* w_hh, float* out, int H, hipStream_t s);
 int dep_pack_cluster_lstm_split(const float* w_hh, float* wp, float* wpT, int H, hipStream_t s);
 int dep_launch_cluster16_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf_bytes);

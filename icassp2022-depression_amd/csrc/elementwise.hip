@@ -404,13 +404,16 @@ __global__ void attn_bcast_kernel(const float* __restrict__ src, int K, long BH,
 }
 
 // one workgroup per utterance.  LDS: q[H] | sc[T] | red[16]
+// RAG (ragged batches, dep_attn_*_varlen): TS is the row stride of the padded arrays, T the utterance's own length (attention.hip)
+template <bool RAG = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__ out, const float* __restrict__ pre,
                                                        float* __restrict__ ctx, float* __restrict__ alpha,
-                                                       int T, int H) {
+                                                       int TS, int H, const int* __restrict__ lengths) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* q = smem; float* sc = smem + H; float* red = sc + T;
+    float* q = smem; float* sc = smem + H; float* red = sc + TS;
     const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const float* ob = out + (size_t)b * T * 2 * H;
+    const int T = RAG ? dep_row_len(lengths, b, TS) : TS;
+    const float* ob = out + (size_t)b * TS * 2 * H;
     for (int j = threadIdx.x; j < H; j += blockDim.x) q[j] = fmaxf(pre[(size_t)b * H + j], 0.f);
     __syncthreads();
     for (int t = w; t < T; t += nw) {
@@ -428,7 +431,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__
     for (int t = threadIdx.x; t < T; t += blockDim.x) { const float e = expf(sc[t] - mx); sc[t] = e; se += e; }
     se = block_sum(se, red);
     __syncthreads();
-    for (int t = threadIdx.x; t < T; t += blockDim.x) { const float a = sc[t] / se; sc[t] = a; alpha[(size_t)b * T + t] = a; }
+    for (int t = threadIdx.x; t < T; t += blockDim.x) { const float a = sc[t] / se; sc[t] = a; alpha[(size_t)b * TS + t] = a; }
+    if constexpr (RAG) for (int t = T + threadIdx.x; t < TS; t += blockDim.x) alpha[(size_t)b * TS + t] = 0.f;
     __syncthreads();
     for (int j = threadIdx.x; j < H; j += blockDim.x) {
         float s = 0.f;
@@ -438,19 +442,22 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__
 }
 
 // LDS: q[H] | dc[H] | al[T] | ds[T] | red[16]
+template <bool RAG = false>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__ dctx, const float* __restrict__ out,
                                                        const float* __restrict__ alpha, const float* __restrict__ pre,
-                                                       float* __restrict__ dout, float* __restrict__ dpre, int T, int H) {
+                                                       float* __restrict__ dout, float* __restrict__ dpre, int TS, int H,
+                                                       const int* __restrict__ lengths) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* q = smem; float* dc = q + H; float* al = dc + H; float* ds = al + T; float* red = ds + T;
+    float* q = smem; float* dc = q + H; float* al = dc + H; float* ds = al + TS; float* red = ds + TS;
     const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const float* ob = out + (size_t)b * T * 2 * H;
-    float* dob = dout + (size_t)b * T * 2 * H;
+    const int T = RAG ? dep_row_len(lengths, b, TS) : TS;
+    const float* ob = out + (size_t)b * TS * 2 * H;
+    float* dob = dout + (size_t)b * TS * 2 * H;
     for (int j = threadIdx.x; j < H; j += blockDim.x) {
         q[j] = fmaxf(pre[(size_t)b * H + j], 0.f);
         dc[j] = dctx[(size_t)b * H + j];
     }
-    for (int t = threadIdx.x; t < T; t += blockDim.x) al[t] = alpha[(size_t)b * T + t];
+    for (int t = threadIdx.x; t < T; t += blockDim.x) al[t] = alpha[(size_t)b * TS + t];
     __syncthreads();
     for (int t = w; t < T; t += nw) {
         const float* r = ob + (size_t)t * 2 * H;
@@ -477,6 +484,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
             dob[(size_t)t * 2 * H + j] = dh;
             dob[(size_t)t * 2 * H + H + j] = dh;
         }
+        if constexpr (RAG) for (int t = T; t < TS; ++t) { dob[(size_t)t * 2 * H + j] = 0.f; dob[(size_t)t * 2 * H + H + j] = 0.f; }
         dpre[(size_t)b * H + j] = pre[(size_t)b * H + j] > 0.f ? dq : 0.f;
     }
 }
@@ -671,20 +679,30 @@ extern "C" int dep_argmax_count(const float* p, const void* labels, int labels_i
     return DEP_OK;
 }
 
-extern "C" int dep_attn_fwd(const float* out, const float* h_n, int K, const float* Wa, const float* ba, float* ctx,
-                            float* alpha, float* pre, float* hsum, int B, int T, int H, void* stream) {
+static int attn_fwd_impl(const float* out, const float* h_n, int K, const float* Wa, const float* ba, float* ctx,
+                         float* alpha, float* pre, float* hsum, int B, int T, int H, const int* lengths, void* stream) {
     DEP_CHECK_ARG(out && h_n && Wa && ba && ctx && alpha && pre && hsum && B > 0 && T > 0 && H > 0 && K > 0);
     const long BH = (long)B * H;
     DEP_LAUNCH(attn_hsum_kernel, dim3(nblk(BH)), dim3(256), 0, S_, h_n, K, BH, hsum);
     DEP_CHECK_LAUNCH();
     int rc = dep_gemm_internal(0, 1, B, H, H, hsum, H, Wa, H, pre, H, ba, 0.f, 0, 0, nullptr, 0, DepGemmOpts{}, S_);
     if (rc) return rc;
-    if (!dep_attn2_fwd(out, pre, ctx, alpha, B, T, H, S_)) {
+    if (!dep_attn2_fwd(out, pre, ctx, alpha, B, T, H, lengths, S_)) {
         const size_t lds = (size_t)(H + T + 16) * sizeof(float);
-        DEP_LAUNCH(attn_fwd_kernel, dim3(B), dim3(256), lds, S_, out, pre, ctx, alpha, T, H);
+        if (lengths) DEP_LAUNCH(attn_fwd_kernel<true>, dim3(B), dim3(256), lds, S_, out, pre, ctx, alpha, T, H, lengths);
+        else DEP_LAUNCH(attn_fwd_kernel<>, dim3(B), dim3(256), lds, S_, out, pre, ctx, alpha, T, H, lengths);
     }
     DEP_CHECK_LAUNCH();
     return DEP_OK;
+}
+extern "C" int dep_attn_fwd(const float* out, const float* h_n, int K, const float* Wa, const float* ba, float* ctx,
+                            float* alpha, float* pre, float* hsum, int B, int T, int H, void* stream) {
+    return attn_fwd_impl(out, h_n, K, Wa, ba, ctx, alpha, pre, hsum, B, T, H, nullptr, stream);
+}
+extern "C" int dep_attn_fwd_varlen(const float* out, const int32_t* lengths, const float* h_n, int K, const float* Wa, const float* ba,
+                                   float* ctx, float* alpha, float* pre, float* hsum, int B, int T, int H, void* stream) {
+    DEP_CHECK_ARG(lengths);
+    return attn_fwd_impl(out, h_n, K, Wa, ba, ctx, alpha, pre, hsum, B, T, H, lengths, stream);
 }
 
 extern "C" size_t dep_attn_bwd_workspace_bytes(int B, int T, int H) {
@@ -692,9 +710,9 @@ extern "C" size_t dep_attn_bwd_workspace_bytes(int B, int T, int H) {
     return dep_align((size_t)2 * B * H * sizeof(float)) + dep_gemm_workspace_bytes(1, 0, H, H, B);
 }
 
-extern "C" int dep_attn_bwd(const float* dctx, const float* out, const float* Wa, const float* alpha, const float* pre,
-                            const float* hsum, int K, float* dout, float* dh_n, float* dWa, float* dba, int B, int T,
-                            int H, void* workspace, size_t workspace_bytes, void* stream) {
+static int attn_bwd_impl(const float* dctx, const float* out, const float* Wa, const float* alpha, const float* pre,
+                         const float* hsum, int K, float* dout, float* dh_n, float* dWa, float* dba, int B, int T,
+                         int H, const int* lengths, void* workspace, size_t workspace_bytes, void* stream) {
     DEP_CHECK_ARG(dctx && out && Wa && alpha && pre && hsum && dout && dh_n && dWa && dba && B > 0 && T > 0 && H > 0);
     if (!workspace || workspace_bytes < dep_attn_bwd_workspace_bytes(B, T, H)) {
         dep_set_error("dep_attn_bwd: workspace too small"); return DEP_ERR_WORKSPACE;
@@ -703,9 +721,10 @@ extern "C" int dep_attn_bwd(const float* dctx, const float* out, const float* Wa
     float* dhs = dpre + (size_t)B * H;
     char* gws = (char*)workspace + dep_align((size_t)2 * B * H * sizeof(float));
     const size_t gws_bytes = workspace_bytes - dep_align((size_t)2 * B * H * sizeof(float));
-    if (!dep_attn2_bwd(dctx, out, alpha, pre, dout, dpre, B, T, H, S_)) {
+    if (!dep_attn2_bwd(dctx, out, alpha, pre, dout, dpre, B, T, H, lengths, S_)) {
         const size_t lds = (size_t)(2 * H + 2 * T + 16) * sizeof(float);
-        DEP_LAUNCH(attn_bwd_kernel, dim3(B), dim3(256), lds, S_, dctx, out, alpha, pre, dout, dpre, T, H);
+        if (lengths) DEP_LAUNCH(attn_bwd_kernel<true>, dim3(B), dim3(256), lds, S_, dctx, out, alpha, pre, dout, dpre, T, H, lengths);
+        else DEP_LAUNCH(attn_bwd_kernel<>, dim3(B), dim3(256), lds, S_, dctx, out, alpha, pre, dout, dpre, T, H, lengths);
     }
     DEP_CHECK_LAUNCH();
     // dWa (H,H) = dpre^T (H,B) * hsum (B,H) ; dba = colsum(dpre) ; dhsum = dpre * Wa
@@ -719,4 +738,15 @@ extern "C" int dep_attn_bwd(const float* dctx, const float* out, const float* Wa
     DEP_LAUNCH(attn_bcast_kernel, dim3(nblk(BH)), dim3(256), 0, S_, dhs, K, BH, dh_n);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
+}
+extern "C" int dep_attn_bwd(const float* dctx, const float* out, const float* Wa, const float* alpha, const float* pre,
+                            const float* hsum, int K, float* dout, float* dh_n, float* dWa, float* dba, int B, int T,
+                            int H, void* workspace, size_t workspace_bytes, void* stream) {
+    return attn_bwd_impl(dctx, out, Wa, alpha, pre, hsum, K, dout, dh_n, dWa, dba, B, T, H, nullptr, workspace, workspace_bytes, stream);
+}
+extern "C" int dep_attn_bwd_varlen(const float* dctx, const float* out, const int32_t* lengths, const float* Wa, const float* alpha,
+                                   const float* pre, const float* hsum, int K, float* dout, float* dh_n, float* dWa, float* dba,
+                                   int B, int T, int H, void* workspace, size_t workspace_bytes, void* stream) {
+    DEP_CHECK_ARG(lengths);
+    return attn_bwd_impl(dctx, out, Wa, alpha, pre, hsum, K, dout, dh_n, dWa, dba, B, T, H, lengths, workspace, workspace_bytes, stream);
 }

@@ -37,6 +37,7 @@ struct P2 {
     int ntload;              // non-temporal one-touch input streams (default on; DEP_BWD_NTLD=0: plain loads)
     int wflags;              // DEP_BWD_WFLAGS: every compute wave raises its OWN epoch flag once its own payload stores are acknowledged (no workgroup barrier in front of the flag; the pollers watch 4 NC words)
     int dgpk;                // round 4: write the gate gradients as the PK image the bf16x3 GEMMs read without converting (gemm_bf16x3.hip FMT_PK): rows (t even, t+1) of an utterance hold the (hi, lo) bf16 pairs of both steps; burst kernel, 4H-wide layout, T even
+    const int* lengths; int pool_mean;      // ragged instances (RAG): row b is live for t < lengths[b]; dpooled of a mean is scaled by 1 / lengths[b]
 };
 
 struct StepIn { float2 r, z, n, hn, hp, dy; };
@@ -79,7 +80,11 @@ constexpr size_t burst_lds_bytes_ag(int KB) { return (size_t)(AG_IBUF_F + KB * 6
 // just issued (both settings 5-20 % slower than the kernel without the switch, profiles/r04_ab_pairs.txt).
 // BF (bf16-storage mode, dep_set_gemm_mode(3); implies SV16, burst kernel only): hn and the hidden sequence y are bf16 arrays (2-byte
 // elements at the same positions), and the gate gradients go out as the PKH image (only the hi rows of the PK image).
-template <int NTW, bool SPLIT, int KB, bool SV16 = false, bool BF = false, bool AG = false>      // output tiles per wave = H/64
+// RAG: the ragged-batch instances (dep_rnn_backward_varlen).  The row is owned by a lane, so the predicate live = t < lengths[b] is a
+// handful of selects in the gate phase: a dead step's gate gradients are 0 (what the members exchange, the write-out and the bias sums
+// see) and its incoming dh passes through to step t-1 unchanged.  Trip counts, epochs, flags, the service waves and the burst write-out
+// are those of the dense instances: every workgroup runs all T steps.
+template <int NTW, bool SPLIT, int KB, bool SV16 = false, bool BF = false, bool AG = false, bool RAG = false>      // output tiles per wave = H/64
 __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1(P2 p) {
     static_assert(!BF || (SV16 && KB > 0), "bf16 storage: 16-bit gates, burst kernel");
     static_assert(!AG || (SPLIT && KB == 4 && NTW == 4), "all-gather exchange: H = 256, split products, burst length 4");
@@ -140,7 +145,10 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
     }
     float2 dhrec = (p.dh_n && valid && !svc) ? ld2(p.dh_n + (size_t)b * H + col) : f2(0.f, 0.f);
     float2 dpl = f2(0.f, 0.f);
-    if (p.dpooled && valid && !svc) { dpl = ld2(p.dpooled + (size_t)b * H + col); dpl.x *= p.pool_scale; dpl.y *= p.pool_scale; }
+    int len = T;
+    if constexpr (RAG) len = (valid && !svc) ? dep_row_len(p.lengths, b, T) : 0;
+    const float dps = RAG ? dep_ragged_pool_scale(p.pool_mean, len, T, p.pool_scale) : p.pool_scale;
+    if (p.dpooled && valid && !svc) { dpl = ld2(p.dpooled + (size_t)b * H + col); dpl.x *= dps; dpl.y *= dps; }
     float2 dbr = f2(0.f, 0.f), dbz = dbr, dbn = dbr, dbh = dbr;
     const size_t pstride = (size_t)p.nbtp * NC * BT * H;                   // floats per parity buffer
     const size_t tile_base = (size_t)bt * NC * BT * H;                     // this tile's [NC][NTT][64][4] block
@@ -447,10 +455,21 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
             dr.x = dn.x * hn.x * r.x * (1.0f - r.x); dr.y = dn.y * hn.y * r.y * (1.0f - r.y);
             dnr.x = dn.x * r.x; dnr.y = dn.y * r.y;
             dzt.x = d.x * z.x; dzt.y = d.y * z.y;
+            const float2 drr = dr, dzr = dz, dnrr = dnr;
+            if constexpr (RAG) {
+                const bool live = t < len;
+                const float2 z2 = f2(0.f, 0.f);
+                dn = dep_sel2(live, dn, z2); dz = dep_sel2(live, dz, z2); dr = dep_sel2(live, dr, z2); dnr = dep_sel2(live, dnr, z2);
+            }
             const unsigned epoch = (unsigned)(k + 1);
             if (t > 0) {      // publish first: the (hi, lo) pair words of dr, dz, dn*r -- what every member's MFMAs read
                 unsigned h0, l0, h1, l1, h2, l2;
-                split_pair(dr.x, dr.y, h0, l0); split_pair(dz.x, dz.y, h1, l1); split_pair(dnr.x, dnr.y, h2, l2);
+                if constexpr (RAG) {      // the words of the unselected values (rounded as the dense instance rounds them), zeroed for a dead step
+                    split_pair(drr.x, drr.y, h0, l0); split_pair(dzr.x, dzr.y, h1, l1); split_pair(dnrr.x, dnrr.y, h2, l2);
+                    if (t >= len) { h0 = l0 = h1 = l1 = h2 = l2 = 0u; }
+                } else {
+                    split_pair(dr.x, dr.y, h0, l0); split_pair(dz.x, dz.y, h1, l1); split_pair(dnr.x, dnr.y, h2, l2);
+                }
                 const unsigned po = (unsigned)(t & 1) * par_bytes + pub0;
                 const unsigned wds[6] = {h0, l0, h1, l1, h2, l2};
                 if (fast) {           // same-XCD clusters: plain stores (that XCD's L2 is the coherence point)
@@ -508,7 +527,8 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
             float2 s = f2(0.f, 0.f);
 #pragma unroll
             for (int q4 = 0; q4 < 4; ++q4) { const float2 v = ld2(rr + q4 * 512); s.x += v.x; s.y += v.y; }      // fixed order: deterministic
-            dhrec = f2(dzt.x + s.x, dzt.y + s.y);
+            if constexpr (RAG) dhrec = dep_sel2(t < len, f2(dzt.x + s.x, dzt.y + s.y), dhrec);      // dead step: the incoming dh passes through
+            else dhrec = f2(dzt.x + s.x, dzt.y + s.y);
             BSTAMP(6);
         }
     } else
@@ -530,9 +550,20 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
         dr.x = dn.x * hn.x * r.x * (1.0f - r.x); dr.y = dn.y * hn.y * r.y * (1.0f - r.y);
         dnr.x = dn.x * r.x; dnr.y = dn.y * r.y;
         dzt.x = d.x * z.x; dzt.y = d.y * z.y;
+        const float2 drr = dr, dzr = dz, dnrr = dnr;
+        if constexpr (RAG) {
+            const bool live = t < len;
+            const float2 z2 = f2(0.f, 0.f);
+            dn = dep_sel2(live, dn, z2); dz = dep_sel2(live, dz, z2); dr = dep_sel2(live, dr, z2); dnr = dep_sel2(live, dnr, z2);
+        }
         if constexpr (SPLIT) {                        // one (hi, lo) bf16 pair word per gate: units ul, ul+1
             unsigned h0, l0, h1, l1, h2, l2;
-            split_pair(dr.x, dr.y, h0, l0); split_pair(dz.x, dz.y, h1, l1); split_pair(dnr.x, dnr.y, h2, l2);
+            if constexpr (RAG) {          // the words of the unselected values (rounded as the dense instance rounds them), zeroed for a dead step
+                split_pair(drr.x, drr.y, h0, l0); split_pair(dzr.x, dzr.y, h1, l1); split_pair(dnrr.x, dnrr.y, h2, l2);
+                if (t >= len) { h0 = l0 = h1 = l1 = h2 = l2 = 0u; }
+            } else {
+                split_pair(dr.x, dr.y, h0, l0); split_pair(dz.x, dz.y, h1, l1); split_pair(dnr.x, dnr.y, h2, l2);
+            }
             const int o = j * LDGB + ul;
             *reinterpret_cast<unsigned*>(dg_hi + o) = h0; *reinterpret_cast<unsigned*>(dg_lo + o) = l0;
             *reinterpret_cast<unsigned*>(dg_hi + o + 32) = h1; *reinterpret_cast<unsigned*>(dg_lo + o + 32) = l1;
@@ -629,7 +660,8 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
         for (int m = 0; m < NCM; ++m) part[m] = ld2_agent(src + (size_t)m * NTT * 256);
 #pragma unroll
         for (int m = 0; m < NCM; ++m) { s.x += part[m].x; s.y += part[m].y; }
-        dhrec = f2(dzt.x + s.x, dzt.y + s.y);
+        if constexpr (RAG) dhrec = dep_sel2(t < len, f2(dzt.x + s.x, dzt.y + s.y), dhrec);      // dead step: the incoming dh passes through
+        else dhrec = f2(dzt.x + s.x, dzt.y + s.y);
         if constexpr (!BURST) cur = nxt;
         BSTAMP(6);
     }
@@ -670,10 +702,15 @@ struct F2 {
     long long* trace;        // debug: s_memtime stamps of workgroup 0 (DEP_TRACE=1), else nullptr
     const unsigned* only_if; // run only if this word is set (fallback behind an exclusive forward kernel), or nullptr
     int sv16;                // saved gates r, z, n written as 16-bit fixed point
+    const int* lengths; int pool_mean;      // ragged instances (RAG): row b is live for t < lengths[b]; a mean pool divides by lengths[b]
 };
 
-template <int KCH, bool SPLIT>      // SPLIT: 3-term bf16 split of the recurrent product, as in gru_fwd_cluster16
+// RAG: the ragged-batch instances (dep_rnn_forward_varlen): h = live ? new : previous (what is published, kept and returned as h_n),
+// y / dropout(y) / the pool take live ? h : 0.  Everything about the hand-off is the dense instance's.
+template <int KCH, bool SPLIT, bool RAG = false>      // SPLIT: 3-term bf16 split of the recurrent product, as in gru_fwd_cluster16
 __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
+    // contraction by syntax: see DEP_FP_CONTRACT_NOTE in dep_common.h (why, and how to re-verify the dense instances after a compiler change)
+#pragma clang fp contract(on)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H = p.H, T = p.T, LDH = H + LPAD, KC = H / 16, NC = H / 32;
     const int c = blockIdx.x / p.nbtp, bt = blockIdx.x % p.nbtp;
@@ -685,6 +722,8 @@ __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
     const int jt = c * 2 + jl;
     const int b = p.b0 + bt * BT + j;
     const bool valid = b < p.B;
+    int len = T;
+    if constexpr (RAG) len = valid ? dep_row_len(p.lengths, b, T) : 0;
     const int LDHB = H + 8;                           // bf16 elements per row of a split plane
     float* hs = smem;                                 // [16][LDH] fp32, or (SPLIT) two bf16 planes [16][LDHB]
     const int hs_floats = SPLIT ? BT * LDHB : BT * LDH;
@@ -794,8 +833,14 @@ __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
         z.x = fast_sigmoid(gi[1].x + tot[1].x + bh[1].x); z.y = fast_sigmoid(gi[1].y + tot[1].y + bh[1].y);
         hn.x = tot[2].x + bh[2].x; hn.y = tot[2].y + bh[2].y;
         n.x = fast_tanh(gi[2].x + r.x * hn.x); n.y = fast_tanh(gi[2].y + r.y * hn.y);
-        h.x = (1.0f - z.x) * n.x + z.x * hprev.x; h.y = (1.0f - z.y) * n.y + z.y * hprev.y;
-        hprev = h; pool.x += h.x; pool.y += h.y;
+        h.x = z.x * hprev.x + (1.0f - z.x) * n.x; h.y = z.y * hprev.y + (1.0f - z.y) * n.y;      // (the fused product is z * h_{t-1}: contraction by syntax, see above)
+        float2 hy = h;                                // what y, dropout(y) and the pool see
+        if constexpr (RAG) {
+            const bool live = t < len;
+            h = dep_sel2(live, h, hprev);             // the state freezes behind the row's last step: published and kept as it is
+            hy = dep_sel2(live, h, f2(0.f, 0.f));
+        }
+        hprev = h; pool.x += hy.x; pool.y += hy.y;
         const unsigned epoch = (unsigned)t + 1u;
         const size_t pbase = (size_t)(t & 1) * pstride + tile_base;
         const bool more = t + 1 < T;
@@ -812,10 +857,10 @@ __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
         }
         if (valid) {
             const size_t o = row * p.ldy + col;
-            st2(p.y + o, h);
+            st2(p.y + o, hy);
             if (p.ydrop) {
                 const f32x4 m = dep_dropmask4(p.seed, p.site, o >> 2, p.drop_p, p.drop_scale);
-                st2(p.ydrop + o, f2(h.x * (kh ? m[2] : m[0]), h.y * (kh ? m[3] : m[1])));
+                st2(p.ydrop + o, f2(hy.x * (kh ? m[2] : m[0]), hy.y * (kh ? m[3] : m[1])));
             }
             if (p.sv0) {
                 const size_t so = row * H + col;
@@ -853,7 +898,8 @@ __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
         }
     }
     if (valid) {
-        if (p.pooled) st2(p.pooled + (size_t)b * H + col, f2(pool.x * p.pool_scale, pool.y * p.pool_scale));
+        const float ps = RAG ? dep_ragged_pool_scale(p.pool_mean, len, T, p.pool_scale) : p.pool_scale;
+        if (p.pooled) st2(p.pooled + (size_t)b * H + col, f2(pool.x * ps, pool.y * ps));
         if (p.h_n) st2(p.h_n + (size_t)b * H + col, hprev);
     }
 }
@@ -890,13 +936,19 @@ __global__ void pack_cluster_split_multi_kernel(PackJobs j, int H) {
 
 // ---- the launchable instances.  Every one asks for more than half of the CU's 160 KiB LDS: the dispatcher can then never co-locate
 // two members on one CU (they would share the four matrix pipes and stretch every step of BOTH clusters).
-Instance<F2>& fwd_instance(int H, bool split) {      // KCH = H / 32; exact fp32 | split products
+Instance<F2>& fwd_instance(int H, bool split, bool rag) {      // KCH = H / 32; exact fp32 | split products
     static Instance<F2> rows[4][2] = {
         { DEP_INSTANCE((gru_fwd_cluster_r1<2, false>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<2, true>), EXCLUSIVE_LDS) },
         { DEP_INSTANCE((gru_fwd_cluster_r1<4, false>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<4, true>), EXCLUSIVE_LDS) },
         { DEP_INSTANCE((gru_fwd_cluster_r1<8, false>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<8, true>), EXCLUSIVE_LDS) },
         { DEP_INSTANCE((gru_fwd_cluster_r1<16, false>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<16, true>), EXCLUSIVE_LDS) } };
-    return rows[H == 64 ? 0 : H == 128 ? 1 : H == 256 ? 2 : 3][split];
+    // ... and the ragged-batch instances of the same forms (dep_rnn_forward_varlen)
+    static Instance<F2> ragged[4][2] = {
+        { DEP_INSTANCE((gru_fwd_cluster_r1<2, false, true>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<2, true, true>), EXCLUSIVE_LDS) },
+        { DEP_INSTANCE((gru_fwd_cluster_r1<4, false, true>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<4, true, true>), EXCLUSIVE_LDS) },
+        { DEP_INSTANCE((gru_fwd_cluster_r1<8, false, true>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<8, true, true>), EXCLUSIVE_LDS) },
+        { DEP_INSTANCE((gru_fwd_cluster_r1<16, false, true>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<16, true, true>), EXCLUSIVE_LDS) } };
+    return (rag ? ragged : rows)[H == 64 ? 0 : H == 128 ? 1 : H == 256 ? 2 : 3][split];
 }
 
 // NTW = H / 64.  Burst length 4 up to H = 256; H = 512 keeps the round-1 schedule (KB = 0): 192 weight registers per
@@ -904,7 +956,7 @@ Instance<F2>& fwd_instance(int H, bool split) {      // KCH = H / 32; exact fp32
 // gradients (round 5); every other shape / the exact-fp32 mode: the reduce-scatter of fp32 partial dh.  The last 2048 bytes of a
 // launch's LDS hold the trace stamps.
 constexpr int bwd_burst(int H) { return H >= 512 ? 0 : 4; }
-Instance<P2>& bwd_instance(int H, bool split, bool sv16, bool bf16st) {
+Instance<P2>& bwd_instance(int H, bool split, bool sv16, bool bf16st, bool rag) {
     constexpr size_t R1 = EXCLUSIVE_LDS + 2048, AG = burst_lds_bytes_ag(4) + 2048;
     constexpr size_t BURST = (burst_lds_bytes(4) > EXCLUSIVE_LDS ? burst_lds_bytes(4) : EXCLUSIVE_LDS) + 2048;
     // per H: exact fp32 | split products, 16-bit saved gates | split products
@@ -919,6 +971,17 @@ Instance<P2>& bwd_instance(int H, bool split, bool sv16, bool bf16st) {
     static Instance<P2> h256_ag[3] = { DEP_INSTANCE((gru_bwd_cluster_r1<4, true, 4, false, false, true>), AG), DEP_INSTANCE((gru_bwd_cluster_r1<4, true, 4, true, false, true>), AG),
                                        DEP_INSTANCE((gru_bwd_cluster_r1<4, true, 4, true, true, true>), AG) };
     const int form = !split ? 0 : sv16 ? 1 : 2;
+    if (rag) {      // the ragged-batch instances of the same forms (dep_rnn_backward_varlen; no bf16-storage variant: modes 2 / 3 refuse a ragged call)
+        static Instance<P2> r64[3] = { DEP_INSTANCE((gru_bwd_cluster_r1<1, false, 4, false, false, false, true>), BURST), DEP_INSTANCE((gru_bwd_cluster_r1<1, true, 4, true, false, false, true>), BURST),
+                                       DEP_INSTANCE((gru_bwd_cluster_r1<1, true, 4, false, false, false, true>), BURST) };
+        static Instance<P2> r128[3] = { DEP_INSTANCE((gru_bwd_cluster_r1<2, false, 4, false, false, false, true>), BURST), DEP_INSTANCE((gru_bwd_cluster_r1<2, true, 4, true, false, false, true>), BURST),
+                                        DEP_INSTANCE((gru_bwd_cluster_r1<2, true, 4, false, false, false, true>), BURST) };
+        static Instance<P2> r256[3] = { DEP_INSTANCE((gru_bwd_cluster_r1<4, false, 4, false, false, false, true>), BURST), DEP_INSTANCE((gru_bwd_cluster_r1<4, true, 4, true, false, true, true>), AG),
+                                        DEP_INSTANCE((gru_bwd_cluster_r1<4, true, 4, false, false, true, true>), AG) };
+        static Instance<P2> r512[3] = { DEP_INSTANCE((gru_bwd_cluster_r1<8, false, 0, false, false, false, true>), R1), DEP_INSTANCE((gru_bwd_cluster_r1<8, true, 0, true, false, false, true>), R1),
+                                        DEP_INSTANCE((gru_bwd_cluster_r1<8, true, 0, false, false, false, true>), R1) };
+        return (H == 64 ? r64 : H == 128 ? r128 : H == 256 ? r256 : r512)[form];
+    }
     switch (H) {
         case 64: return h64[form];
         case 128: return h128[form];
@@ -967,8 +1030,9 @@ int dep_launch_cluster_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf_byte
     DEP_CHECK_ARG(PAYLOAD_OFF + pay <= xbuf_bytes && g.resident());
     p.flags = bind_exchange(p, xbuf, a.hdr_slot, pay);
     p.only_if = a.only_if; p.sv16 = a.training ? a.sv16 : 0;
+    p.lengths = a.lengths; p.pool_mean = a.pool_mean;
     DepProfScope prof(DEP_PROF_GRU_FWD, a.stream, a.only_if == nullptr);      // a conditional fallback launch is not a sweep of the step
-    return launch_chunks(fwd_instance(a.H, a.split), g, dim3(CT), p, a.stream, __PRETTY_FUNCTION__,
+    return launch_chunks(fwd_instance(a.H, a.split, a.lengths != nullptr), g, dim3(CT), p, a.stream, __PRETTY_FUNCTION__,
                          [&](int b0) { return hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); });
 }
 
@@ -990,6 +1054,8 @@ int dep_launch_cluster_bwd(const dep_sweep_bwd_args& a, void* xbuf, size_t xbuf_
     p.sv0 = a.sv0; p.sv1 = a.sv1; p.sv2 = a.sv2; p.sv3 = a.sv3;
     p.dgi = a.dgi; p.lddg = a.lddg ? a.lddg : 3 * a.H; p.dghn = a.dghn; p.lddghn = a.lddghn ? a.lddghn : a.H; p.dbpart = a.dbpart;
     p.dgpk = a.dg_pk;
+    p.lengths = a.lengths; p.pool_mean = a.pool_mean;
+    DEP_CHECK_ARG(!(a.lengths && a.bf16st));         // no ragged bf16-storage instance
     DEP_CHECK_ARG(!a.sv16 || a.split);               // the 16-bit saved gates exist in split-precision mode only
     DEP_CHECK_ARG(!a.bf16st || (a.H == 256 && a.split && a.sv16 && a.dg_pk));      // bf16-storage mode: H = 256, burst kernel (checked below via dg_pk)
     DEP_CHECK_ARG(a.dbpart_rows >= nbt);
@@ -1003,7 +1069,7 @@ int dep_launch_cluster_bwd(const dep_sweep_bwd_args& a, void* xbuf, size_t xbuf_
     // (one tile's rows of the widest array must fit a 32-bit buffer offset)
     { const int mxl = p.lddg > p.lddy ? p.lddg : p.lddy; DEP_CHECK_ARG((size_t)(BT * a.T + 1) * (mxl > p.ldy ? mxl : p.ldy) * 4 < 0xffffffffull); }
     const int kb = bwd_burst(a.H);
-    Instance<P2>& k = bwd_instance(a.H, a.split, a.sv16, a.bf16st);
+    Instance<P2>& k = bwd_instance(a.H, a.split, a.sv16, a.bf16st, a.lengths != nullptr);
     p.trall_off = (int)((k.lds - 2048) / 4);
     if (p.dgpk) {       // the PK image needs the burst kernel's flush, the 4H-wide rows and whole step pairs (dep_cluster_bwd_pk_ok)
         DEP_CHECK_ARG(kb == 4 && a.split && a.T % 2 == 0 && a.lddg == 4 * a.H && a.lddghn == 4 * a.H && a.dghn == a.dgi + 3 * a.H);

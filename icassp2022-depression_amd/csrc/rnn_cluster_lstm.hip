@@ -21,6 +21,7 @@ struct LF {
     unsigned* status; unsigned* flags; unsigned* hello; float* payload; unsigned payload_bytes;
     int nofast;
     long long* trace;        // debug: shader-clock stamps of workgroup 0 (DEP_TRACE=1, tools/trace_lstm.py), else nullptr
+    const int* lengths;      // ragged instances (RAG): row b is live for t < lengths[b]
 };
 
 struct LB {
@@ -36,6 +37,7 @@ struct LB {
     int nofast;
     int dgpk;                // gate gradients as the PK image of gemm_bf16x3.hip (burst kernel, T even)
     long long* trace;        // debug: shader-clock stamps of workgroup 0 (DEP_TRACE=1, tools/trace_lstm.py bwd), else nullptr
+    const int* lengths;      // ragged instances (RAG): row b is live for t < lengths[b]
 };
 
 // block id = (dir*NC + c)*nbtp + bt  (nbtp a multiple of 8: all members of a cluster share blockIdx % 8)
@@ -80,8 +82,14 @@ constexpr unsigned DF_SENT = 0xffffffffu;
 
 // SV16 (burst kernels only): the saved activated gates are 16-bit fixed point -- i, f, o in (0, 1) as unorm16, g in (-1, 1) as
 // snorm16 (rnn_cluster_common.h; same element positions inside the (B,T,dirs*4H) array, 2 bytes each); c stays fp32.
-template <int KCH, bool SPLIT, int KB, bool SV16 = false, int DF = 0>      // k-chunks of 16 per wave = H/32
+// RAG: the ragged-batch instances (dep_rnn_forward_varlen).  live = t < lengths[b], per lane, in the gate phase of the compute waves:
+// (h, c) = live ? new : previous -- what is published, carried and returned as h_n, so the forward direction freezes behind its last
+// step and the reverse direction walks the padding with its zero state and starts for real at t = lengths[b] - 1; h, dropout(h) and
+// the saved c go out as 0 at dead positions (the backward reads c_{t-1} there).  The hand-off is the dense instance's, step for step.
+template <int KCH, bool SPLIT, int KB, bool SV16 = false, int DF = 0, bool RAG = false>      // k-chunks of 16 per wave = H/32
 __global__ __launch_bounds__(KB ? CT + L_SVC : CT) void lstm_fwd_cluster(LF p) {
+    // contraction by syntax: see DEP_FP_CONTRACT_NOTE in dep_common.h (why, and how to re-verify the dense instances after a compiler change)
+#pragma clang fp contract(on)
     static_assert(!DF || (SPLIT && KB == 4 && KCH == 4), "direct-fragment exchange: H = 128, split products, burst length 4");
     static_assert(DF >= 0 && DF <= 3, "DF: 0 LDS planes, 1 direct fragments + bursts, 2 + per-step streams, 3 + sentinel hand-off");
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -95,6 +103,8 @@ __global__ __launch_bounds__(KB ? CT + L_SVC : CT) void lstm_fwd_cluster(LF p) {
     const int jt = c * 2 + jl;
     const int b = p.b0 + bt * BT + j;
     const bool valid = b < p.B;
+    int len = T;
+    if constexpr (RAG) len = (valid && tid < CT) ? dep_row_len(p.lengths, b, T) : 0;
     float* hs = smem;                                 // [16][LDH] fp32, or (SPLIT) two bf16 planes [16][LDHB]
     const int hs_floats = SPLIT ? BT * LDHB : BT * LDH;
     unsigned short* hs_hi = reinterpret_cast<unsigned short*>(smem);
@@ -326,8 +336,16 @@ __global__ __launch_bounds__(KB ? CT + L_SVC : CT) void lstm_fwd_cluster(LF p) {
             fg.x = fast_sigmoid(tot[1].x); fg.y = fast_sigmoid(tot[1].y);
             gg.x = fast_tanh(tot[2].x); gg.y = fast_tanh(tot[2].y);
             og.x = fast_sigmoid(tot[3].x); og.y = fast_sigmoid(tot[3].y);
-            cst.x = fg.x * cst.x + ig.x * gg.x; cst.y = fg.y * cst.y + ig.y * gg.y;
-            h.x = og.x * fast_tanh(cst.x); h.y = og.y * fast_tanh(cst.y);
+            float2 cn = f2(fg.x * cst.x + ig.x * gg.x, fg.y * cst.y + ig.y * gg.y);
+            h.x = og.x * fast_tanh(cn.x); h.y = og.y * fast_tanh(cn.y);
+            float2 hy = h;                            // what h, dropout(h) and the saved c show of this step
+            if constexpr (RAG) {
+                const bool live = (dir ? T - 1 - k : k) < len;
+                h = dep_sel2(live, h, hlast); cst = dep_sel2(live, cn, cst);
+                hy = dep_sel2(live, h, f2(0.f, 0.f)); cn = dep_sel2(live, cn, f2(0.f, 0.f));
+            } else {
+                cst = cn;
+            }
             hlast = h;
             if (more) {       // publish first: the (hi, lo) pair words of h_k -- what every member's MFMAs read
                 unsigned hw, lw;
@@ -354,9 +372,9 @@ __global__ __launch_bounds__(KB ? CT + L_SVC : CT) void lstm_fwd_cluster(LF p) {
             }
             {
                 float* ob = obuf + (k % (KBX + 1)) * 7 * LARR + j * LROW + ulc;
-                st2(ob, h);
-                if (masked) st2(ob + LARR, f2(h.x * mk.x, h.y * mk.y));
-                if (p.svg) { st2(ob + 2 * LARR, ig); st2(ob + 3 * LARR, fg); st2(ob + 4 * LARR, gg); st2(ob + 5 * LARR, og); st2(ob + 6 * LARR, cst); }
+                st2(ob, hy);
+                if (masked) st2(ob + LARR, f2(hy.x * mk.x, hy.y * mk.y));
+                if (p.svg) { st2(ob + 2 * LARR, ig); st2(ob + 3 * LARR, fg); st2(ob + 4 * LARR, gg); st2(ob + 5 * LARR, og); st2(ob + 6 * LARR, cn); }
             }
             LSTAMP(k, 1);
             if (!more) { bar_lds(); break; }          // (the service waves' final flush reads obuf behind this barrier)
@@ -507,8 +525,16 @@ __global__ __launch_bounds__(KB ? CT + L_SVC : CT) void lstm_fwd_cluster(LF p) {
         fg.x = fast_sigmoid(tot[1].x); fg.y = fast_sigmoid(tot[1].y);
         gg.x = fast_tanh(tot[2].x); gg.y = fast_tanh(tot[2].y);
         og.x = fast_sigmoid(tot[3].x); og.y = fast_sigmoid(tot[3].y);
-        cst.x = fg.x * cst.x + ig.x * gg.x; cst.y = fg.y * cst.y + ig.y * gg.y;
-        h.x = og.x * fast_tanh(cst.x); h.y = og.y * fast_tanh(cst.y);
+        float2 cn = f2(fg.x * cst.x + ig.x * gg.x, fg.y * cst.y + ig.y * gg.y);
+        h.x = og.x * fast_tanh(cn.x); h.y = og.y * fast_tanh(cn.y);
+        float2 hy = h;                                // what h, dropout(h) and the saved c show of this step
+        if constexpr (RAG) {
+            const bool live = t < len;
+            h = dep_sel2(live, h, hlast); cst = dep_sel2(live, cn, cst);
+            hy = dep_sel2(live, h, f2(0.f, 0.f)); cn = dep_sel2(live, cn, f2(0.f, 0.f));
+        } else {
+            cst = cn;
+        }
         hlast = h;
         const unsigned epoch = (unsigned)s + 1u;
         const size_t pbase = (size_t)(s & 1) * pstride + tile_base;
@@ -526,24 +552,24 @@ __global__ __launch_bounds__(KB ? CT + L_SVC : CT) void lstm_fwd_cluster(LF p) {
         }
         if constexpr (BURST) {
             float* ob = obuf + (s % (KBX + 1)) * 7 * LARR + j * LROW + ulc;
-            st2(ob, h);
+            st2(ob, hy);
             if (p.ydrop) {
                 const size_t o = row * p.ldy + dir * H + col;
                 const f32x4 m = dep_dropmask4(p.seed, p.site, o >> 2, p.drop_p, p.drop_scale);
-                st2(ob + LARR, f2(h.x * (kh ? m[2] : m[0]), h.y * (kh ? m[3] : m[1])));
+                st2(ob + LARR, f2(hy.x * (kh ? m[2] : m[0]), hy.y * (kh ? m[3] : m[1])));
             }
-            if (p.svg) { st2(ob + 2 * LARR, ig); st2(ob + 3 * LARR, fg); st2(ob + 4 * LARR, gg); st2(ob + 5 * LARR, og); st2(ob + 6 * LARR, cst); }
+            if (p.svg) { st2(ob + 2 * LARR, ig); st2(ob + 3 * LARR, fg); st2(ob + 4 * LARR, gg); st2(ob + 5 * LARR, og); st2(ob + 6 * LARR, cn); }
         } else if (valid) {
             const size_t o = row * p.ldy + dir * H + col;
-            if (p.y) st2(p.y + o, h);
+            if (p.y) st2(p.y + o, hy);
             if (p.ydrop) {
                 const f32x4 m = dep_dropmask4(p.seed, p.site, o >> 2, p.drop_p, p.drop_scale);
-                st2(p.ydrop + o, f2(h.x * (kh ? m[2] : m[0]), h.y * (kh ? m[3] : m[1])));
+                st2(p.ydrop + o, f2(hy.x * (kh ? m[2] : m[0]), hy.y * (kh ? m[3] : m[1])));
             }
             if (p.svg) {
                 float* gs = p.svg + row * ldsg + dir * 4 * H + col;
                 st2(gs, ig); st2(gs + H, fg); st2(gs + 2 * H, gg); st2(gs + 3 * H, og);
-                st2(p.svc + row * ldsc + dir * H + col, cst);
+                st2(p.svc + row * ldsc + dir * H + col, cn);
             }
         }
         if (more) {
@@ -593,7 +619,9 @@ constexpr size_t lstm_bwd_lds_floats(int KB) { return KB ? (size_t)LB_IBUF + KB 
 // * the service waves stream every step instead of every fourth: the gate gradients of step k-1 (8 KB, or a PK pair every other step) go out
 //   at the top of their iteration, the saved gates / c / dy of step k+2 (14 KB) are requested once the four compute waves have their gather
 //   loads of step k-1 in the CU's queue (an LDS counter) and land in the ring an iteration later -- no dirty step.
-template <int NTW, bool SPLIT, int KB, bool SV16 = false, bool SE = false>      // output tiles per wave = H/64; SV16: 16-bit saved gates (burst kernel only)
+// RAG: the ragged-batch instances (dep_rnn_backward_varlen): a dead step's four gate gradients are 0 and its incoming dh, dc pass through
+// to the next BPTT step unchanged (selects in the compute waves' gate phase; the hand-off and the streams are the dense instance's).
+template <int NTW, bool SPLIT, int KB, bool SV16 = false, bool SE = false, bool RAG = false>      // output tiles per wave = H/64; SV16: 16-bit saved gates (burst kernel only)
 __global__ __launch_bounds__(KB ? CT + L_SVC : CT) void lstm_bwd_cluster(LB p) {
     static_assert(!SE || (SPLIT && KB == 4), "per-step streams: the split-precision burst kernel's rings");
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -642,6 +670,8 @@ __global__ __launch_bounds__(KB ? CT + L_SVC : CT) void lstm_bwd_cluster(LB p) {
     }
     float2 dhrec = (p.dh_n && valid && !svc) ? ld2(p.dh_n + ((size_t)dir * p.B + b) * H + col) : f2(0.f, 0.f);
     float2 dcrec = f2(0.f, 0.f);
+    int len = T;
+    if constexpr (RAG) len = (valid && !svc) ? dep_row_len(p.lengths, b, T) : 0;
     float2 db[4] = {f2(0.f, 0.f), f2(0.f, 0.f), f2(0.f, 0.f), f2(0.f, 0.f)};
     const int cl = dir * p.nbtp + bt;
     const size_t pstride = (size_t)p.dirs * p.nbtp * NC * BT * H;
@@ -850,11 +880,25 @@ __global__ __launch_bounds__(KB ? CT + L_SVC : CT) void lstm_bwd_cluster(LB p) {
         dig.x = dct.x * gg.x * ig.x * (1.0f - ig.x); dig.y = dct.y * gg.y * ig.y * (1.0f - ig.y);
         dfg.x = dct.x * cp.x * fg.x * (1.0f - fg.x); dfg.y = dct.y * cp.y * fg.y * (1.0f - fg.y);
         dgg.x = dct.x * ig.x * (1.0f - gg.x * gg.x); dgg.y = dct.y * ig.y * (1.0f - gg.y * gg.y);
-        dcrec.x = dct.x * fg.x; dcrec.y = dct.y * fg.y;
+        const bool live = !RAG || t < len;
+        const float2 digr = dig, dfgr = dfg, dggr = dgg, dogr = dog;
+        if constexpr (RAG) {
+            const float2 z2 = f2(0.f, 0.f);
+            dog = dep_sel2(live, dog, z2); dig = dep_sel2(live, dig, z2); dfg = dep_sel2(live, dfg, z2); dgg = dep_sel2(live, dgg, z2);
+            dcrec = dep_sel2(live, f2(dct.x * fg.x, dct.y * fg.y), dcrec);
+        } else {
+            dcrec.x = dct.x * fg.x; dcrec.y = dct.y * fg.y;
+        }
         if constexpr (SPLIT) {
             unsigned hh[4], ll[4];
-            split_pair(dig.x, dig.y, hh[0], ll[0]); split_pair(dfg.x, dfg.y, hh[1], ll[1]);
-            split_pair(dgg.x, dgg.y, hh[2], ll[2]); split_pair(dog.x, dog.y, hh[3], ll[3]);
+            if constexpr (RAG) {          // the words of the unselected values (rounded as the dense instance rounds them), zeroed for a dead step
+                split_pair(digr.x, digr.y, hh[0], ll[0]); split_pair(dfgr.x, dfgr.y, hh[1], ll[1]);
+                split_pair(dggr.x, dggr.y, hh[2], ll[2]); split_pair(dogr.x, dogr.y, hh[3], ll[3]);
+                if (!live) { for (int g = 0; g < 4; ++g) { hh[g] = 0u; ll[g] = 0u; } }
+            } else {
+                split_pair(dig.x, dig.y, hh[0], ll[0]); split_pair(dfg.x, dfg.y, hh[1], ll[1]);
+                split_pair(dgg.x, dgg.y, hh[2], ll[2]); split_pair(dog.x, dog.y, hh[3], ll[3]);
+            }
             const int o = j * LDGB + ul;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -950,7 +994,8 @@ __global__ __launch_bounds__(KB ? CT + L_SVC : CT) void lstm_bwd_cluster(LB p) {
         float2 sum = f2(0.f, 0.f);
 #pragma unroll
         for (int m = 0; m < 4; ++m) { sum.x += part[m].x; sum.y += part[m].y; }
-        dhrec = sum;
+        if constexpr (RAG) dhrec = dep_sel2(live, sum, dhrec);      // dead step: the incoming dh passes through
+        else dhrec = sum;
         if constexpr (!BURST) cur = nxt;
         LSTAMP(T - 1 - s, 6);
     }
@@ -978,17 +1023,24 @@ __global__ void pack_lstm_split_kernel(const float* __restrict__ W, u32x4* __res
 
 // ---- the launchable instances (H = 128: KCH = 4, NTW = 2; burst length 4, the service waves own the HBM streams -- DESIGN 4.1c)
 // exact-fp32 mode: h_t through LDS planes (DF = 0); split products: the direct-fragment exchange with sentinel slots (DF = 3, round 5)
-Instance<LF>& fwd_instance(bool split, bool sv16) {
+Instance<LF>& fwd_instance(bool split, bool sv16, bool rag) {
     constexpr size_t PLANES = lstm_fwd_lds_floats(128, 4) * sizeof(float), DIRECT = lstm_fwd_lds_floats(128, 4, true) * sizeof(float);
     static Instance<LF> exact DEP_INSTANCE((lstm_fwd_cluster<4, false, 4>), PLANES);
     static Instance<LF> df3[2] = { DEP_INSTANCE((lstm_fwd_cluster<4, true, 4, false, 3>), DIRECT), DEP_INSTANCE((lstm_fwd_cluster<4, true, 4, true, 3>), DIRECT) };
+    // ... and the ragged-batch instances of the same forms (dep_rnn_forward_varlen)
+    static Instance<LF> rexact DEP_INSTANCE((lstm_fwd_cluster<4, false, 4, false, 0, true>), PLANES);
+    static Instance<LF> rdf3[2] = { DEP_INSTANCE((lstm_fwd_cluster<4, true, 4, false, 3, true>), DIRECT), DEP_INSTANCE((lstm_fwd_cluster<4, true, 4, true, 3, true>), DIRECT) };
+    if (rag) return split ? rdf3[sv16] : rexact;
     return split ? df3[sv16] : exact;
 }
 // exact-fp32 mode: burst streams, one flag per member behind a drain barrier; split products: per-step streams + per-wave flags (SE, round 5)
-Instance<LB>& bwd_instance(bool split, bool sv16) {
+Instance<LB>& bwd_instance(bool split, bool sv16, bool rag) {
     constexpr size_t LDS = lstm_bwd_lds_floats(4) * sizeof(float);
     static Instance<LB> exact DEP_INSTANCE((lstm_bwd_cluster<2, false, 4>), LDS);
     static Instance<LB> se[2] = { DEP_INSTANCE((lstm_bwd_cluster<2, true, 4, false, true>), LDS), DEP_INSTANCE((lstm_bwd_cluster<2, true, 4, true, true>), LDS) };
+    static Instance<LB> rexact DEP_INSTANCE((lstm_bwd_cluster<2, false, 4, false, false, true>), LDS);
+    static Instance<LB> rse[2] = { DEP_INSTANCE((lstm_bwd_cluster<2, true, 4, false, true, true>), LDS), DEP_INSTANCE((lstm_bwd_cluster<2, true, 4, true, true, true>), LDS) };
+    if (rag) return split ? rse[sv16] : rexact;
     return split ? se[sv16] : exact;
 }
 
@@ -1026,12 +1078,12 @@ int dep_launch_cluster_lstm_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf
     p.ydrop = (a.drop_p > 0.f) ? a.ydrop : nullptr;
     p.drop_p = a.drop_p; p.drop_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f; p.seed = a.seed; p.site = a.site;
     p.h_n = a.h_n;
-    p.svg = a.training ? a.sv0 : nullptr; p.svc = a.sv1;
+    p.svg = a.training ? a.sv0 : nullptr; p.svc = a.sv1; p.lengths = a.lengths;
     const size_t pay = lstm_fwd_payload_bytes(g, a.H, a.dirs);
     DEP_CHECK_ARG(xbuf && PAYLOAD_OFF + pay <= xbuf_bytes && g.resident());
     p.flags = bind_exchange(p, xbuf, a.hdr_slot, pay);
     DepProfScope prof(DEP_PROF_LSTM_FWD, a.stream);
-    return launch_chunks(fwd_instance(a.split, a.sv16 && a.training), g, dim3(CT + L_SVC), p, a.stream, __PRETTY_FUNCTION__,
+    return launch_chunks(fwd_instance(a.split, a.sv16 && a.training, a.lengths != nullptr), g, dim3(CT + L_SVC), p, a.stream, __PRETTY_FUNCTION__,
                          [&](int b0) { return hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); });
 }
 
@@ -1054,7 +1106,7 @@ int dep_launch_cluster_lstm_bwd(const dep_sweep_bwd_args& a, void* xbuf, size_t 
     p.drop_p = a.dy ? a.drop_p : 0.f; p.drop_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f;
     p.seed = a.seed; p.site = a.site;
     p.dh_n = a.dh_n; p.svg = a.sv0; p.svc = a.sv1;
-    p.dgi = a.dgi; p.lddg = a.dirs * 4 * a.H; p.dbpart = a.dbpart; p.nwg = nbt; p.dgpk = a.dg_pk;
+    p.dgi = a.dgi; p.lddg = a.dirs * 4 * a.H; p.dbpart = a.dbpart; p.nwg = nbt; p.dgpk = a.dg_pk; p.lengths = a.lengths;
     DEP_CHECK_ARG(a.dbpart_rows >= nbt * a.dirs);
     const size_t pay = lstm_bwd_payload_bytes(g, a.H);
     DEP_CHECK_ARG(xbuf && PAYLOAD_OFF + pay <= xbuf_bytes && g.resident());
@@ -1062,6 +1114,6 @@ int dep_launch_cluster_lstm_bwd(const dep_sweep_bwd_args& a, void* xbuf, size_t 
     DepProfScope prof(DEP_PROF_LSTM_BWD, a.stream);
     DEP_CHECK_ARG(!a.dg_pk || a.T % 2 == 0);         // the PK image comes out of the burst kernel's flush in whole step pairs (dep_cluster_lstm_bwd_pk_ok)
     DEP_CHECK_ARG(!a.sv16 || a.split);               // 16-bit saved gates: split-precision mode
-    return launch_chunks(bwd_instance(a.split, a.sv16), g, dim3(CT + L_SVC), p, a.stream, __PRETTY_FUNCTION__,
+    return launch_chunks(bwd_instance(a.split, a.sv16, a.lengths != nullptr), g, dim3(CT + L_SVC), p, a.stream, __PRETTY_FUNCTION__,
                          [&](int b0) { return hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); });
 }

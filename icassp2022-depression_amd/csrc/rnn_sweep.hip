@@ -33,6 +33,7 @@ struct FwdP {
     float* pooled; float pool_scale;     // (B,H)
     float* h_n;                          // (dirs,B,H)
     float* sv0; float* sv1; float* sv2; float* sv3;   // GRU: r,z,n,hn (B,T,H) ; LSTM: gates (B,T,dirs*4H), c (B,T,dirs*H)
+    const int* lengths; int pool_mean;   // ragged instances (RAG): row b is live for t < lengths[b]
 };
 
 struct BwdP {
@@ -48,6 +49,7 @@ struct BwdP {
     float* dghn;                         // GRU (B,T,H)
     float* dbpart;                       // [dirs][nwg][G'][H]  G' = 4
     int nwg;
+    const int* lengths; int pool_mean;   // ragged instances (RAG)
 };
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
@@ -96,15 +98,24 @@ __device__ __forceinline__ f32x4 rowsum16(f32x4 v) {
     return v;
 }
 
+// RAG (every kernel of this file): the ragged-batch instances (dep_rnn_forward_varlen).  One per-row predicate, live = t < lengths[b]:
+//   forward : state (h, c) = live ? new : previous ; y[b,t] = live ? h_t : 0 ; the pool takes live steps only ; saved c = live ? c_t : 0
+//   backward: gate gradients of (b,t) = live ? computed : 0 ; dh (dc) carried to the previous step = live ? computed : incoming
+// Selects, never value * 0: the saved gates / dy of dead positions may be anything.  Every workgroup still runs all T steps.
+// RAG = false is the dense text: the predicate is compiled out.
 // =============================================================================== GRU forward
-template <int JPW>
+template <int JPW, bool RAG = false>
 __global__ __launch_bounds__(512) void gru_fwd_mfma(FwdP p) {
+    // contraction by syntax: see DEP_FP_CONTRACT_NOTE in dep_common.h (why, and how to re-verify the dense instances after a compiler change)
+#pragma clang fp contract(on)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H = p.H, T = p.T, LDH = H + LPAD, KC = H / 16;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int j = lane & 15, q = lane >> 4;
     const int b = blockIdx.x * BT + j;
     const bool valid = b < p.B;
+    int len = T;
+    if constexpr (RAG) len = valid ? dep_row_len(p.lengths, b, T) : 0;
     float* hs0 = smem; float* hs1 = smem + BT * LDH;
     for (int i = threadIdx.x; i < 2 * BT * LDH; i += blockDim.x) smem[i] = 0.f;
 
@@ -142,10 +153,16 @@ __global__ __launch_bounds__(512) void gru_fwd_mfma(FwdP p) {
             const f32x4 z = sig4(gi[jj][1] + acc[jj * 3 + 1] + bh[jj][1]);
             const f32x4 hn = acc[jj * 3 + 2] + bh[jj][2];
             const f32x4 n = tanh4(gi[jj][2] + r * hn);
-            const f32x4 h = (1.0f - z) * n + z * hprev[jj];
-            hprev[jj] = h;
+            f32x4 h = z * hprev[jj] + (1.0f - z) * n;         // (the fused product is z * h_{t-1}: contraction by syntax, see above)
+            if constexpr (RAG) {
+                const bool live = t < len;
+                hprev[jj] = dep_sel4(live, h, hprev[jj]);      // the state freezes behind the row's last step
+                h = dep_sel4(live, h, zero4());                // what y, dropout(y) and the pool see
+            } else {
+                hprev[jj] = h;
+            }
             pool[jj] += h;
-            st4(hnext + j * LDH + col0, h);
+            st4(hnext + j * LDH + col0, hprev[jj]);
             if (valid) {
                 const size_t o = row * p.ldy + col0;
                 st4(p.y + o, h);
@@ -162,14 +179,15 @@ __global__ __launch_bounds__(512) void gru_fwd_mfma(FwdP p) {
 #pragma unroll
         for (int jj = 0; jj < JPW; ++jj) {
             const int col0 = (w * JPW + jj) * 16 + q * 4;
-            if (p.pooled) st4(p.pooled + (size_t)b * H + col0, pool[jj] * p.pool_scale);
+            const float ps = RAG ? dep_ragged_pool_scale(p.pool_mean, len, T, p.pool_scale) : p.pool_scale;
+            if (p.pooled) st4(p.pooled + (size_t)b * H + col0, pool[jj] * ps);
             if (p.h_n) st4(p.h_n + (size_t)b * H + col0, hprev[jj]);
         }
     }
 }
 
 // =============================================================================== GRU backward
-template <int JPW>
+template <int JPW, bool RAG = false>
 __global__ __launch_bounds__(512) void gru_bwd_mfma(BwdP p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H = p.H, T = p.T, G3 = 3 * H, LDG = G3 + LPAD, KC = G3 / 16;
@@ -177,6 +195,9 @@ __global__ __launch_bounds__(512) void gru_bwd_mfma(BwdP p) {
     const int j = lane & 15, q = lane >> 4;
     const int b = blockIdx.x * BT + j;
     const bool valid = b < p.B;
+    int len = T;
+    if constexpr (RAG) len = valid ? dep_row_len(p.lengths, b, T) : 0;
+    const float dps = RAG ? dep_ragged_pool_scale(p.pool_mean, len, T, p.pool_scale) : p.pool_scale;
     float* ds0 = smem; float* ds1 = smem + BT * LDG;
 
     const f32x4* wp = p.d[0].wp + (size_t)(w * JPW) * KC * 64 + lane;
@@ -185,7 +206,7 @@ __global__ __launch_bounds__(512) void gru_bwd_mfma(BwdP p) {
     for (int jj = 0; jj < JPW; ++jj) {
         const int col0 = (w * JPW + jj) * 16 + q * 4;
         dhrec[jj] = (p.dh_n && valid) ? ld4(p.dh_n + (size_t)b * H + col0) : zero4();
-        dpl[jj] = (p.dpooled && valid) ? ld4(p.dpooled + (size_t)b * H + col0) * p.pool_scale : zero4();
+        dpl[jj] = (p.dpooled && valid) ? ld4(p.dpooled + (size_t)b * H + col0) * dps : zero4();
         dbr[jj] = zero4(); dbz[jj] = zero4(); dbn[jj] = zero4(); dbh[jj] = zero4();
     }
 
@@ -208,11 +229,16 @@ __global__ __launch_bounds__(512) void gru_bwd_mfma(BwdP p) {
                     d += dyv;
                 }
             }
-            const f32x4 dn = d * (1.0f - z) * (1.0f - n * n);
-            const f32x4 dz = d * (hp - n) * z * (1.0f - z);
-            const f32x4 dr = dn * hn * r * (1.0f - r);
-            const f32x4 dnr = dn * r;
+            f32x4 dn = d * (1.0f - z) * (1.0f - n * n);
+            f32x4 dz = d * (hp - n) * z * (1.0f - z);
+            f32x4 dr = dn * hn * r * (1.0f - r);
+            f32x4 dnr = dn * r;
             dzt[jj] = d * z;
+            if constexpr (RAG) {
+                const bool live = t < len;
+                dn = dep_sel4(live, dn, zero4()); dz = dep_sel4(live, dz, zero4());
+                dr = dep_sel4(live, dr, zero4()); dnr = dep_sel4(live, dnr, zero4());
+            }
             st4(dcur + j * LDG + col0, dr);
             st4(dcur + j * LDG + H + col0, dz);
             st4(dcur + j * LDG + 2 * H + col0, dnr);
@@ -229,7 +255,10 @@ __global__ __launch_bounds__(512) void gru_bwd_mfma(BwdP p) {
         for (int i = 0; i < JPW; ++i) acc[i] = zero4();
         matvec_tiles<JPW>(acc, wp, KC, dcur + j * LDG + q * 4);
 #pragma unroll
-        for (int jj = 0; jj < JPW; ++jj) dhrec[jj] = dzt[jj] + acc[jj];
+        for (int jj = 0; jj < JPW; ++jj) {
+            if constexpr (RAG) dhrec[jj] = dep_sel4(t < len, dzt[jj] + acc[jj], dhrec[jj]);      // dead step: the incoming dh passes through
+            else dhrec[jj] = dzt[jj] + acc[jj];
+        }
     }
     // bias-gradient partials of this workgroup: dbpart[wg][4][H]  (r, z, n_input, n_hidden)
 #pragma unroll
@@ -244,8 +273,10 @@ __global__ __launch_bounds__(512) void gru_bwd_mfma(BwdP p) {
 }
 
 // =============================================================================== LSTM forward
-template <int JPW>
+template <int JPW, bool RAG = false>
 __global__ __launch_bounds__(512) void lstm_fwd_mfma(FwdP p) {
+    // contraction by syntax: see DEP_FP_CONTRACT_NOTE in dep_common.h (why, and how to re-verify the dense instances after a compiler change)
+#pragma clang fp contract(on)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H = p.H, T = p.T, LDH = H + LPAD, KC = H / 16;
     const int dir = blockIdx.y;
@@ -253,6 +284,8 @@ __global__ __launch_bounds__(512) void lstm_fwd_mfma(FwdP p) {
     const int j = lane & 15, q = lane >> 4;
     const int b = blockIdx.x * BT + j;
     const bool valid = b < p.B;
+    int len = T;
+    if constexpr (RAG) len = valid ? dep_row_len(p.lengths, b, T) : 0;
     float* hs0 = smem; float* hs1 = smem + BT * LDH;
     for (int i = threadIdx.x; i < 2 * BT * LDH; i += blockDim.x) smem[i] = 0.f;
     const f32x4* wp = p.d[dir].wp + (size_t)(w * JPW * 4) * KC * 64 + lane;
@@ -286,10 +319,16 @@ __global__ __launch_bounds__(512) void lstm_fwd_mfma(FwdP p) {
             const f32x4 fg = sig4(gi[jj][1] + acc[jj * 4 + 1]);
             const f32x4 gg = tanh4(gi[jj][2] + acc[jj * 4 + 2]);
             const f32x4 og = sig4(gi[jj][3] + acc[jj * 4 + 3]);
-            c[jj] = fg * c[jj] + ig * gg;
-            const f32x4 h = og * tanh4(c[jj]);
-            hlast[jj] = h;
-            st4(hnext + j * LDH + col0, h);
+            f32x4 cn = fg * c[jj] + ig * gg;
+            f32x4 h = og * tanh4(cn);
+            if constexpr (RAG) {
+                const bool live = t < len;
+                c[jj] = dep_sel4(live, cn, c[jj]); hlast[jj] = dep_sel4(live, h, hlast[jj]);
+                h = dep_sel4(live, h, zero4()); cn = dep_sel4(live, cn, zero4());      // y and the saved c are 0 at dead positions (the backward reads c_{t-1} there)
+            } else {
+                c[jj] = cn; hlast[jj] = h;
+            }
+            st4(hnext + j * LDH + col0, hlast[jj]);
             if (valid) {
                 const size_t o = row * p.ldy + dir * H + col0;
                 st4(p.y + o, h);
@@ -297,7 +336,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_mfma(FwdP p) {
                 if (p.sv0) {
                     float* gs = p.sv0 + row * ldsg + dir * 4 * H + col0;
                     st4(gs, ig); st4(gs + H, fg); st4(gs + 2 * H, gg); st4(gs + 3 * H, og);
-                    st4(p.sv1 + row * ldsc + dir * H + col0, c[jj]);
+                    st4(p.sv1 + row * ldsc + dir * H + col0, cn);
                 }
             }
         }
@@ -313,7 +352,7 @@ __global__ __launch_bounds__(512) void lstm_fwd_mfma(FwdP p) {
 }
 
 // =============================================================================== LSTM backward
-template <int JPW>
+template <int JPW, bool RAG = false>
 __global__ __launch_bounds__(512) void lstm_bwd_mfma(BwdP p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H = p.H, T = p.T, G4 = 4 * H, LDG = G4 + LPAD, KC = G4 / 16;
@@ -322,6 +361,8 @@ __global__ __launch_bounds__(512) void lstm_bwd_mfma(BwdP p) {
     const int j = lane & 15, q = lane >> 4;
     const int b = blockIdx.x * BT + j;
     const bool valid = b < p.B;
+    int len = T;
+    if constexpr (RAG) len = valid ? dep_row_len(p.lengths, b, T) : 0;
     float* ds0 = smem; float* ds1 = smem + BT * LDG;
     const f32x4* wp = p.d[dir].wp + (size_t)(w * JPW) * KC * 64 + lane;
     const int ldsg = p.dirs * 4 * H, ldsc = p.dirs * H;
@@ -360,17 +401,25 @@ __global__ __launch_bounds__(512) void lstm_bwd_mfma(BwdP p) {
             const f32x4 tc = tanh4(ct);
             const f32x4 dog = d * tc * og * (1.0f - og);
             const f32x4 dct = d * og * (1.0f - tc * tc) + dcrec[jj];
-            const f32x4 dig = dct * gg * ig * (1.0f - ig);
-            const f32x4 dfg = dct * cp * fg * (1.0f - fg);
-            const f32x4 dgg = dct * ig * (1.0f - gg * gg);
-            dcrec[jj] = dct * fg;
+            f32x4 dig = dct * gg * ig * (1.0f - ig);
+            f32x4 dfg = dct * cp * fg * (1.0f - fg);
+            f32x4 dgg = dct * ig * (1.0f - gg * gg);
+            f32x4 dogl = dog;
+            if constexpr (RAG) {
+                const bool live = t < len;
+                dig = dep_sel4(live, dig, zero4()); dfg = dep_sel4(live, dfg, zero4());
+                dgg = dep_sel4(live, dgg, zero4()); dogl = dep_sel4(live, dog, zero4());
+                dcrec[jj] = dep_sel4(live, dct * fg, dcrec[jj]);
+            } else {
+                dcrec[jj] = dct * fg;
+            }
             float* dl = dcur + j * LDG + col0;
-            st4(dl, dig); st4(dl + H, dfg); st4(dl + 2 * H, dgg); st4(dl + 3 * H, dog);
+            st4(dl, dig); st4(dl + H, dfg); st4(dl + 2 * H, dgg); st4(dl + 3 * H, dogl);
             if (valid) {
                 float* g = p.dgi + row * p.lddg + dir * 4 * H + col0;
-                st4(g, dig); st4(g + H, dfg); st4(g + 2 * H, dgg); st4(g + 3 * H, dog);
+                st4(g, dig); st4(g + H, dfg); st4(g + 2 * H, dgg); st4(g + 3 * H, dogl);
             }
-            db[jj][0] += dig; db[jj][1] += dfg; db[jj][2] += dgg; db[jj][3] += dog;
+            db[jj][0] += dig; db[jj][1] += dfg; db[jj][2] += dgg; db[jj][3] += dogl;
         }
         __syncthreads();
         f32x4 acc[JPW];
@@ -378,7 +427,10 @@ __global__ __launch_bounds__(512) void lstm_bwd_mfma(BwdP p) {
         for (int i = 0; i < JPW; ++i) acc[i] = zero4();
         matvec_tiles<JPW>(acc, wp, KC, dcur + j * LDG + q * 4);
 #pragma unroll
-        for (int jj = 0; jj < JPW; ++jj) dhrec[jj] = acc[jj];
+        for (int jj = 0; jj < JPW; ++jj) {
+            if constexpr (RAG) dhrec[jj] = dep_sel4(t < len, acc[jj], dhrec[jj]);      // dead step: the incoming dh passes through
+            else dhrec[jj] = acc[jj];
+        }
     }
 #pragma unroll
     for (int jj = 0; jj < JPW; ++jj) {
@@ -397,9 +449,13 @@ __global__ __launch_bounds__(512) void lstm_bwd_mfma(BwdP p) {
 // not cover (H % 16 != 0) and as an in-library cross-check (desc.impl = 1).
 constexpr int GEN_T = 128;
 
+template <bool RAG = false>
 __global__ __launch_bounds__(GEN_T) void gru_fwd_generic(FwdP p) {
+    // contraction by syntax: see DEP_FP_CONTRACT_NOTE in dep_common.h (why, and how to re-verify the dense instances after a compiler change)
+#pragma clang fp contract(on)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H = p.H, T = p.T, b = blockIdx.x;
+    const int len = RAG ? dep_row_len(p.lengths, b, T) : T;
     float* hs = smem;            // [H] h_{t-1}
     float* hnew = smem + H;      // [H]
     const float* W = p.d[0].w; const float* bh = p.d[0].b_hh;
@@ -420,8 +476,10 @@ __global__ __launch_bounds__(GEN_T) void gru_fwd_generic(FwdP p) {
             const float z = dep_sigmoid(g[H + i] + az + bh[H + i]);
             const float hn = an + bh[2 * H + i];
             const float n = tanhf(g[2 * H + i] + r * hn);
-            const float h = (1.0f - z) * n + z * hs[i];
-            hnew[i] = h;
+            float h = (1.0f - z) * n + z * hs[i];
+            const bool live = !RAG || t < len;
+            hnew[i] = live ? h : hs[i];
+            h = live ? h : 0.f;
             const size_t o = row * p.ldy + i;
             p.y[o] = h;
             if (p.ydrop) p.ydrop[o] = h * dep_dropmask1(p.seed, p.site, o, p.drop_p, p.drop_scale);
@@ -436,14 +494,17 @@ __global__ __launch_bounds__(GEN_T) void gru_fwd_generic(FwdP p) {
         for (int i = threadIdx.x; i < H; i += GEN_T) {
             float s = 0.f;
             for (int t = 0; t < T; ++t) s += p.y[((size_t)b * T + t) * p.ldy + i];
-            p.pooled[(size_t)b * H + i] = s * p.pool_scale;
+            p.pooled[(size_t)b * H + i] = s * (RAG ? dep_ragged_pool_scale(p.pool_mean, len, T, p.pool_scale) : p.pool_scale);
         }
     }
 }
 
+template <bool RAG = false>
 __global__ __launch_bounds__(GEN_T) void gru_bwd_generic(BwdP p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H = p.H, T = p.T, b = blockIdx.x, G3 = 3 * H;
+    const int len = RAG ? dep_row_len(p.lengths, b, T) : T;
+    const float dps = RAG ? dep_ragged_pool_scale(p.pool_mean, len, T, p.pool_scale) : p.pool_scale;
     float* dg = smem;            // [3H] dgh of this step
     float* dh = smem + G3;       // [H] recurrent dh
     float* dbp = p.dbpart + (size_t)b * 4 * H;
@@ -458,12 +519,21 @@ __global__ __launch_bounds__(GEN_T) void gru_bwd_generic(BwdP p) {
             const float r = p.sv0[so], z = p.sv1[so], n = p.sv2[so], hn = p.sv3[so];
             const float hp = t > 0 ? p.y[(row - 1) * p.ldy + i] : 0.f;
             float d = dh[i];
-            if (p.dpooled) d += p.dpooled[(size_t)b * H + i] * p.pool_scale;
+            if (p.dpooled) d += p.dpooled[(size_t)b * H + i] * dps;
             if (p.dy) {
                 const size_t o = row * p.lddy + i;
                 float dyv = p.dy[o];
                 if (p.drop_p > 0.f) dyv *= dep_dropmask1(p.seed, p.site, o, p.drop_p, p.drop_scale);
                 d += dyv;
+            }
+            if constexpr (RAG) {
+                if (t >= len) {           // dead step (uniform over the workgroup): no gate gradient, the incoming dh stays
+                    dg[i] = 0.f; dg[H + i] = 0.f; dg[2 * H + i] = 0.f;
+                    float* g0 = p.dgi + row * p.lddg;
+                    g0[i] = 0.f; g0[H + i] = 0.f; g0[2 * H + i] = 0.f;
+                    p.dghn[row * H + i] = 0.f;
+                    continue;
+                }
             }
             const float dn = d * (1.0f - z) * (1.0f - n * n);
             const float dz = d * (hp - n) * z * (1.0f - z);
@@ -486,9 +556,11 @@ __global__ __launch_bounds__(GEN_T) void gru_bwd_generic(BwdP p) {
     }
 }
 
+template <bool RAG = false>
 __global__ __launch_bounds__(GEN_T) void lstm_fwd_generic(FwdP p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H = p.H, T = p.T, b = blockIdx.x, dir = blockIdx.y;
+    const int len = RAG ? dep_row_len(p.lengths, b, T) : T;
     float* hs = smem; float* hnew = smem + H; float* cs = smem + 2 * H;
     const float* W = p.d[dir].w;
     const int ldsg = p.dirs * 4 * H, ldsc = p.dirs * H;
@@ -507,6 +579,18 @@ __global__ __launch_bounds__(GEN_T) void lstm_fwd_generic(FwdP p) {
             const float* gi = p.gi + row * p.ldgi + dir * 4 * H;
             const float ig = dep_sigmoid(gi[i] + a[0]), fg = dep_sigmoid(gi[H + i] + a[1]);
             const float gg = tanhf(gi[2 * H + i] + a[2]), og = dep_sigmoid(gi[3 * H + i] + a[3]);
+            // (no contract(on) here, unlike gru_fwd_generic: the dead step is a workgroup-uniform branch, so the live path below IS the
+            // dense instance's statement sequence and rounds like it; gru_fwd_generic selects per value and needs the pragma)
+            if constexpr (RAG) {
+                if (t >= len) {           // dead step (uniform over the workgroup): the state stays, y / dropout(y) / the saved c are 0
+                    hnew[i] = hs[i];
+                    const size_t o0 = row * p.ldy + dir * H + i;
+                    p.y[o0] = 0.f;
+                    if (p.ydrop) p.ydrop[o0] = 0.f;
+                    if (p.sv0) p.sv1[row * ldsc + dir * H + i] = 0.f;
+                    continue;
+                }
+            }
             const float c = fg * cs[i] + ig * gg;
             const float h = og * tanhf(c);
             cs[i] = c; hnew[i] = h;
@@ -526,9 +610,11 @@ __global__ __launch_bounds__(GEN_T) void lstm_fwd_generic(FwdP p) {
     if (p.h_n) for (int i = threadIdx.x; i < H; i += GEN_T) p.h_n[((size_t)dir * p.B + b) * H + i] = hs[i];
 }
 
+template <bool RAG = false>
 __global__ __launch_bounds__(GEN_T) void lstm_bwd_generic(BwdP p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H = p.H, T = p.T, b = blockIdx.x, dir = blockIdx.y, G4 = 4 * H;
+    const int len = RAG ? dep_row_len(p.lengths, b, T) : T;
     float* dg = smem; float* dh = smem + G4; float* dc = smem + G4 + H;
     const float* W = p.d[dir].w;
     const int ldsg = p.dirs * 4 * H, ldsc = p.dirs * H;
@@ -556,6 +642,14 @@ __global__ __launch_bounds__(GEN_T) void lstm_bwd_generic(BwdP p) {
                 d += dyv;
             }
             const float tc = tanhf(ct);
+            if constexpr (RAG) {
+                if (t >= len) {           // dead step (uniform over the workgroup): no gate gradient, dc and dh pass through
+                    dg[i] = 0.f; dg[H + i] = 0.f; dg[2 * H + i] = 0.f; dg[3 * H + i] = 0.f;
+                    float* g0 = p.dgi + row * p.lddg + dir * 4 * H;
+                    g0[i] = 0.f; g0[H + i] = 0.f; g0[2 * H + i] = 0.f; g0[3 * H + i] = 0.f;
+                    continue;
+                }
+            }
             const float dog = d * tc * og * (1.0f - og);
             const float dct = d * og * (1.0f - tc * tc) + dc[i];
             const float dig = dct * gg * ig * (1.0f - ig);
@@ -571,7 +665,7 @@ __global__ __launch_bounds__(GEN_T) void lstm_bwd_generic(BwdP p) {
         for (int i = threadIdx.x; i < H; i += GEN_T) {
             float sum = 0.f;
             for (int k = 0; k < G4; ++k) sum = fmaf(dg[k], W[(size_t)k * H + i], sum);
-            dh[i] = sum;
+            if (!RAG || t < len) dh[i] = sum;      // (dead step: the incoming dh passes through)
         }
         __syncthreads();
     }
@@ -656,6 +750,18 @@ int dep_pack_whh(const float* w_hh, float* wp, float* wpT, int G, int H, hipStre
 
 #define LAUNCH_JPW(kern, grid, nthr, lds, s, P)                                                    \
     do {                                                                                           \
+        if (P.lengths) {                                                                           \
+            switch (jpw) {                                                                         \
+                case 1: (void)hipFuncSetAttribute((const void*)kern<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds)); \
+                        DEP_LAUNCH((kern<1, true>), grid, dim3(nthr), lds, s, P); break;           \
+                case 2: (void)hipFuncSetAttribute((const void*)kern<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds)); \
+                        DEP_LAUNCH((kern<2, true>), grid, dim3(nthr), lds, s, P); break;           \
+                case 3: (void)hipFuncSetAttribute((const void*)kern<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds)); \
+                        DEP_LAUNCH((kern<3, true>), grid, dim3(nthr), lds, s, P); break;           \
+                default: (void)hipFuncSetAttribute((const void*)kern<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds)); \
+                        DEP_LAUNCH((kern<4, true>), grid, dim3(nthr), lds, s, P); break;           \
+            }                                                                                      \
+        } else                                                                                     \
         switch (jpw) {                                                                             \
             case 1: (void)hipFuncSetAttribute((const void*)kern<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds)); \
                     DEP_LAUNCH(kern<1>, grid, dim3(nthr), lds, s, P); break;               \
@@ -678,6 +784,7 @@ int dep_launch_sweep_fwd(const dep_sweep_args& a) {
     p.drop_p = a.drop_p; p.drop_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f; p.seed = a.seed; p.site = a.site;
     p.pooled = a.pooled; p.pool_scale = a.pool_scale; p.h_n = a.h_n;
     p.sv0 = a.training ? a.sv0 : nullptr; p.sv1 = a.sv1; p.sv2 = a.sv2; p.sv3 = a.sv3;
+    p.lengths = a.lengths; p.pool_mean = a.pool_mean;
     DEP_CHECK_ARG(a.y && a.gi);
     DepProfScope prof(a.cell == DEP_CELL_GRU ? DEP_PROF_GRU_FWD : DEP_PROF_LSTM_FWD, a.stream);
     if (dep_sweep_use_mfma(a.H, a.impl)) {
@@ -689,8 +796,11 @@ int dep_launch_sweep_fwd(const dep_sweep_args& a) {
     } else {
         dim3 grid(a.B, a.dirs);
         const size_t lds = (size_t)3 * a.H * sizeof(float);
-        if (a.cell == DEP_CELL_GRU) DEP_LAUNCH(gru_fwd_generic, grid, dim3(GEN_T), lds, a.stream, p);
-        else DEP_LAUNCH(lstm_fwd_generic, grid, dim3(GEN_T), lds, a.stream, p);
+        if (a.lengths) {
+            if (a.cell == DEP_CELL_GRU) DEP_LAUNCH(gru_fwd_generic<true>, grid, dim3(GEN_T), lds, a.stream, p);
+            else DEP_LAUNCH(lstm_fwd_generic<true>, grid, dim3(GEN_T), lds, a.stream, p);
+        } else if (a.cell == DEP_CELL_GRU) DEP_LAUNCH(gru_fwd_generic<>, grid, dim3(GEN_T), lds, a.stream, p);
+        else DEP_LAUNCH(lstm_fwd_generic<>, grid, dim3(GEN_T), lds, a.stream, p);
     }
     DEP_CHECK_LAUNCH();
     return DEP_OK;
@@ -708,6 +818,7 @@ int dep_launch_sweep_bwd(const dep_sweep_bwd_args& a) {
     p.sv0 = a.sv0; p.sv1 = a.sv1; p.sv2 = a.sv2; p.sv3 = a.sv3;
     p.dgi = a.dgi; p.lddg = a.dirs * G * a.H; p.dghn = a.dghn; p.dbpart = a.dbpart;
     p.nwg = dep_sweep_num_wg(a.B, a.H, a.impl);
+    p.lengths = a.lengths; p.pool_mean = a.pool_mean;
     DEP_CHECK_ARG(a.dbpart_rows >= p.nwg * a.dirs);
     DEP_CHECK_ARG(a.sv0 && a.dgi && a.dbpart);
     DepProfScope prof(a.cell == DEP_CELL_GRU ? DEP_PROF_GRU_BWD : DEP_PROF_LSTM_BWD, a.stream);
@@ -720,8 +831,11 @@ int dep_launch_sweep_bwd(const dep_sweep_bwd_args& a) {
     } else {
         dim3 grid(a.B, a.dirs);
         const size_t lds = (size_t)(G * a.H + 2 * a.H) * sizeof(float);
-        if (a.cell == DEP_CELL_GRU) DEP_LAUNCH(gru_bwd_generic, grid, dim3(GEN_T), lds, a.stream, p);
-        else DEP_LAUNCH(lstm_bwd_generic, grid, dim3(GEN_T), lds, a.stream, p);
+        if (a.lengths) {
+            if (a.cell == DEP_CELL_GRU) DEP_LAUNCH(gru_bwd_generic<true>, grid, dim3(GEN_T), lds, a.stream, p);
+            else DEP_LAUNCH(lstm_bwd_generic<true>, grid, dim3(GEN_T), lds, a.stream, p);
+        } else if (a.cell == DEP_CELL_GRU) DEP_LAUNCH(gru_bwd_generic<>, grid, dim3(GEN_T), lds, a.stream, p);
+        else DEP_LAUNCH(lstm_bwd_generic<>, grid, dim3(GEN_T), lds, a.stream, p);
     }
     DEP_CHECK_LAUNCH();
     return DEP_OK;

@@ -38,6 +38,17 @@ class _RnnCache:
         self.args = (cell, F, H, Lyr, dirs, p, pool, device)
         self.cache = {}
 
+    @staticmethod
+    def lengths_on(lengths, B, device):
+        """A model call's `lengths` (None = dense; a sequence / array / tensor of B ints) as the int32 device vector the ragged
+        entry points read."""
+        if lengths is None:
+            return None
+        t = lengths if torch.is_tensor(lengths) else torch.as_tensor(np.asarray(lengths))
+        if t.is_floating_point() or t.dim() != 1 or t.numel() != B:
+            raise L.DepError(f'lengths: expected {B} integers, one per utterance, got {tuple(t.shape)} {t.dtype}')
+        return t.to(device=device, dtype=torch.int32).contiguous()
+
     def get(self, B, T, training):
         """training: a run mode (L.RUN_*); a bool means RUN_TRAIN / RUN_EVAL."""
         training = int(training)
@@ -217,7 +228,9 @@ class AudioGRU(nn.Module):
         return [] if w is None else [w]
 
     # encoder part shared with FusionNet
-    def encode(self, x, training, seed):
+    def encode(self, x, training, seed, lengths=None):
+        """lengths: int32 device vector (B), the utterances' own lengths inside the padded batch (None: dense).  The padding
+        must be finite (pad_ragged pads with zeros; LayerNorm maps a zero row to a zero row)."""
         B, T, F = x.shape
         P = self._params
         if self.variant == 'clf':
@@ -228,14 +241,17 @@ class AudioGRU(nn.Module):
             xn, weights = x.view(B * T, F), self._rnn_w
         rnn = self._rnns.get(B, T, training)
         pooled = torch.empty(B, self.hidden_dims, dtype=torch.float32, device=self.device)
-        rnn.forward(xn, weights, seed=seed, pooled=pooled)
-        return pooled, (x, xn, rnn)
+        rnn.forward(xn, weights, seed=seed, pooled=pooled, lengths=lengths)
+        return pooled, (x, xn, rnn, lengths)
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        """lengths: the ragged call -- x is padded to its longest utterance, row b is lengths[b] steps long (mean / sum pool over
+        its own steps); see _common.pad_ragged."""
         x = self._to_dev(x)
+        lengths = _RnnCache.lengths_on(lengths, x.shape[0], self.device)
         training = self.training
         seed = nn.next_dropout_seed() if training else 0
-        pooled, enc = self.encode(x, training, seed)
+        pooled, enc = self.encode(x, training, seed, lengths)
         z = self._head.forward(pooled, seed, training)
         out = torch.empty_like(z)
         kind = L.LOSS_CE_ON_SOFTMAX if self.variant == 'clf' else L.LOSS_L1_RELU
@@ -258,17 +274,17 @@ class AudioGRU(nn.Module):
         return in_call, post
 
     def backward(self, dz):
-        x, xn, rnn = self._saved
+        x, xn, rnn, lengths = self._saved
         dpool = self._head.backward(dz)
         P = self._params
         in_call, post = self.sync_plan()
         gs = parallel.make_grad_sync(self, in_call)
         if self.variant == 'clf':
-            rnn.backward(xn, self._rnn_w_fold, self._rnn_g_fold, dpooled=dpool, dx=None, grad_sync=gs)
+            rnn.backward(xn, self._rnn_w_fold, self._rnn_g_fold, dpooled=dpool, dx=None, grad_sync=gs, lengths=lengths)
             L.ln_fold_bwd(self._rnn_w[0], self._fold[2], self._fold[3], P['ln.weight'].data, P['ln.bias'].data,
                           self._rnn_g[0], self._rnn_g[2], P['ln.weight']._grad, P['ln.bias']._grad)
         else:
-            rnn.backward(xn, self._rnn_w, self._rnn_g, dpooled=dpool, dx=None, grad_sync=gs)
+            rnn.backward(xn, self._rnn_w, self._rnn_g, dpooled=dpool, dx=None, grad_sync=gs, lengths=lengths)
         self._grad_ready = True
         parallel.finish_grad_sync(self, in_call, post)
 
@@ -328,23 +344,26 @@ class TextBiLSTM(nn.Module):
             in_call[l] = self._span(first, last)
         return in_call, []
 
-    def encode(self, x, training, seed):
+    def encode(self, x, training, seed, lengths=None):
         B, T, F = x.shape
         P = self._params
         rnn = self._rnns.get(B, T, training)
         h_n = torch.empty(2 * self.rnn_layers, B, self.hidden_dims, dtype=torch.float32, device=self.device)
-        rnn.forward(x, self._rnn_w, seed=seed, h_n=h_n)
+        rnn.forward(x, self._rnn_w, seed=seed, h_n=h_n, lengths=lengths)
         out = rnn.layer_output()
-        ctx, att = L.attn_fwd(out, h_n, P['attention_layer.0.weight'].data, P['attention_layer.0.bias'].data)
-        return ctx, (x, rnn, out, att)
+        ctx, att = L.attn_fwd(out, h_n, P['attention_layer.0.weight'].data, P['attention_layer.0.bias'].data, lengths=lengths)
+        return ctx, (x, rnn, out, att, lengths)
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
         """x: (B,T,F) batch-first like the reference's call site (it permutes to time-first internally,
-        text_bilstm_whole.py:103; the HIP operator consumes batch-first directly)."""
+        text_bilstm_whole.py:103; the HIP operator consumes batch-first directly).
+        lengths: the ragged call -- row b is lengths[b] steps long (the reverse direction starts at its last step, the attention
+        softmax runs over its own steps); see _common.pad_ragged."""
         x = self._to_dev(x)
+        lengths = _RnnCache.lengths_on(lengths, x.shape[0], self.device)
         training = self.training
         seed = nn.next_dropout_seed() if training else 0
-        ctx, enc = self.encode(x, training, seed)
+        ctx, enc = self.encode(x, training, seed, lengths)
         z = self._head.forward(ctx, seed, training)
         out = torch.empty_like(z)
         kind = L.LOSS_CE_ON_SOFTMAX if self.variant == 'clf' else L.LOSS_SMOOTHL1_RELU
@@ -354,13 +373,14 @@ class TextBiLSTM(nn.Module):
         return nn.Output(out, self, z)
 
     def backward(self, dz):
-        x, rnn, out, att = self._saved
+        x, rnn, out, att, lengths = self._saved
         P = self._params
         dctx = self._head.backward(dz)
         dout, dh_n = L.attn_bwd(dctx, out, P['attention_layer.0.weight'].data, att, 2 * self.rnn_layers,
-                                P['attention_layer.0.weight']._grad, P['attention_layer.0.bias']._grad)
+                                P['attention_layer.0.weight']._grad, P['attention_layer.0.bias']._grad, lengths=lengths)
         in_call, post = self.sync_plan()
-        rnn.backward(x, self._rnn_w, self._rnn_g, dy=dout, dh_n=dh_n, dx=None, grad_sync=parallel.make_grad_sync(self, in_call))
+        rnn.backward(x, self._rnn_w, self._rnn_g, dy=dout, dh_n=dh_n, dx=None, grad_sync=parallel.make_grad_sync(self, in_call),
+                     lengths=lengths)
         self._grad_ready = True
         parallel.finish_grad_sync(self, in_call, post)
 

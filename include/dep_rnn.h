@@ -15,7 +15,8 @@
  *   - return 0 on success, negative dep_status on error; dep_last_error() returns a message;
  *   - no allocation happens inside the library: workspace / reserve sizes come from the *_bytes
  *     queries and the caller provides the buffers (16-byte aligned);
- *   - gate order is PyTorch's: GRU r,z,n ; LSTM i,f,g,o ; h0 = c0 = 0 always.
+ *   - gate order is PyTorch's: GRU r,z,n ; LSTM i,f,g,o ; h0 = c0 = 0 always;
+ *   - batches are dense (all B utterances T steps long) unless an entry point takes `lengths` (the *_varlen calls).
  *   - threads: entry points may be called concurrently from several host threads as long as each call has its own stream,
  *     workspace and reserve (dep_last_error is per thread; the launch-time recorder behind dep_profile_* and the
  *     reserve-mode record are mutex-guarded).  PROCESS-GLOBAL, not per stream: dep_set_gemm_mode (precision mode of every
@@ -149,6 +150,38 @@ int dep_rnn_backward(const dep_rnn_desc* d, const float* x, const float* const* 
                      void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ------------------------------------------------------------------ ragged batches -- */
+/* Variable-length batches: x is a padded (B,T,F) batch and `lengths` a DEVICE pointer to B int32 values, caller-owned and read by the
+ * kernels (no host copy, no synchronisation); row b is len_b = lengths[b] steps long, clamped on the device to [0, T].  The contract:
+ *
+ *   row b of every result equals what the dense entry point gives for that utterance alone, x[b:b+1, :len_b], at T' = len_b;
+ *   positions t >= len_b of every output sequence (y, the layers' outputs in the reserve, alpha, dout) are exactly 0.0;
+ *   weight gradients are the sum over rows of the per-row gradients; dx is exactly 0.0 at padded positions.
+ *
+ * i.e. pack_padded_sequence(enforce_sorted=False) -> nn.GRU / nn.LSTM -> pad_packed_sequence(total_length=T):
+ *   - h_n is the state after step len_b - 1 (forward direction) / after step 0 (reverse direction, which STARTS at t = len_b - 1);
+ *     dh_n enters there;
+ *   - pooled (DEP_POOL_MEAN / _SUM) sums t < len_b and the mean divides by len_b; dpooled is scaled by 1 / len_b and reaches live steps only;
+ *   - inter-layer dropout draws the masks of the dense call (the Philox element index of (b, t, col) is unchanged: a ragged call whose
+ *     lengths all equal T draws the dense call's masks); padded positions are 0 before and after the mask;
+ *   - len_b = 0: the row's y, pooled, h_n are 0, it contributes no gradient and divides by nothing.
+ * The PADDED POSITIONS OF x MUST BE FINITE (zeros are customary): the weight-gradient contractions multiply them by exact zeros.  What
+ * the reserve holds at dead positions besides the output sequences (saved gates) is unspecified.
+ * All three run modes; GEMM modes 0 and 1 (modes 2 / 3 return DEP_ERR_ARG).  Reserve / workspace sizes and offsets are those of the
+ * dense call.  A ragged call never runs a kernel without the length predicate: it takes the per-layer sweeps (tile, generic, cluster
+ * GRU, cluster BiLSTM), not the fused two-layer GRU launches or the 16-unit-member forward.  A reserve written by a ragged forward is
+ * consumed by a ragged backward with the SAME lengths; mixing a dense forward with a ragged backward (or the reverse) is the
+ * caller's error and is not detected.  lengths == NULL is DEP_ERR_ARG here: the dense call is dep_rnn_forward / dep_rnn_backward. */
+int dep_rnn_forward_varlen(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights,
+                           float* y, float* pooled, float* h_n,
+                           void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int dep_rnn_backward_varlen(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights,
+                            const float* dy, const float* dpooled, const float* dh_n,
+                            float* const* dweights, float* dx,
+                            void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
 /* ------------------------------------------------------------------ data parallel -- */
 /* RCCL over xGMI, one process per GPU (north_star; SURVEY 8b `dep_comm_{init,allreduce,destroy}`, 8e).  The reference has no
  * distributed code: these entry points are what a data-parallel `train()` binds -- the utterances of every global
@@ -198,6 +231,13 @@ int dep_rnn_backward_overlapped(const dep_rnn_desc* d, const float* x, const flo
                                 float* const* dweights, float* dx,
                                 void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
                                 void* stream, const dep_grad_sync* gs);
+
+/* dep_rnn_backward_overlapped for a ragged batch (dep_rnn_backward_varlen above; a rank passes its own shard of lengths). */
+int dep_rnn_backward_overlapped_varlen(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights,
+                                       const float* dy, const float* dpooled, const float* dh_n,
+                                       float* const* dweights, float* dx,
+                                       void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
+                                       void* stream, const dep_grad_sync* gs);
 
 /* ------------------------------------------------------------------ dense --------- */
 /* C[M,N] = opA(A)[M,K] * opB(B)[K,N] + bias[N] + beta*C      (fp32 MFMA, exact f32 products)
@@ -284,6 +324,17 @@ int dep_attn_bwd(const float* dctx, const float* out, const float* Wa, const flo
                  const float* pre, const float* hsum, int K,
                  float* dout, float* dh_n, float* dWa, float* dba, int B, int T, int H,
                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* Ragged batches (see dep_rnn_forward_varlen): `lengths` is a device pointer to B int32 values.  The softmax runs over t < len_b only,
+ * alpha[b, t >= len_b] and dout[b, t >= len_b] are exactly 0; a row with len_b = 0 gives ctx = 0 and zero gradients.  `out` is never
+ * read at padded positions. */
+int dep_attn_fwd_varlen(const float* out, const int32_t* lengths, const float* h_n, int K, const float* Wa, const float* ba,
+                        float* ctx, float* alpha, float* pre, float* hsum, int B, int T, int H,
+                        void* stream);
+int dep_attn_bwd_varlen(const float* dctx, const float* out, const int32_t* lengths, const float* Wa, const float* alpha,
+                        const float* pre, const float* hsum, int K,
+                        float* dout, float* dh_n, float* dWa, float* dba, int B, int T, int H,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ heads / losses - */
 /* Dropout as nn.Dropout(p) in training mode: y = x * m / (1-p), m ~ Bernoulli(1-p) from
