@@ -1,4 +1,4 @@
-"""Bits shared by the five script-shaped modules: metrics, checkpoint I/O, mini-batch slicing,
+"""Bits shared by the script-shaped modules: metrics, checkpoint I/O, mini-batch slicing and the training epoch loop,
 permutation augmentation.  (Reference: the duplicated helpers at Classification/audio_gru_whole.py:123-159,
 text_bilstm_whole.py:116-152, fuse_net_whole.py:30-68.)"""
 import itertools
@@ -7,7 +7,7 @@ import os
 import numpy as np
 import torch
 
-from . import parallel
+from . import nn, parallel
 from . import _lib as L
 
 
@@ -184,6 +184,67 @@ def rank_slice(lo, hi):
     """Rows of the global mini-batch [lo, hi) this data-parallel rank works on."""
     a, b = parallel.shard_slice(hi - lo)
     return lo + a, lo + b
+
+
+def train_epoch(model, optimizer, n_rows, batch_size, step, after_step=None):
+    """The mini-batch loop of every script's train() (audio_gru_whole.py:161-201 of the reference), which is also the data-parallel
+    protocol: per global mini-batch every rank issues the gradient ranges, then (lazily, in LossSum.item) the loss reduce; a rank
+    that owns no row of a small mini-batch joins both with a zero contribution.  Returns the summed loss, read from the device
+    once -- the epoch's only host synchronisation in here (it raises if a sweep gave up); the caller's ONE epoch-end collective
+    (correct count / prediction buffer) follows it on every rank.
+      step(a, b, then) -> (loss, output): forward, whatever is enqueued BEFORE the criterion (count_correct), the criterion.
+                                          `then` = the next mini-batch's rank slice, None after the last one, for
+                                          FeatureFeeder.rows(a, b, then=): a streamed feeder starts that upload beside this step.
+      after_step(a, b, output):           whatever is enqueued AFTER optimizer.step() (store_predictions).
+    The scripts differ in two ways only: the classification loops count before the criterion and the regression loops store
+    after the update (hence two hooks), and the fusion loops ignore `then` (PairFeeder.rows takes none: the pairs are resident)."""
+    total = nn.LossSum(model.device)                 # device-side sum of the step losses
+    batches = [(rank_slice(lo, hi), hi - lo) for lo, hi in minibatches(n_rows, batch_size)]
+    for bi, ((a, b), n_glob) in enumerate(batches):
+        parallel.set_global_count(n_glob)
+        if b <= a:                                  # this rank owns no row of a small (ragged) mini-batch: zero-contribution step
+            total.add(nn.empty_shard_step(model, optimizer))
+            continue
+        optimizer.zero_grad()
+        loss, output = step(a, b, batches[bi + 1][0] if bi + 1 < len(batches) else None)
+        loss.backward()
+        optimizer.step()
+        if after_step is not None:
+            after_step(a, b, output)
+        total.add(loss, model)
+    parallel.set_global_count(None)
+    return total.item()
+
+
+def fusion_forward(model, rows):
+    """pretrained_feature -> cat(text, audio) -> head of the fusion loops (fuse_net_whole.py:441-448): `rows` is what
+    fusion_net.pretrained_feature takes, PairFeeder rows or a list slice of pairs.  Returns (text_feature, audio_feature, output)."""
+    text_feature, audio_feature = model.pretrained_feature(rows)
+    return text_feature, audio_feature, model(concat_features(text_feature, audio_feature))
+
+
+def mae_rmse(y, pred):
+    """(MAE, RMSE) in float64, as sklearn's mean_absolute_error / sqrt(mean_squared_error) give them (Regression/audio_bilstm_perm.py:167-171)."""
+    y =np.asarray(y, np.float64); pred = np.asarray(pred, np.float64)
+    return float(np.mean(np.abs(y - pred))), float(np.sqrt(np.mean((y - pred) ** 2)))
+
+
+def epoch_mae_rmse(y, pred_dev):
+    """Epoch end of the regression train() loops: the ranks' prediction buffers (own rows, zeros elsewhere) are assembled by ONE
+    all-reduce, on every rank -- same sequence on working and empty-shard ranks, no per-step host copy."""
+    pred = parallel.all_reduce_sum(pred_dev).cpu().numpy().astype(np.float64) if len(y) else np.array([])
+    return mae_rmse(y, pred)
+
+
+def report_prf(conf_matrix):
+    """The metric block the classification evaluate()s print after the confusion matrix (audio_gru_whole.py:227-231)."""
+    accuracy, precision, recall, f1_score = prf(conf_matrix)
+    print("Accuracy: {}".format(accuracy))
+    print("Precision: {}".format(precision))
+    print("Recall: {}".format(recall))
+    print("F1-Score: {}\n".format(f1_score))
+    print('=' * 89)
+    return accuracy, precision, recall, f1_score
 
 
 def permutation_augment(features, targets, idxs, is_positive, keep, label=None):

@@ -56,41 +56,23 @@ class AudioBiLSTM(models.AudioGRU):
         super().__init__(config, variant='reg', seed=seed)
 
 
-def _mae_rmse(y, pred):
-    y = np.asarray(y, np.float64); pred = np.asarray(pred, np.float64)
-    return float(np.mean(np.abs(y - pred))), float(np.sqrt(np.mean((y - pred) ** 2)))
-
-
 def train(epoch):
     """Reference lines 134-172."""
     model.train()
-    total = nn.LossSum(model.device)                 # device-side sum of the step losses, read once per epoch
     idx = list(train_dep_idxs) + list(train_non_idxs)
     pred_dev = _common.prediction_buffer(len(idx), model.device)       # zero-filled; every rank writes its own rows
     Y_train = audio_targets[idx]
     Y_dev = _common.device_labels(Y_train, model.device)
     feed = _common.FeatureFeeder(audio_features, idx, model.device, role='audio_features')       # rows of X_train = audio_features[idx], in HBM
-    batches = [((lo, hi), _common.rank_slice(lo, hi)) for lo, hi in _common.minibatches(len(idx), config['batch_size'])]
-    for bi, ((lo, hi), (a, b)) in enumerate(batches):
-        parallel.set_global_count(hi - lo)
-        if b <= a:                                  # empty shard of a small (ragged) mini-batch: zero-contribution step
-            total.add(nn.empty_shard_step(model, optimizer))
-            continue
-        x = feed.rows(a, b, then=batches[bi + 1][1] if bi + 1 < len(batches) else None)
-        y = Y_dev[a:b]
-        optimizer.zero_grad()
-        output = model(x)
-        loss = criterion(output, y.view(-1, 1))
-        loss.backward()
-        optimizer.step()
+
+    def step(a, b, then):
+        output = model(feed.rows(a, b, then=then))
+        return criterion(output, Y_dev[a:b].view(-1, 1)), output
+
+    def after_step(a, b, output):
         _common.store_predictions(pred_dev, a, output)     # this rank's rows; the others' stay zero until the epoch-end SUM
-        total.add(loss, model)
-    parallel.set_global_count(None)
-    total_loss = total.item()                        # the epoch's only host synchronisation on the loss (raises if a sweep gave up)
-    # per step every rank issues: the gradient exchange, then the loss scalar (nn.Loss.item); the predictions of the whole epoch
-    # are assembled by ONE all-reduce here -- same sequence on working and empty-shard ranks (ADVICE r2), no per-step host copy
-    pred = parallel.all_reduce_sum(pred_dev).cpu().numpy().astype(np.float64) if len(idx) else np.array([])
-    train_mae, train_rmse = _mae_rmse(Y_train, pred)
+    total_loss = _common.train_epoch(model, optimizer, len(idx), config['batch_size'], step, after_step)
+    train_mae, train_rmse = _common.epoch_mae_rmse(Y_train, pred_dev)
     if parallel.rank() == 0:
         print('Train Epoch: {:2d}\t Learning rate: {:.4f}\t Loss: {:.4f}\t MAE: {:.4f}\t RMSE: {:.4f}\n '
               .format(epoch + 1, config['learning_rate'], total_loss, train_mae, train_rmse))
@@ -109,7 +91,7 @@ def evaluate(fold, model, train_mae):
     loss = criterion(output, y.view(-1, 1))
     total_loss = loss.item()
     pred = output.data.flatten().cpu().numpy()
-    mae, rmse = _mae_rmse(Y_test, pred)
+    mae, rmse = _common.mae_rmse(Y_test, pred)
     print('MAE: {:.4f}\t RMSE: {:.4f}\n'.format(mae, rmse))
     print('=' * 89)
     if mae <= min_mae and mae < 8.5 and train_mae < 13:

@@ -70,28 +70,17 @@ def train(epoch, train_idxs):
     mini-batch is split across ranks; the result equals the single-process run on the same data."""
     global train_acc
     model.train()
-    total = nn.LossSum(model.device)                 # device-side sum of the step losses, read once per epoch
     correct_dev = torch.zeros((), dtype=torch.int64, device=model.device)      # counted on the device, read once per epoch
     n_train = len(train_idxs)
     Y_dev = _common.device_labels(audio_targets[train_idxs], model.device, config['num_classes'])
     feed = _common.FeatureFeeder(audio_features, train_idxs, model.device, role='audio_features')       # rows of X_train = audio_features[train_idxs], in HBM
-    batches = [(_common.rank_slice(lo, hi), hi - lo) for lo, hi in _common.minibatches(n_train, config['batch_size'])]
-    for bi, ((a, b), n_glob) in enumerate(batches):
-        parallel.set_global_count(n_glob)
-        if b <= a:                                  # this rank owns no row of a small (ragged) mini-batch: zero-contribution step
-            total.add(nn.empty_shard_step(model, optimizer))
-            continue
-        x = feed.rows(a, b, then=batches[bi + 1][0] if bi + 1 < len(batches) else None)
+
+    def step(a, b, then):
         y = Y_dev[a:b]
-        optimizer.zero_grad()
-        output = model(x)
+        output = model(feed.rows(a, b, then=then))
         _common.count_correct(output, y, correct_dev)          # arg-max, comparison and running count: one launch
-        loss = criterion(output, y)
-        loss.backward()
-        optimizer.step()
-        total.add(loss, model)
-    parallel.set_global_count(None)
-    total_loss = total.item()                        # the epoch's only host synchronisation on the loss (raises if a sweep gave up)
+        return criterion(output, y), output
+    total_loss = _common.train_epoch(model, optimizer, n_train, config['batch_size'], step)
     correct = int(parallel.all_reduce_sum(correct_dev).item())                  # one collective per epoch, on every rank
     train_acc = correct
     if parallel.rank() == 0:
@@ -110,12 +99,7 @@ def evaluate(model, test_idxs, fold, train_idxs_tmp, train_idxs):
     loss = criterion(output, y)
     total_loss = loss.item()
     y_test_pred, conf_matrix = model_performance(y, output)
-    accuracy, precision, recall, f1_score = _common.prf(conf_matrix)
-    print("Accuracy: {}".format(accuracy))
-    print("Precision: {}".format(precision))
-    print("Recall: {}".format(recall))
-    print("F1-Score: {}\n".format(f1_score))
-    print('=' * 89)
+    accuracy, precision, recall, f1_score = _common.report_prf(conf_matrix)
     if max_f1 <= f1_score and train_acc > len(train_idxs) * 0.90 and f1_score > 0.5:
         max_f1, max_acc, max_rec, max_prec = f1_score, accuracy, recall, precision
         save(model, os.path.join(prefix, 'Model/ClassificationWhole/Audio/BiLSTM_{}_vlad{}_{}_{:.2f}_{}'.format(

@@ -83,40 +83,22 @@ def build(seed=None):
     return model
 
 
-def _mae_rmse(y, pred):
-    y = np.asarray(y, np.float64); pred = np.asarray(pred, np.float64)
-    return float(np.mean(np.abs(y - pred))), float(np.sqrt(np.mean((y - pred) ** 2)))
-
-
 def train(model, epoch):
     """Reference lines 373-412."""
     model.train()
-    total = nn.LossSum(model.device)                 # device-side sum of the step losses, read once per epoch
     idx = list(train_dep_idxs) + list(train_non_idxs)
     pred_dev = _common.prediction_buffer(len(idx), model.device)       # zero-filled; every rank writes its own rows
     Y_train = [fuse_targets[i] for i in idx]
     feed = _common.PairFeeder(fuse_features, idx, model.device)
-    for lo, hi in _common.minibatches(len(idx), config['batch_size']):
-        a, b = _common.rank_slice(lo, hi)
-        parallel.set_global_count(hi - lo)
-        y = Y_train[a:b]
-        if b <= a:                                  # empty shard of a small mini-batch: zero-contribution step
-            total.add(nn.empty_shard_step(model, optimizer))
-            continue
-        optimizer.zero_grad()
-        text_feature, audio_feature = model.pretrained_feature(feed.rows(a, b))
-        output = model(_common.concat_features(text_feature, audio_feature))
-        loss = criterion(text_feature, audio_feature, y, model)
-        loss.backward()
-        optimizer.step()
+
+    def step(a, b, then):
+        text_feature, audio_feature, output = _common.fusion_forward(model, feed.rows(a, b))
+        return criterion(text_feature, audio_feature, Y_train[a:b], model), output
+
+    def after_step(a, b, output):
         _common.store_predictions(pred_dev, a, output)     # this rank's rows; the others' stay zero until the epoch-end SUM
-        total.add(loss, model)
-    parallel.set_global_count(None)
-    total_loss = total.item()                        # the epoch's only host synchronisation on the loss (raises if a sweep gave up)
-    # per step every rank issues: the gradient exchange, then the loss scalar (nn.Loss.item); the predictions of the whole epoch
-    # are assembled by ONE all-reduce here -- same sequence on working and empty-shard ranks (ADVICE r2), no per-step host copy
-    pred = parallel.all_reduce_sum(pred_dev).cpu().numpy().astype(np.float64) if len(idx) else np.array([])
-    train_mae, train_rmse = _mae_rmse(Y_train, pred)
+    total_loss = _common.train_epoch(model, optimizer, len(idx), config['batch_size'], step, after_step)
+    train_mae, train_rmse = _common.epoch_mae_rmse(Y_train, pred_dev)
     if parallel.rank() == 0:
         print('Train Epoch: {:2d}\t Learning rate: {:.4f}\t Loss: {:.4f}\t MAE: {:.4f}\t RMSE: {:.4f}\n '
               .format(epoch + 1, config['learning_rate'], total_loss, train_mae, train_rmse))
@@ -133,13 +115,11 @@ def evaluate(model, fold, train_mae):
     Y_test = [fuse_targets[i] for i in idx]
     feed = _common.PairFeeder(fuse_features, idx, model.device)
     for lo, hi in _common.minibatches(len(idx), config['batch_size']):
-        y = Y_test[lo:hi]
-        text_feature, audio_feature = model.pretrained_feature(feed.rows(lo, hi))
-        output = model(_common.concat_features(text_feature, audio_feature))
-        loss = criterion(text_feature, audio_feature, y, model)
+        text_feature, audio_feature, output = _common.fusion_forward(model, feed.rows(lo, hi))
+        loss = criterion(text_feature, audio_feature, Y_test[lo:hi], model)
         pred = np.hstack((pred, output.data.flatten().cpu().numpy()))
         total_loss += loss.item()
-    mae, rmse = _mae_rmse(Y_test, pred)
+    mae, rmse = _common.mae_rmse(Y_test, pred)
     print('MAE: {:.4f}\t RMSE: {:.4f}\n'.format(mae, rmse))
     print('=' * 89)
     if mae <= min_mae and mae < 8.2 and train_mae < 13:
@@ -163,7 +143,7 @@ def _single_modality_eval(model, col, crit):
     loss = crit(output, y.view(-1, 1))
     loss.item()
     pred = output.data.flatten().cpu().numpy()
-    mae, rmse = _mae_rmse(Y_test, pred)
+    mae, rmse = _common.mae_rmse(Y_test, pred)
     print('MAE: {:.4f}\t RMSE: {:.4f}\n'.format(mae, rmse))
     print('=' * 89)
 

@@ -92,39 +92,21 @@ def build(seed=None):
     return model
 
 
-def _batch(items, labels, lo, hi):
-    a, b = _common.rank_slice(lo, hi)
-    return items[a:b], labels[a:b]
-
-
 def train(epoch, train_idxs):
     """Reference lines 421-465."""
     global max_train_acc, train_acc
     model.train()
-    total = nn.LossSum(model.device)                 # device-side sum of the step losses, read once per epoch
     correct_dev = torch.zeros((), dtype=torch.int64, device=model.device)      # counted on the device, read once per epoch
     n_train = len(train_idxs)
     Y_train = [fuse_targets[idx] for idx in train_idxs]
     Y_dev = _common.device_labels(np.asarray(Y_train), model.device, config['num_classes'])
     feed = _common.PairFeeder(fuse_features, train_idxs, model.device)       # the pairs X_train = [fuse_features[i] ...], in HBM
-    for lo, hi in _common.minibatches(n_train, config['batch_size']):
-        a, b = _common.rank_slice(lo, hi)
-        y = Y_train[a:b]
-        parallel.set_global_count(hi - lo)
-        if b <= a:                             # empty shard of a small mini-batch (batch_size 2 < world): zero-contribution step
-            total.add(nn.empty_shard_step(model, optimizer))
-            continue
-        optimizer.zero_grad()
-        text_feature, audio_feature = model.pretrained_feature(feed.rows(a, b))
-        concat_x = _common.concat_features(text_feature, audio_feature)
-        output = model(concat_x)
+
+    def step(a, b, then):
+        text_feature, audio_feature, output = _common.fusion_forward(model, feed.rows(a, b))
         _common.count_correct(output, Y_dev[a:b], correct_dev)
-        loss = criterion(text_feature, audio_feature, y, model)
-        loss.backward()
-        optimizer.step()
-        total.add(loss, model)
-    parallel.set_global_count(None)
-    total_loss = total.item()                        # the epoch's only host synchronisation on the loss (raises if a sweep gave up)
+        return criterion(text_feature, audio_feature, Y_train[a:b], model), output
+    total_loss = _common.train_epoch(model, optimizer, n_train, config['batch_size'], step)
     correct = int(parallel.all_reduce_sum(correct_dev).item())                  # one collective per epoch, on every rank
     max_train_acc = correct
     train_acc = correct
@@ -143,22 +125,15 @@ def evaluate(model, test_idxs, fold, train_idxs):
     pred_dev = torch.empty(len(Y_test), 1, dtype=torch.int64, device=model.device)      # every mini-batch's arg-max lands here
     feed = _common.PairFeeder(fuse_features, test_idxs, model.device)
     for lo, hi in _common.minibatches(len(Y_test), config['batch_size']):
-        y = Y_test[lo:hi]
-        text_feature, audio_feature = model.pretrained_feature(feed.rows(lo, hi))
-        output = model(_common.concat_features(text_feature, audio_feature))
-        loss = criterion(text_feature, audio_feature, y, model)
+        text_feature, audio_feature, output = _common.fusion_forward(model, feed.rows(lo, hi))
+        loss = criterion(text_feature, audio_feature, Y_test[lo:hi], model)
         _common.predict(output, out=pred_dev[lo:hi])
         total_loss += loss.item()
     pred = pred_dev.cpu()
     y_test_pred, conf_matrix = model_performance(Y_test, pred)
     print('\nTest set: Average loss: {:.4f}'.format(total_loss / len(Y_test)))
     print('Calculating additional test metrics...')
-    accuracy, precision, recall, f1_score = _common.prf(conf_matrix)
-    print("Accuracy: {}".format(accuracy))
-    print("Precision: {}".format(precision))
-    print("Recall: {}".format(recall))
-    print("F1-Score: {}\n".format(f1_score))
-    print('=' * 89)
+    accuracy, precision, recall, f1_score = _common.report_prf(conf_matrix)
     if max_f1 < f1_score and max_train_acc >= len(train_idxs) * 0.9 and f1_score > 0.61:
         max_f1, max_acc = f1_score, accuracy
         save(model, os.path.join(prefix, 'Model/ClassificationWhole/Fuse/fuse_{:.2f}_{}'.format(max_f1, fold)))

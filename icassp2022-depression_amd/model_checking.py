@@ -30,10 +30,7 @@ def _load_into(model, path, strict=True):
 def _report(conf_matrix):
     """The metric block every classification checker prints after model_performance (AudioModelChecking.py:150-160)."""
     print('Calculating additional test metrics...')
-    accuracy, precision, recall, f1_score = _common.prf(conf_matrix)
-    print("Accuracy: {}".format(accuracy)); print("Precision: {}".format(precision))
-    print("Recall: {}".format(recall)); print("F1-Score: {}\n".format(f1_score)); print('=' * 89)
-    return precision, recall, f1_score
+    return _common.report_prf(conf_matrix)[1:]
 
 
 def evaluate_classifier(model, features, targets, test_idxs, batch_size):
@@ -57,8 +54,7 @@ def evaluate_fusion(model, fuse_features, fuse_targets, test_idxs, batch_size):
     X = [fuse_features[i] for i in test_idxs]; Y = [fuse_targets[i] for i in test_idxs]
     preds = []
     for lo, hi in _common.minibatches(len(X), batch_size):
-        tf, af = model.pretrained_feature(X[lo:hi])
-        preds.append(_common.predict(model(_common.concat_features(tf, af))).cpu().numpy())
+        preds.append(_common.predict(_common.fusion_forward(model, X[lo:hi])[2]).cpu().numpy())
     conf_matrix = _common.standard_confusion_matrix(np.asarray(Y), np.concatenate(preds) if preds else np.zeros((0, 1), np.int64))
     print("Confusion Matrix:"); print(conf_matrix)
     return _report(conf_matrix)
@@ -153,8 +149,7 @@ def check_audio_regressor(root, model_path, fold=2, config=None):
     idx = list(m.test_dep_idxs) + list(m.test_non_idxs)
     model.eval()
     pred = model(np.ascontiguousarray(m.audio_features[idx], dtype=np.float32)).data.flatten().cpu().numpy()
-    y = np.asarray(m.audio_targets[idx], np.float64)
-    mae = float(np.mean(np.abs(y - pred))); rmse = float(np.sqrt(np.mean((y - pred) ** 2)))
+    mae, rmse = _common.mae_rmse(m.audio_targets[idx], pred)
     print('MAE: {:.4f}\t RMSE: {:.4f}\n'.format(mae, rmse))
     print('=' * 89)
     return mae, rmse

@@ -233,7 +233,11 @@ def test_checkpoint_loader_is_safe_first_and_the_exporter_writes_a_module(tmp_pa
     assert list(again) == list(sd)
 
 
-# ----------------------------------------------------------------------------- collective order of the regression train() loops
+# ----------------------------------------------------------------------------- collective order of the train() loops
+_CLF_LABELS = np.array([1, 0, 1, 0, 1, 0, 0], dtype=np.int64)
+_CLF_THRESHOLD = 12.0
+
+
 def _order_worker(rank, world, port, q, modname):
     """a rank whose shard of the last mini-batch is empty must issue the step's collectives in the order
     the working ranks do -- gradients, predictions (hi - lo floats), loss scalar.  The script's real train() runs on every
@@ -247,6 +251,7 @@ def _order_worker(rank, world, port, q, modname):
     import torch.distributed as dist
     from icassp2022_depression_amd import nn, parallel as par
     m = importlib.import_module('icassp2022_depression_amd.' + modname)
+    clf = modname.endswith('_whole')
     par.init_from_env('gloo')
 
     class Out:
@@ -278,7 +283,10 @@ def _order_worker(rank, world, port, q, modname):
             return x.reshape(x.shape[0], -1).sum(1)
 
         def __call__(self, x):
-            return Out(self._rows(x).view(-1, 1) if not isinstance(x, torch.Tensor) or x.dim() != 2 else x.sum(1, keepdim=True))
+            out = self._rows(x).view(-1, 1) if not isinstance(x, torch.Tensor) or x.dim() != 2 else x.sum(1, keepdim=True)
+            if clf:                                         # two-column score: class 1 wherever the row's value is below the threshold
+                out = torch.cat((out, torch.full_like(out, _CLF_THRESHOLD * (3 if modname == 'fuse_net_whole' else 1))), dim=1)
+            return Out(out)
 
         def pretrained_feature(self, x):
             r = self._rows(x).view(-1, 1)
@@ -308,7 +316,15 @@ def _order_worker(rank, world, port, q, modname):
     targs = np.arange(N, dtype=np.float32)
     m.config.update(batch_size=5)
     m.train_dep_idxs, m.train_non_idxs = [0, 1, 2], [3, 4, 5, 6]
-    if modname == 'fuse_net':
+    if clf:
+        if modname == 'fuse_net_whole':
+            m.fuse_features = [[feats[i], feats[i] * 2] for i in range(N)]; m.fuse_targets = _CLF_LABELS
+        else:
+            which = 'audio' if modname.startswith('audio') else 'text'
+            setattr(m, which + '_features', feats); setattr(m, which + '_targets', _CLF_LABELS)
+        m.model, m.optimizer, m.criterion = fake, Opt(), crit
+        args = (1, list(range(N)))
+    elif modname == 'fuse_net':
         m.fuse_features = [[feats[i], feats[i] * 2] for i in range(N)]; m.fuse_targets = targs
         m.optimizer, m.criterion = Opt(), crit
         args = (fake, 1)
@@ -320,6 +336,8 @@ def _order_worker(rank, world, port, q, modname):
     import contextlib, io
     with contextlib.redirect_stdout(io.StringIO()):
         mae = m.train(*args)
+    if clf:                                                 # these return nothing: the count is left in the module global
+        mae = m.max_train_acc if modname == 'fuse_net_whole' else m.train_acc
     q.put((rank, float(mae)))
     dist.barrier(); dist.destroy_process_group()
 
@@ -343,6 +361,94 @@ def test_regression_train_empty_shard_collective_order_gloo(modname):
     expect = float(np.mean(np.abs(np.arange(7) - pred)))
     for r in range(3):
         assert abs(got[r] - expect) < 1e-5, (r, got[r], expect)
+
+
+@pytest.mark.parametrize('modname', ['audio_gru_whole', 'text_bilstm_whole', 'fuse_net_whole'])
+def test_classification_train_empty_shard_collective_order_gloo(modname):
+    """The same geometry on the classification loops (7 rows, batch 5, world 3: rank 2 owns no row of the tail batch).  They have
+    no prediction buffer: every rank must finish, and the epoch-end all-reduce must leave the serial correct count on each."""
+    import torch.multiprocessing as mp
+    ctx = mp.get_context('spawn')
+    q = ctx.Queue()
+    port = 27100 + os.getpid() % 800 + {'audio_gru_whole': 0, 'text_bilstm_whole': 1, 'fuse_net_whole': 2}[modname]
+    procs = [ctx.Process(target=_order_worker, args=(r, 3, port, q, modname)) for r in range(3)]
+    for p in procs:
+        p.start()
+    got = dict(q.get(timeout=180) for _ in range(3))
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    # the stand-in scores a row [v, threshold] with v = its feature sum (fusion: text + audio = 3 x): first arg-max per row
+    feats = np.arange(7 * 6, dtype=np.float32).reshape(7, 3, 2) / 10
+    scale = 3 if modname == 'fuse_net_whole' else 1
+    score = np.stack([feats.reshape(7, -1).sum(1) * scale, np.full(7, _CLF_THRESHOLD * scale, np.float32)], axis=1)
+    expect = int(np.sum(np.argmax(score, axis=1) == _CLF_LABELS))
+    assert 0 < expect < 7                                    # both classes predicted, some rows wrong: the count says something
+    for r in range(3):
+        assert got[r] == expect, (r, got[r], expect)
+
+
+def test_train_epoch_call_sequence(monkeypatch):
+    """_common.train_epoch at world size 1 with recording stand-ins: the global count per batch, the rank slices and the look-ahead
+    slice handed to step, the order of the calls inside a batch, and the summed loss."""
+    from icassp2022_depression_amd import nn
+    log = []
+    monkeypatch.setattr(parallel, 'set_global_count', lambda n: log.append(('count', n)))
+
+    class Sum(nn.LossSum):
+        def add(self, loss, model=None):
+            log.append(('add', float(loss._v), model))
+            return super().add(loss, model)
+
+    monkeypatch.setattr(nn, 'LossSum', Sum)
+
+    class Model:
+        device = torch.device('cpu')
+
+    class Opt:
+        def zero_grad(self):
+            log.append(('zero_grad',))
+
+        def step(self):
+            log.append(('opt_step',))
+
+    losses = iter([0.5, 0.25, 2.0])
+
+    def step(a, b, then):
+        log.append(('step', a, b, then))
+        return nn.Loss(torch.tensor([next(losses)]), lambda: log.append(('backward',))), ('out', a)
+
+    model = Model()
+    total = _common.train_epoch(model, Opt(), 7, 3, step, lambda a, b, out: log.append(('after', a, b, out)))
+    expect = []
+    for (a, b), then, v in (((0, 3), (3, 6), 0.5), ((3, 6), (6, 7), 0.25), ((6, 7), None, 2.0)):
+        expect += [('count', b - a), ('zero_grad',), ('step', a, b, then), ('backward',), ('opt_step',), ('after', a, b, ('out', a)),
+                   ('add', v, model)]
+    assert log == expect + [('count', None)]
+    assert total == 2.75
+    # no rows: as the loops always did, the global count is still cleared and the (empty) sum read; nothing else runs
+    del log[:]
+    assert _common.train_epoch(model, Opt(), 0, 3, step) == 0.0 and log == [('count', None)]
+    # without an after-step hook the rest of the sequence is unchanged
+    losses = iter([1.0])
+    assert _common.train_epoch(model, Opt(), 2, 3, step) == 1.0
+    assert log == [('count', None), ('count', 2), ('zero_grad',), ('step', 0, 2, None), ('backward',), ('opt_step',),
+                   ('add', 1.0, model), ('count', None)]
+
+
+def test_shared_metric_helpers_equal_the_copies_they_replace(capsys):
+    """_common.mae_rmse / report_prf against the blocks the scripts used to carry, on test_confusion_matrix_and_prf's inputs."""
+    y = np.array([1, 1, 0, 0, 1, 0]); p = np.array([1, 0, 0, 1, 1, 0])
+    yf = np.asarray(y, np.float64); pf = np.asarray(p, np.float64)
+    assert _common.mae_rmse(y, p) == (float(np.mean(np.abs(yf - pf))), float(np.sqrt(np.mean((yf - pf) ** 2))))
+    assert _common.mae_rmse(y, p.astype(np.float32)) == (2 / 6, float(np.sqrt(2 / 6)))
+    cm = _common.standard_confusion_matrix(y, p)
+    capsys.readouterr()
+    got = _common.report_prf(cm)
+    accuracy, precision, recall, f1_score = _common.prf(cm)
+    assert got == (accuracy, precision, recall, f1_score)
+    assert capsys.readouterr().out == ("Accuracy: {}\n".format(accuracy) + "Precision: {}\n".format(precision) + "Recall: {}\n".format(recall)
+                                       + "F1-Score: {}\n\n".format(f1_score) + '=' * 89 + '\n')
 
 
 def test_device_feature_cache_notices_in_place_edits(monkeypatch):
