@@ -100,6 +100,12 @@ _SIGS = {
     'dep_head_mlp_bwd': (C.c_int, [_P] * 12 + [C.c_int] * 4 + [C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, _P]),
     'dep_adam_step': (C.c_int, [_P, _P, _P, _P, C.c_long, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                 C.c_int, C.c_int, _P]),
+    'dep_grad_norm_slots': (C.c_int, []),
+    'dep_grad_norm_chunk': (C.c_int, []),
+    'dep_grad_sqnorm': (C.c_int, [C.POINTER(_P), C.POINTER(C.c_long), C.c_int, _P, _P]),
+    'dep_adam_step_clipped': (C.c_int, [_P, _P, _P, _P, C.c_long, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                        C.c_int, C.c_int, _P, C.c_float, C.c_int, _P, _P, _P]),
+    'dep_grad_clip_scale': (C.c_int, [C.POINTER(_P), C.POINTER(C.c_long), C.c_int, _P, C.c_float, _P, _P]),
     'dep_frame_window': (C.c_int, [_P, C.c_long, C.c_int, C.c_int, C.c_int, _P, _P]),
     'dep_power_spectrum': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
     'dep_log_floor': (C.c_int, [_P, _P, C.c_long, C.c_float, _P]),
@@ -309,6 +315,36 @@ def reduce_loss(loss_rows, norm, loss_out, accumulate=False):
 def adam_step(p, g, m, v, lr, b1, b2, eps, wd, decoupled, step):
     check(load().dep_adam_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, b1, b2, eps, wd, int(decoupled),
                                int(step), stream()), 'dep_adam_step')
+
+
+def grad_norm_slots():
+    return int(load().dep_grad_norm_slots())
+
+
+def _range_arrays(ranges):
+    ptrs = (_P * len(ranges))(*[_ptr(f32(t)) for t in ranges])
+    cnts = (C.c_long * len(ranges))(*[t.numel() for t in ranges])
+    return ptrs, cnts
+
+
+def grad_sqnorm(ranges, partials):
+    """partials (dep_grad_norm_slots() float64 on the device) <- the deterministic partial sums of g^2 over `ranges`, a list of up
+    to 16 contiguous fp32 device tensors (dep_grad_sqnorm).  One launch."""
+    ptrs, cnts = _range_arrays(ranges)
+    check(load().dep_grad_sqnorm(ptrs, cnts, len(ranges), _ptr(partials), stream()), 'dep_grad_sqnorm')
+
+
+def adam_step_clipped(p, g, m, v, lr, b1, b2, eps, wd, decoupled, step, partials, max_norm, skip_nonfinite=False, clip_out=None,
+                      stats=None):
+    check(load().dep_adam_step_clipped(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, b1, b2, eps, wd, int(decoupled),
+                                       int(step), _ptr(partials), float(max_norm), int(skip_nonfinite), _ptr(clip_out),
+                                       _ptr(stats), stream()), 'dep_adam_step_clipped')
+
+
+def grad_clip_scale(ranges, partials, max_norm, clip_out=None):
+    ptrs, cnts = _range_arrays(ranges)
+    check(load().dep_grad_clip_scale(ptrs, cnts, len(ranges), _ptr(partials), float(max_norm), _ptr(clip_out), stream()),
+          'dep_grad_clip_scale')
 
 
 def fill(t, value):

@@ -1,0 +1,201 @@
+// Global-norm gradient clipping on the device (dep_grad_sqnorm, dep_adam_step_clipped, dep_grad_clip_scale; include/dep_rnn.h).
+//
+// The sum of squares is a pure function of the data.  The ranges are read as ONE concatenated array cut into chunks of
+// GN_CHUNK floats; partial slot s holds the sum over chunks s, s + GN_SLOTS, ... in that order, and ONE workgroup owns a slot
+// whatever the size (the grid is always GN_SLOTS workgroups).  Inside a chunk thread t squares elements 4t .. 4t+3 in fp64 (the
+// product of two fp32 values is exact there), adds them as (p0 + p1) + (p2 + p3), and the workgroup sums its threads through a
+// fixed butterfly in the wave and a fixed tree over the four waves.  No atomics, no cross-workgroup hand-off: the partials are
+// plain stores that the kernel boundary publishes.  The consumers re-sum the GN_SLOTS partials with the same fixed tree in EVERY
+// workgroup, so every workgroup -- and every data-parallel rank, which holds the same reduced gradients -- forms the same bits.
+#include "dep_common.h"
+
+namespace {
+
+constexpr int GN_SLOTS = 256;              // partial sums (doubles) the caller provides: dep_grad_norm_slots()
+constexpr int GN_THREADS = 256;
+constexpr int GN_CHUNK = GN_THREADS * 4;   // floats per chunk, one 16-byte load per thread: dep_grad_norm_chunk()
+constexpr int GN_MAXR = 16;
+static_assert(GN_SLOTS == GN_THREADS, "the consumers load one partial per thread");
+
+struct GradRanges {
+    const float* ptr[GN_MAXR];
+    long start[GN_MAXR + 1];               // start[r] = index of range r's first element in the concatenation; start[count] = total
+    int count;
+};
+struct GradRangesRW { float* ptr[GN_MAXR]; long n[GN_MAXR]; int count; };
+
+// sum over the workgroup's GN_THREADS threads, the same bits in every thread: xor butterfly in the wave (commutative pairs, so all
+// lanes agree), then (w0 + w1) + (w2 + w3) over the waves
+__device__ __forceinline__ double gn_block_sum(double v, double* red) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(GN_THREADS) void grad_sqnorm_kernel(GradRanges R, double* __restrict__ partials) {
+    __shared__ double red[4];
+    const long total = R.start[R.count];
+    const long nchunks = (total + GN_CHUNK - 1) / GN_CHUNK;
+    double acc = 0.0;
+    for (long c = blockIdx.x; c < nchunks; c += GN_SLOTS) {
+        const long i = c * GN_CHUNK + (long)threadIdx.x * 4;
+        double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
+        if (i < total) {
+            int r = 0;
+            while (i >= R.start[r + 1]) ++r;                       // i < total = start[count]: stops at r < count
+            const long off = i - R.start[r];
+            if (i + 3 < R.start[r + 1] && (off & 3) == 0) {        // the four elements sit in one range at a 16-byte boundary
+                const f32x4 x = *reinterpret_cast<const f32x4*>(R.ptr[r] + off);
+                p0 = (double)x[0] * (double)x[0]; p1 = (double)x[1] * (double)x[1];
+                p2 = (double)x[2] * (double)x[2]; p3 = (double)x[3] * (double)x[3];
+            } else {                                               // a range boundary or the tail: element by element (absent = +0)
+                double p[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const long k = i + e;
+                    if (k < total) {
+                        while (k >= R.start[r + 1]) ++r;
+                        const double x = (double)R.ptr[r][k - R.start[r]];
+                        p[e] = x * x;
+                    }
+                }
+                p0 = p[0]; p1 = p[1]; p2 = p[2]; p3 = p[3];
+            }
+        }
+        acc += (p0 + p1) + (p2 + p3);
+    }
+    const double s = gn_block_sum(acc, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;                // every slot is written (0 for a slot without a chunk)
+}
+
+// What every consumer workgroup derives from the partials: S, norm = sqrt(S), and torch's clip coefficient
+//     coef = (float) min(1, max_norm / (norm + 1e-6))          (division in double, ONE rounding to fp32; a NaN quotient stays NaN)
+// max_norm <= 0 ("measure only", +inf arrives here as 0): coef = 1.
+struct ClipCoef { float coef; double norm; bool finite; };
+__device__ __forceinline__ ClipCoef gn_coef(const double* __restrict__ partials, double max_norm, double* red) {
+    const double S = gn_block_sum(partials[threadIdx.x], red);     // blockDim.x == GN_THREADS == GN_SLOTS
+    ClipCoef c;
+    c.norm = sqrt(S);
+    c.finite = S - S == 0.0;                                        // false for inf and NaN
+    if (max_norm > 0.0) {
+        const double q = max_norm / (c.norm + 1e-6);
+        c.coef = (float)(q > 1.0 ? 1.0 : q);
+    } else {
+        c.coef = 1.0f;
+    }
+    return c;
+}
+// clip_out = [coef, norm, finite, 0]; stats (doubles) = [steps, clipped steps, skipped steps, largest finite norm]
+__device__ __forceinline__ void gn_report(const ClipCoef& c, bool skipped, float* clip_out, double* stats) {
+    if (clip_out) { clip_out[0] = c.coef; clip_out[1] = (float)c.norm; clip_out[2] = c.finite ? 1.f : 0.f; clip_out[3] = 0.f; }
+    if (stats) {
+        stats[0] += 1.0;
+        if (skipped) stats[2] += 1.0;
+        else if (c.coef < 1.0f) stats[1] += 1.0;
+        if (c.finite && c.norm > stats[3]) stats[3] = c.norm;
+    }
+}
+
+// adam_kernel (elementwise.hip) with gv = g[i] * coef in front; the rest of the expression is that kernel's, operand for operand,
+// so that coef == 1 (g * 1.0f is exact) gives dep_adam_step's bits
+constexpr int AC_PER_THREAD = 8;           // elements per thread: the partials are re-summed once per 2048 elements
+__global__ __launch_bounds__(GN_THREADS) void adam_clipped_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                  float* __restrict__ m, float* __restrict__ v, long n, float lr,
+                                                                  float b1, float b2, float eps, float wd, int decoupled,
+                                                                  float step_size, float inv_sqrt_bc2,
+                                                                  const double* __restrict__ partials, double max_norm,
+                                                                  int skip_nonfinite, float* clip_out, double* stats) {
+    __shared__ double red[4];
+    const ClipCoef c = gn_coef(partials, max_norm, red);
+    const bool skipped = skip_nonfinite && !c.finite;
+    if (blockIdx.x == 0 && threadIdx.x == 0) gn_report(c, skipped, clip_out, stats);
+    if (skipped) return;                                           // p, m, v untouched
+    const float coef = c.coef;
+    const long base = (long)blockIdx.x * (GN_THREADS * AC_PER_THREAD) + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < AC_PER_THREAD; ++k) {
+        const long i = base + (long)k * GN_THREADS;
+        if (i >= n) break;
+        float pv = p[i], gv = g[i] * coef;
+        if (decoupled) pv *= (1.0f - lr * wd);
+        else if (wd != 0.f) gv = fmaf(wd, pv, gv);
+        const float mv = b1 * m[i] + (1.0f - b1) * gv;
+        const float vv = b2 * v[i] + (1.0f - b2) * gv * gv;
+        m[i] = mv; v[i] = vv;
+        const float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
+        p[i] = pv - step_size * (mv / denom);
+    }
+}
+
+// g *= coef over the ranges, blockIdx.y = range (torch.nn.utils.clip_grad_norm_ leaves .grad clipped)
+__global__ __launch_bounds__(GN_THREADS) void grad_clip_scale_kernel(GradRangesRW R, const double* __restrict__ partials,
+                                                                     double max_norm, float* clip_out) {
+    __shared__ double red[4];
+    const ClipCoef c = gn_coef(partials, max_norm, red);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) gn_report(c, false, clip_out, nullptr);
+    const float coef = c.coef;
+    if (coef == 1.0f) return;                                      // g * 1.0f is g
+    float* __restrict__ gp = R.ptr[blockIdx.y];
+    const long n = R.n[blockIdx.y], stride = (long)gridDim.x * GN_THREADS;
+    for (long i = (long)blockIdx.x * GN_THREADS + threadIdx.x; i < n; i += stride) gp[i] = gp[i] * coef;
+}
+
+// the argument checks of the three entry points that take ranges: before any HIP call
+int check_ranges(const float* const* bufs, const long* counts, int nranges) {
+    DEP_CHECK_ARG(bufs && counts && nranges >= 1 && nranges <= GN_MAXR);
+    for (int r = 0; r < nranges; ++r) DEP_CHECK_ARG(bufs[r] && counts[r] > 0 && ((uintptr_t)bufs[r] & 15) == 0);
+    return DEP_OK;
+}
+// "measure only": max_norm <= 0 or +inf -> 0 for the kernels
+inline double kernel_max_norm(float max_norm) { return (max_norm > 0.f && max_norm <= 3.402823466e38f) ? (double)max_norm : 0.0; }
+
+}  // namespace
+
+#define S_ ((hipStream_t)stream)
+
+extern "C" int dep_grad_norm_slots(void) { return GN_SLOTS; }
+extern "C" int dep_grad_norm_chunk(void) { return GN_CHUNK; }
+
+extern "C" int dep_grad_sqnorm(const float* const* bufs, const long* counts, int nranges, double* partials, void* stream) {
+    if (int rc = check_ranges(bufs, counts, nranges)) return rc;
+    DEP_CHECK_ARG(partials);
+    GradRanges R{};
+    long at = 0;
+    for (int r = 0; r < nranges; ++r) { R.ptr[r] = bufs[r]; R.start[r] = at; at += counts[r]; }
+    for (int r = nranges; r <= GN_MAXR; ++r) R.start[r] = at;
+    R.count = nranges;
+    DEP_LAUNCH(grad_sqnorm_kernel, dim3(GN_SLOTS), dim3(GN_THREADS), 0, S_, R, partials);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+
+extern "C" int dep_adam_step_clipped(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
+                                     float eps, float weight_decay, int decoupled, int step, const double* partials,
+                                     float max_norm, int skip_nonfinite, float* clip_out, double* stats, void* stream) {
+    DEP_CHECK_ARG(p && g && m && v && n > 0 && step >= 1 && partials && max_norm == max_norm);
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    const float step_size = (float)((double)lr / bc1);
+    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    DEP_LAUNCH(adam_clipped_kernel, dim3(dep_cdiv(n, GN_THREADS * AC_PER_THREAD)), dim3(GN_THREADS), 0, S_, p, g, m, v, n, lr,
+               beta1, beta2, eps, weight_decay, decoupled, step_size, inv_sqrt_bc2, partials, kernel_max_norm(max_norm),
+               skip_nonfinite, clip_out, stats);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+
+extern "C" int dep_grad_clip_scale(float* const* bufs, const long* counts, int nranges, const double* partials, float max_norm,
+                                   float* clip_out, void* stream) {
+    if (int rc = check_ranges(bufs, counts, nranges)) return rc;
+    DEP_CHECK_ARG(partials && max_norm == max_norm);
+    GradRangesRW R{};
+    long mx = 0;
+    for (int r = 0; r < nranges; ++r) { R.ptr[r] = bufs[r]; R.n[r] = counts[r]; if (counts[r] > mx) mx = counts[r]; }
+    R.count = nranges;
+    int gx = dep_cdiv(mx, GN_THREADS * 4); if (gx > 512) gx = 512;
+    DEP_LAUNCH(grad_clip_scale_kernel, dim3(gx, nranges), dim3(GN_THREADS), 0, S_, R, partials, kernel_max_norm(max_norm), clip_out);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}

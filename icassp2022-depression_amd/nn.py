@@ -90,6 +90,9 @@ class Module:
         for p in order:
             p.offset = off
             off += (p.numel + 3) // 4 * 4            # keep every tensor 16-byte aligned
+        # The alignment pads between tensors are LOAD-BEARING zeros in _flat_grad: the optimizer's ranges run over them, so the global
+        # gradient norm of a clipped step (dep_grad_sqnorm) sums them too.  The buffer is allocated zeroed below and every kernel writes
+        # gradients through the per-tensor views only (tests/test_clip_gpu.py holds the pads at exactly zero after a step).
         self._n_live = sum((p.numel + 3) // 4 * 4 for p in order if p.live)
         host = np.zeros(off, np.float32)
         for p in order:
@@ -370,8 +373,17 @@ def empty_shard_step(model, optimizer):
 class _AdamBase:
     decoupled = False
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=None, max_grad_norm=None, skip_nonfinite=False):
+        """max_grad_norm: clip the GLOBAL 2-norm of the gradients of all groups to it inside the update (torch's
+        clip_grad_norm_(all parameters, max_grad_norm) in front of step(), without its host read; None = no clipping).
+        skip_nonfinite: a step whose gradient norm is inf / NaN leaves parameters and moments untouched (it still counts in the bias
+        correction).  With both at their defaults step() enqueues exactly the dep_adam_step launches it always did."""
         params = list(params)
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f'max_grad_norm must be None or a non-negative number, got {max_grad_norm!r}')
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._clip = None         # device side of the clipped step: (partials, clip_out, stats), made by the first such step
         default_wd = (1e-2 if self.decoupled else 0.0) if weight_decay is None else weight_decay
         if params and isinstance(params[0], dict):
             groups = [dict(g) for g in params]
@@ -395,36 +407,128 @@ class _AdamBase:
     def _ranges(self, g):
         """Contiguous [start, end) ranges (in the owner's flat buffer) of the parameters of group g that
         currently hold a gradient -- parameters whose grad is None are skipped like torch does."""
-        per_owner = {}
-        for p in g['params']:
-            if p.grad is None:
-                continue
-            per_owner.setdefault(id(p.owner), (p.owner, []))[1].append((p.offset, p.offset + (p.numel + 3) // 4 * 4))
-        out = []
-        for owner, rs in per_owner.values():
-            rs.sort()
-            cur_s, cur_e = rs[0]
-            for s, e in rs[1:]:
-                if s == cur_e:
-                    cur_e = e
-                else:
-                    out.append((owner, cur_s, cur_e)); cur_s, cur_e = s, e
-            out.append((owner, cur_s, cur_e))
-        return out
+        return _grad_ranges(g['params'])
+
+    def _state_of(self, owner):
+        st = self._state.get(id(owner))
+        if st is None:
+            st = (torch.zeros_like(owner._flat_grad), torch.zeros_like(owner._flat_grad))
+            self._state[id(owner)] = st
+        return st
 
     def step(self):
         self._step += 1
         L.order_note('optimizer step')
+        if self.max_grad_norm is not None or self.skip_nonfinite:
+            return self._step_clipped()
         for g in self.param_groups:
             b1, b2 = g['betas']
             for owner, s, e in self._ranges(g):
-                st = self._state.get(id(owner))
-                if st is None:
-                    st = (torch.zeros_like(owner._flat_grad), torch.zeros_like(owner._flat_grad))
-                    self._state[id(owner)] = st
-                m, v = st
+                m, v = self._state_of(owner)
                 L.adam_step(owner._flat[s:e], owner._flat_grad[s:e], m[s:e], v[s:e], g['lr'], b1, b2, g['eps'],
                             g['weight_decay'], self.decoupled, self._step)
+
+    def _step_clipped(self):
+        """ONE dep_grad_sqnorm over the ranges of ALL groups (a global norm, as torch's function takes all parameters at once), then
+        dep_adam_step_clipped per range: one launch more than the plain step.  Every launch derives the coefficient from the same
+        partial sums, with the same bits; the first one also updates the statistics record.  Under data parallelism this runs after
+        the compute stream joined the communication stream, on the reduced gradients every rank holds alike: the ranks form the same
+        coefficient without a collective."""
+        plan = [(g, self._ranges(g)) for g in self.param_groups]
+        grads = [owner._flat_grad[s:e] for _, rs in plan for owner, s, e in rs]
+        if not grads:
+            return
+        if len(grads) > _MAX_CLIP_RANGES:
+            raise L.DepError(f'gradient clipping covers at most {_MAX_CLIP_RANGES} contiguous gradient ranges per step, this optimizer has {len(grads)}')
+        if self._clip is None:
+            dev = grads[0].device
+            self._clip = (torch.empty(L.grad_norm_slots(), dtype=torch.float64, device=dev),
+                          torch.zeros(4, dtype=torch.float32, device=dev), torch.zeros(4, dtype=torch.float64, device=dev))
+        partials, clip_out, stats = self._clip
+        L.grad_sqnorm(grads, partials)
+        max_norm = 0.0 if self.max_grad_norm is None else self.max_grad_norm          # 0: measure only (skip_nonfinite alone)
+        first = True
+        for g, rs in plan:
+            b1, b2 = g['betas']
+            for owner, s, e in rs:
+                m, v = self._state_of(owner)
+                L.adam_step_clipped(owner._flat[s:e], owner._flat_grad[s:e], m[s:e], v[s:e], g['lr'], b1, b2, g['eps'],
+                                    g['weight_decay'], self.decoupled, self._step, partials, max_norm, self.skip_nonfinite,
+                                    clip_out if first else None, stats if first else None)
+                first = False
+
+    def grad_stats(self):
+        """The record of the clipped steps so far, read from the device: the ONLY host synchronisation of the clipping path.
+        steps / clipped / skipped count optimizer steps (clipped: coefficient < 1; skipped: non-finite norm under skip_nonfinite);
+        max_norm is the largest finite gradient norm seen, last_norm / last_coef / last_finite describe the latest step."""
+        if self._clip is None:
+            return {'steps': 0, 'clipped': 0, 'skipped': 0, 'max_norm': 0.0, 'last_norm': None, 'last_coef': None, 'last_finite': None}
+        _, clip_out, stats = self._clip
+        st, co = stats.tolist(), clip_out.tolist()
+        return {'steps': int(st[0]), 'clipped': int(st[1]), 'skipped': int(st[2]), 'max_norm': float(st[3]),
+                'last_norm': float(co[1]), 'last_coef': float(co[0]), 'last_finite': bool(co[2])}
+
+
+_MAX_CLIP_RANGES = 16          # dep_grad_sqnorm takes up to 16 ranges per launch (include/dep_rnn.h)
+
+
+def _grad_ranges(params):
+    """[(owner, start, end), ...]: the contiguous runs, in each owner's flat buffers, of those of `params` that currently hold a
+    gradient.  The runs include the alignment pads between tensors (Module._finalize keeps them zero)."""
+    per_owner = {}
+    for p in params:
+        if p.grad is None:
+            continue
+        per_owner.setdefault(id(p.owner), (p.owner, []))[1].append((p.offset, p.offset + (p.numel + 3) // 4 * 4))
+    out = []
+    for owner, rs in per_owner.values():
+        rs.sort()
+        cur_s, cur_e = rs[0]
+        for s, e in rs[1:]:
+            if s == cur_e:
+                cur_e = e
+            else:
+                out.append((owner, cur_s, cur_e)); cur_s, cur_e = s, e
+        out.append((owner, cur_s, cur_e))
+    return out
+
+
+class GradNorm:
+    """What clip_grad_norm_ returns: the total norm, still on the device.  item() reads it (a host synchronisation, like Loss.item())."""
+
+    def __init__(self, clip_out=None):
+        self._out = clip_out            # [coef, norm, finite, 0] written by dep_grad_clip_scale, or None: no gradient at all
+
+    def item(self):
+        return 0.0 if self._out is None else float(self._out[1].item())
+
+    def coef(self):
+        return 1.0 if self._out is None else float(self._out[0].item())
+
+    def __float__(self):
+        return self.item()
+
+
+def clip_grad_norm_(parameters, max_norm):
+    """torch.nn.utils.clip_grad_norm_(parameters, max_norm) (norm_type 2, error_if_nonfinite=False) for hand-written loops: scales the
+    gradients of `parameters` in place so that their global 2-norm is at most max_norm, in two launches (dep_grad_sqnorm,
+    dep_grad_clip_scale) and without a host read; the returned GradNorm reads the norm lazily.  Parameters whose grad is None are
+    left out, as torch leaves them out.  Training loops that step with nn.Adam / nn.AdamW pass max_grad_norm to the optimizer instead:
+    that clips inside the update and costs one launch, not two plus a pass over the gradients."""
+    if isinstance(parameters, Parameter):
+        parameters = [parameters]
+    rs = _grad_ranges(list(parameters))
+    if not rs:
+        return GradNorm()
+    if len(rs) > _MAX_CLIP_RANGES:
+        raise L.DepError(f'clip_grad_norm_ covers at most {_MAX_CLIP_RANGES} contiguous gradient ranges, got {len(rs)}')
+    grads = [owner._flat_grad[s:e] for owner, s, e in rs]
+    dev = grads[0].device
+    partials = torch.empty(L.grad_norm_slots(), dtype=torch.float64, device=dev)
+    clip_out = torch.empty(4, dtype=torch.float32, device=dev)
+    L.grad_sqnorm(grads, partials)
+    L.grad_clip_scale(grads, partials, float(max_norm), clip_out)
+    return GradNorm(clip_out)
 
 
 class Adam(_AdamBase):

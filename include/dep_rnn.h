@@ -395,6 +395,37 @@ int dep_head_mlp_bwd(const float* dz2, const float* a0, const float* z1, const f
 int dep_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int decoupled, int step, void* stream);
 
+/* Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, norm_type 2, error_if_nonfinite=False) without a host read.
+ *   dep_grad_sqnorm       : S = sum of g^2 over up to 16 ranges (bufs[r], counts[r]) -- HOST arrays of 16-byte aligned device
+ *                           pointers and element counts >= 1 -- accumulated in fp64 (the product of two fp32 values is exact
+ *                           there) into `partials`: dep_grad_norm_slots() doubles on the device, caller-owned, all overwritten.
+ *                           Slot s sums the chunks s, s + slots, ... (dep_grad_norm_chunk() floats each) of the CONCATENATED
+ *                           ranges in that order, one workgroup per slot, fixed tree, plain stores, no atomics: the result is a
+ *                           pure function of the data -- the same bits on every run and every rank, and the same bits however
+ *                           the data is cut into ranges.  One launch.
+ *   dep_adam_step_clipped : dep_adam_step on g * coef.  Every workgroup sums the partials in slot order (fixed tree: the same bits
+ *                           everywhere) and forms, in double,
+ *                               norm = sqrt(S) ;  coef = (float) min(1, max_norm / (norm + 1e-6))         (torch's formula)
+ *                           with ONE rounding to fp32; g is not written.  coef == 1 gives dep_adam_step's bits.  max_norm <= 0
+ *                           or +inf: measure only (coef = 1).  skip_nonfinite != 0 and S not finite: p, m, v are left untouched
+ *                           bit for bit; the caller's step number still advances, i.e. a skipped step counts in the bias
+ *                           correction.  skip_nonfinite == 0: the arithmetic follows (coef = 0 for S = inf, NaN for S = NaN).
+ *                           clip_out (4 floats, or NULL) = [coef, norm, S finite ? 1 : 0, 0].  stats (4 doubles, or NULL), a
+ *                           running record: [0] += 1, [1] += 1 if coef < 1, [2] += 1 if the step was skipped, [3] = max([3], norm)
+ *                           over finite norms; pass it to ONE launch per optimizer step.  Both are written by workgroup 0.
+ *   dep_grad_clip_scale   : g *= coef in place over the ranges (coef as above), one launch; what clip_grad_norm_ leaves in .grad.
+ *                           dep_grad_clip_scale followed by dep_adam_step gives dep_adam_step_clipped's bits.
+ * Nothing allocates or synchronises; the argument checks (NULL, nranges outside 1..16, count <= 0, a NaN max_norm) come before any
+ * HIP call. */
+int dep_grad_norm_slots(void);
+int dep_grad_norm_chunk(void);
+int dep_grad_sqnorm(const float* const* bufs, const long* counts, int nranges, double* partials, void* stream);
+int dep_adam_step_clipped(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
+                          float eps, float weight_decay, int decoupled, int step, const double* partials, float max_norm,
+                          int skip_nonfinite, float* clip_out, double* stats, void* stream);
+int dep_grad_clip_scale(float* const* bufs, const long* counts, int nranges, const double* partials, float max_norm,
+                        float* clip_out, void* stream);
+
 /* ------------------------------------------------------------------ feature front-end */
 /* wav2vlad of Classification/audio_features_whole.py:57-72: log-mel spectrogram (librosa.feature.melspectrogram defaults:
  * n_fft 2048, hop 512, periodic Hann, centred frames with reflect padding, power 2, 80 Slaney mel filters) followed by
