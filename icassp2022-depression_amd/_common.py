@@ -186,6 +186,16 @@ def rank_slice(lo, hi):
     return lo + a, lo + b
 
 
+def accumulation_groups(counts, k):
+    """Pure helper: cut the epoch's mini-batches (`counts` = their global row counts, in order) into consecutive groups of `k` --
+    the last one may be shorter -- and return [(first, stop, rows), ...]: mini-batches first .. stop - 1 form one optimizer update
+    whose criteria divide by `rows`, the rows of the whole group."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError(f'accumulation_groups: k must be an integer >= 1, got {k!r}')
+    counts = [int(c) for c in counts]
+    return [(i, min(i + k, len(counts)), sum(counts[i:i + k])) for i in range(0, len(counts), int(k))]
+
+
 def train_epoch(model, optimizer, n_rows, batch_size, step, after_step=None):
     """The mini-batch loop of every script's train() (audio_gru_whole.py:161-201 of the reference), which is also the data-parallel
     protocol: per global mini-batch every rank issues the gradient ranges, then (lazily, in LossSum.item) the loss reduce; a rank
@@ -197,11 +207,19 @@ def train_epoch(model, optimizer, n_rows, batch_size, step, after_step=None):
                                           FeatureFeeder.rows(a, b, then=): a streamed feeder starts that upload beside this step.
       after_step(a, b, output):           whatever is enqueued AFTER optimizer.step() (store_predictions).
     The scripts differ in two ways only: the classification loops count before the criterion and the regression loops store
-    after the update (hence two hooks), and the fusion loops ignore `then` (PairFeeder.rows takes none: the pairs are resident)."""
+    after the update (hence two hooks), and the fusion loops ignore `then` (PairFeeder.rows takes none: the pairs are resident).
+    An optimizer built with accumulate_steps = K > 1 turns K consecutive mini-batches into one update: the rows of each group are
+    declared before its criteria run (every micro-loss is then its rows' sum over the GROUP's rows, so the summed epoch loss is the
+    big-batch loop's), optimizer.step() is still called per mini-batch (it accumulates, and updates on the K-th), and flush()
+    updates from a shorter last group.  Both hooks, the count and the prediction buffers stay per mini-batch."""
     total = nn.LossSum(model.device)                 # device-side sum of the step losses
     batches = [(rank_slice(lo, hi), hi - lo) for lo, hi in minibatches(n_rows, batch_size)]
+    accum = getattr(optimizer, 'accumulate_steps', 1)
+    group_rows = {first: rows for first, _, rows in accumulation_groups([n for _, n in batches], accum)} if accum > 1 else {}
     for bi, ((a, b), n_glob) in enumerate(batches):
         parallel.set_global_count(n_glob)
+        if bi in group_rows:
+            parallel.set_accumulated_count(group_rows[bi])
         if b <= a:                                  # this rank owns no row of a small (ragged) mini-batch: zero-contribution step
             total.add(nn.empty_shard_step(model, optimizer))
             continue
@@ -212,6 +230,9 @@ def train_epoch(model, optimizer, n_rows, batch_size, step, after_step=None):
         if after_step is not None:
             after_step(a, b, output)
         total.add(loss, model)
+    if accum > 1:
+        optimizer.flush()                           # a last group shorter than K (every rank: it holds that group's collective)
+        parallel.set_accumulated_count(None)
     parallel.set_global_count(None)
     return total.item()
 

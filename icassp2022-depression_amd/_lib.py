@@ -106,6 +106,7 @@ _SIGS = {
     'dep_adam_step_clipped': (C.c_int, [_P, _P, _P, _P, C.c_long, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                         C.c_int, C.c_int, _P, C.c_float, C.c_int, _P, _P, _P]),
     'dep_grad_clip_scale': (C.c_int, [C.POINTER(_P), C.POINTER(C.c_long), C.c_int, _P, C.c_float, _P, _P]),
+    'dep_grad_accumulate': (C.c_int, [C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_long), C.c_int, C.c_float, C.c_int, _P, _P]),
     'dep_frame_window': (C.c_int, [_P, C.c_long, C.c_int, C.c_int, C.c_int, _P, _P]),
     'dep_power_spectrum': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
     'dep_log_floor': (C.c_int, [_P, _P, C.c_long, C.c_float, _P]),
@@ -345,6 +346,17 @@ def grad_clip_scale(ranges, partials, max_norm, clip_out=None):
     ptrs, cnts = _range_arrays(ranges)
     check(load().dep_grad_clip_scale(ptrs, cnts, len(ranges), _ptr(partials), float(max_norm), _ptr(clip_out), stream()),
           'dep_grad_clip_scale')
+
+
+def grad_accumulate(acc_ranges, g_ranges, scale=1.0, first=False, partials=None):
+    """acc = g * scale (first) or acc + g * scale over up to 16 pairs of contiguous fp32 device tensors, in one launch
+    (dep_grad_accumulate); `partials` (dep_grad_norm_slots() float64 on the device) also receives grad_sqnorm's partial sums of the result."""
+    if len(acc_ranges) != len(g_ranges) or any(a.numel() != g.numel() for a, g in zip(acc_ranges, g_ranges)):
+        raise DepError('grad_accumulate: the accumulator ranges and the gradient ranges differ in number or size')
+    aptrs, _ = _range_arrays(acc_ranges)
+    gptrs, cnts = _range_arrays(g_ranges)
+    check(load().dep_grad_accumulate(aptrs, gptrs, cnts, len(g_ranges), float(scale), int(bool(first)), _ptr(partials), stream()),
+          'dep_grad_accumulate')
 
 
 def fill(t, value):

@@ -1,4 +1,5 @@
-// Global-norm gradient clipping on the device (dep_grad_sqnorm, dep_adam_step_clipped, dep_grad_clip_scale; include/dep_rnn.h).
+// Global-norm gradient clipping on the device (dep_grad_sqnorm, dep_adam_step_clipped, dep_grad_clip_scale) and gradient accumulation over
+// micro-batches (dep_grad_accumulate); include/dep_rnn.h.
 //
 // The sum of squares is a pure function of the data.  The ranges are read as ONE concatenated array cut into chunks of
 // GN_CHUNK floats; partial slot s holds the sum over chunks s, s + GN_SLOTS, ... in that order, and ONE workgroup owns a slot
@@ -23,6 +24,12 @@ struct GradRanges {
     int count;
 };
 struct GradRangesRW { float* ptr[GN_MAXR]; long n[GN_MAXR]; int count; };
+struct AccumRanges {                       // GradRanges with an accumulator beside every gradient range (same counts, same concatenation)
+    float* acc[GN_MAXR];
+    const float* g[GN_MAXR];
+    long start[GN_MAXR + 1];
+    int count;
+};
 
 // sum over the workgroup's GN_THREADS threads, the same bits in every thread: xor butterfly in the wave (commutative pairs, so all
 // lanes agree), then (w0 + w1) + (w2 + w3) over the waves
@@ -66,6 +73,64 @@ __global__ __launch_bounds__(GN_THREADS) void grad_sqnorm_kernel(GradRanges R, d
         }
         acc += (p0 + p1) + (p2 + p3);
     }
+    const double s = gn_block_sum(acc, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;                // every slot is written (0 for a slot without a chunk)
+}
+
+// acc = first ? g * scale : acc + g * scale over the ranges, and (partials != NULL) grad_sqnorm_kernel's partial sums of the STORED result in
+// the same pass.  The walk is that kernel's, statement for statement -- GN_SLOTS workgroups, the same chunks per slot, the same choice
+// between the 16-byte path and the element path, the same (p0 + p1) + (p2 + p3) and gn_block_sum -- so the partials carry the bits
+// dep_grad_sqnorm forms afterwards from the accumulator.  The product and the sum are two fp32 roundings (no FMA): numpy float32
+// reproduces the result, and scale == 1 is the plain IEEE add.  `first`: acc is written without being read.
+__device__ __forceinline__ float ga_value(float a, float g, float scale, int first) {
+    // contraction off for THESE two operations: hipcc's __fmul_rn / __fadd_rn are inline * and + compiled under the default
+    // (contract = fast), and their pair came out as one v_fmac_f32 -- 12 ulp from numpy's float32 where the sum cancels
+#pragma clang fp contract(off)
+    const float t = g * scale;
+    return first ? t : a + t;
+}
+__global__ __launch_bounds__(GN_THREADS) void grad_accumulate_kernel(AccumRanges R, float scale, int first, double* __restrict__ partials) {
+    __shared__ double red[4];
+    const long total = R.start[R.count];
+    const long nchunks = (total + GN_CHUNK - 1) / GN_CHUNK;
+    double acc = 0.0;
+    for (long c = blockIdx.x; c < nchunks; c += GN_SLOTS) {
+        const long i = c * GN_CHUNK + (long)threadIdx.x * 4;
+        double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
+        if (i < total) {
+            int r = 0;
+            while (i >= R.start[r + 1]) ++r;                       // i < total = start[count]: stops at r < count
+            const long off = i - R.start[r];
+            if (i + 3 < R.start[r + 1] && (off & 3) == 0) {        // the four elements sit in one range at a 16-byte boundary
+                const f32x4 gv = *reinterpret_cast<const f32x4*>(R.g[r] + off);
+                f32x4 a = {0.f, 0.f, 0.f, 0.f};
+                if (!first) a = *reinterpret_cast<const f32x4*>(R.acc[r] + off);
+                f32x4 x;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) x[e] = ga_value(a[e], gv[e], scale, first);
+                *reinterpret_cast<f32x4*>(R.acc[r] + off) = x;
+                p0 = (double)x[0] * (double)x[0]; p1 = (double)x[1] * (double)x[1];
+                p2 = (double)x[2] * (double)x[2]; p3 = (double)x[3] * (double)x[3];
+            } else {                                               // a range boundary or the tail: element by element (absent = +0)
+                double p[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const long k = i + e;
+                    if (k < total) {
+                        while (k >= R.start[r + 1]) ++r;
+                        float* ap = R.acc[r] + (k - R.start[r]);
+                        const float xf = ga_value(first ? 0.f : *ap, R.g[r][k - R.start[r]], scale, first);
+                        *ap = xf;
+                        const double x = (double)xf;
+                        p[e] = x * x;
+                    }
+                }
+                p0 = p[0]; p1 = p[1]; p2 = p[2]; p3 = p[3];
+            }
+        }
+        acc += (p0 + p1) + (p2 + p3);
+    }
+    if (partials == nullptr) return;                               // uniform over the grid
     const double s = gn_block_sum(acc, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;                // every slot is written (0 for a slot without a chunk)
 }
@@ -167,6 +232,21 @@ extern "C" int dep_grad_sqnorm(const float* const* bufs, const long* counts, int
     for (int r = nranges; r <= GN_MAXR; ++r) R.start[r] = at;
     R.count = nranges;
     DEP_LAUNCH(grad_sqnorm_kernel, dim3(GN_SLOTS), dim3(GN_THREADS), 0, S_, R, partials);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+
+extern "C" int dep_grad_accumulate(float* const* acc, const float* const* g, const long* counts, int nranges, float scale, int first,
+                                   double* partials, void* stream) {
+    if (int rc = check_ranges(g, counts, nranges)) return rc;
+    DEP_CHECK_ARG(acc && scale == scale);
+    for (int r = 0; r < nranges; ++r) DEP_CHECK_ARG(acc[r] && ((uintptr_t)acc[r] & 15) == 0);
+    AccumRanges R{};
+    long at = 0;
+    for (int r = 0; r < nranges; ++r) { R.acc[r] = acc[r]; R.g[r] = g[r]; R.start[r] = at; at += counts[r]; }
+    for (int r = nranges; r <= GN_MAXR; ++r) R.start[r] = at;
+    R.count = nranges;
+    DEP_LAUNCH(grad_accumulate_kernel, dim3(GN_SLOTS), dim3(GN_THREADS), 0, S_, R, scale, first ? 1 : 0, partials);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }

@@ -78,7 +78,8 @@ def build(seed=None):
     global model, optimizer, criterion
     model = fusion_net(config['text_embed_size'], config['text_hidden_dims'], config['rnn_layers'], config['dropout'],
                        config['num_classes'], config['audio_hidden_dims'], config['audio_embed_size'], seed=seed)
-    optimizer = nn.Adam(model.parameters(), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'))
+    optimizer = nn.Adam(model.parameters(), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'),
+                        accumulate_steps=config.get('accum_steps', 1))
     criterion = MyLoss()
     return model
 

@@ -515,7 +515,7 @@ class MyLoss:
         if self.variant == 'clf':
             t = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target)
             nn._check_labels(t, Cc)
-            kind = L.LOSS_CE_LOGITS; norm_local = B
+            kind = L.LOSS_CE_LOGITS; norm_local = B; per_row = 1
             if t.dtype == torch.int64:
                 t = t.to(device=dev).contiguous().view(-1); kind |= L.LOSS_LABELS_I64
             else:
@@ -523,8 +523,8 @@ class MyLoss:
         else:
             t = torch.as_tensor(np.asarray(target, dtype=np.float32) if not torch.is_tensor(target) else target)
             t = t.to(device=dev, dtype=torch.float32).contiguous().view(B, Cc)
-            kind = L.LOSS_SMOOTHL1; norm_local = B * Cc
-        norm = parallel.global_count(norm_local) if train else norm_local
+            kind = L.LOSS_SMOOTHL1; norm_local = B * Cc; per_row = Cc
+        norm = parallel.loss_count(B, per_row) if train else norm_local
         rows = torch.empty(B, dtype=torch.float32, device=dev)
         val = torch.empty(1, dtype=torch.float32, device=dev)                       # overwritten by the first dep_reduce_loss
         dzt = torch.empty_like(zt) if train else None

@@ -323,11 +323,12 @@ class _HeadLoss:
         else:
             t = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target)
             t = t.to(device=dev, dtype=torch.float32).contiguous().view(B, Cc)
-        norm_local = B * (1 if self.target_dtype == 'int' else Cc)
+        per_row = 1 if self.target_dtype == 'int' else Cc
+        norm_local = B * per_row
         train = owner is not None and owner.training
         # data parallel: every rank normalises by the GLOBAL batch so that summed gradients equal
-        # the reference's batch-mean gradient (ragged shards included)
-        norm = parallel.global_count(norm_local) if train else norm_local
+        # the reference's batch-mean gradient (ragged shards included); accumulation: by the rows of the whole accumulated batch
+        norm = parallel.loss_count(B, per_row) if train else norm_local
         rows = torch.empty(B, dtype=torch.float32, device=dev)
         dz = torch.empty_like(z) if train else None
         L.head_loss(kind, z, t, None, rows, dz, norm)
@@ -373,12 +374,23 @@ def empty_shard_step(model, optimizer):
 class _AdamBase:
     decoupled = False
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=None, max_grad_norm=None, skip_nonfinite=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=None, max_grad_norm=None, skip_nonfinite=False,
+                 accumulate_steps=1):
         """max_grad_norm: clip the GLOBAL 2-norm of the gradients of all groups to it inside the update (torch's
         clip_grad_norm_(all parameters, max_grad_norm) in front of step(), without its host read; None = no clipping).
         skip_nonfinite: a step whose gradient norm is inf / NaN leaves parameters and moments untouched (it still counts in the bias
-        correction).  With both at their defaults step() enqueues exactly the dep_adam_step launches it always did."""
+        correction).  With both at their defaults step() enqueues exactly the dep_adam_step launches it always did.
+        accumulate_steps: K > 1 makes step() a MICRO-step: it adds the gradients the last backward wrote into a flat accumulator
+        per owner module (one dep_grad_accumulate launch over the ranges of all groups) and only every K-th call -- or flush() --
+        updates, from the accumulator; clipping and skip_nonfinite then act on the accumulated gradient.  The criteria must divide
+        by the rows of the whole accumulated batch (parallel.set_accumulated_count), not by their own.  1: step() is what it was."""
         params = list(params)
+        if isinstance(accumulate_steps, bool) or not isinstance(accumulate_steps, (int, np.integer)) or accumulate_steps < 1:
+            raise ValueError(f'accumulate_steps must be an integer >= 1, got {accumulate_steps!r}')
+        self.accumulate_steps = int(accumulate_steps)
+        self._pending = 0         # micro-steps in the accumulator since the last update
+        self._accum = {}          # id(module) -> flat accumulator, laid out like the module's _flat_grad
+        self._accum_plan = None   # [(group, [(owner, start, end), ...]), ...] of the group being accumulated / last updated from
         if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
             raise ValueError(f'max_grad_norm must be None or a non-negative number, got {max_grad_norm!r}')
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
@@ -398,6 +410,10 @@ class _AdamBase:
             self.param_groups.append(g)
         self._step = 0
         self._state = {}          # id(module) -> (m, v)
+        if self.accumulate_steps > 1:                      # data parallel: ONE gradient exchange per update, of the accumulator
+            for g in self.param_groups:
+                for p in g['params']:
+                    p.owner._defer_grad_sync = True
 
     def zero_grad(self):
         for g in self.param_groups:
@@ -417,6 +433,8 @@ class _AdamBase:
         return st
 
     def step(self):
+        if self.accumulate_steps > 1:
+            return self._micro_step()
         self._step += 1
         L.order_note('optimizer step')
         if self.max_grad_norm is not None or self.skip_nonfinite:
@@ -440,11 +458,7 @@ class _AdamBase:
             return
         if len(grads) > _MAX_CLIP_RANGES:
             raise L.DepError(f'gradient clipping covers at most {_MAX_CLIP_RANGES} contiguous gradient ranges per step, this optimizer has {len(grads)}')
-        if self._clip is None:
-            dev = grads[0].device
-            self._clip = (torch.empty(L.grad_norm_slots(), dtype=torch.float64, device=dev),
-                          torch.zeros(4, dtype=torch.float32, device=dev), torch.zeros(4, dtype=torch.float64, device=dev))
-        partials, clip_out, stats = self._clip
+        partials, clip_out, stats = self._clip_buffers(grads[0].device)
         L.grad_sqnorm(grads, partials)
         max_norm = 0.0 if self.max_grad_norm is None else self.max_grad_norm          # 0: measure only (skip_nonfinite alone)
         first = True
@@ -455,6 +469,98 @@ class _AdamBase:
                 L.adam_step_clipped(owner._flat[s:e], owner._flat_grad[s:e], m[s:e], v[s:e], g['lr'], b1, b2, g['eps'],
                                     g['weight_decay'], self.decoupled, self._step, partials, max_norm, self.skip_nonfinite,
                                     clip_out if first else None, stats if first else None)
+                first = False
+
+    # -- accumulation over micro-batches (accumulate_steps > 1) -------------------------------------------------------
+    @property
+    def pending(self):
+        """Micro-steps accumulated since the last update."""
+        return self._pending
+
+    def accumulated_grad(self, p):
+        """View of p's accumulated gradient (None for a parameter that receives none): the sum over the micro-steps so far, and after
+        an update what that update was made from -- valid until the next group's first micro-step overwrites it."""
+        acc = self._accum.get(id(p.owner))
+        if acc is None or not p.live or not p.requires_grad:
+            return None
+        return acc[p.offset:p.offset + p.numel].view(p.shape)
+
+    def _clip_buffers(self, dev):
+        """(partials, clip_out, stats): the device side of the clipped update, made by the first step that needs it."""
+        if self._clip is None:
+            self._clip = (torch.empty(L.grad_norm_slots(), dtype=torch.float64, device=dev),
+                          torch.zeros(4, dtype=torch.float32, device=dev), torch.zeros(4, dtype=torch.float64, device=dev))
+        return self._clip
+
+    def _micro_step(self):
+        """accumulator (+)= the gradients of the last backward: ONE launch over the ranges of all groups (`first` on a group's first
+        micro-step: the accumulator is overwritten, nothing clears it).  The K-th micro-step updates; on one rank its launch also
+        leaves the partial sums of squares a clipped update needs, so that update launches no dep_grad_sqnorm."""
+        L.order_note('optimizer micro-step')
+        plan = [(g, self._ranges(g)) for g in self.param_groups]
+        spans = [r for _, rs in plan for r in rs]
+        if not spans:
+            return
+        if len(spans) > _MAX_CLIP_RANGES:
+            raise L.DepError(f'gradient accumulation covers at most {_MAX_CLIP_RANGES} contiguous gradient ranges per step, this optimizer has {len(spans)}')
+        first = self._pending == 0
+        if first:
+            self._accum_plan = plan
+        elif spans != [r for _, rs in self._accum_plan for r in rs]:
+            raise L.DepError('the parameters that hold a gradient changed inside an accumulation group')
+        for owner, _, _ in spans:
+            if id(owner) not in self._accum:
+                self._accum[id(owner)] = torch.zeros_like(owner._flat_grad)
+        boundary = self._pending + 1 == self.accumulate_steps
+        clip = self.max_grad_norm is not None or self.skip_nonfinite
+        partials = None
+        if boundary and clip and parallel.transport() == 'none':            # (an exchange follows otherwise: the norm is the reduced sums')
+            partials = self._clip_buffers(spans[0][0]._flat_grad.device)[0]
+        L.grad_accumulate([self._accum[id(o)][s:e] for o, s, e in spans], [o._flat_grad[s:e] for o, s, e in spans], 1.0, first, partials)
+        self._pending += 1
+        if boundary:
+            self._update_from_accumulator(partials is not None)
+
+    def flush(self):
+        """Update from a partial group (an epoch whose number of mini-batches is no multiple of accumulate_steps); nothing pending:
+        nothing is launched.  Under data parallelism every rank calls it at the same point (it holds the group's one collective)."""
+        if self._pending:
+            self._update_from_accumulator(False)
+
+    def _update_from_accumulator(self, have_partials):
+        """The update of step() / _step_clipped() with the accumulator in the place of _flat_grad.  Data parallel: each owner's live
+        bucket of the accumulator is all-reduced first, ONCE, and the norm is that of the reduced sums (dep_grad_sqnorm after the
+        join), which every rank holds alike."""
+        self._step += 1
+        self._pending = 0
+        plan = self._accum_plan
+        spans = [r for _, rs in plan for r in rs]
+        if parallel.transport() != 'none':
+            done = set()
+            for owner, _, _ in spans:
+                if id(owner) not in done:
+                    done.add(id(owner))
+                    parallel.all_reduce_accumulated(owner, self._accum[id(owner)][:owner._n_live])
+        L.order_note('optimizer step')
+        clip = self.max_grad_norm is not None or self.skip_nonfinite
+        if clip:
+            partials, clip_out, stats = self._clip_buffers(spans[0][0]._flat_grad.device)
+            if not have_partials:
+                L.grad_sqnorm([self._accum[id(o)][s:e] for o, s, e in spans], partials)
+            max_norm = 0.0 if self.max_grad_norm is None else self.max_grad_norm
+        first = True
+        for g, rs in plan:
+            b1, b2 = g['betas']
+            for owner, s, e in rs:
+                m, v = self._state_of(owner)
+                acc = self._accum[id(owner)]
+                if clip:
+                    L.adam_step_clipped(owner._flat[s:e], acc[s:e], m[s:e], v[s:e], g['lr'], b1, b2, g['eps'], g['weight_decay'],
+                                        self.decoupled, self._step, partials, max_norm, self.skip_nonfinite,
+                                        clip_out if first else None, stats if first else None)
+                else:
+                    L.adam_step(owner._flat[s:e], acc[s:e], m[s:e], v[s:e], g['lr'], b1, b2, g['eps'], g['weight_decay'],
+                                self.decoupled, self._step)
                 first = False
 
     def grad_stats(self):

@@ -16,6 +16,9 @@ loss is a batch mean, so the path shards naturally:
     DEP_COMM=torch) the whole bucket is reduced in one torch.distributed all-reduce after the backward.
     Every rank issues the same sequence of collectives each step -- also a rank whose shard of a small mini-batch is
     empty (`nn.empty_shard_step`).
+  * gradient accumulation (nn.Adam / AdamW accumulate_steps = K > 1): nothing is exchanged per micro-batch; the optimizer's
+    accumulator is reduced once per update (`all_reduce_accumulated`), and every criterion divides by the rows of the whole
+    accumulated global batch (`set_accumulated_count`).
 """
 import os
 
@@ -93,6 +96,25 @@ def global_count(local):
     if world_size() == 1 or n is None:
         return local
     return n
+
+
+_accum_count = [None]
+
+
+def set_accumulated_count(n):
+    """Gradient accumulation: the rows of the WHOLE accumulated global batch (all micro-batches of the group, all ranks), declared
+    before the group's criteria run; every criterion then divides by it instead of by its own batch, so that the micro-batch
+    gradients SUM to the big batch's mean gradient and the micro-losses to its loss.  None clears it."""
+    _accum_count[0] = None if n is None else int(n)
+
+
+def loss_count(rows, per_row=1):
+    """What a criterion divides its `rows` x `per_row` terms by: the declared accumulated count (x per_row: the regression losses
+    average over the output columns too) when one is set, else global_count of the local number of terms."""
+    n = _accum_count[0]
+    if n is not None:
+        return n * per_row
+    return global_count(rows * per_row)
 
 
 def all_reduce_sum(t):
@@ -202,9 +224,40 @@ def layer_buckets(spans, n_live):
     return [(s, c) for s, c in spans if c > 0]
 
 
+def defers_grad_sync(model):
+    """An accumulating optimizer (nn.Adam / AdamW accumulate_steps > 1) owns this model's gradient exchange: nothing is reduced per
+    backward, the accumulator is reduced once per update (all_reduce_accumulated)."""
+    return bool(getattr(model, '_defer_grad_sync', False))
+
+
+def all_reduce_accumulated(model, bucket):
+    """The ONE gradient collective of an accumulated update: SUM all-reduce of `bucket`, the live part of the model's accumulator,
+    after the group's last dep_grad_accumulate and joined before the update that follows -- nothing that needs every CU is
+    launched in between.  Native communicator: on the communication stream behind an event of the compute stream, which then waits
+    for it (the order log shows `C allreduce`, then the join note); otherwise one torch.distributed all-reduce on the compute stream."""
+    if _comm_off[0] or bucket.numel() == 0:
+        return
+    from . import _lib as L
+    if _native['comm'] is None:
+        d = _dist()
+        if d:
+            L.order_note('C torch.distributed all_reduce of the accumulated live bucket (on the compute stream)')
+            d.all_reduce(bucket, op=d.ReduceOp.SUM)
+        return
+    cs = _native['stream']
+    cur = torch.cuda.current_stream()
+    ev = torch.cuda.Event(); ev.record(cur)
+    cs.wait_event(ev)
+    L.check(L.load().dep_comm_allreduce(_native['comm'], bucket.data_ptr(), bucket.numel(), cs.cuda_stream), 'dep_comm_allreduce')
+    ev2 = torch.cuda.Event(); ev2.record(cs)
+    cur.wait_event(ev2)
+    L.order_note('join: the compute stream waits for the communication stream')
+
+
 def make_grad_sync(model, in_call):
-    """GradSync for dep_rnn_backward_overlapped, or None without a native communicator.  in_call: {layer: (start, count)}."""
-    if _native['comm'] is None or not in_call or _comm_off[0]:
+    """GradSync for dep_rnn_backward_overlapped, or None without a native communicator or for a model whose optimizer accumulates.
+    in_call: {layer: (start, count)}."""
+    if _native['comm'] is None or not in_call or _comm_off[0] or defers_grad_sync(model):
         return None
     from . import _lib as L
     gs = L.GradSync()
@@ -221,7 +274,7 @@ def finish_grad_sync(model, in_call, post):
     """After the model's backward: reduce what is still local and join the streams.
     native communicator: `post` ranges (final only now) as one grouped RCCL operation on the communication stream, then the
     compute stream waits for that stream; otherwise one torch.distributed all-reduce of the whole bucket."""
-    if _comm_off[0]:
+    if _comm_off[0] or defers_grad_sync(model):
         return
     if _native['comm'] is None:
         all_reduce_grads(model)
@@ -246,7 +299,10 @@ def finish_grad_sync(model, in_call, post):
 
 
 def reduce_zero_contribution(model, in_call, post):
-    """A rank whose shard is empty: same collectives, in the same order, on a zeroed gradient buffer."""
+    """A rank whose shard is empty: same collectives, in the same order, on a zeroed gradient buffer (none for a model whose
+    optimizer accumulates: its ranks meet at the update)."""
+    if defers_grad_sync(model):
+        return
     if _native['comm'] is None:
         all_reduce_grads(model)
         return

@@ -123,7 +123,8 @@ def main(epochs=None):
         test_dep_idxs = test_dep_idxs_tmp
         model = TextBiLSTM(config)
         parallel.broadcast_params(model)
-        optimizer = nn.Adam(model.parameters(), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'))
+        optimizer = nn.Adam(model.parameters(), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'),
+                            accumulate_steps=config.get('accum_steps', 1))
         criterion = nn.SmoothL1Loss()
         min_mae = 100; min_rmse = 100
         train_mae = 100

@@ -139,7 +139,8 @@ def main(fold_files=('train_idxs_0.63_1.npy', 'train_idxs_0.60_2.npy', 'train_id
         train_idxs, test_idxs = fold_split(train_idxs_tmp)
         model = TextBiLSTM(config)
         parallel.broadcast_params(model)
-        optimizer = nn.AdamW(get_param_group(model), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'))
+        optimizer = nn.AdamW(get_param_group(model), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'),
+                             accumulate_steps=config.get('accum_steps', 1))
         criterion = nn.CrossEntropyLoss()
         max_f1 = max_acc = max_rec = max_prec = -1
         train_acc = -1

@@ -138,7 +138,7 @@ int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const float* const* w
 
 /* Backward of dep_rnn_forward (what loss.backward() does through nn.GRU/nn.LSTM,
  * audio_gru_whole.py:190).  Gradients are WRITTEN (not accumulated) to dweights (same order and
- * shapes as weights).
+ * shapes as weights); dep_grad_accumulate adds them into an accumulator of the caller's.
  *   dy      (B,T,H*dirs) grad of y, or NULL
  *   dpooled (B,H) grad of pooled, or NULL  (the 1/T of a mean pool is applied inside)
  *   dh_n    (L*dirs,B,H) grad of h_n, or NULL
@@ -425,6 +425,24 @@ int dep_adam_step_clipped(float* p, const float* g, float* m, float* v, long n, 
                           int skip_nonfinite, float* clip_out, double* stats, void* stream);
 int dep_grad_clip_scale(float* const* bufs, const long* counts, int nranges, const double* partials, float max_norm,
                         float* clip_out, void* stream);
+
+/* Gradient accumulation over micro-batches: every backward WRITES its gradients, so a caller that wants K backward passes per
+ * update adds each pass's gradients into an accumulator of its own and steps from that.
+ *   dep_grad_accumulate   : over up to 16 range pairs (acc[r], g[r], counts[r]) -- HOST arrays of 16-byte aligned device pointers,
+ *                           counts >= 1, acc and g not overlapping -- in ONE launch
+ *                               t = fp32(g[i] * scale) ;  acc[i] = first ? t : fp32(acc[i] + t)
+ *                           two roundings, never contracted into an FMA: numpy float32 gives the same bits, and scale == 1 is the
+ *                           plain IEEE add.  first != 0: acc is not read (it may hold anything, NaN included: no memset needed).
+ *                           scale serves the `loss / K` idiom; a caller whose losses already divide by the rows of the whole
+ *                           accumulated batch passes 1.  partials != NULL (dep_grad_norm_slots() doubles): the same pass also
+ *                           leaves the partial sums of squares of the STORED result, bit-identical to dep_grad_sqnorm(acc, counts,
+ *                           nranges, ...) run afterwards (the same chunks per slot, the same vector / element paths, the same
+ *                           fixed trees, no atomics), so that the last accumulation of a group feeds dep_adam_step_clipped
+ *                           without a launch of its own for the norm.
+ * Nothing allocates or synchronises; the argument checks (NULL, nranges outside 1..16, count <= 0, a misaligned pointer, a NaN
+ * scale) come before any HIP call. */
+int dep_grad_accumulate(float* const* acc, const float* const* g, const long* counts, int nranges, float scale, int first,
+                        double* partials, void* stream);
 
 /* ------------------------------------------------------------------ feature front-end */
 /* wav2vlad of Classification/audio_features_whole.py:57-72: log-mel spectrogram (librosa.feature.melspectrogram defaults:
