@@ -267,7 +267,12 @@ int dep_gemm_bf16x3(int transA, int transB, int M, int N, int K,
                     void* workspace, size_t workspace_bytes, void* stream);
 /* Same contract, precision chosen exactly as dep_rnn_forward / dep_rnn_backward choose it for a contraction of this size under
  * the current dep_set_gemm_mode (0: exact, 1: three-term split above min_macs, 2: single bf16 products).  dep_gemm_bf16x3 above
- * is ALWAYS the three-term split, whatever the mode. */
+ * never follows the mode: where the split kernel runs it forms all three terms.
+ * A SMALL problem runs one exact fp32 kernel (gemm_small: 32x32 output tiles, exact f32 products) under EVERY entry and EVERY mode,
+ * dep_gemm_bf16x3 and mode 2 included -- the plan tests this first, before it looks at the precision:
+ *     seq_T <= 0  and  ceil(M/128) * ceil(N/128) < 32  and  K <= 8192  and  M*N*K <= 2^27.
+ * Such a call splits no K and needs no workspace.  Every other shape takes the kernel of its entry / mode: exact fp32 MFMA tiles, or the
+ * split-precision kernel (tests/test_gemm_forms_gpu.py pins the routing of each form through the launch-instance log). */
 int dep_gemm(int transA, int transB, int M, int N, int K,
              const float* A, int lda, const float* B, int ldb, float* C, int ldc,
              const float* bias, float beta, int seq_T, int shiftB,

@@ -49,7 +49,11 @@ def test_gemm_shapes(tA, tB, M, N, K):
 @pytest.mark.parametrize('tA,tB', [(0, 1), (0, 0), (1, 0)])
 @pytest.mark.parametrize('M,N,K', [(300, 200, 64), (77, 45, 39), (513, 260, 100), (256, 384, 2048)])
 def test_gemm_bf16x3_split_accuracy(tA, tB, M, N, K):
-    """3-term bf16 split: error relative to sum_k |a||b| must stay ~1e-5 (exact-f32 kernel: ~1e-7)."""
+    """dep_gemm_bf16x3 at shapes on either side of the plan's small-problem test: error relative to sum_k |a||b| inside the three-term split's bound.
+    The three ragged shapes (6, 1 and 15 tiles of 128x128, M*N*K <= 2^27) meet that test and run the EXACT gemm_small -- the entry never follows the
+    mode, but a small problem runs the small kernel under every entry; only (256, 384, 2048) (M*N*K > 2^27) runs the split kernel, with split-K.
+    The launch-instance log proves which.  The split kernel's ragged edges are in tests/test_gemm_forms_gpu.py."""
+    small = (M, N, K) != (256, 384, 2048)
     rng = np.random.default_rng(M + N * 3 + K * 5 + tA * 2 + tB)
     A = rng.standard_normal((K, M) if tA else (M, K)).astype(np.float32).astype(np.float64)
     B = rng.standard_normal((N, K) if tB else (K, N)).astype(np.float32).astype(np.float64)
@@ -62,6 +66,12 @@ def test_gemm_bf16x3_split_accuracy(tA, tB, M, N, K):
     ws = L.gemm_ws(tA, tB, M, N, K, DEV)
     L.gemm_split(tA, tB, M, N, K, a, a.stride(0), b, b.stride(0), c, N, bias=bi, ws=ws)
     err = np.abs(host(c) - ref) / scale
+    launched = L.instance_log_read()                        # (conftest.py switched the launch-instance log on for this test)
+    if small:
+        assert launched == {'gemm_small'}, launched
+    else:
+        tf = ('false', 'true')
+        assert launched == {'(gemm_bf16x3<%s, %s, true, 128, 3>)' % (tf[tA], tf[tB]), 'splitk_reduce2'}, launched
     assert err.max() < 1.5e-5, err.max()
     assert err.mean() < 2e-6
 
