@@ -77,16 +77,16 @@ __device__ __forceinline__ float dep_ragged_pool_scale(int pool_mean, int len, i
 __device__ __forceinline__ float2 dep_sel2(bool c, float2 a, float2 b) { return make_float2(c ? a.x : b.x, c ? a.y : b.y); }
 __device__ __forceinline__ f32x4 dep_sel4(bool c, f32x4 a, f32x4 b) { f32x4 r = {c ? a[0] : b[0], c ? a[1] : b[1], c ? a[2] : b[2], c ? a[3] : b[3]}; return r; }
 
-// DEP_FP_CONTRACT_NOTE.  The forward sweeps that have a ragged instance (gru_fwd_mfma, lstm_fwd_mfma, gru_fwd_generic, gru_fwd_cluster_r1,
-// lstm_fwd_cluster) open with `#pragma clang fp contract(on)`: a * b + c written in ONE expression is one fma (the product on the left
+// DEP_FP_CONTRACT_NOTE.  The forward sweeps that have a ragged instance (gru_fwd_mfma<JPW, RAG>, lstm_fwd_mfma<JPW, RAG>, gru_fwd_generic<RAG>
+// of rnn_sweep.hip, gru_fwd_cluster_r1<KCH, SPLIT, RAG> of rnn_cluster_bwd.hip, lstm_fwd_cluster<SPLIT, SV16, RAG> of rnn_cluster_lstm.hip) open with `#pragma clang fp contract(on)`: a * b + c written in ONE expression is one fma (the product on the left
 // of the sum is the fused one) and nothing else is fused.  Under the default (contract = fast) the backend decides, and its choice
 // depends on what surrounds the expression -- the selects of a ragged instance, or a neighbouring product the vectoriser pairs it
 // with -- so the dense and the ragged instance of one kernel rounded differently; a ragged call whose lengths all equal T must reproduce
 // the dense call's bits (tests/test_varlen_gpu.py).  The expressions are written so that the dense instances keep the operations the
-// backend chose before (h = z * h_prev + (1 - z) * n: the fused product first).  To re-verify after a compiler change: compile the
-// file at the commit before the pragma and now with `hipcc --offload-arch=gfx950 -O3 --cuda-device-only -S`, and compare the dense
-// instances' v_fma / v_mul / v_add / v_pk_* instructions (same multiset; operands of a product may swap); tests/golden/device_bits.json
-// (tests/test_presplit_gpu.py) anchors the results on the device.  The backward sweeps keep the default: there the ragged instances
+// backend chose before (h = z * h_prev + (1 - z) * n: the fused product first).  To re-verify after a compiler change: run
+// `tools/isa_diff.py <csrc file> <the commit before the pragma>` (it compiles both sides with the build's flags and prints, per kernel,
+// `identical` or the first differing lines) and compare the dense instances' v_fma / v_mul / v_add / v_pk_* instructions (same multiset;
+// operands of a product may swap); tests/golden/device_bits.json (tests/test_presplit_gpu.py) anchors the results on the device.  The backward sweeps keep the default: there the ragged instances
 // select on final results only (the split words, the summed dh), which leaves the arithmetic of a live step as the dense instance has it.
 
 // dropout sites (Philox counter word 2): distinct per place a mask is drawn in one step

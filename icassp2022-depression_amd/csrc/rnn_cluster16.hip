@@ -50,7 +50,8 @@ struct F16 {
 // (and draws the dropout mask once per 4 values).  The four compute waves therefore never have an HBM access outstanding:
 // the s_waitcnt vmcnt(0) in front of the flag publication waits for the payload store alone, and the flag polls / gather
 // loads (VMEM returns in order) never queue behind an HBM load or a write acknowledgement.
-template <int KCQ, bool SPLIT>      // k-chunks of 16 per wave = H/64
+constexpr int KCQ = 4;              // k-chunks of 16 per wave = H/64: the launcher takes H == 256 only (DEP_CHECK_ARG in dep_launch_cluster16_fwd, dep_cluster16_ok)
+template <bool SPLIT>
 // launch bounds: two 5-wave workgroups must fit on a CU wherever their wave rotations start, i.e. 4 waves on one SIMD:
 // <= 128 VGPRs.  (At 136 the second workgroup of a CU could not always be placed, part of the cluster members never became
 // resident and every step ran into the spin limit: 395 ms instead of 2.)
@@ -271,7 +272,7 @@ __global__ __launch_bounds__(CT + 64, 4) void gru_fwd_cluster16(F16 p) {
     }
 }
 
-// split-precision forward image (see gru_fwd_cluster16<., true>): 16-byte piece
+// split-precision forward image (see gru_fwd_cluster16<true>): 16-byte piece
 //   [((((c*3 + g)*4 + w)*KS2 + ks)*2 + plane)*64 + lane]  =  bf16 plane (0 hi, 1 lo) of
 //   W[(g*H + 16c + (lane&15)) * H + 64w + 32ks + 8(lane>>4) + 0..7]          (KS2 = H/128 k-steps of 32 per wave)
 __host__ __device__ inline long pack16_fwd_pieces(int H) { const int KS2 = H / 128; return (long)(H / 16) * 3 * 4 * KS2 * 64; }
@@ -296,11 +297,11 @@ __global__ void pack_cluster16_fwd_split_kernel(const float* __restrict__ W, u32
     out[(idx - lane) * 2 + 64 + lane] = lo;
 }
 
-// the launchable instances (H = 256: KCQ = 4); below the default dynamic-LDS limit, so no attribute is asked for
+// the launchable instances (H = 256); below the default dynamic-LDS limit, so no attribute is asked for
 Instance<F16>& fwd16_instance(bool split) {
     constexpr size_t LDS = (size_t)(BT * (256 + 8) + 4 * 3 * RED_BLK + 2 * 768 + 2 * 1280 + 64) * sizeof(float);
     static_assert(LDS <= DEFAULT_DYNAMIC_LDS, "two members per CU: each well below half of the CU's LDS");
-    static Instance<F16> split3 DEP_INSTANCE((gru_fwd_cluster16<4, true>), LDS), exact DEP_INSTANCE((gru_fwd_cluster16<4, false>), LDS);
+    static Instance<F16> split3 DEP_INSTANCE((gru_fwd_cluster16<true>), LDS), exact DEP_INSTANCE((gru_fwd_cluster16<false>), LDS);
     return split ? split3 : exact;
 }
 

@@ -33,9 +33,6 @@ struct P2 {
     int nofast;              // DEP_CLUSTER_NOFAST=1: always use the write-through (placement-agnostic) stores
     long long* trace;        // debug: s_memtime stamps of workgroup 0 (DEP_TRACE=1), else nullptr
     int trall_off;           // debug: LDS offset (32-bit words) of the per-step stamp array
-    int ntstream;            // non-temporal gate-gradient write-out (default on; DEP_BWD_NT=0: plain stores)
-    int ntload;              // non-temporal one-touch input streams (default on; DEP_BWD_NTLD=0: plain loads)
-    int wflags;              // DEP_BWD_WFLAGS: every compute wave raises its OWN epoch flag once its own payload stores are acknowledged (no workgroup barrier in front of the flag; the pollers watch 4 NC words)
     int dgpk;                // round 4: write the gate gradients as the PK image the bf16x3 GEMMs read without converting (gemm_bf16x3.hip FMT_PK): rows (t even, t+1) of an utterance hold the (hi, lo) bf16 pairs of both steps; burst kernel, 4H-wide layout, T even
     const int* lengths; int pool_mean;      // ragged instances (RAG): row b is live for t < lengths[b]; dpooled of a mean is scaled by 1 / lengths[b]
 };
@@ -153,10 +150,11 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
     const size_t pstride = (size_t)p.nbtp * NC * BT * H;                   // floats per parity buffer
     const size_t tile_base = (size_t)bt * NC * BT * H;                     // this tile's [NC][NTT][64][4] block
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.payload, 0, p.payload_bytes, 0x00020000);
-    const bool wf = p.wflags != 0;                    // uniform
-    unsigned* tflags = wf ? p.flags + bt * NC * 4 : p.flags + bt * NC;
-    unsigned* myflag = wf ? tflags + c * 4 + (w & 3) : tflags + c;
-    const int nflags = wf ? NC * 4 : NC;
+    // per-wave flags: every compute wave raises its OWN epoch flag once its own payload stores are acknowledged (no workgroup barrier
+    // in front of the flag); the pollers watch all 4 NC words of the tile
+    unsigned* tflags = p.flags + bt * NC * 4;
+    unsigned* myflag = tflags + c * 4 + (w & 3);
+    const int nflags = NC * 4;
     const int ml = lane & 15, mq = lane >> 4;
     const int sx = p.nofast ? 0 : cluster_same_xcd(p.hello + bt * NC, NC, c, p.status);
     if (sx < 0) return;
@@ -197,26 +195,21 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
     const float* sbase1 = SV16 ? (sodd ? p.sv1 : p.y) : (sodd ? p.sv3 : p.sv2);
     const float* sbase2 = SV16 ? (sodd ? p.sv2 : p.dy) : (sodd ? p.dy : p.y);
     const int sld2 = sodd ? p.lddy : p.ldy;
-    // DEP_BWD_NT=1: the service waves' one-touch streams carry the non-temporal hint, so that they do not displace the
-    // exchange payload (rewritten every other step) from this XCD's L2 and turn it into HBM write-backs
-    // Round 4: the gate-gradient write-out goes out NON-TEMPORAL (buffer stores with the nt bit).  tools/micro/l2wb.hip + PMC:
-    // one-touch stores that allocate in L2 are what evicts the exchange payload (1 MB per XCD, rewritten in place every other step)
-    // before its next rewrite -- 0.8 GB of write-backs per launch; with nt stores the payload stays.  (Round 3's DEP_BWD_NT went
-    // through __builtin_nontemporal_store, which hipcc compiled to PLAIN stores -- no nt bit in the ISA -- so it measured nothing.)
-    const bool snt = p.ntstream != 0;
+    // The service waves' one-touch streams carry the non-temporal hint, so that they do not displace the exchange payload
+    // (rewritten every other step) from this XCD's L2 and turn it into HBM write-backs.  The gate-gradient write-out goes out as
+    // buffer stores with the nt bit (tools/micro/l2wb.hip + PMC: one-touch stores that allocate in L2 are what evicts the payload
+    // -- 1 MB per XCD, rewritten in place every other step -- before its next rewrite: 0.8 GB of write-backs per launch; with nt
+    // stores the payload stays.  __builtin_nontemporal_store compiles to PLAIN stores here -- no nt bit in the ISA.)
     // (resources are TILE-relative -- base = the tile's first row, extent = its 16 utterances -- so 32-bit offsets always suffice)
     const size_t trow0 = (size_t)(p.b0 + bt * BT) * T;
     float* const dgi_t = p.dgi + trow0 * p.lddg; float* const dghn_t = p.dghn + trow0 * p.lddghn;
     __amdgpu_buffer_rsrc_t rs_dgi = __builtin_amdgcn_make_buffer_rsrc((void*)dgi_t, 0, (unsigned)((size_t)BT * T * p.lddg * 4), 0x00020000);
     __amdgpu_buffer_rsrc_t rs_dghn = __builtin_amdgcn_make_buffer_rsrc((void*)dghn_t, 0, (unsigned)((size_t)BT * T * p.lddghn * 4), 0x00020000);
-    // q inside the tile's rows of the array of `rs` (tile base `base`): 16-byte store, nt when enabled
+    // q inside the tile's rows of the array of `rs` (tile base `base`): 16-byte nt store
     auto stnt2 = [&](__amdgpu_buffer_rsrc_t rs, const float* base, float* q, f32x4 v) {
-        if (snt) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, (unsigned)((const char*)q - (const char*)base), 0, 2 /* nt */);
-        else *reinterpret_cast<f32x4*>(q) = v;
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, (unsigned)((const char*)q - (const char*)base), 0, 2 /* nt */);
     };
-    // ... and so do the service waves' one-touch READS (the saved gates, h_{t-1}, dy): p.ntload (DEP_BWD_NTLD, default on).  NT is a
-    // compile-time tag of the service waves' code (svc_life below), not a select per load: two load forms meeting in one register
-    // make hipcc wait for every load it has just issued.
+    // ... and so do the service waves' one-touch READS (the saved gates, h_{t-1}, dy).
     const int mld = H > p.ldy ? (H > p.lddy ? H : p.lddy) : (p.ldy > p.lddy ? p.ldy : p.lddy);
     const unsigned span = (unsigned)((size_t)(BT * T + 1) * mld * 4);        // bounds the tile's rows of every input array (+ the h_{t-1} row in front)
     // bases one row in front of the tile's first row (h_{t-1} of t = 0 is never read; the offset stays non-negative)
@@ -231,66 +224,58 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
     __amdgpu_buffer_rsrc_t rs_in0 = __builtin_amdgcn_make_buffer_rsrc((void*)in0_t, 0, span, 0x00020000);
     __amdgpu_buffer_rsrc_t rs_in1 = __builtin_amdgcn_make_buffer_rsrc((void*)in1_t, 0, span, 0x00020000);
     __amdgpu_buffer_rsrc_t rs_in2 = __builtin_amdgcn_make_buffer_rsrc((void*)in2_t, 0, span, 0x00020000);
-    auto ldnt = [&](auto NT, int which, const float* q) -> f32x4 {      // 16 bytes at q, inside input array `which` of this wave
-        if constexpr (decltype(NT)::value) {
-            const float* base = which == 0 ? in0_t : (which == 1 ? in1_t : in2_t);
-            const unsigned off = (unsigned)((const char*)q - (const char*)base);
-            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(which == 0 ? rs_in0 : (which == 1 ? rs_in1 : rs_in2), off, 0, 2 /* nt */);
-            return __builtin_bit_cast(f32x4, v);
-        } else {
-            return ld4(q);
-        }
+    auto ldnt = [&](int which, const float* q) -> f32x4 {      // 16 bytes at q, inside input array `which` of this wave
+        const float* base = which == 0 ? in0_t : (which == 1 ? in1_t : in2_t);
+        const unsigned off = (unsigned)((const char*)q - (const char*)base);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(which == 0 ? rs_in0 : (which == 1 ? rs_in1 : rs_in2), off, 0, 2 /* nt */);
+        return __builtin_bit_cast(f32x4, v);
     };
-    auto ldnt8 = [&](auto NT, int which, const unsigned short* q) -> float2 {
-        if constexpr (decltype(NT)::value) {
-            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-            const float* base = which == 0 ? in0_t : (which == 1 ? in1_t : in2_t);
-            const unsigned off = (unsigned)((const char*)q - (const char*)base);
-            const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(which == 0 ? rs_in0 : (which == 1 ? rs_in1 : rs_in2), off, 0, 2 /* nt */);
-            return make_float2(__uint_as_float(v[0]), __uint_as_float(v[1]));
-        } else {
-            return *reinterpret_cast<const float2*>(q);
-        }
+    auto ldnt8 = [&](int which, const unsigned short* q) -> float2 {
+        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+        const float* base = which == 0 ? in0_t : (which == 1 ? in1_t : in2_t);
+        const unsigned off = (unsigned)((const char*)q - (const char*)base);
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(which == 0 ? rs_in0 : (which == 1 ? rs_in1 : rs_in2), off, 0, 2 /* nt */);
+        return make_float2(__uint_as_float(v[0]), __uint_as_float(v[1]));
     };
     // W16 (a std::bool_constant): this wave streams the 16-bit arrays
-    auto svc_load1 = [&](auto W16, auto NT, int k, int i) -> f32x4 {     // input i of this wave for step k
+    auto svc_load1 = [&](auto W16, int k, int i) -> f32x4 {     // input i of this wave for step k
         const int t = T - 1 - k;
         if (!svalid || t < 0) return zero4();
         const size_t row = (size_t)sb * T + t;
         if constexpr (SV16) {
             if constexpr (decltype(W16)::value) {             // four 16-bit values = 8 bytes
                 const float* base = i == 0 ? sbase0 : (i == 1 ? sbase1 : sbase2);
-                const float2 w = ldnt8(NT, i, reinterpret_cast<const unsigned short*>(base) + row * H + scol);
+                const float2 w = ldnt8(i, reinterpret_cast<const unsigned short*>(base) + row * H + scol);
                 const f32x4 r4 = {w.x, w.y, 0.f, 0.f};
                 return r4;
             } else {
                 if constexpr (BF) {                           // hn, h_{t-1}: bf16 arrays, four values = 8 bytes (decoded in svc_put)
-                    if (i == 0) { const float2 w = ldnt8(NT, 0, reinterpret_cast<const unsigned short*>(sbase0) + row * H + scol); const f32x4 r4 = {w.x, w.y, 0.f, 0.f}; return r4; }
+                    if (i == 0) { const float2 w = ldnt8(0, reinterpret_cast<const unsigned short*>(sbase0) + row * H + scol); const f32x4 r4 = {w.x, w.y, 0.f, 0.f}; return r4; }
                     if (i == 1) {
                         if (t <= 0) return zero4();
-                        const float2 w = ldnt8(NT, 1, reinterpret_cast<const unsigned short*>(sbase1) + (row - 1) * p.ldy + scol);
+                        const float2 w = ldnt8(1, reinterpret_cast<const unsigned short*>(sbase1) + (row - 1) * p.ldy + scol);
                         const f32x4 r4 = {w.x, w.y, 0.f, 0.f}; return r4;
                     }
-                    return sbase2 ? ldnt(NT, 2, sbase2 + row * p.lddy + scol) : zero4();
+                    return sbase2 ? ldnt(2, sbase2 + row * p.lddy + scol) : zero4();
                 } else {
-                    if (i == 0) return ldnt(NT, 0, sbase0 + row * H + scol);
-                    if (i == 1) return t > 0 ? ldnt(NT, 1, sbase1 + (row - 1) * p.ldy + scol) : zero4();
-                    return sbase2 ? ldnt(NT, 2, sbase2 + row * p.lddy + scol) : zero4();
+                    if (i == 0) return ldnt(0, sbase0 + row * H + scol);
+                    if (i == 1) return t > 0 ? ldnt(1, sbase1 + (row - 1) * p.ldy + scol) : zero4();
+                    return sbase2 ? ldnt(2, sbase2 + row * p.lddy + scol) : zero4();
                 }
             }
         } else {
-            if (i == 0) return ldnt(NT, 0, sbase0 + row * H + scol);
-            if (i == 1) return ldnt(NT, 1, sbase1 + row * H + scol);
-            if (sodd) return sbase2 ? ldnt(NT, 2, sbase2 + row * sld2 + scol) : zero4();
-            return t > 0 ? ldnt(NT, 2, sbase2 + (row - 1) * sld2 + scol) : zero4();
+            if (i == 0) return ldnt(0, sbase0 + row * H + scol);
+            if (i == 1) return ldnt(1, sbase1 + row * H + scol);
+            if (sodd) return sbase2 ? ldnt(2, sbase2 + row * sld2 + scol) : zero4();
+            return t > 0 ? ldnt(2, sbase2 + (row - 1) * sld2 + scol) : zero4();
         }
     };
-    auto svc_issue = [&](auto W16, auto NT, int k0, int n) {   // inputs of steps k0 .. k0+n-1 -> registers
+    auto svc_issue = [&](auto W16, int k0, int n) {   // inputs of steps k0 .. k0+n-1 -> registers
 #pragma unroll
         for (int d = 0; d < KBX; ++d)
             if (d < n) {
 #pragma unroll
-                for (int i = 0; i < 3; ++i) sreg[d][i] = svc_load1(W16, NT, k0 + d, i);
+                for (int i = 0; i < 3; ++i) sreg[d][i] = svc_load1(W16, k0 + d, i);
             }
     };
     auto svc_put = [&](auto W16, int k0, int n, int dlo = 0) {     // registers -> ibuf slots of steps k0+dlo .. k0+n-1
@@ -354,10 +339,10 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
     };
     if constexpr (BURST) {
         // the service waves' whole life (W16: this wave pair streams the 16-bit arrays)
-        auto svc_life = [&](auto W16, auto NT) {
-            // the service waves' whole life: same barrier sequence as the compute waves' loop below (two per step, one in the last)
-            svc_issue(W16, NT, 0, KBX); svc_put(W16, 0, KBX);       // steps 0 .. KB-1 straight into the ring
-            svc_issue(W16, NT, KBX, phi);                      // steps KB .. KB+phi-1: written at step phi-1, before the first dirty step (k = phi)
+        auto svc_life = [&](auto W16) {
+            // the service waves' whole life: same barrier sequence as the compute waves' loop below (one per step)
+            svc_issue(W16, 0, KBX); svc_put(W16, 0, KBX);       // steps 0 .. KB-1 straight into the ring
+            svc_issue(W16, KBX, phi);                      // steps KB .. KB+phi-1: written at step phi-1, before the first dirty step (k = phi)
             __syncthreads();
             for (int k = 0; k < T; ++k) {
                 const int jj = (k + KBX - phi) % KBX;                  // jj == 0: this tile's dirty step
@@ -369,7 +354,7 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
                     // ahead of the compute waves -- nothing holds them after barrier #2 -- so the burst starts during the
                     // previous step's poll; holding it back until the compute waves reach the dirty step's gate phase
                     // measured the same launch time: the burst occupies the CU's memory pipeline for ~1.3 steps either way.)
-                    svc_issue(W16, NT, k + KBX, KBX);
+                    svc_issue(W16, k + KBX, KBX);
                     if (trs) p.trace[32 + (k - 100) * 4 + 1] = (long long)__builtin_readcyclecounter();
                     if (p.dgpk) svc_flush_pk(k - KBX - (phi & 1), k - (phi & 1));      // whole pairs: one step later for the tiles with an odd phase
                     else svc_flush(k - KBX, k);
@@ -396,20 +381,17 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
                     if (last >= 0) svc_put(W16, last + KBX, KBX);
                     else svc_put(W16, KBX, phi);
                 }
-                if (k == T - 1) break;
-                if (!p.wflags) bar_lds();            // #2 (the compute waves' drain barrier; absent with per-wave flags)
+                if (k == T - 1) break;                // (per-wave flags: the compute waves have no drain barrier)
             }
             const int jl2 = (T - 1 + KBX - phi) % KBX;
             if (p.dgpk) svc_flush_pk(T - 1 - jl2 - (phi & 1), T);      // T is even: the last pair is complete
             else svc_flush(T - 1 - jl2, T);           // the gate gradients since the last dirty step
         };
         if (svc) {
-            const bool ntl = p.ntload != 0;             // uniform
             if constexpr (SV16) {
-                if (sodd) { if (ntl) svc_life(std::true_type{}, std::true_type{}); else svc_life(std::true_type{}, std::false_type{}); }
-                else { if (ntl) svc_life(std::false_type{}, std::true_type{}); else svc_life(std::false_type{}, std::false_type{}); }
+                if (sodd) svc_life(std::true_type{}); else svc_life(std::false_type{});
             } else {
-                if (ntl) svc_life(std::false_type{}, std::true_type{}); else svc_life(std::false_type{}, std::false_type{});
+                svc_life(std::false_type{});
             }
             return;
         }
@@ -635,15 +617,10 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every storing wave drains its write-through stores
         BSTAMP(3);
-        if (wf) {
-            // per-wave flags: this wave's partials are acknowledged -> say so; nobody waits for the sibling waves here (their
-            // flags are among the 4 NC words every wave polls below, which also orders this step's LDS reads before the next
-            // step's LDS writes: a sibling raises its flag only after its MFMAs have read the gate-gradient planes)
-            if (lane == 0) { if (fast) st_local(myflag, epoch); else st_agent(myflag, epoch); }
-        } else {
-            __builtin_amdgcn_s_barrier();            // every wave drained its payload stores (vmcnt(0) above)
-            if (tid == 0) { if (fast) st_local(myflag, epoch); else st_agent(myflag, epoch); }
-        }
+        // per-wave flags: this wave's partials are acknowledged -> say so; nobody waits for the sibling waves here (their
+        // flags are among the 4 NC words every wave polls below, which also orders this step's LDS reads before the next
+        // step's LDS writes: a sibling raises its flag only after its MFMAs have read the gate-gradient planes)
+        if (lane == 0) { if (fast) st_local(myflag, epoch); else st_agent(myflag, epoch); }
         if (masked) mk = draw(t - 1);                // next step's mask, in the shadow of the wait below
         BSTAMP(4);
         // wait for every member's flag (one wave polls, relaxed; flags are monotonic)
@@ -1063,9 +1040,6 @@ int dep_launch_cluster_bwd(const dep_sweep_bwd_args& a, void* xbuf, size_t xbuf_
     DEP_CHECK_ARG(PAYLOAD_OFF + pay <= xbuf_bytes && g.resident());
     p.flags = bind_exchange(p, xbuf, a.hdr_slot, pay);
     DepProfScope prof(DEP_PROF_GRU_BWD, a.stream);
-    // per-wave epoch flags, non-temporal one-touch streams: the measured winners of rounds 2-5 (profiles/r04_ab_pairs.txt,
-    // r05_final_ab_switches.txt); the losers live in the git history
-    p.wflags = 1; p.ntstream = 1; p.ntload = 1;
     // (one tile's rows of the widest array must fit a 32-bit buffer offset)
     { const int mxl = p.lddg > p.lddy ? p.lddg : p.lddy; DEP_CHECK_ARG((size_t)(BT * a.T + 1) * (mxl > p.ldy ? mxl : p.ldy) * 4 < 0xffffffffull); }
     const int kb = bwd_burst(a.H);

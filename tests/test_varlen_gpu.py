@@ -330,9 +330,10 @@ def test_ragged_cfg2_and_cfg3_shaped_calls_launch_the_ragged_cluster_instances(g
             assert not re.search(r'gru_fwd_cluster_r1<8, (true|false)>', text), text          # ... and no dense instance
             assert not re.search(r'gru_bwd_cluster_r1<4, (\w+, ){1,4}\w+>', text), text
         else:
-            assert re.search(r'lstm_fwd_cluster<(\w+, ){5}true>', text), text
-            assert re.search(r'lstm_bwd_cluster<(\w+, ){5}true>', text), text
-            assert not re.search(r'lstm_(fwd|bwd)_cluster<(\w+, ){2,4}\w+>', text), text
+            assert re.search(r'lstm_fwd_cluster<(\w+, ){2}true>', text), text                # <SPLIT, SV16, RAG>: the dense instances are written
+            assert re.search(r'lstm_bwd_cluster<(\w+, ){2}true>', text), text                # with one or two arguments, RAG defaulted
+            assert not re.search(r'lstm_(fwd|bwd)_cluster<(\w+, ){0,1}\w+>', text), text
+            assert not re.search(r'lstm_(fwd|bwd)_cluster<(\w+, ){2}false>', text), text
 
 
 # ----------------------------------------------------------------------------- attention

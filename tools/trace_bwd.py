@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""DEP_TRACE=1 python tools/trace_bwd.py : phase timings (shader cycles) of workgroup 0 of the backward cluster sweep."""
+"""DEP_TRACE=1 python tools/trace_bwd.py : phase timings (shader cycles) of workgroup 0 of the backward cluster sweep at H = 256.  The
+precision mode selects the form, and with it the labels: DEP_GEMM_MODE=f32 traces the reduce-scatter of the exact-fp32 mode, the default
+the all-gather step of the split products."""
 import ctypes as C
 import os
 import sys
@@ -25,8 +27,8 @@ for _ in range(2):
 torch.cuda.synchronize()
 off = L.load().dep_rnn_workspace_xbuf_offset(C.byref(rnn.desc))
 tr = rnn.workspace[(off + 6400) // 4:(off + 6400) // 4 + 64].view(torch.int64).cpu().numpy().reshape(4, 8)
-names = ['gate grads + LDS + barrier', 'prefetch issue + MFMA', 'payload stores + drain', 'barrier + flag', 'poll', 'gather + sum']
-if os.environ.get('DEP_BWD_AG', '1') != '0':      # the all-gather step (default since round 5) (rnn_cluster_bwd.hip, AG): one barrier, at the end
+names = ['ring read + gate grads + LDS + barrier', 'MFMA', 'payload stores + drain', 'wave flag', 'poll', 'gather + sum']
+if L.get_gemm_mode() != 0:      # split products: the all-gather step (rnn_cluster_bwd.hip, AG): one barrier, at the end
     names = ['ring read + gate grads + publish issue', 'publish acknowledged', 'flag + mask draw', 'poll (2 source members)',
              '12 fragment loads + 36 MFMAs + red write', 'barrier + K-quarter sum']
 for s in range(4):

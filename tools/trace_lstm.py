@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """DEP_TRACE=1 python tools/trace_lstm.py [bwd] : phase timings (shader clocks) of workgroup 0, wave 0 of the BiLSTM-128 forward (or, with
-`bwd', backward) cluster sweep of layer 0 (rnn_cluster_lstm.hip) at cfg3's T and B; DEP_LSTM_DF=0/1 and DEP_LSTM_SE=0 trace the forms the
-defaults replaced."""
+`bwd', backward) cluster sweep of layer 0 (rnn_cluster_lstm.hip) at cfg3's T and B.  The precision mode selects the form, and with it the labels: DEP_GEMM_MODE=f32
+traces the exact-fp32 sweeps, the default the split-precision ones."""
 import ctypes as C
 import os
 import sys
@@ -35,18 +35,19 @@ torch.cuda.synchronize()
 rnn.check()
 off = L.load().dep_rnn_workspace_xbuf_offset(C.byref(rnn.desc))
 tr = rnn.workspace[(off + 6400) // 4:(off + 6400) // 4 + 64].view(torch.int64).cpu().numpy().reshape(4, 8)
-if bwd:
+split = L.get_gemm_mode() != 0        # the only thing that selects a form: exact fp32 (mode 0) or split products
+if bwd and split:
     names = ['ring read + gate gradients + planes + write-out ring', 'barrier', 'LDS fragment reads + 24 MFMAs + partial-dh stores issued',
-             'stores acknowledged (+ drain barrier) + flag', 'mask draw + poll', 'gather 4 partials + sum']
-elif os.environ.get('DEP_LSTM_DF', '2') == '3':
+             'stores acknowledged + wave flag', 'poll (16 wave flags)', 'gather 4 partials + sum']
+elif bwd:
+    names = ['ring read + gate gradients + planes + write-out ring', 'barrier', 'LDS reads + 64 MFMAs + partial-dh stores issued',
+             'stores acknowledged + drain barrier + flag', 'mask draw + poll (4 member flags)', 'gather 4 partials + sum']
+elif split:
     names = ['ring read + gates + c, h + publish + re-arm issue + write-out ring', '-', '-', 'fragment loads until no word is the sentinel',
              '24 MFMAs + partial write', 'barrier + K-half sum']
-elif os.environ.get('DEP_LSTM_DF', '2') != '0':
-    names = ['ring read + gates + c, h + publish issue + write-out ring', 'publish acknowledged', 'flag', 'poll (2 source members, 8 wave flags)',
-             '4 fragment loads + mask draw + 24 MFMAs + partial write', 'barrier + K-half sum']
 else:
-    names = ['LDS fragment reads + 24 MFMAs + partial write', 'barrier + ring read + K-half sum + gates + c, h + publish issue',
-             'publish acknowledged + barrier + flag', 'write-out ring (+ mask draw)', 'poll (4 member flags)', 'gather 8 KB + unpack to LDS planes + barrier']
+    names = ['LDS reads + 64 MFMAs + partial write', 'barrier + ring read + K-half sum + gates + c, h + publish issue',
+             'publish acknowledged + barrier + flag', 'write-out ring (+ mask draw)', 'poll (4 member flags)', 'gather 8 KB into the LDS plane + barrier']
 for s in range(4):
     d = [int(tr[s, i + 1] - tr[s, i]) for i in range(6)]
     print(f'step {196 + s}: total {int(tr[s, 6] - tr[s, 0])} ticks ; ' + ' | '.join(f'{n}: {v}' for n, v in zip(names, d)))
