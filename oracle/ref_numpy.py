@@ -472,5 +472,54 @@ def adam_step(p, g, m, v, step, lr, wd=0.0, decoupled=False, b1=0.9, b2=0.999, e
     return p, m, v
 
 
+# ----------------------------------------------------------------------------- dropout draw
+_M32 = np.uint64(0xFFFFFFFF)
+_PHILOX_M = (np.uint64(0xD2511F53), np.uint64(0xCD9E8D57))       # the two round multipliers
+_PHILOX_W = (np.uint64(0x9E3779B9), np.uint64(0xBB67AE85))       # the key schedule's two Weyl increments
+
+
+def philox4x32_10(counter4, key2):
+    """Philox4x32 with 10 rounds (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11).
+    counter4: four and key2: two integers or integer arrays below 2**32 that broadcast against each other.  Returns the four
+    output words as a uint32 array of shape broadcast + (4,).
+
+    One round maps (c0, c1, c2, c3) under the round key (k0, k1) to
+        (hi(M1 c2) ^ c1 ^ k0,  lo(M1 c2),  hi(M0 c0) ^ c3 ^ k1,  lo(M0 c0))
+    where hi / lo are the halves of the 64-bit product; round r uses the key (k0 + r W0, k1 + r W1) mod 2**32.
+    All arithmetic is uint64 masked to 32 bits: a 32 x 32 product fits in 64."""
+    c = [np.asarray(w, dtype=np.uint64) & _M32 for w in counter4]
+    k = [np.asarray(w, dtype=np.uint64) & _M32 for w in key2]
+    if len(c) != 4 or len(k) != 2:
+        raise ValueError('philox4x32_10 takes a 4-word counter and a 2-word key')
+    shape = np.broadcast_shapes(*[w.shape for w in c + k])
+    c = [np.broadcast_to(w, shape) for w in c]
+    for r in range(10):
+        rk = [(k[j] + np.uint64(r) * _PHILOX_W[j]) & _M32 for j in (0, 1)]
+        p0 = _PHILOX_M[0] * c[0]
+        p1 = _PHILOX_M[1] * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ rk[0], p1 & _M32, (p0 >> np.uint64(32)) ^ c[3] ^ rk[1], p0 & _M32]
+    return np.stack(c, axis=-1).astype(np.uint32)
+
+
+def dropout_mask(n, p, seed, site):
+    """The pre-scaled keep mask (0 or 1 / (1 - p), float32) of the first n elements of dropout site `site` under the 64-bit
+    `seed`, as the library draws it (the convention of csrc/dep_common.h, restated, not shared):
+      key     = (seed mod 2**32, seed >> 32)
+      counter = (g mod 2**32, g >> 32, site, 0x2545F491) for the group g of the four elements 4g .. 4g+3; output word i is
+                element 4g + i's
+      uniform = float32(word >> 8) * 2**-24, kept iff uniform >= float32(p)
+      scale   = float32(1) / (float32(1) - float32(p)), every step rounded to float32 as the host wrapper computes it."""
+    n = int(n); seed = int(seed); site = int(site)
+    if n < 0 or not 0 <= seed < 2 ** 64 or not 0 <= site < 2 ** 32:
+        raise ValueError('dropout_mask: n >= 0, a 64-bit seed and a 32-bit site')
+    g = np.arange((n + 3) // 4, dtype=np.uint64)
+    words = philox4x32_10((g & _M32, g >> np.uint64(32), site, 0x2545F491), (seed & 0xFFFFFFFF, seed >> 32))
+    words = words.reshape(-1)[:n]
+    u = (words >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    pf = np.float32(p)
+    scale = np.float32(1) / (np.float32(1) - pf)
+    return np.where(u >= pf, scale, np.float32(0)).astype(np.float32)
+
+
 def to_f64(P):
     return {k: np.asarray(v, dtype=F64) for k, v in P.items()}
