@@ -1,5 +1,5 @@
 // Memory-bound and small kernels of the hot path: LayerNorm, dropout, ReLU, bias-gradient column
-// sums, the fused output-nonlinearity + loss + gradient kernel, attention_net_with_w, Adam/AdamW.
+// sums, the fused output-nonlinearity + loss + gradient kernel, attention_net_with_w.  (Adam/AdamW: optim.hip.)
 // Reference call sites are cited on each entry point in include/dep_rnn.h.
 #include "dep_common.h"
 
@@ -296,22 +296,6 @@ __global__ __launch_bounds__(256) void reduce_loss_kernel(const float* __restric
     if (threadIdx.x == 0) out[0] = (accumulate ? out[0] : 0.f) + s * inv_norm;
 }
 
-// ------------------------------------------------------------------------------ Adam / AdamW
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
-                            int decoupled, float step_size, float inv_sqrt_bc2) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float pv = p[i], gv = g[i];
-    if (decoupled) pv *= (1.0f - lr * wd);
-    else if (wd != 0.f) gv = fmaf(wd, pv, gv);
-    const float mv = b1 * m[i] + (1.0f - b1) * gv;
-    const float vv = b2 * v[i] + (1.0f - b2) * gv * gv;
-    m[i] = mv; v[i] = vv;
-    const float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
-    p[i] = pv - step_size * (mv / denom);
-}
-
 __global__ void fill_kernel(float* p, long n, float v) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
@@ -599,18 +583,6 @@ extern "C" int dep_head_loss(int kind, const float* z, const void* target, float
 extern "C" int dep_reduce_loss(const float* loss_rows, int B, float norm, float* loss_out, int accumulate, void* stream) {
     DEP_CHECK_ARG(loss_rows && loss_out && B > 0 && norm > 0.f);
     DEP_LAUNCH(reduce_loss_kernel, dim3(1), dim3(256), 0, S_, loss_rows, B, 1.0f / norm, loss_out, accumulate);
-    DEP_CHECK_LAUNCH();
-    return DEP_OK;
-}
-extern "C" int dep_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
-                             float eps, float weight_decay, int decoupled, int step, void* stream) {
-    DEP_CHECK_ARG(p && g && m && v && n > 0 && step >= 1);
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    const float step_size = (float)((double)lr / bc1);
-    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-    DEP_LAUNCH(adam_kernel, dim3(nblk(n)), dim3(256), 0, S_, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay,
-                       decoupled, step_size, inv_sqrt_bc2);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }

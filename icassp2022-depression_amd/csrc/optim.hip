@@ -1,5 +1,9 @@
-// Global-norm gradient clipping on the device (dep_grad_sqnorm, dep_adam_step_clipped, dep_grad_clip_scale) and gradient accumulation over
-// micro-batches (dep_grad_accumulate); include/dep_rnn.h.
+// The optimizer on the device: Adam / AdamW (dep_adam_step), global-norm gradient clipping (dep_grad_sqnorm, dep_adam_step_clipped,
+// dep_grad_clip_scale) and gradient accumulation over micro-batches (dep_grad_accumulate); include/dep_rnn.h.
+//
+// Two equalities hold by construction.  adam_kernel and adam_clipped_kernel both call adam_element, the one Adam expression, so a clip
+// coefficient of one gives the plain step's bits.  grad_sqnorm_kernel and grad_accumulate_kernel are both gn_walk<> over their ranges,
+// so the partial sums the accumulate launch leaves are the ones dep_grad_sqnorm forms from the accumulator.
 //
 // The sum of squares is a pure function of the data.  The ranges are read as ONE concatenated array cut into chunks of
 // GN_CHUNK floats; partial slot s holds the sum over chunks s, s + GN_SLOTS, ... in that order, and ONE workgroup owns a slot
@@ -41,8 +45,11 @@ __device__ __forceinline__ double gn_block_sum(double v, double* red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__global__ __launch_bounds__(GN_THREADS) void grad_sqnorm_kernel(GradRanges R, double* __restrict__ partials) {
-    __shared__ double red[4];
+// The walk of both range kernels.  Ranges: GradRanges or AccumRanges (start[], count).  one(r, off): the value of element off of range r;
+// four(r, off): the four values from off on, which sit in range r at a 16-byte boundary.  The callables may store as well as load.
+// Returns this thread's sum of squares over the chunks of its workgroup's slot, (p0 + p1) + (p2 + p3) per chunk.
+template <class Ranges, class One, class Four>
+__device__ __forceinline__ double gn_walk(const Ranges& R, One one, Four four) {
     const long total = R.start[R.count];
     const long nchunks = (total + GN_CHUNK - 1) / GN_CHUNK;
     double acc = 0.0;
@@ -54,7 +61,7 @@ __global__ __launch_bounds__(GN_THREADS) void grad_sqnorm_kernel(GradRanges R, d
             while (i >= R.start[r + 1]) ++r;                       // i < total = start[count]: stops at r < count
             const long off = i - R.start[r];
             if (i + 3 < R.start[r + 1] && (off & 3) == 0) {        // the four elements sit in one range at a 16-byte boundary
-                const f32x4 x = *reinterpret_cast<const f32x4*>(R.ptr[r] + off);
+                const f32x4 x = four(r, off);
                 p0 = (double)x[0] * (double)x[0]; p1 = (double)x[1] * (double)x[1];
                 p2 = (double)x[2] * (double)x[2]; p3 = (double)x[3] * (double)x[3];
             } else {                                               // a range boundary or the tail: element by element (absent = +0)
@@ -64,7 +71,7 @@ __global__ __launch_bounds__(GN_THREADS) void grad_sqnorm_kernel(GradRanges R, d
                     const long k = i + e;
                     if (k < total) {
                         while (k >= R.start[r + 1]) ++r;
-                        const double x = (double)R.ptr[r][k - R.start[r]];
+                        const double x = (double)one(r, k - R.start[r]);
                         p[e] = x * x;
                     }
                 }
@@ -73,14 +80,20 @@ __global__ __launch_bounds__(GN_THREADS) void grad_sqnorm_kernel(GradRanges R, d
         }
         acc += (p0 + p1) + (p2 + p3);
     }
+    return acc;
+}
+
+__global__ __launch_bounds__(GN_THREADS) void grad_sqnorm_kernel(GradRanges R, double* __restrict__ partials) {
+    __shared__ double red[4];
+    const double acc = gn_walk(R, [&](int r, long off) { return R.ptr[r][off]; },
+                               [&](int r, long off) { return *reinterpret_cast<const f32x4*>(R.ptr[r] + off); });
     const double s = gn_block_sum(acc, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;                // every slot is written (0 for a slot without a chunk)
 }
 
 // acc = first ? g * scale : acc + g * scale over the ranges, and (partials != NULL) grad_sqnorm_kernel's partial sums of the STORED result in
-// the same pass.  The walk is that kernel's, statement for statement -- GN_SLOTS workgroups, the same chunks per slot, the same choice
-// between the 16-byte path and the element path, the same (p0 + p1) + (p2 + p3) and gn_block_sum -- so the partials carry the bits
-// dep_grad_sqnorm forms afterwards from the accumulator.  The product and the sum are two fp32 roundings (no FMA): numpy float32
+// the same pass: both kernels are gn_walk and gn_block_sum, this one with callables that store what they return, so the partials carry
+// the bits dep_grad_sqnorm forms afterwards from the accumulator.  The product and the sum are two fp32 roundings (no FMA): numpy float32
 // reproduces the result, and scale == 1 is the plain IEEE add.  `first`: acc is written without being read.
 __device__ __forceinline__ float ga_value(float a, float g, float scale, int first) {
     // contraction off for THESE two operations: hipcc's __fmul_rn / __fadd_rn are inline * and + compiled under the default
@@ -91,45 +104,23 @@ __device__ __forceinline__ float ga_value(float a, float g, float scale, int fir
 }
 __global__ __launch_bounds__(GN_THREADS) void grad_accumulate_kernel(AccumRanges R, float scale, int first, double* __restrict__ partials) {
     __shared__ double red[4];
-    const long total = R.start[R.count];
-    const long nchunks = (total + GN_CHUNK - 1) / GN_CHUNK;
-    double acc = 0.0;
-    for (long c = blockIdx.x; c < nchunks; c += GN_SLOTS) {
-        const long i = c * GN_CHUNK + (long)threadIdx.x * 4;
-        double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
-        if (i < total) {
-            int r = 0;
-            while (i >= R.start[r + 1]) ++r;                       // i < total = start[count]: stops at r < count
-            const long off = i - R.start[r];
-            if (i + 3 < R.start[r + 1] && (off & 3) == 0) {        // the four elements sit in one range at a 16-byte boundary
-                const f32x4 gv = *reinterpret_cast<const f32x4*>(R.g[r] + off);
-                f32x4 a = {0.f, 0.f, 0.f, 0.f};
-                if (!first) a = *reinterpret_cast<const f32x4*>(R.acc[r] + off);
-                f32x4 x;
+    const double acc = gn_walk(R,
+        [&](int r, long off) {
+            float* ap = R.acc[r] + off;
+            const float x = ga_value(first ? 0.f : *ap, R.g[r][off], scale, first);
+            *ap = x;
+            return x;
+        },
+        [&](int r, long off) {
+            const f32x4 gv = *reinterpret_cast<const f32x4*>(R.g[r] + off);
+            f32x4 a = {0.f, 0.f, 0.f, 0.f};
+            if (!first) a = *reinterpret_cast<const f32x4*>(R.acc[r] + off);
+            f32x4 x;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) x[e] = ga_value(a[e], gv[e], scale, first);
-                *reinterpret_cast<f32x4*>(R.acc[r] + off) = x;
-                p0 = (double)x[0] * (double)x[0]; p1 = (double)x[1] * (double)x[1];
-                p2 = (double)x[2] * (double)x[2]; p3 = (double)x[3] * (double)x[3];
-            } else {                                               // a range boundary or the tail: element by element (absent = +0)
-                double p[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const long k = i + e;
-                    if (k < total) {
-                        while (k >= R.start[r + 1]) ++r;
-                        float* ap = R.acc[r] + (k - R.start[r]);
-                        const float xf = ga_value(first ? 0.f : *ap, R.g[r][k - R.start[r]], scale, first);
-                        *ap = xf;
-                        const double x = (double)xf;
-                        p[e] = x * x;
-                    }
-                }
-                p0 = p[0]; p1 = p[1]; p2 = p[2]; p3 = p[3];
-            }
-        }
-        acc += (p0 + p1) + (p2 + p3);
-    }
+            for (int e = 0; e < 4; ++e) x[e] = ga_value(a[e], gv[e], scale, first);
+            *reinterpret_cast<f32x4*>(R.acc[r] + off) = x;
+            return x;
+        });
     if (partials == nullptr) return;                               // uniform over the grid
     const double s = gn_block_sum(acc, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;                // every slot is written (0 for a slot without a chunk)
@@ -163,8 +154,37 @@ __device__ __forceinline__ void gn_report(const ClipCoef& c, bool skipped, float
     }
 }
 
-// adam_kernel (elementwise.hip) with gv = g[i] * coef in front; the rest of the expression is that kernel's, operand for operand,
-// so that coef == 1 (g * 1.0f is exact) gives dep_adam_step's bits
+// ------------------------------------------------------------------------------ Adam / AdamW
+// The bias correction of update `step`, as the kernels take it.
+struct AdamBias { float step_size, inv_sqrt_bc2; };
+inline AdamBias adam_bias(float lr, float beta1, float beta2, int step) {
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    return {(float)((double)lr / bc1), (float)(1.0 / sqrt(bc2))};
+}
+// The update of element i, the ONE Adam expression of the library.  The caller loads pv = p[i] and gv = g[i] (adam_clipped_kernel: times
+// the clip coefficient; g * 1.0f is exact, so a coefficient of one gives the plain step's bits) in that order and passes the values.
+__device__ __forceinline__ void adam_element(float pv, float gv, float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                             long i, float lr, float b1, float b2, float eps, float wd, int decoupled, float step_size,
+                                             float inv_sqrt_bc2) {
+    if (decoupled) pv *= (1.0f - lr * wd);
+    else if (wd != 0.f) gv = fmaf(wd, pv, gv);
+    const float mv = b1 * m[i] + (1.0f - b1) * gv;
+    const float vv = b2 * v[i] + (1.0f - b2) * gv * gv;
+    m[i] = mv; v[i] = vv;
+    const float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
+    p[i] = pv - step_size * (mv / denom);
+}
+
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                            float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
+                            int decoupled, float step_size, float inv_sqrt_bc2) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float pv = p[i], gv = g[i];
+    adam_element(pv, gv, p, m, v, i, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2);
+}
+
 constexpr int AC_PER_THREAD = 8;           // elements per thread: the partials are re-summed once per 2048 elements
 __global__ __launch_bounds__(GN_THREADS) void adam_clipped_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                                   float* __restrict__ m, float* __restrict__ v, long n, float lr,
@@ -183,14 +203,8 @@ __global__ __launch_bounds__(GN_THREADS) void adam_clipped_kernel(float* __restr
     for (int k = 0; k < AC_PER_THREAD; ++k) {
         const long i = base + (long)k * GN_THREADS;
         if (i >= n) break;
-        float pv = p[i], gv = g[i] * coef;
-        if (decoupled) pv *= (1.0f - lr * wd);
-        else if (wd != 0.f) gv = fmaf(wd, pv, gv);
-        const float mv = b1 * m[i] + (1.0f - b1) * gv;
-        const float vv = b2 * v[i] + (1.0f - b2) * gv * gv;
-        m[i] = mv; v[i] = vv;
-        const float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
-        p[i] = pv - step_size * (mv / denom);
+        const float pv = p[i], gv = g[i] * coef;
+        adam_element(pv, gv, p, m, v, i, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2);
     }
 }
 
@@ -213,6 +227,14 @@ int check_ranges(const float* const* bufs, const long* counts, int nranges) {
     for (int r = 0; r < nranges; ++r) DEP_CHECK_ARG(bufs[r] && counts[r] > 0 && ((uintptr_t)bufs[r] & 15) == 0);
     return DEP_OK;
 }
+// start[] of the concatenation the walk reads, and count
+template <class Ranges>
+void set_starts(Ranges& R, const long* counts, int nranges) {
+    long at = 0;
+    for (int r = 0; r < nranges; ++r) { R.start[r] = at; at += counts[r]; }
+    for (int r = nranges; r <= GN_MAXR; ++r) R.start[r] = at;
+    R.count = nranges;
+}
 // "measure only": max_norm <= 0 or +inf -> 0 for the kernels
 inline double kernel_max_norm(float max_norm) { return (max_norm > 0.f && max_norm <= 3.402823466e38f) ? (double)max_norm : 0.0; }
 
@@ -227,10 +249,8 @@ extern "C" int dep_grad_sqnorm(const float* const* bufs, const long* counts, int
     if (int rc = check_ranges(bufs, counts, nranges)) return rc;
     DEP_CHECK_ARG(partials);
     GradRanges R{};
-    long at = 0;
-    for (int r = 0; r < nranges; ++r) { R.ptr[r] = bufs[r]; R.start[r] = at; at += counts[r]; }
-    for (int r = nranges; r <= GN_MAXR; ++r) R.start[r] = at;
-    R.count = nranges;
+    for (int r = 0; r < nranges; ++r) R.ptr[r] = bufs[r];
+    set_starts(R, counts, nranges);
     DEP_LAUNCH(grad_sqnorm_kernel, dim3(GN_SLOTS), dim3(GN_THREADS), 0, S_, R, partials);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
@@ -242,11 +262,19 @@ extern "C" int dep_grad_accumulate(float* const* acc, const float* const* g, con
     DEP_CHECK_ARG(acc && scale == scale);
     for (int r = 0; r < nranges; ++r) DEP_CHECK_ARG(acc[r] && ((uintptr_t)acc[r] & 15) == 0);
     AccumRanges R{};
-    long at = 0;
-    for (int r = 0; r < nranges; ++r) { R.acc[r] = acc[r]; R.g[r] = g[r]; R.start[r] = at; at += counts[r]; }
-    for (int r = nranges; r <= GN_MAXR; ++r) R.start[r] = at;
-    R.count = nranges;
+    for (int r = 0; r < nranges; ++r) { R.acc[r] = acc[r]; R.g[r] = g[r]; }
+    set_starts(R, counts, nranges);
     DEP_LAUNCH(grad_accumulate_kernel, dim3(GN_SLOTS), dim3(GN_THREADS), 0, S_, R, scale, first ? 1 : 0, partials);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+
+extern "C" int dep_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
+                             float eps, float weight_decay, int decoupled, int step, void* stream) {
+    DEP_CHECK_ARG(p && g && m && v && n > 0 && step >= 1);
+    const AdamBias bc = adam_bias(lr, beta1, beta2, step);
+    DEP_LAUNCH(adam_kernel, dim3(dep_cdiv(n, 256)), dim3(256), 0, S_, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, decoupled,
+               bc.step_size, bc.inv_sqrt_bc2);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }
@@ -255,12 +283,9 @@ extern "C" int dep_adam_step_clipped(float* p, const float* g, float* m, float* 
                                      float eps, float weight_decay, int decoupled, int step, const double* partials,
                                      float max_norm, int skip_nonfinite, float* clip_out, double* stats, void* stream) {
     DEP_CHECK_ARG(p && g && m && v && n > 0 && step >= 1 && partials && max_norm == max_norm);
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    const float step_size = (float)((double)lr / bc1);
-    const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    const AdamBias bc = adam_bias(lr, beta1, beta2, step);
     DEP_LAUNCH(adam_clipped_kernel, dim3(dep_cdiv(n, GN_THREADS * AC_PER_THREAD)), dim3(GN_THREADS), 0, S_, p, g, m, v, n, lr,
-               beta1, beta2, eps, weight_decay, decoupled, step_size, inv_sqrt_bc2, partials, kernel_max_norm(max_norm),
+               beta1, beta2, eps, weight_decay, decoupled, bc.step_size, bc.inv_sqrt_bc2, partials, kernel_max_norm(max_norm),
                skip_nonfinite, clip_out, stats);
     DEP_CHECK_LAUNCH();
     return DEP_OK;

@@ -420,11 +420,6 @@ class _AdamBase:
             for p in g['params']:
                 p.owner._grad_ready = False
 
-    def _ranges(self, g):
-        """Contiguous [start, end) ranges (in the owner's flat buffer) of the parameters of group g that
-        currently hold a gradient -- parameters whose grad is None are skipped like torch does."""
-        return _grad_ranges(g['params'])
-
     def _state_of(self, owner):
         st = self._state.get(id(owner))
         if st is None:
@@ -432,43 +427,57 @@ class _AdamBase:
             self._state[id(owner)] = st
         return st
 
+    def _plan(self):
+        """[(group, [(owner, start, end), ...]), ...]: per group the ranges (_grad_ranges) that hold a gradient right now."""
+        return [(g, _grad_ranges(g['params'])) for g in self.param_groups]
+
+    def _clips(self):
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    @staticmethod
+    def _spans(plan, what):
+        """The ranges of all groups in launch order; `what` names the feature whose single launch has to take them all (None: no limit)."""
+        spans = [r for _, rs in plan for r in rs]
+        if what and len(spans) > _MAX_CLIP_RANGES:
+            raise L.DepError(f'gradient {what} covers at most {_MAX_CLIP_RANGES} contiguous gradient ranges per step, this optimizer has {len(spans)}')
+        return spans
+
     def step(self):
         if self.accumulate_steps > 1:
             return self._micro_step()
         self._step += 1
         L.order_note('optimizer step')
-        if self.max_grad_norm is not None or self.skip_nonfinite:
-            return self._step_clipped()
-        for g in self.param_groups:
-            b1, b2 = g['betas']
-            for owner, s, e in self._ranges(g):
-                m, v = self._state_of(owner)
-                L.adam_step(owner._flat[s:e], owner._flat_grad[s:e], m[s:e], v[s:e], g['lr'], b1, b2, g['eps'],
-                            g['weight_decay'], self.decoupled, self._step)
+        self._update(self._plan(), lambda owner: owner._flat_grad, 'clipping' if self._clips() else None)
 
-    def _step_clipped(self):
-        """ONE dep_grad_sqnorm over the ranges of ALL groups (a global norm, as torch's function takes all parameters at once), then
-        dep_adam_step_clipped per range: one launch more than the plain step.  Every launch derives the coefficient from the same
+    def _update(self, plan, grad_of, what, have_partials=False):
+        """THE update, of every path: one launch per range of `plan`, reading grad_of(owner) -- the owner's _flat_grad or its accumulator.
+        Without clipping that is dep_adam_step and nothing else.  With it: ONE dep_grad_sqnorm over the ranges of ALL groups (a global
+        norm, as torch's function takes all parameters at once; none when have_partials says the accumulate launch left the sums), then
+        dep_adam_step_clipped per range -- one launch more than the plain step.  Every launch derives the coefficient from the same
         partial sums, with the same bits; the first one also updates the statistics record.  Under data parallelism this runs after
         the compute stream joined the communication stream, on the reduced gradients every rank holds alike: the ranks form the same
-        coefficient without a collective."""
-        plan = [(g, self._ranges(g)) for g in self.param_groups]
-        grads = [owner._flat_grad[s:e] for _, rs in plan for owner, s, e in rs]
-        if not grads:
+        coefficient without a collective.  No parameter holds a gradient: nothing is launched."""
+        spans = self._spans(plan, what)
+        if not spans:
             return
-        if len(grads) > _MAX_CLIP_RANGES:
-            raise L.DepError(f'gradient clipping covers at most {_MAX_CLIP_RANGES} contiguous gradient ranges per step, this optimizer has {len(grads)}')
-        partials, clip_out, stats = self._clip_buffers(grads[0].device)
-        L.grad_sqnorm(grads, partials)
-        max_norm = 0.0 if self.max_grad_norm is None else self.max_grad_norm          # 0: measure only (skip_nonfinite alone)
+        clip = self._clips()
+        if clip:
+            partials, clip_out, stats = self._clip_buffers(spans[0][0]._flat_grad.device)
+            if not have_partials:
+                L.grad_sqnorm([grad_of(o)[s:e] for o, s, e in spans], partials)
+            max_norm = 0.0 if self.max_grad_norm is None else self.max_grad_norm          # 0: measure only (skip_nonfinite alone)
         first = True
         for g, rs in plan:
             b1, b2 = g['betas']
             for owner, s, e in rs:
                 m, v = self._state_of(owner)
-                L.adam_step_clipped(owner._flat[s:e], owner._flat_grad[s:e], m[s:e], v[s:e], g['lr'], b1, b2, g['eps'],
-                                    g['weight_decay'], self.decoupled, self._step, partials, max_norm, self.skip_nonfinite,
-                                    clip_out if first else None, stats if first else None)
+                args = (owner._flat[s:e], grad_of(owner)[s:e], m[s:e], v[s:e], g['lr'], b1, b2, g['eps'], g['weight_decay'],
+                        self.decoupled, self._step)
+                if clip:
+                    L.adam_step_clipped(*args, partials, max_norm, self.skip_nonfinite, clip_out if first else None,
+                                        stats if first else None)
+                else:
+                    L.adam_step(*args)
                 first = False
 
     # -- accumulation over micro-batches (accumulate_steps > 1) -------------------------------------------------------
@@ -497,24 +506,21 @@ class _AdamBase:
         micro-step: the accumulator is overwritten, nothing clears it).  The K-th micro-step updates; on one rank its launch also
         leaves the partial sums of squares a clipped update needs, so that update launches no dep_grad_sqnorm."""
         L.order_note('optimizer micro-step')
-        plan = [(g, self._ranges(g)) for g in self.param_groups]
-        spans = [r for _, rs in plan for r in rs]
+        plan = self._plan()
+        spans = self._spans(plan, 'accumulation')
         if not spans:
             return
-        if len(spans) > _MAX_CLIP_RANGES:
-            raise L.DepError(f'gradient accumulation covers at most {_MAX_CLIP_RANGES} contiguous gradient ranges per step, this optimizer has {len(spans)}')
         first = self._pending == 0
         if first:
             self._accum_plan = plan
-        elif spans != [r for _, rs in self._accum_plan for r in rs]:
+        elif spans != self._spans(self._accum_plan, None):
             raise L.DepError('the parameters that hold a gradient changed inside an accumulation group')
         for owner, _, _ in spans:
             if id(owner) not in self._accum:
                 self._accum[id(owner)] = torch.zeros_like(owner._flat_grad)
         boundary = self._pending + 1 == self.accumulate_steps
-        clip = self.max_grad_norm is not None or self.skip_nonfinite
         partials = None
-        if boundary and clip and parallel.transport() == 'none':            # (an exchange follows otherwise: the norm is the reduced sums')
+        if boundary and self._clips() and parallel.transport() == 'none':   # (an exchange follows otherwise: the norm is the reduced sums')
             partials = self._clip_buffers(spans[0][0]._flat_grad.device)[0]
         L.grad_accumulate([self._accum[id(o)][s:e] for o, s, e in spans], [o._flat_grad[s:e] for o, s, e in spans], 1.0, first, partials)
         self._pending += 1
@@ -528,40 +534,16 @@ class _AdamBase:
             self._update_from_accumulator(False)
 
     def _update_from_accumulator(self, have_partials):
-        """The update of step() / _step_clipped() with the accumulator in the place of _flat_grad.  Data parallel: each owner's live
-        bucket of the accumulator is all-reduced first, ONCE, and the norm is that of the reduced sums (dep_grad_sqnorm after the
-        join), which every rank holds alike."""
+        """_update with the accumulator in the place of _flat_grad, over the plan saved (and its range count checked) at the group's
+        first micro-step.  Data parallel: each owner's live bucket of the accumulator is all-reduced first, ONCE, and the norm is that
+        of the reduced sums (dep_grad_sqnorm after the join), which every rank holds alike."""
         self._step += 1
         self._pending = 0
-        plan = self._accum_plan
-        spans = [r for _, rs in plan for r in rs]
         if parallel.transport() != 'none':
-            done = set()
-            for owner, _, _ in spans:
-                if id(owner) not in done:
-                    done.add(id(owner))
-                    parallel.all_reduce_accumulated(owner, self._accum[id(owner)][:owner._n_live])
+            for owner in {id(o): o for o, _, _ in self._spans(self._accum_plan, None)}.values():
+                parallel.all_reduce_accumulated(owner, self._accum[id(owner)][:owner._n_live])
         L.order_note('optimizer step')
-        clip = self.max_grad_norm is not None or self.skip_nonfinite
-        if clip:
-            partials, clip_out, stats = self._clip_buffers(spans[0][0]._flat_grad.device)
-            if not have_partials:
-                L.grad_sqnorm([self._accum[id(o)][s:e] for o, s, e in spans], partials)
-            max_norm = 0.0 if self.max_grad_norm is None else self.max_grad_norm
-        first = True
-        for g, rs in plan:
-            b1, b2 = g['betas']
-            for owner, s, e in rs:
-                m, v = self._state_of(owner)
-                acc = self._accum[id(owner)]
-                if clip:
-                    L.adam_step_clipped(owner._flat[s:e], acc[s:e], m[s:e], v[s:e], g['lr'], b1, b2, g['eps'], g['weight_decay'],
-                                        self.decoupled, self._step, partials, max_norm, self.skip_nonfinite,
-                                        clip_out if first else None, stats if first else None)
-                else:
-                    L.adam_step(owner._flat[s:e], acc[s:e], m[s:e], v[s:e], g['lr'], b1, b2, g['eps'], g['weight_decay'],
-                                self.decoupled, self._step)
-                first = False
+        self._update(self._accum_plan, lambda owner: self._accum[id(owner)], None, have_partials)
 
     def grad_stats(self):
         """The record of the clipped steps so far, read from the device: the ONLY host synchronisation of the clipping path.

@@ -20,9 +20,13 @@ loss is a batch mean, so the path shards naturally:
     accumulator is reduced once per update (`all_reduce_accumulated`), and every criterion divides by the rows of the whole
     accumulated global batch (`set_accumulated_count`).
 """
+import contextlib
+import ctypes as C
 import os
 
 import torch
+
+from . import _lib as L
 
 _state = {'init': False}
 
@@ -128,7 +132,6 @@ def all_reduce_grads(model):
     """SUM all-reduce of the model's single contiguous live-gradient bucket (torch.distributed transport)."""
     d = _dist()
     if d and model._grad_ready:
-        from . import _lib as L
         L.order_note('C torch.distributed all_reduce of the live bucket (on the compute stream)')
         d.all_reduce(model.live_grad_bucket(), op=d.ReduceOp.SUM)
 
@@ -156,8 +159,6 @@ def init_native_comm(force_single=False):
     No rank may enter a collective the others will not reach: the ranks first agree that librccl resolves
     everywhere (dep_comm_available + MIN), rank 0's id travels WITH a status byte, and after ncclCommInitRank they agree
     again.  Any disagreement -> None on EVERY rank (the torch.distributed all-reduce of the whole bucket is used instead)."""
-    import ctypes as C
-    from . import _lib as L
     if _native['comm'] is not None:
         return _native['comm']
     d = _dist()
@@ -203,7 +204,6 @@ def native_comm():
 
 
 def destroy_native_comm():
-    from . import _lib as L
     if _native['comm'] is not None:
         torch.cuda.synchronize()
         L.load().dep_comm_destroy(_native['comm'])
@@ -230,28 +230,35 @@ def defers_grad_sync(model):
     return bool(getattr(model, '_defer_grad_sync', False))
 
 
+@contextlib.contextmanager
+def _on_comm_stream():
+    """The fork and join around every native collective: the communication stream waits for an event of the compute stream, the body
+    enqueues on the yielded stream handle, and the compute stream waits for an event behind it (the join note of the order log)."""
+    cs = _native['stream']
+    cur = torch.cuda.current_stream()
+    ev = torch.cuda.Event(); ev.record(cur)
+    cs.wait_event(ev)
+    yield cs.cuda_stream
+    ev2 = torch.cuda.Event(); ev2.record(cs)
+    cur.wait_event(ev2)
+    L.order_note('join: the compute stream waits for the communication stream')
+
+
 def all_reduce_accumulated(model, bucket):
     """The ONE gradient collective of an accumulated update: SUM all-reduce of `bucket`, the live part of the model's accumulator,
     after the group's last dep_grad_accumulate and joined before the update that follows -- nothing that needs every CU is
-    launched in between.  Native communicator: on the communication stream behind an event of the compute stream, which then waits
-    for it (the order log shows `C allreduce`, then the join note); otherwise one torch.distributed all-reduce on the compute stream."""
+    launched in between.  Native communicator: on the communication stream (the order log shows `C allreduce`, then the join
+    note); otherwise one torch.distributed all-reduce on the compute stream."""
     if _comm_off[0] or bucket.numel() == 0:
         return
-    from . import _lib as L
     if _native['comm'] is None:
         d = _dist()
         if d:
             L.order_note('C torch.distributed all_reduce of the accumulated live bucket (on the compute stream)')
             d.all_reduce(bucket, op=d.ReduceOp.SUM)
         return
-    cs = _native['stream']
-    cur = torch.cuda.current_stream()
-    ev = torch.cuda.Event(); ev.record(cur)
-    cs.wait_event(ev)
-    L.check(L.load().dep_comm_allreduce(_native['comm'], bucket.data_ptr(), bucket.numel(), cs.cuda_stream), 'dep_comm_allreduce')
-    ev2 = torch.cuda.Event(); ev2.record(cs)
-    cur.wait_event(ev2)
-    L.order_note('join: the compute stream waits for the communication stream')
+    with _on_comm_stream() as stream:
+        L.check(L.load().dep_comm_allreduce(_native['comm'], bucket.data_ptr(), bucket.numel(), stream), 'dep_comm_allreduce')
 
 
 def make_grad_sync(model, in_call):
@@ -259,7 +266,6 @@ def make_grad_sync(model, in_call):
     in_call: {layer: (start, count)}."""
     if _native['comm'] is None or not in_call or _comm_off[0] or defers_grad_sync(model):
         return None
-    from . import _lib as L
     gs = L.GradSync()
     gs.comm = _native['comm']
     gs.comm_stream = _native['stream'].cuda_stream
@@ -270,32 +276,27 @@ def make_grad_sync(model, in_call):
     return gs
 
 
-def finish_grad_sync(model, in_call, post):
-    """After the model's backward: reduce what is still local and join the streams.
-    native communicator: `post` ranges (final only now) as one grouped RCCL operation on the communication stream, then the
-    compute stream waits for that stream; otherwise one torch.distributed all-reduce of the whole bucket."""
-    if _comm_off[0] or defers_grad_sync(model):
-        return
-    if _native['comm'] is None:
-        all_reduce_grads(model)
-        return
-    import ctypes as C
-    from . import _lib as L
+def _reduce_late_ranges(model, in_call, post, stream):
     layer_buckets(list(in_call.values()) + list(post), model._n_live)          # every live float is reduced exactly once
-    cs = _native['stream']
-    cur = torch.cuda.current_stream()
-    ev = torch.cuda.Event(); ev.record(cur)
-    cs.wait_event(ev)
     post = [(s, c) for s, c in post if c > 0]
     if post:
         base = model._flat_grad.data_ptr()
         ptrs = (C.c_void_p * len(post))(*[base + 4 * s for s, _ in post])
         cnts = (C.c_long * len(post))(*[c for _, c in post])
-        L.check(L.load().dep_comm_allreduce_ranges(_native['comm'], ptrs, cnts, len(post), cs.cuda_stream),
-                'dep_comm_allreduce_ranges')
-    ev2 = torch.cuda.Event(); ev2.record(cs)
-    cur.wait_event(ev2)
-    L.order_note('join: the compute stream waits for the communication stream')
+        L.check(L.load().dep_comm_allreduce_ranges(_native['comm'], ptrs, cnts, len(post), stream), 'dep_comm_allreduce_ranges')
+
+
+def finish_grad_sync(model, in_call, post):
+    """After the model's backward: reduce what is still local and join the streams.
+    native communicator: `post` ranges (final only now) as one grouped RCCL operation on the communication stream, which the
+    compute stream then waits for; otherwise one torch.distributed all-reduce of the whole bucket."""
+    if _comm_off[0] or defers_grad_sync(model):
+        return
+    if _native['comm'] is None:
+        all_reduce_grads(model)
+        return
+    with _on_comm_stream() as stream:
+        _reduce_late_ranges(model, in_call, post, stream)
 
 
 def reduce_zero_contribution(model, in_call, post):
@@ -306,17 +307,14 @@ def reduce_zero_contribution(model, in_call, post):
     if _native['comm'] is None:
         all_reduce_grads(model)
         return
-    from . import _lib as L
-    cs = _native['stream']
-    cur = torch.cuda.current_stream()
-    ev = torch.cuda.Event(); ev.record(cur)
-    cs.wait_event(ev)
-    base = model._flat_grad.data_ptr()
-    for l in sorted(in_call, reverse=True):                                    # the backward walks the layers top -> bottom
-        s, c = in_call[l]
-        if c > 0:
-            L.check(L.load().dep_comm_allreduce(_native['comm'], base + 4 * s, c, cs.cuda_stream), 'dep_comm_allreduce')
-    finish_grad_sync(model, in_call, post)
+    with _on_comm_stream() as stream:
+        base = model._flat_grad.data_ptr()
+        for l in sorted(in_call, reverse=True):                                # the backward walks the layers top -> bottom
+            s, c = in_call[l]
+            if c > 0:
+                L.check(L.load().dep_comm_allreduce(_native['comm'], base + 4 * s, c, stream), 'dep_comm_allreduce')
+        if not _comm_off[0]:
+            _reduce_late_ranges(model, in_call, post, stream)
 
 
 def broadcast_params(model, src=0):

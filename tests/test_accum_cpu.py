@@ -6,30 +6,14 @@
    which calls carry `partials`, when the step number advances, what the updates read.
 4. The data-parallel deferral flag and the declared row count.
 """
-import ctypes as C
-
 import pytest
 
 torch = pytest.importorskip('torch')
 
+from optim_rec import ERR_ARG, _Owner, _arrs, _params, lib, name_buffers, record_binding  # noqa: E402,F401 -- lib is a fixture
+
 
 # ------------------------------------------------------------------------------------------------ argument refusals
-@pytest.fixture(scope='module')
-def lib():
-    import __graft_entry__ as g
-    g.build()
-    from icassp2022_depression_amd import _lib
-    return _lib.load()
-
-
-ERR_ARG = -1
-_P = C.c_void_p
-
-
-def _arrs(ptrs, counts):
-    return (_P * len(ptrs))(*ptrs), (C.c_long * len(counts))(*counts)
-
-
 def test_grad_accumulate_refuses_bad_arguments(lib):
     ok = 0x1000                                                       # never dereferenced on the host: the checks come first
     acc, cnts = _arrs([ok], [8])
@@ -104,58 +88,14 @@ def test_train_epoch_declares_each_group_before_its_criteria_and_flushes(monkeyp
 
 
 # ------------------------------------------------------------------------------------------------ host logic, recording binding
-class _Owner:
-    def __init__(self, n, n_live):
-        self._flat = torch.zeros(n)
-        self._flat_grad = torch.zeros(n)
-        self._grad_ready = True
-        self._n_live = n_live
-
-
-def _params(nn, owner, sizes, dead=()):
-    out, off = [], 0
-    for i, n in enumerate(sizes):
-        p = nn.Parameter(f'p{i}', (n,), owner)
-        p.offset = off
-        p.live = i not in dead
-        p._grad = owner._flat_grad[off:off + n]
-        out.append(p)
-        off += (n + 3) // 4 * 4
-    return out
-
-
 @pytest.fixture()
 def rec(monkeypatch):
-    from icassp2022_depression_amd import nn
-    log, names = [], {}
-
-    class span(tuple):
-        """(buffer name, start, end) of a tensor; the name is looked up when the span is COMPARED (the accumulators get theirs only
-        after the optimizer made them)."""
-        def __new__(cls, t):
-            return super().__new__(cls, (t.untyped_storage().data_ptr(), t.storage_offset(), t.storage_offset() + t.numel()))
-
-        def __eq__(self, other):
-            return (names.get(self[0]),) + tuple(self[1:]) == tuple(other)
-
-        def __ne__(self, other):
-            return not self == other
-
-        __hash__ = tuple.__hash__
-
-    monkeypatch.setattr(nn.L, 'grad_norm_slots', lambda: 256)
-    monkeypatch.setattr(nn.L, 'adam_step', lambda p, g, m, v, *a: log.append(('adam', span(p), span(g)) + a))
-    monkeypatch.setattr(nn.L, 'grad_sqnorm', lambda ranges, partials: log.append(('sqnorm', [span(t) for t in ranges], partials)))
-    monkeypatch.setattr(nn.L, 'adam_step_clipped', lambda p, g, m, v, *a: log.append(('clipped', span(p), span(g)) + a))
-    monkeypatch.setattr(nn.L, 'grad_accumulate', lambda acc, g, scale=1.0, first=False, partials=None:
-                        log.append(('accum', [span(t) for t in acc], [span(t) for t in g], scale, first, partials)))
-    return nn, log, names
+    return record_binding(monkeypatch, adam_logs_p=True)
 
 
 def _groups(nn, names):
     a, b = _Owner(32, 20), _Owner(16, 12)
-    names[a._flat.untyped_storage().data_ptr()] = 'aP'; names[a._flat_grad.untyped_storage().data_ptr()] = 'aG'
-    names[b._flat.untyped_storage().data_ptr()] = 'bP'; names[b._flat_grad.untyped_storage().data_ptr()] = 'bG'
+    name_buffers(names, a=a, b=b)
     pa = _params(nn, a, [5, 8, 3, 6], dead=(3,))           # offsets 0, 8, 16, 20; the last one is dead (grad None)
     pb = _params(nn, b, [10])
     return [{'params': [pa[0], pa[1]], 'weight_decay': 0.0}, {'params': [pa[2], pa[3], pb[0]], 'weight_decay': 1e-5, 'lr': 5e-4}], (a, b), pa, pb

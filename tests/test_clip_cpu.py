@@ -9,12 +9,11 @@
    with max_grad_norm set there is exactly one dep_grad_sqnorm per step(), over the ranges of all groups, then one clipped update
    per range.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from clip_ref import clip_coef, clipped_adam_steps
+from optim_rec import ERR_ARG, _Owner, _arrs, _params, lib, name_buffers, record_binding  # noqa: F401 -- lib is a fixture
 
 torch = pytest.importorskip('torch')
 
@@ -67,22 +66,6 @@ def test_coefficient_formula():
 
 
 # ------------------------------------------------------------------------------------------------ argument refusals
-@pytest.fixture(scope='module')
-def lib():
-    import __graft_entry__ as g
-    g.build()
-    from icassp2022_depression_amd import _lib
-    return _lib.load()
-
-
-ERR_ARG = -1
-_P = C.c_void_p
-
-
-def _arrs(ptrs, counts):
-    return (_P * len(ptrs))(*ptrs), (C.c_long * len(counts))(*counts)
-
-
 def test_entry_points_refuse_bad_arguments(lib):
     assert lib.dep_grad_norm_slots() == 256 and lib.dep_grad_norm_chunk() > 0 and lib.dep_grad_norm_chunk() % 4 == 0
     ok = 0x1000                                                       # never dereferenced on the host: the checks come first
@@ -115,46 +98,14 @@ def test_entry_points_refuse_bad_arguments(lib):
 
 
 # ------------------------------------------------------------------------------------------------ host logic, recording binding
-class _Owner:
-    def __init__(self, n):
-        self._flat = torch.zeros(n)
-        self._flat_grad = torch.zeros(n)
-        self._grad_ready = True
-
-
-def _params(nn, owner, sizes, dead=()):
-    out, off = [], 0
-    for i, n in enumerate(sizes):
-        p = nn.Parameter(f'p{i}', (n,), owner)
-        p.offset = off
-        p.live = i not in dead
-        p._grad = owner._flat_grad[off:off + n]
-        out.append(p)
-        off += (n + 3) // 4 * 4
-    return out
-
-
 @pytest.fixture()
 def rec(monkeypatch):
-    from icassp2022_depression_amd import nn
-    log = []
-
-    def span(t, owner_of):
-        return (owner_of[t.untyped_storage().data_ptr()], t.storage_offset(), t.storage_offset() + t.numel())
-
-    owners = {}
-    monkeypatch.setattr(nn.L, 'grad_norm_slots', lambda: 256)
-    monkeypatch.setattr(nn.L, 'adam_step', lambda p, g, m, v, *a: log.append(('adam', span(g, owners)) + a))
-    monkeypatch.setattr(nn.L, 'grad_sqnorm', lambda ranges, partials: log.append(('sqnorm', [span(t, owners) for t in ranges], partials)))
-    monkeypatch.setattr(nn.L, 'adam_step_clipped', lambda p, g, m, v, *a: log.append(('clipped', span(p, owners), span(g, owners)) + a))
-    monkeypatch.setattr(nn.L, 'grad_clip_scale', lambda *a: log.append(('scale',) + a))
-    return nn, log, owners
+    return record_binding(monkeypatch, adam_logs_p=False)
 
 
 def _two_owner_groups(nn, owners):
     a, b = _Owner(32), _Owner(16)
-    owners[a._flat.untyped_storage().data_ptr()] = 'aP'; owners[a._flat_grad.untyped_storage().data_ptr()] = 'aG'
-    owners[b._flat.untyped_storage().data_ptr()] = 'bP'; owners[b._flat_grad.untyped_storage().data_ptr()] = 'bG'
+    name_buffers(owners, a=a, b=b)
     pa = _params(nn, a, [5, 8, 3, 6], dead=(3,))           # offsets 0, 8, 16, 20; the last one is dead (grad None)
     pb = _params(nn, b, [10])
     groups = [{'params': [pa[0], pa[1]], 'weight_decay': 0.0}, {'params': [pa[2], pa[3], pb[0]], 'weight_decay': 1e-5, 'lr': 5e-4}]
@@ -216,7 +167,7 @@ def test_clip_grad_norm_function_covers_the_merged_ranges(rec):
 def test_more_ranges_than_one_launch_takes_is_an_error(rec):
     nn, log, owners = rec
     o = _Owner(17 * 8)
-    owners[o._flat.untyped_storage().data_ptr()] = 'P'; owners[o._flat_grad.untyped_storage().data_ptr()] = 'G'
+    name_buffers(owners, **{'': o})
     ps = _params(nn, o, [4] * 34, dead=tuple(range(1, 34, 2)))          # 17 live tensors, none adjacent to another
     with pytest.raises(nn.L.DepError):
         nn.Adam(ps, max_grad_norm=1.0).step()

@@ -143,10 +143,13 @@ def test_clipped_update_against_numpy(decoupled, wd, max_norm):
     assert abs(co[0] - q) <= 1e-6 * q and abs(co[1] - np.sqrt(S)) <= 1e-6 * np.sqrt(S) and co[2] == 1.0 and co[3] == 0.0
 
 
-@pytest.mark.parametrize('decoupled,wd', [(True, 1e-5), (False, 1e-3)])
-@pytest.mark.parametrize('max_norm', [float('inf'), 0.0, 1e9])
-def test_coefficient_one_gives_the_plain_update_bit_for_bit(decoupled, wd, max_norm):
-    st = _state(5000, 31)
+# every size of SIZES (the plain kernel takes one element per thread, the clipped one eight: a ragged tail, one element, one element past a
+# clipped workgroup's 2048) in each of the three forms of the expression; the cases at 5000 keep the ids they always had
+@pytest.mark.parametrize('n,decoupled,wd,max_norm', [
+    pytest.param(n, decoupled, wd, max_norm, id=f'{max_norm}-{decoupled}-{wd}' + ('' if n == SIZES[0] else f'-{n}'))
+    for n in SIZES for max_norm in (float('inf'), 0.0, 1e9) for decoupled, wd in [(True, 1e-5), (False, 0.0), (False, 1e-3)]])
+def test_coefficient_one_gives_the_plain_update_bit_for_bit(n, decoupled, wd, max_norm):
+    st = _state(n, 31)
     part = torch.empty(SLOTS, dtype=torch.float64, device=DEV)
     L.grad_sqnorm([dev(st[1])], part)
     clip_out = torch.zeros(4, device=DEV)

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Per-kernel gfx950 ISA of one csrc file, at a git revision against the work tree.
 
-    tools/isa_diff.py rnn_cluster_lstm [REV] [--map 'old substring=new substring' ...]
+    tools/isa_diff.py rnn_cluster_lstm [REV] [--map 'old substring=new substring' ...] [--old-stem STEM [--only SUBSTRING]]
 
 Both sides compile with build_ext.FLAGS + --cuda-device-only -S in a temporary directory, each with the headers of its own side.
 Per kernel pair: `identical`, or the first differing lines; plus VGPRs, SGPRs, spills, LDS, scratch and kernarg size.  Own symbol,
 .LBB<n>_ function index and __hip_cuid_* are normalised.  --map renames a (demangled) revision-side kernel before pairing.
+--old-stem: the revision side is csrc/<STEM>.hip (a kernel that moved between files); --only keeps the kernels whose name has SUBSTRING.
 """
 import argparse, difflib, os, re, shutil, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,13 +38,15 @@ def kernels(tree, stem, tmp):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('stem'); ap.add_argument('rev', nargs='?', default='HEAD'); ap.add_argument('--map', action='append', default=[])
+    ap.add_argument('--old-stem'); ap.add_argument('--only', default='')
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         old = os.path.join(tmp, 'old'); os.makedirs(old)
         tar = subprocess.run(['git', '-C', ROOT, 'archive', a.rev, 'include', PKG + '/csrc'], capture_output=True, check=True).stdout
         subprocess.run(['tar', '-x', '-C', old], input=tar, check=True)
-        ko, kn = kernels(old, a.stem, tmp), kernels(ROOT, a.stem, tmp)
-    print(f'# {a.stem}.hip: {a.rev} -> work tree    ({" ".join(FLAGS)} --cuda-device-only -S)' + ''.join(f'\n# --map {m!r}' for m in a.map))
+        ko, kn = kernels(old, a.old_stem or a.stem, tmp), kernels(ROOT, a.stem, tmp)
+        ko, kn = ({k: v for k, v in d.items() if a.only in k} for d in (ko, kn))
+    print(f'# {a.old_stem or a.stem}.hip at {a.rev} -> {a.stem}.hip in the work tree' if a.old_stem else f'# {a.stem}.hip: {a.rev} -> work tree    ({" ".join(FLAGS)} --cuda-device-only -S)' + ''.join(f'\n# --map {m!r}' for m in a.map))
     for name, (body, r) in ko.items():
         new = name
         for m in a.map:
