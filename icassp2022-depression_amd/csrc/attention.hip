@@ -14,6 +14,9 @@ namespace {
 constexpr int AT = 512;          // threads per workgroup (8 waves)
 constexpr int AU = 4;            // rows in flight per thread
 constexpr int LDS_MAX = 160 * 1024;
+// CACHE while fixed + max(T, R) H 4 <= LDS_MAX with fixed = (Tp + 32) 4 in the forward and (2 Tp + 32) 4 in the backward (Tp: T rounded up to 4), so the
+// two directions change form at different T.  Last cached T, forward / backward: H = 64: 629 / 620, H = 128: 317 / 314, H = 256: 159 / 158 -- in the
+// band between them the forward caches h_t and the backward re-reads `out`.
 
 __device__ __forceinline__ float wmax(float v) {
 #pragma unroll

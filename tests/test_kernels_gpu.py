@@ -469,8 +469,9 @@ def test_rnn_generic_and_mfma_agree_on_cfg1_shape():
 
 
 # ----------------------------------------------------------------------------- attention
-# H in {64,128,256}: attention.hip (rows cached in LDS up to T H ~ 39 K floats, re-read beyond: T = 330 at H = 128, 170 at 256);
-# other widths: the first-generation kernels
+# H in {64,128,256}: attention.hip.  h_t is cached in LDS up to T = 629 / 317 / 159 in the forward and 620 / 314 / 158 in the backward (H = 64 / 128 /
+# 256) and `out` re-read beyond, so 330 and 170 below re-read in both directions; other widths: the first-generation kernels.  The borders themselves,
+# the tile edges and a softmax in which every step carries weight are in tests/test_attention_forms_gpu.py.
 @pytest.mark.parametrize('B,T,H', [(3, 6, 8), (7, 50, 128), (2, 300, 16), (5, 300, 128), (3, 330, 128), (4, 33, 64), (5, 60, 256), (6, 90, 256),
                                    (2, 170, 256), (2, 1, 128), (3, 17, 128)])
 def test_attention(B, T, H):
