@@ -196,7 +196,57 @@ def accumulation_groups(counts, k):
     return [(i, min(i + k, len(counts)), sum(counts[i:i + k])) for i in range(0, len(counts), int(k))]
 
 
-def train_epoch(model, optimizer, n_rows, batch_size, step, after_step=None):
+def class_row_weight(targets, class_weight, ignore_index=-100):
+    """Pure helper: the float64 vector train_epoch(row_weight=) takes -- class_weight[y_i] for a live row, 0 for a row whose label is
+    `ignore_index`.  Its sums are the denominators of torch's weighted-mean cross-entropy."""
+    y = np.asarray(targets).reshape(-1).astype(np.int64)
+    w = np.asarray(class_weight, dtype=np.float64).reshape(-1)
+    live = y != ignore_index
+    if live.any() and (y[live].min() < 0 or y[live].max() >= w.size):
+        bad = int(y[live].min()) if y[live].min() < 0 else int(y[live].max())
+        raise IndexError(f'Target {bad} is out of bounds for {w.size} classes')
+    out = np.zeros(y.size, dtype=np.float64)
+    out[live] = w[y[live]]
+    return out
+
+
+def balanced_class_weight(targets, num_classes, ignore_index=-100):
+    """Pure helper: n_live / (C * count_c) per class (sklearn's 'balanced' heuristic) over the rows whose label is not
+    `ignore_index`; a class without a row has no finite weight: ValueError."""
+    y = np.asarray(targets).reshape(-1).astype(np.int64)
+    y = y[y != ignore_index]
+    if y.size and (y.min() < 0 or y.max() >= num_classes):
+        raise IndexError(f'Target {int(y.min()) if y.min() < 0 else int(y.max())} is out of bounds for {num_classes} classes')
+    counts = np.bincount(y, minlength=num_classes).astype(np.float64)
+    if np.any(counts == 0):
+        raise ValueError('balanced_class_weight: no row of class(es) %s' % np.flatnonzero(counts == 0).tolist())
+    return y.size / (num_classes * counts)
+
+
+def ce_options(config, targets):
+    """The scripts' two optional config keys as keyword arguments of the CE criteria: `class_weights` (None, a list of num_classes
+    floats, or 'balanced' = balanced_class_weight of `targets`, the labels of the fold being trained AFTER augmentation: the set train()
+    iterates) and `label_smoothing` (default 0.0).  Both absent or at their defaults: {} -- the criterion built is the one it always was."""
+    cw, eps = config.get('class_weights'), float(config.get('label_smoothing', 0.0) or 0.0)
+    if cw is None and eps == 0.0:
+        return {}
+    if isinstance(cw, str):
+        if cw != 'balanced':
+            raise ValueError(f"class_weights must be None, a list of num_classes floats or 'balanced', got {cw!r}")
+        cw = balanced_class_weight(targets, config['num_classes'])
+    elif cw is not None and len(cw) != config['num_classes']:
+        raise ValueError(f"class_weights has {len(cw)} entries for {config['num_classes']} classes")
+    return {'weight': cw, 'label_smoothing': eps}
+
+
+def criterion_row_weight(criterion, targets):
+    """row_weight for train_epoch: None for a criterion without options (the loop then declares counts only), else the criterion's
+    weight of every training row in loop order."""
+    opt = getattr(criterion, 'options', None)
+    return opt.row_weight(targets) if opt is not None and opt.active else None
+
+
+def train_epoch(model, optimizer, n_rows, batch_size, step, after_step=None, row_weight=None):
     """The mini-batch loop of every script's train() (audio_gru_whole.py:161-201 of the reference), which is also the data-parallel
     protocol: per global mini-batch every rank issues the gradient ranges, then (lazily, in LossSum.item) the loss reduce; a rank
     that owns no row of a small mini-batch joins both with a zero contribution.  Returns the summed loss, read from the device
@@ -211,15 +261,31 @@ def train_epoch(model, optimizer, n_rows, batch_size, step, after_step=None):
     An optimizer built with accumulate_steps = K > 1 turns K consecutive mini-batches into one update: the rows of each group are
     declared before its criteria run (every micro-loss is then its rows' sum over the GROUP's rows, so the summed epoch loss is the
     big-batch loop's), optimizer.step() is still called per mini-batch (it accumulates, and updates on the K-th), and flush()
-    updates from a shorter last group.  Both hooks, the count and the prediction buffers stay per mini-batch."""
+    updates from a shorter last group.  Both hooks, the count and the prediction buffers stay per mini-batch.
+      row_weight: for a criterion with class weights / label smoothing / ignore_index (class_row_weight: w[y_i] per training row in
+                  loop order, 0 for an ignored row).  Its sum over each global mini-batch and over each accumulation group is declared
+                  beside the counts (parallel.set_global_weight / set_accumulated_weight): the criteria divide by those sums.  None:
+                  none of that is called."""
     total = nn.LossSum(model.device)                 # device-side sum of the step losses
-    batches = [(rank_slice(lo, hi), hi - lo) for lo, hi in minibatches(n_rows, batch_size)]
+    bounds = list(minibatches(n_rows, batch_size))
+    batches = [(rank_slice(lo, hi), hi - lo) for lo, hi in bounds]
     accum = getattr(optimizer, 'accumulate_steps', 1)
-    group_rows = {first: rows for first, _, rows in accumulation_groups([n for _, n in batches], accum)} if accum > 1 else {}
+    groups = accumulation_groups([n for _, n in batches], accum) if accum > 1 else []
+    group_rows = {first: rows for first, _, rows in groups}
+    if row_weight is not None:
+        row_weight = np.asarray(row_weight, dtype=np.float64).reshape(-1)
+        if row_weight.size != n_rows:
+            raise ValueError(f'row_weight has {row_weight.size} entries for {n_rows} training rows')
+        batch_weight = [float(row_weight[lo:hi].sum()) for lo, hi in bounds]
+        group_weight = {first: float(row_weight[bounds[first][0]:bounds[stop - 1][1]].sum()) for first, stop, _ in groups}
     for bi, ((a, b), n_glob) in enumerate(batches):
         parallel.set_global_count(n_glob)
+        if row_weight is not None:
+            parallel.set_global_weight(batch_weight[bi])
         if bi in group_rows:
             parallel.set_accumulated_count(group_rows[bi])
+            if row_weight is not None:
+                parallel.set_accumulated_weight(group_weight[bi])
         if b <= a:                                  # this rank owns no row of a small (ragged) mini-batch: zero-contribution step
             total.add(nn.empty_shard_step(model, optimizer))
             continue
@@ -234,6 +300,9 @@ def train_epoch(model, optimizer, n_rows, batch_size, step, after_step=None):
         optimizer.flush()                           # a last group shorter than K (every rank: it holds that group's collective)
         parallel.set_accumulated_count(None)
     parallel.set_global_count(None)
+    if row_weight is not None:
+        parallel.set_accumulated_weight(None)
+        parallel.set_global_weight(None)
     return total.item()
 
 

@@ -94,6 +94,9 @@ _SIGS = {
     'dep_colsum': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
     'dep_head_loss': (C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P]),
     'dep_reduce_loss': (C.c_int, [_P, C.c_int, C.c_float, _P, C.c_int, _P]),
+    'dep_head_loss_ce': (C.c_int, [C.c_int, _P, _P, _P, C.c_float, C.c_longlong, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P, _P]),
+    'dep_ce_weight_sum': (C.c_int, [_P, C.c_int, _P, C.c_longlong, C.c_int, C.c_int, _P, _P]),
+    'dep_reduce_loss_by': (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P]),
     'dep_gemm_set_xcds': (C.c_int, [C.c_int, C.c_int]),
     'dep_head_mlp_supported': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'dep_head_mlp_fwd': (C.c_int, [_P] * 9 + [C.c_int] * 4 + [C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, _P]),
@@ -311,6 +314,29 @@ def head_mlp_bwd(dz2, a0, z1, a1, W1, W2, dW1, db1, dW2, db2, dx, dz1, p, seed, 
 def reduce_loss(loss_rows, norm, loss_out, accumulate=False):
     check(load().dep_reduce_loss(_ptr(loss_rows), loss_rows.numel(), float(norm), _ptr(loss_out), int(accumulate),
                                  stream()), 'dep_reduce_loss')
+
+
+def head_loss_ce(kind, z, target, out, loss_rows, dz, norm, class_weight=None, label_smoothing=0.0, ignore_index=-100):
+    """dep_head_loss_ce: the CE kinds with class weights (C floats on the device, or None), label smoothing and ignore_index.
+    norm: a number, or a 1-element fp32 device tensor the kernel reads the denominator from (no host read)."""
+    B, Cc = z.shape
+    by_dev = torch.is_tensor(norm)
+    check(load().dep_head_loss_ce(kind, _ptr(z), _ptr(target), _ptr(class_weight), float(label_smoothing), int(ignore_index), _ptr(out),
+                                  _ptr(loss_rows), _ptr(dz), B, Cc, 0.0 if by_dev else float(norm), _ptr(f32(norm)) if by_dev else None,
+                                  stream()), 'dep_head_loss_ce')
+
+
+def ce_weight_sum(target, class_weight, ignore_index, num_classes, den_out):
+    """den_out (1 fp32 on the device) <- sum of class_weight[y] over the labels that are not ignore_index (dep_ce_weight_sum)."""
+    assert target.is_cuda and target.is_contiguous() and target.dtype in (torch.int64, torch.int32)
+    check(load().dep_ce_weight_sum(_ptr(target), int(target.dtype == torch.int64), _ptr(class_weight), int(ignore_index), target.numel(),
+                                   int(num_classes), _ptr(f32(den_out)), stream()), 'dep_ce_weight_sum')
+
+
+def reduce_loss_by(loss_rows, norm_dev, loss_out, accumulate=False):
+    """dep_reduce_loss with the divisor in a 1-element fp32 device tensor (dep_reduce_loss_by)."""
+    check(load().dep_reduce_loss_by(_ptr(loss_rows), loss_rows.numel(), _ptr(f32(norm_dev)), _ptr(loss_out), int(accumulate), stream()),
+          'dep_reduce_loss_by')
 
 
 def adam_step(p, g, m, v, lr, b1, b2, eps, wd, decoupled, step):

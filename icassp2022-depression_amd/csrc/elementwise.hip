@@ -296,6 +296,146 @@ __global__ __launch_bounds__(256) void reduce_loss_kernel(const float* __restric
     if (threadIdx.x == 0) out[0] = (accumulate ? out[0] : 0.f) + s * inv_norm;
 }
 
+// ------------------------------------------------------------------------------ CE with class weights / label smoothing / ignore_index
+// dep_head_loss_ce: torch.nn.CrossEntropyLoss(weight, ignore_index, label_smoothing, reduction='mean') on a = z (CE_LOGITS) or
+// a = softmax(z) (CE_ON_SOFTMAX), one thread per row like head_loss_kernel.  With lq = log_softmax(a), q = exp(lq), W = sum_c w_c:
+//     row   = (1-eps) w[y] (-lq[y]) + (eps/C) sum_c w_c (-lq[c])
+//     dL/da = ((1-eps) w[y] (q - onehot(y)) + (eps/C) (q W - w)) / den              (0 for a row whose label is ignore_index)
+// Every per-class array is indexed by the counters of fully unrolled loops only -- the label selects by comparison, never by address --
+// so the arrays stay in VGPRs (no scratch).  The neutral case (no weights, eps == 0) keeps head_loss_kernel's expressions in
+// head_loss_kernel's order: its out / loss_rows / dz are the same bits.
+template <bool ON_SOFTMAX>
+__global__ __launch_bounds__(128) void head_loss_ce_kernel(const float* __restrict__ z, const void* __restrict__ target, int wide,
+                                                           const float* __restrict__ cw, float eps, long long ignore_index,
+                                                           float* __restrict__ out, float* __restrict__ loss_rows,
+                                                           float* __restrict__ dz, int B, int C, float inv_norm,
+                                                           const float* __restrict__ norm_dev) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const float* zr = z + (size_t)b * C;
+    float zc[MAXC], v[MAXC];
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) zc[c] = c < C ? zr[c] : 0.f;
+    float mx = zc[0];
+#pragma unroll
+    for (int c = 1; c < MAXC; ++c) if (c < C) mx = fmaxf(mx, zc[c]);
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) if (c < C) { v[c] = expf(zc[c] - mx); s += v[c]; } else v[c] = 0.f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) if (c < C) { v[c] /= s; if (out) out[(size_t)b * C + c] = v[c]; }   // softmax(z)
+    if (!target) return;
+    const long long y = wide ? ((const long long*)target)[b] : (long long)((const int*)target)[b];
+    if (y == ignore_index) {                                     // an ignored row: no loss, no gradient (exact zeros)
+        if (loss_rows) loss_rows[b] = 0.f;
+        if (dz) {
+#pragma unroll
+            for (int c = 0; c < MAXC; ++c) if (c < C) dz[(size_t)b * C + c] = 0.f;
+        }
+        return;
+    }
+    if (norm_dev) inv_norm = 1.0f / norm_dev[0];
+    // a = z or softmax(z): a - max(a) in d[], exp of it in e[], its sum in sa
+    float d[MAXC], e[MAXC];
+    float sa;
+    if (ON_SOFTMAX) {
+        float pm = v[0];
+#pragma unroll
+        for (int c = 1; c < MAXC; ++c) if (c < C) pm = fmaxf(pm, v[c]);
+        sa = 0.f;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) if (c < C) { d[c] = v[c] - pm; e[c] = expf(v[c] - pm); sa += e[c]; } else { d[c] = 0.f; e[c] = 0.f; }
+    } else {
+        sa = s;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) { d[c] = zc[c] - mx; e[c] = 0.f; }
+    }
+    const float lse = logf(sa);
+    float g[MAXC];
+    if (!cw && eps == 0.f) {                                     // neutral options: head_loss_kernel's own arithmetic
+        float dy = 0.f;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) if (c == y) dy = d[c];
+        if (loss_rows) loss_rows[b] = -(dy - lse);
+        if (!dz) return;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) g[c] = ((ON_SOFTMAX ? e[c] / sa : v[c]) - (c == y ? 1.f : 0.f)) * inv_norm;
+    } else {
+        const bool ok = y >= 0 && y < C;                         // a label outside [0, C) is the caller's error: NaN, never an access
+        const float wy = !ok ? NAN : (cw ? cw[y] : 1.f);
+        const float keep = (1.0f - eps) * wy, spread = eps / (float)C;
+        float W = 0.f, nll = 0.f, smooth = 0.f;
+        float w[MAXC];
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) {
+            w[c] = c < C ? (cw ? cw[c] : 1.f) : 0.f;
+            if (c < C) {
+                const float nl = lse - d[c];                     // -lq[c] >= 0
+                W += w[c];
+                smooth = fmaf(w[c], nl, smooth);
+                if (c == y) nll = nl;
+            }
+        }
+        if (loss_rows) loss_rows[b] = keep * nll + spread * smooth;
+        if (!dz) return;
+        // q - onehot(y) without the cancellation of q[y] - 1 on a confident row: q[y] - 1 = -(sum of the other q)
+        float rest = 0.f;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) if (c < C && c != y) rest += ON_SOFTMAX ? e[c] / sa : v[c];
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) {
+            const float q = ON_SOFTMAX ? e[c] / sa : v[c];
+            g[c] = (keep * (c == y ? -rest : q) + spread * (q * W - w[c])) * inv_norm;
+        }
+        if (ON_SOFTMAX) {                                        // dz = p (g - <g, p>), as sum_k p_k (g_c - g_k): no cancellation against the dot
+#pragma unroll
+            for (int c = 0; c < MAXC; ++c) {
+                if (c < C) {
+                    float acc = 0.f;
+#pragma unroll
+                    for (int k = 0; k < MAXC; ++k) if (k < C) acc = fmaf(v[k], g[c] - g[k], acc);
+                    dz[(size_t)b * C + c] = v[c] * acc;
+                }
+            }
+            return;
+        }
+    }
+    if (ON_SOFTMAX) {                                            // through the first softmax: dz = p (g - <g, p>)
+        float dot = 0.f;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) if (c < C) dot = fmaf(g[c], v[c], dot);
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) if (c < C) dz[(size_t)b * C + c] = v[c] * (g[c] - dot);
+    } else {
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c) if (c < C) dz[(size_t)b * C + c] = g[c];
+    }
+}
+
+// den = sum_i [y_i != ignore_index] w[y_i] into one device float: one block, fixed order (dep_ce_weight_sum)
+__global__ __launch_bounds__(256) void ce_weight_sum_kernel(const void* __restrict__ target, int wide, const float* __restrict__ cw,
+                                                            long long ignore_index, int B, int C, float* __restrict__ den) {
+    __shared__ float red[16];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) {
+        const long long y = wide ? ((const long long*)target)[i] : (long long)((const int*)target)[i];
+        if (y == ignore_index) continue;
+        s += (y >= 0 && y < C) ? (cw ? cw[y] : 1.f) : NAN;
+    }
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) den[0] = s;
+}
+
+// reduce_loss_kernel with the divisor read from the device (dep_reduce_loss_by)
+__global__ __launch_bounds__(256) void reduce_loss_by_kernel(const float* __restrict__ rows, int B, const float* __restrict__ norm_dev,
+                                                             float* out, int accumulate) {
+    __shared__ float red[16];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) s += rows[i];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) out[0] = (accumulate ? out[0] : 0.f) + s * (1.0f / norm_dev[0]);
+}
+
 __global__ void fill_kernel(float* p, long n, float v) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
@@ -583,6 +723,39 @@ extern "C" int dep_head_loss(int kind, const float* z, const void* target, float
 extern "C" int dep_reduce_loss(const float* loss_rows, int B, float norm, float* loss_out, int accumulate, void* stream) {
     DEP_CHECK_ARG(loss_rows && loss_out && B > 0 && norm > 0.f);
     DEP_LAUNCH(reduce_loss_kernel, dim3(1), dim3(256), 0, S_, loss_rows, B, 1.0f / norm, loss_out, accumulate);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+extern "C" int dep_head_loss_ce(int kind, const float* z, const void* target, const float* class_weight, float label_smoothing,
+                                long long ignore_index, float* out, float* loss_rows, float* dz, int B, int C, float norm,
+                                const float* norm_dev, void* stream) {
+    const int k = kind & ~DEP_LOSS_LABELS_I64;
+    DEP_CHECK_ARG(k == DEP_LOSS_CE_ON_SOFTMAX || k == DEP_LOSS_CE_LOGITS);
+    DEP_CHECK_ARG(z && B > 0 && C > 0 && C <= MAXC);
+    DEP_CHECK_ARG(label_smoothing >= 0.f && label_smoothing < 1.f);
+    DEP_CHECK_ARG(norm_dev || norm > 0.f);
+    DEP_CHECK_ARG(target || (!dz && !loss_rows));
+    const int wide = (kind & DEP_LOSS_LABELS_I64) ? 1 : 0;
+    const float inv_norm = norm_dev ? 0.f : 1.0f / norm;
+    if (k == DEP_LOSS_CE_ON_SOFTMAX)
+        DEP_LAUNCH(head_loss_ce_kernel<true>, dim3(nblk(B, 128)), dim3(128), 0, S_, z, target, wide, class_weight, label_smoothing,
+                   ignore_index, out, loss_rows, dz, B, C, inv_norm, norm_dev);
+    else
+        DEP_LAUNCH(head_loss_ce_kernel<false>, dim3(nblk(B, 128)), dim3(128), 0, S_, z, target, wide, class_weight, label_smoothing,
+                   ignore_index, out, loss_rows, dz, B, C, inv_norm, norm_dev);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+extern "C" int dep_ce_weight_sum(const void* target, int labels_i64, const float* class_weight, long long ignore_index, int B, int C,
+                                 float* den_out, void* stream) {
+    DEP_CHECK_ARG(target && den_out && B > 0 && C > 0 && C <= MAXC);
+    DEP_LAUNCH(ce_weight_sum_kernel, dim3(1), dim3(256), 0, S_, target, labels_i64 ? 1 : 0, class_weight, ignore_index, B, C, den_out);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+extern "C" int dep_reduce_loss_by(const float* loss_rows, int B, const float* norm_dev, float* loss_out, int accumulate, void* stream) {
+    DEP_CHECK_ARG(loss_rows && loss_out && norm_dev && B > 0);
+    DEP_LAUNCH(reduce_loss_by_kernel, dim3(1), dim3(256), 0, S_, loss_rows, B, norm_dev, loss_out, accumulate);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }

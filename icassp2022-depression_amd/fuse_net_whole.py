@@ -78,8 +78,14 @@ class fusion_net(models.FusionNet):
 class MyLoss(models.MyLoss):
     """CE(text half) + CE(audio half) on the split fc_final weight (reference lines 376-395)."""
 
-    def __init__(self):
-        super().__init__('clf')
+    def __init__(self, weight=None, ignore_index=-100, label_smoothing=0.0, reduction='mean'):
+        super().__init__('clf', weight, ignore_index, label_smoothing, reduction)
+
+
+def make_criterion(train_idxs):
+    """The fold's criterion: MyLoss() unless config['class_weights'] (None, a list of num_classes floats, or 'balanced': from the
+    labels of `train_idxs`, i.e. after the fold's augmentation) or config['label_smoothing'] asks for more."""
+    return MyLoss(**_common.ce_options(config, np.asarray([fuse_targets[i] for i in train_idxs])))
 
 
 def build(seed=None):
@@ -107,7 +113,8 @@ def train(epoch, train_idxs):
         text_feature, audio_feature, output = _common.fusion_forward(model, feed.rows(a, b))
         _common.count_correct(output, Y_dev[a:b], correct_dev)
         return criterion(text_feature, audio_feature, Y_train[a:b], model), output
-    total_loss = _common.train_epoch(model, optimizer, n_train, config['batch_size'], step)
+    total_loss = _common.train_epoch(model, optimizer, n_train, config['batch_size'], step,
+                                     row_weight=_common.criterion_row_weight(criterion, Y_train))
     correct = int(parallel.all_reduce_sum(correct_dev).item())                  # one collective per epoch, on every rank
     max_train_acc = correct
     train_acc = correct
@@ -188,7 +195,7 @@ def main(idxs_paths=('train_idxs_0.63_1.npy', 'train_idxs_0.65_2.npy', 'train_id
          audio_model_paths=('BiLSTM_gru_vlad256_256_0.67_1.pt', 'BiLSTM_gru_vlad256_256_0.67_2.pt',
                             'BiLSTM_gru_vlad256_256_0.63_3.pt'), epochs=None):
     """3-fold driver (reference lines 522-603)."""
-    global max_f1, max_acc, max_train_acc
+    global max_f1, max_acc, max_train_acc, criterion
     parallel.init_from_env()
     if fuse_features is None:
         load_features()
@@ -198,6 +205,7 @@ def main(idxs_paths=('train_idxs_0.63_1.npy', 'train_idxs_0.65_2.npy', 'train_id
         train_idxs_tmp = np.load(os.path.join(prefix, 'Features/TextWhole/{}'.format(idxs_paths[fold - 1])), allow_pickle=True)
         test_idxs_tmp = list(set(list(fuse_dep_idxs) + list(fuse_non_idxs)) - set(train_idxs_tmp))
         train_idxs, test_idxs = augment_pairs(train_idxs_tmp, test_idxs_tmp)
+        criterion = make_criterion(train_idxs)
         tsd = _common.load_checkpoint_state_dict(os.path.join(prefix, 'Model/ClassificationWhole/Text', text_model_paths[fold - 1]))
         asd = _common.load_checkpoint_state_dict(os.path.join(prefix, 'Model/ClassificationWhole/Audio', audio_model_paths[fold - 1]))
         transplant(model, tsd, asd)

@@ -496,10 +496,15 @@ class FusionNet(nn.Module):
 
 class MyLoss:
     """Split-weight loss (fuse_net_whole.py:376-395 ; Regression/fuse_net.py:353-366):
-    loss(text_feature W[:, :Ht]^T, y) + loss(audio_feature W[:, Ht:]^T, y), gradient to W only."""
+    loss(text_feature W[:, :Ht]^T, y) + loss(audio_feature W[:, Ht:]^T, y), gradient to W only.
+    The classification variant takes torch.nn.CrossEntropyLoss's weight / ignore_index / label_smoothing (nn.CEOptions): both halves
+    then run dep_head_loss_ce over ONE shared denominator.  All defaults: the launches it always enqueued."""
 
-    def __init__(self, variant='clf'):
+    def __init__(self, variant='clf', weight=None, ignore_index=-100, label_smoothing=0.0, reduction='mean'):
         self.variant = variant
+        self.options = nn.CEOptions(weight, ignore_index, label_smoothing, reduction)
+        if variant != 'clf' and self.options.active:
+            raise ValueError('class weights, ignore_index and label_smoothing belong to the classification loss')
 
     def __call__(self, text_feature, audio_feature, target, model):
         Wp = model._params['fc_final.0.weight']
@@ -512,7 +517,11 @@ class MyLoss:
         zt = torch.empty(B, Cc, dtype=torch.float32, device=dev); za = torch.empty_like(zt)
         L.gemm(0, 1, B, Cc, Ht, text_feature, Ht, W, D, zt, Cc)
         L.gemm(0, 1, B, Cc, Ha, audio_feature, Ha, W[:, Ht:], D, za, Cc)
-        if self.variant == 'clf':
+        opt = self.options if self.options.active else None
+        if opt is not None:
+            t, wide, t_host = opt.labels(target, Cc, dev)
+            kind = L.LOSS_CE_LOGITS | wide
+        elif self.variant == 'clf':
             t = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target)
             nn._check_labels(t, Cc)
             kind = L.LOSS_CE_LOGITS; norm_local = B; per_row = 1
@@ -524,13 +533,18 @@ class MyLoss:
             t = torch.as_tensor(np.asarray(target, dtype=np.float32) if not torch.is_tensor(target) else target)
             t = t.to(device=dev, dtype=torch.float32).contiguous().view(B, Cc)
             kind = L.LOSS_SMOOTHL1; norm_local = B * Cc; per_row = Cc
-        norm = parallel.loss_count(B, per_row) if train else norm_local
         rows = torch.empty(B, dtype=torch.float32, device=dev)
         val = torch.empty(1, dtype=torch.float32, device=dev)                       # overwritten by the first dep_reduce_loss
         dzt = torch.empty_like(zt) if train else None
         dza = torch.empty_like(za) if train else None
-        L.head_loss(kind, zt, t, None, rows, dzt, norm); L.reduce_loss(rows, norm, val)
-        L.head_loss(kind, za, t, None, rows, dza, norm); L.reduce_loss(rows, norm, val, accumulate=True)
+        if opt is not None:
+            norm = opt.denominator(t, t_host, Cc, train)                            # one denominator for both halves
+            opt.head_loss(kind, zt, t, rows, dzt, norm); opt.reduce(rows, norm, val)
+            opt.head_loss(kind, za, t, rows, dza, norm); opt.reduce(rows, norm, val, accumulate=True)
+        else:
+            norm = parallel.loss_count(B, per_row) if train else norm_local
+            L.head_loss(kind, zt, t, None, rows, dzt, norm); L.reduce_loss(rows, norm, val)
+            L.head_loss(kind, za, t, None, rows, dza, norm); L.reduce_loss(rows, norm, val, accumulate=True)
 
         def bw():
             g = Wp._grad
@@ -538,5 +552,7 @@ class MyLoss:
             L.gemm(1, 0, Cc, Ha, B, dza, Cc, audio_feature, Ha, g[:, Ht:], D)      # dW[:, Ht:] = dza^T audio
             model._grad_ready = True
             parallel.finish_grad_sync(model, *model.sync_plan())
-        return nn.Loss(val, bw if train else None, reduce=train and parallel.world_size() > 1,
+        loss = nn.Loss(val, bw if train else None, reduce=train and parallel.world_size() > 1,
                        health=getattr(model, 'check_health', None))
+        loss.dz_halves = (dzt, dza)             # dLoss/dz of the text and the audio half (None under evaluate())
+        return loss

@@ -293,13 +293,98 @@ class LossSum:
         return v
 
 
-def _check_labels(t, num_classes):
+def _check_labels(t, num_classes, ignore_index=None):
     """torch's CrossEntropyLoss raises on a class index outside [0, C); the loss kernel indexes with the label, so the
-    range is validated here, on the host copy the training loops hand over (device-resident labels are the caller's)."""
+    range is validated here, on the host copy the training loops hand over (device-resident labels are the caller's).
+    ignore_index: labels equal to it are exempt (a criterion that ignores rows)."""
     if not t.is_cuda and t.numel() > 0:
+        if ignore_index is not None:
+            t = t[t != ignore_index]
+            if t.numel() == 0:
+                return
         lo, hi = int(t.min()), int(t.max())
         if lo < 0 or hi >= num_classes:
             raise IndexError(f'Target {lo if lo < 0 else hi} is out of bounds for {num_classes} classes')
+
+
+class CEOptions:
+    """torch.nn.CrossEntropyLoss's `weight`, `ignore_index` and `label_smoothing` (reduction 'mean') for the fused CE criteria
+    (CrossEntropyLoss below, models.MyLoss): validation, the device copy of the weights -- uploaded once, here -- and the choice of
+    the denominator sum_i live_i w[y_i] that torch's weighted mean divides by."""
+
+    def __init__(self, weight=None, ignore_index=-100, label_smoothing=0.0, reduction='mean'):
+        if reduction != 'mean':
+            raise ValueError(f"only reduction='mean' is implemented, got {reduction!r}")
+        eps = float(label_smoothing)
+        if not 0.0 <= eps < 1.0:
+            raise ValueError(f'label_smoothing must be in [0, 1), got {label_smoothing!r}')
+        if isinstance(ignore_index, bool) or not isinstance(ignore_index, (int, np.integer)):
+            raise ValueError(f'ignore_index must be an integer, got {ignore_index!r}')
+        self.label_smoothing = eps
+        self.ignore_index = int(ignore_index)
+        self.weight = None                  # host float64 copy (what row weights and host denominators are made from)
+        self.weight_dev = None
+        if weight is not None:
+            w = np.asarray(weight.detach().cpu().numpy() if torch.is_tensor(weight) else weight, dtype=np.float64).reshape(-1)
+            if w.size == 0 or not np.all(np.isfinite(w)) or np.any(w < 0):
+                raise ValueError('weight must be a non-empty vector of finite, non-negative class weights')
+            self.weight = w
+            self.weight_dev = torch.from_numpy(w.astype(np.float32)).to(_device())
+        self.active = self.weight is not None or eps != 0.0 or self.ignore_index != -100
+
+    def row_weight(self, targets):
+        """Host vector for _common.train_epoch(row_weight=): w[y_i] per row, 0 for an ignored one."""
+        from ._common import class_row_weight
+        t = np.asarray(targets.cpu().numpy() if torch.is_tensor(targets) else targets).reshape(-1)
+        w = self.weight
+        if w is None:
+            live = t[t != self.ignore_index]
+            w = np.ones(int(live.max()) + 1 if live.size else 1)
+        return class_row_weight(t, w, self.ignore_index)
+
+    def labels(self, target, num_classes, dev):
+        """(device labels, LOSS_LABELS_I64 or 0, host labels or None) of a criterion call."""
+        if self.weight is not None and self.weight.size != num_classes:
+            raise ValueError(f'weight has {self.weight.size} entries, the model has {num_classes} classes')
+        t = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target).reshape(-1)
+        _check_labels(t, num_classes, self.ignore_index)
+        host = None if t.is_cuda else t
+        if t.dtype == torch.int64:
+            return t.to(device=dev).contiguous(), L.LOSS_LABELS_I64, host
+        return t.to(device=dev, dtype=torch.int32).contiguous(), 0, host
+
+    def denominator(self, t_dev, t_host, num_classes, train):
+        """What the loss and dz are divided by: a declared accumulated weight, else (more than one rank) a declared global weight,
+        else the batch's own -- a number summed in float64 from host labels, or a device scalar filled by dep_ce_weight_sum from
+        device-resident ones (one launch more, no host read).  evaluate() (train False) always takes the batch's own."""
+        if train:
+            w = parallel.loss_weight()
+            if w is not None:
+                return w
+            if parallel.world_size() > 1:
+                raise L.DepError('a criterion with class weights / label smoothing / ignore_index under data parallelism needs the global '
+                                 "mini-batch's denominator: declare it with parallel.set_global_weight (or pass row_weight= to "
+                                 '_common.train_epoch)')
+        if t_host is not None:
+            y = t_host.numpy().astype(np.int64)
+            live = y != self.ignore_index
+            den = float(np.float32(live.sum() if self.weight is None else self.weight[y[live]].sum()))
+            if den > 0.0:
+                return den
+            return torch.full((1,), den, dtype=torch.float32, device=t_dev.device)    # no live row: NaN, as in torch (the host `norm` must be > 0)
+        den = torch.empty(1, dtype=torch.float32, device=t_dev.device)
+        L.ce_weight_sum(t_dev, self.weight_dev, self.ignore_index, num_classes, den)
+        return den
+
+    def head_loss(self, kind, z, t_dev, rows, dz, norm):
+        L.head_loss_ce(kind, z, t_dev, None, rows, dz, norm, self.weight_dev, self.label_smoothing, self.ignore_index)
+
+    @staticmethod
+    def reduce(rows, norm, val, accumulate=False):
+        if torch.is_tensor(norm):
+            L.reduce_loss_by(rows, norm, val, accumulate)
+        else:
+            L.reduce_loss(rows, norm, val, accumulate)
 
 
 class _HeadLoss:
@@ -339,9 +424,34 @@ class _HeadLoss:
 
 
 class CrossEntropyLoss(_HeadLoss):
-    """nn.CrossEntropyLoss on the model's Softmax output (audio_gru_whole.py:308)."""
+    """nn.CrossEntropyLoss on the model's Softmax output (audio_gru_whole.py:308), with torch's `weight`, `ignore_index` and
+    `label_smoothing` (reduction 'mean').  All defaults: the call is _HeadLoss's -- dep_head_loss + dep_reduce_loss, the launches it
+    always enqueued, and a label -100 is out of range as it always was.  Any option set: dep_head_loss_ce, divided by
+    sum_i live_i w[y_i] (CEOptions.denominator); rows whose label is ignore_index then count for nothing."""
     kind = L.LOSS_CE_ON_SOFTMAX
     target_dtype = 'int'
+
+    def __init__(self, weight=None, ignore_index=-100, label_smoothing=0.0, reduction='mean'):
+        self.options = CEOptions(weight, ignore_index, label_smoothing, reduction)
+
+    def __call__(self, output, target):
+        opt = self.options
+        if not opt.active:
+            return super().__call__(output, target)
+        owner = output._owner
+        z = output._z
+        B, Cc = z.shape
+        dev = z.device
+        t, wide, t_host = opt.labels(target, Cc, dev)
+        train = owner is not None and owner.training
+        norm = opt.denominator(t, t_host, Cc, train)
+        rows = torch.empty(B, dtype=torch.float32, device=dev)
+        dz = torch.empty_like(z) if train else None
+        opt.head_loss(self.kind | wide, z, t, rows, dz, norm)
+        val = torch.empty(1, dtype=torch.float32, device=dev)         # the reduce overwrites it
+        opt.reduce(rows, norm, val)
+        return Loss(val, (lambda: owner.backward(dz)) if train else None, reduce=train and parallel.world_size() > 1,
+                    health=getattr(owner, 'check_health', None), dz=dz)
 
 
 class L1Loss(_HeadLoss):

@@ -121,6 +121,32 @@ def loss_count(rows, per_row=1):
     return global_count(rows * per_row)
 
 
+_global_weight = [None]
+_accum_weight = [None]
+
+
+def set_global_weight(w):
+    """The weighted counterpart of set_global_count: sum of w[y_i] over the live rows of the GLOBAL mini-batch, which a criterion with
+    class weights / ignore_index divides by under data parallelism (torch's weighted mean).  None clears it."""
+    _global_weight[0] = None if w is None else float(w)
+
+
+def set_accumulated_weight(w):
+    """The weighted counterpart of set_accumulated_count: sum of w[y_i] over the live rows of the WHOLE accumulated global batch.
+    None clears it."""
+    _accum_weight[0] = None if w is None else float(w)
+
+
+def loss_weight():
+    """The declared denominator of a weighted criterion: the accumulated weight when one is set, else -- on more than one rank --
+    the global weight, else None (one rank, nothing declared: the criterion sums its own batch's)."""
+    if _accum_weight[0] is not None:
+        return _accum_weight[0]
+    if world_size() > 1:
+        return _global_weight[0]
+    return None
+
+
 def all_reduce_sum(t):
     d = _dist()
     if d:

@@ -76,7 +76,8 @@ def train(epoch, train_idxs):
         output = model(feed.rows(a, b, then=then))
         _common.count_correct(output, y, correct_dev)          # arg-max, comparison and running count: one launch
         return criterion(output, y), output
-    total_loss = _common.train_epoch(model, optimizer, n_train, config['batch_size'], step)
+    total_loss = _common.train_epoch(model, optimizer, n_train, config['batch_size'], step,
+                                     row_weight=_common.criterion_row_weight(criterion, text_targets[train_idxs]))
     correct = int(parallel.all_reduce_sum(correct_dev).item())                  # one collective per epoch, on every rank
     train_acc = correct
     if parallel.rank() == 0:
@@ -104,6 +105,12 @@ def evaluate(model, test_idxs, fold, train_idxs):
         print('model saved: f1: {}\tacc: {}'.format(max_f1, max_acc))
         print('*' * 64)
     return total_loss
+
+
+def make_criterion(train_idxs):
+    """The fold's criterion: nn.CrossEntropyLoss() unless config['class_weights'] (None, a list of num_classes floats, or 'balanced':
+    from the labels of `train_idxs`, i.e. after the fold's augmentation) or config['label_smoothing'] asks for more."""
+    return nn.CrossEntropyLoss(**_common.ce_options(config, text_targets[train_idxs]))
 
 
 def get_param_group(model):
@@ -141,7 +148,7 @@ def main(fold_files=('train_idxs_0.63_1.npy', 'train_idxs_0.60_2.npy', 'train_id
         parallel.broadcast_params(model)
         optimizer = nn.AdamW(get_param_group(model), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'),
                              accumulate_steps=config.get('accum_steps', 1))
-        criterion = nn.CrossEntropyLoss()
+        criterion = make_criterion(train_idxs)
         max_f1 = max_acc = max_rec = max_prec = -1
         train_acc = -1
         for ep in range(1, config['epochs'] if epochs is None else epochs):

@@ -373,6 +373,27 @@ int dep_head_loss(int kind, const float* z, const void* target, float* out, floa
                   float* dz, int B, int C, float norm, void* stream);
 /* loss = sum(loss_rows[0..B)) / norm, deterministic single-block tree; result on device. */
 int dep_reduce_loss(const float* loss_rows, int B, float norm, float* loss_out, int accumulate, void* stream);
+/* dep_head_loss for the two CE kinds (with or without DEP_LOSS_LABELS_I64) with torch.nn.CrossEntropyLoss's options, reduction
+ * 'mean'.  a = z (CE_LOGITS) or softmax(z) (CE_ON_SOFTMAX), lq = log_softmax(a), q = exp(lq), w = class_weight (C floats on the
+ * device; NULL = ones), W = sum_c w_c, eps = label_smoothing; a row is live when its label != ignore_index:
+ *     loss_rows[i] = live_i [ (1-eps) w[y_i] (-lq[i,y_i]) + (eps/C) sum_c w_c (-lq[i,c]) ]
+ *     dL/da        = live_i [ (1-eps) w[y_i] (q - onehot(y_i)) + (eps/C) (q W - w) ] / den ,   dz = dL/da through the first softmax
+ * den is `norm`, or *norm_dev when norm_dev != NULL (a device float, e.g. dep_ce_weight_sum's: no host read).  For torch's mean it
+ * is sum_i live_i w[y_i] over the WHOLE global / accumulated batch, so that shards and micro-batches sum to the big batch's
+ * gradient.  An ignored row still writes `out`; its loss_rows entry and its dz row are exactly 0.  den == 0 (no live row) gives
+ * NaN, as in torch.  One thread per row, the per-class values in registers; one launch.
+ * With class_weight == NULL, label_smoothing == 0 and no row ignored, out / loss_rows / dz are bit-identical to dep_head_loss.
+ * DEP_ERR_ARG, before anything is launched: any other kind, C > 16, label_smoothing outside [0, 1), z == NULL, norm <= 0 with
+ * norm_dev == NULL.  A label outside [0, C) that is not ignore_index is the caller's error (it gives NaN, never a stray access). */
+int dep_head_loss_ce(int kind, const float* z, const void* target, const float* class_weight, float label_smoothing,
+                     long long ignore_index, float* out, float* loss_rows, float* dz, int B, int C, float norm,
+                     const float* norm_dev, void* stream);
+/* den_out[0] = sum_i [target_i != ignore_index] w[target_i] over B labels (int32, or int64 when labels_i64): the denominator
+ * dep_head_loss_ce / dep_reduce_loss_by take through their device pointer.  Deterministic single-block tree; C <= 16. */
+int dep_ce_weight_sum(const void* target, int labels_i64, const float* class_weight, long long ignore_index, int B, int C,
+                      float* den_out, void* stream);
+/* dep_reduce_loss with the divisor read from a device float: loss = sum(loss_rows[0..B)) / norm_dev[0]. */
+int dep_reduce_loss_by(const float* loss_rows, int B, const float* norm_dev, float* loss_out, int accumulate, void* stream);
 
 /* The models' MLP head as three launches (one forward, two backward) instead of fifteen:
  *     [Dropout(p)] -> Linear(Hin,H1) -> ReLU -> Dropout(p) -> [Linear(H1,C)]
