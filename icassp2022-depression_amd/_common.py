@@ -246,6 +246,56 @@ def criterion_row_weight(criterion, targets):
     return opt.row_weight(targets) if opt is not None and opt.active else None
 
 
+def balanced_group_weight(groups):
+    """Pure helper: the float64 row weights of sample_weights='balanced' -- n / (G * len(group)) for every row of each of the G groups,
+    in the groups' order (the order train() iterates: the fold's depressed list, then its non-depressed list, both after
+    augmentation).  Their sum is n; an empty group has no finite weight: ValueError."""
+    sizes = [len(g) for g in groups]
+    if not sizes or min(sizes) == 0:
+        raise ValueError(f'balanced_group_weight: group sizes {sizes} (every group needs a row)')
+    n = float(sum(sizes))
+    return np.concatenate([np.full(k, n / (len(sizes) * k), dtype=np.float64) for k in sizes])
+
+
+REG_LOSSES = ('l1', 'smooth_l1', 'huber', 'mse')
+
+
+def reg_options(config):
+    """The regression scripts' optional config keys `loss` (None, 'l1', 'smooth_l1', 'huber', 'mse'), `loss_beta` and `loss_delta`
+    (default 1.0) as keyword arguments of nn.RegOptions / models.MyLoss('reg').  `loss` absent or None: {} -- the criterion built is
+    the script's own, the one it always was (a beta or delta without a loss would be ignored silently: ValueError)."""
+    loss = config.get('loss')
+    if loss is None:
+        if config.get('loss_beta') is not None or config.get('loss_delta') is not None:
+            raise ValueError("loss_beta / loss_delta need config['loss'] ('smooth_l1' / 'huber')")
+        return {}
+    if loss not in REG_LOSSES:
+        raise ValueError(f'loss must be None or one of {list(REG_LOSSES)}, got {loss!r}')
+    beta, delta = config.get('loss_beta'), config.get('loss_delta')
+    return {'loss': loss, 'beta': 1.0 if beta is None else float(beta), 'delta': 1.0 if delta is None else float(delta)}
+
+
+def reg_criterion(config, default):
+    """The fold's criterion of a regression script: default() (nn.L1Loss or nn.SmoothL1Loss, as the reference builds it) unless
+    config['loss'] names another one."""
+    o = reg_options(config)
+    if not o:
+        return default()
+    return {'l1': lambda: nn.L1Loss(), 'smooth_l1': lambda: nn.SmoothL1Loss(beta=o['beta']),
+            'huber': lambda: nn.HuberLoss(delta=o['delta']), 'mse': lambda: nn.MSELoss()}[o['loss']]()
+
+
+def sample_row_weight(config, groups):
+    """config['sample_weights'] as the row weights of one train() call, in loop order: None (absent: no weights, nothing new is
+    called) or 'balanced' = balanced_group_weight(groups)."""
+    how = config.get('sample_weights')
+    if how is None:
+        return None
+    if how != 'balanced':
+        raise ValueError(f"sample_weights must be None or 'balanced', got {how!r}")
+    return balanced_group_weight(groups)
+
+
 def train_epoch(model, optimizer, n_rows, batch_size, step, after_step=None, row_weight=None):
     """The mini-batch loop of every script's train() (audio_gru_whole.py:161-201 of the reference), which is also the data-parallel
     protocol: per global mini-batch every rank issues the gradient ranges, then (lazily, in LossSum.item) the loss reduce; a rank
@@ -263,7 +313,7 @@ def train_epoch(model, optimizer, n_rows, batch_size, step, after_step=None, row
     big-batch loop's), optimizer.step() is still called per mini-batch (it accumulates, and updates on the K-th), and flush()
     updates from a shorter last group.  Both hooks, the count and the prediction buffers stay per mini-batch.
       row_weight: for a criterion with class weights / label smoothing / ignore_index (class_row_weight: w[y_i] per training row in
-                  loop order, 0 for an ignored row).  Its sum over each global mini-batch and over each accumulation group is declared
+                  loop order, 0 for an ignored row), or a regression criterion called with row weights (those weights).  Its sum over each global mini-batch and over each accumulation group is declared
                   beside the counts (parallel.set_global_weight / set_accumulated_weight): the criteria divide by those sums.  None:
                   none of that is called."""
     total = nn.LossSum(model.device)                 # device-side sum of the step losses

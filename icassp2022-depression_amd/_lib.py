@@ -17,6 +17,7 @@ POOL_NONE, POOL_MEAN, POOL_SUM = 0, 1, 2
 RUN_EVAL, RUN_TRAIN, RUN_DROPOUT_ONLY = 0, 1, 2
 LOSS_CE_ON_SOFTMAX, LOSS_L1_RELU, LOSS_SMOOTHL1_RELU, LOSS_CE_LOGITS, LOSS_SMOOTHL1 = 0, 1, 2, 3, 4
 LOSS_LABELS_I64 = 0x100                     # OR into a CE kind: int64 labels read in place
+REG_L1, REG_SMOOTHL1, REG_HUBER, REG_MSE = 0, 1, 2, 3      # dep_head_loss_reg's forms
 SITE_FC0, SITE_FC1, SITE_FC2, SITE_FC3 = 1, 2, 3, 4
 
 
@@ -97,6 +98,8 @@ _SIGS = {
     'dep_head_loss_ce': (C.c_int, [C.c_int, _P, _P, _P, C.c_float, C.c_longlong, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P, _P]),
     'dep_ce_weight_sum': (C.c_int, [_P, C.c_int, _P, C.c_longlong, C.c_int, C.c_int, _P, _P]),
     'dep_reduce_loss_by': (C.c_int, [_P, C.c_int, _P, _P, C.c_int, _P]),
+    'dep_head_loss_reg': (C.c_int, [C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P, _P]),
+    'dep_row_weight_sum': (C.c_int, [_P, C.c_int, C.c_float, _P, _P]),
     'dep_gemm_set_xcds': (C.c_int, [C.c_int, C.c_int]),
     'dep_head_mlp_supported': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'dep_head_mlp_fwd': (C.c_int, [_P] * 9 + [C.c_int] * 4 + [C.c_float, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, _P]),
@@ -337,6 +340,23 @@ def reduce_loss_by(loss_rows, norm_dev, loss_out, accumulate=False):
     """dep_reduce_loss with the divisor in a 1-element fp32 device tensor (dep_reduce_loss_by)."""
     check(load().dep_reduce_loss_by(_ptr(loss_rows), loss_rows.numel(), _ptr(f32(norm_dev)), _ptr(loss_out), int(accumulate), stream()),
           'dep_reduce_loss_by')
+
+
+def head_loss_reg(form, relu, param, z, target, out, loss_rows, dz, norm, row_weight=None):
+    """dep_head_loss_reg: L1 / SmoothL1(beta) / Huber(delta) / MSE on z or relu(z), with per-row weights (B floats on the device, or
+    None).  norm: a number, or a 1-element fp32 device tensor the kernel reads the denominator from (no host read)."""
+    B, Cc = z.shape
+    by_dev = torch.is_tensor(norm)
+    assert row_weight is None or row_weight.numel() == B
+    check(load().dep_head_loss_reg(int(form), int(relu), float(param), _ptr(z), _ptr(target), _ptr(None if row_weight is None else f32(row_weight)),
+                                   _ptr(out), _ptr(loss_rows), _ptr(dz), B, Cc, 0.0 if by_dev else float(norm),
+                                   _ptr(f32(norm)) if by_dev else None, stream()), 'dep_head_loss_reg')
+
+
+def row_weight_sum(row_weight, scale, den_out):
+    """den_out (1 fp32 on the device) <- scale * sum of the row weights (dep_row_weight_sum)."""
+    check(load().dep_row_weight_sum(_ptr(f32(row_weight)), row_weight.numel(), float(scale), _ptr(f32(den_out)), stream()),
+          'dep_row_weight_sum')
 
 
 def adam_step(p, g, m, v, lr, b1, b2, eps, wd, decoupled, step):

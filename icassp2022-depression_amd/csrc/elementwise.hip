@@ -436,6 +436,65 @@ __global__ __launch_bounds__(256) void reduce_loss_by_kernel(const float* __rest
     if (threadIdx.x == 0) out[0] = (accumulate ? out[0] : 0.f) + s * (1.0f / norm_dev[0]);
 }
 
+// ------------------------------------------------------------------------------ regression criteria with a parameter / row weights
+// dep_head_loss_reg: L1, SmoothL1(beta), Huber(delta) and MSE on o = relu ? max(z, 0) : z, one thread per row like head_loss_kernel.
+// With d = o - target, a = |d| (torch's CPU formulas):
+//     L1        l = a                                           dl/do = sgn(d)
+//     SMOOTHL1  l = a < beta  ? 0.5 d^2 / beta : a - 0.5 beta   dl/do = a < beta  ? d / beta : sgn(d)         (beta == 0: L1)
+//     HUBER     l = a < delta ? 0.5 d^2 : delta (a - 0.5 delta) dl/do = a < delta ? d : delta sgn(d)
+//     MSE       l = d^2                                         dl/do = 2 d
+//     loss_rows[i] = w_i sum_c l ,  dz = w_i dl/do [relu: z > 0] / den        (w_i = 1 without row weights)
+// A row whose weight is exactly 0 is an ignored row: its loss_rows entry and its dz row are SELECTED to 0.0, never multiplied, so
+// that a NaN target in it stays where it is.  L1, and SMOOTHL1 with beta == 1, repeat head_loss_kernel's expressions in
+// head_loss_kernel's order (w = 1 multiplies exactly): without row weights their out / loss_rows / dz are the same bits.
+__global__ __launch_bounds__(128) void head_loss_reg_kernel(int form, int relu, float param, const float* __restrict__ z,
+                                                            const float* __restrict__ target, const float* __restrict__ rw,
+                                                            float* __restrict__ out, float* __restrict__ loss_rows,
+                                                            float* __restrict__ dz, int B, int C, float inv_norm,
+                                                            const float* __restrict__ norm_dev) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const float w = rw ? rw[b] : 1.f;
+    const bool live = w != 0.f;
+    if (norm_dev) inv_norm = 1.0f / norm_dev[0];
+    const bool l1 = form == DEP_REG_L1;
+    const bool unit = form == DEP_REG_SMOOTHL1 && param == 1.0f;          // the knee head_loss_kernel hard-codes
+    const float* zr = z + (size_t)b * C;
+    float lsum = 0.f;
+    for (int c = 0; c < C; ++c) {
+        const float zz = zr[c];
+        const float o = relu ? fmaxf(zz, 0.f) : zz;
+        if (out) out[(size_t)b * C + c] = o;
+        if (!target) continue;
+        const float d = o - target[(size_t)b * C + c];
+        const float a = fabsf(d);
+        float g;
+        if (l1) { lsum += a; g = sgn(d); }
+        else if (unit) {
+            if (a < 1.0f) { lsum += 0.5f * d * d; g = d; }
+            else { lsum += a - 0.5f; g = sgn(d); }
+        } else if (form == DEP_REG_SMOOTHL1) {
+            if (a < param) { lsum += 0.5f * d * d / param; g = d / param; }
+            else { lsum += a - 0.5f * param; g = sgn(d); }
+        } else if (form == DEP_REG_HUBER) {
+            if (a < param) { lsum += 0.5f * d * d; g = d; }
+            else { lsum += param * (a - 0.5f * param); g = param * sgn(d); }
+        } else { lsum += d * d; g = 2.0f * d; }
+        if (dz) dz[(size_t)b * C + c] = (!live || (relu && !(zz > 0.f))) ? 0.f : (w * g) * inv_norm;
+    }
+    if (target && loss_rows) loss_rows[b] = live ? w * lsum : 0.f;
+}
+
+// den = scale * sum_i row_weight[i] into one device float: one block, fixed order, the scale applied once after the tree
+// (dep_row_weight_sum)
+__global__ __launch_bounds__(256) void row_weight_sum_kernel(const float* __restrict__ rw, int B, float scale, float* __restrict__ den) {
+    __shared__ float red[16];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < B; i += 256) s += rw[i];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) den[0] = scale * s;
+}
+
 __global__ void fill_kernel(float* p, long n, float v) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
@@ -756,6 +815,25 @@ extern "C" int dep_ce_weight_sum(const void* target, int labels_i64, const float
 extern "C" int dep_reduce_loss_by(const float* loss_rows, int B, const float* norm_dev, float* loss_out, int accumulate, void* stream) {
     DEP_CHECK_ARG(loss_rows && loss_out && norm_dev && B > 0);
     DEP_LAUNCH(reduce_loss_by_kernel, dim3(1), dim3(256), 0, S_, loss_rows, B, norm_dev, loss_out, accumulate);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+extern "C" int dep_head_loss_reg(int form, int relu, float param, const float* z, const float* target, const float* row_weight,
+                                 float* out, float* loss_rows, float* dz, int B, int C, float norm, const float* norm_dev, void* stream) {
+    DEP_CHECK_ARG(form == DEP_REG_L1 || form == DEP_REG_SMOOTHL1 || form == DEP_REG_HUBER || form == DEP_REG_MSE);
+    DEP_CHECK_ARG(relu == 0 || relu == 1);
+    DEP_CHECK_ARG(param >= 0.f && (form != DEP_REG_HUBER || param > 0.f));        // NaN fails both
+    DEP_CHECK_ARG(z && B > 0 && C > 0 && C <= MAXC);
+    DEP_CHECK_ARG(norm_dev || norm > 0.f);
+    DEP_CHECK_ARG(target || (!dz && !loss_rows));
+    DEP_LAUNCH(head_loss_reg_kernel, dim3(nblk(B, 128)), dim3(128), 0, S_, form, relu, param, z, target, row_weight, out, loss_rows, dz,
+               B, C, norm_dev ? 0.f : 1.0f / norm, norm_dev);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+extern "C" int dep_row_weight_sum(const float* row_weight, int B, float scale, float* den_out, void* stream) {
+    DEP_CHECK_ARG(row_weight && den_out && B > 0 && scale > 0.f);
+    DEP_LAUNCH(row_weight_sum_kernel, dim3(1), dim3(256), 0, S_, row_weight, B, scale, den_out);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }

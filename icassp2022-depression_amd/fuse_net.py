@@ -70,8 +70,8 @@ class fusion_net(models.FusionNet):
 
 
 class MyLoss(models.MyLoss):
-    def __init__(self):
-        super().__init__('reg')
+    def __init__(self, loss='smooth_l1', beta=1.0, delta=1.0):
+        super().__init__('reg', loss=loss, beta=beta, delta=delta)
 
 
 def build(seed=None):
@@ -80,7 +80,7 @@ def build(seed=None):
                        config['num_classes'], config['audio_hidden_dims'], config['audio_embed_size'], seed=seed)
     optimizer = nn.Adam(model.parameters(), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'),
                         accumulate_steps=config.get('accum_steps', 1))
-    criterion = MyLoss()
+    criterion = MyLoss(**_common.reg_options(config))       # config['loss'] / 'loss_beta' / 'loss_delta'; absent: the reference's SmoothL1
     return model
 
 
@@ -91,14 +91,19 @@ def train(model, epoch):
     pred_dev = _common.prediction_buffer(len(idx), model.device)       # zero-filled; every rank writes its own rows
     Y_train = [fuse_targets[i] for i in idx]
     feed = _common.PairFeeder(fuse_features, idx, model.device)
+    # config['sample_weights']: None, or 'balanced' = n / (2 * size of its group) per row of the two lists iterated here
+    row_weight = _common.sample_row_weight(config, (train_dep_idxs, train_non_idxs))
+    W_dev = None if row_weight is None else _common.device_labels(row_weight, model.device)
 
     def step(a, b, then):
         text_feature, audio_feature, output = _common.fusion_forward(model, feed.rows(a, b))
-        return criterion(text_feature, audio_feature, Y_train[a:b], model), output
+        if W_dev is None:
+            return criterion(text_feature, audio_feature, Y_train[a:b], model), output
+        return criterion(text_feature, audio_feature, Y_train[a:b], model, weight=W_dev[a:b]), output
 
     def after_step(a, b, output):
         _common.store_predictions(pred_dev, a, output)     # this rank's rows; the others' stay zero until the epoch-end SUM
-    total_loss = _common.train_epoch(model, optimizer, len(idx), config['batch_size'], step, after_step)
+    total_loss = _common.train_epoch(model, optimizer, len(idx), config['batch_size'], step, after_step, row_weight=row_weight)
     train_mae, train_rmse = _common.epoch_mae_rmse(Y_train, pred_dev)
     if parallel.rank() == 0:
         print('Train Epoch: {:2d}\t Learning rate: {:.4f}\t Loss: {:.4f}\t MAE: {:.4f}\t RMSE: {:.4f}\n '

@@ -498,15 +498,23 @@ class MyLoss:
     """Split-weight loss (fuse_net_whole.py:376-395 ; Regression/fuse_net.py:353-366):
     loss(text_feature W[:, :Ht]^T, y) + loss(audio_feature W[:, Ht:]^T, y), gradient to W only.
     The classification variant takes torch.nn.CrossEntropyLoss's weight / ignore_index / label_smoothing (nn.CEOptions): both halves
-    then run dep_head_loss_ce over ONE shared denominator.  All defaults: the launches it always enqueued."""
+    then run dep_head_loss_ce over ONE shared denominator.  The regression variant takes `loss` ('l1', 'smooth_l1', 'huber', 'mse'),
+    `beta`, `delta` (nn.RegOptions) and, on its call, `weight`: B row weights; both plain halves (no ReLU) then run dep_head_loss_reg
+    over ONE shared denominator C sum_i w_i.  All defaults and no weight: the launches it always enqueued."""
 
-    def __init__(self, variant='clf', weight=None, ignore_index=-100, label_smoothing=0.0, reduction='mean'):
+    def __init__(self, variant='clf', weight=None, ignore_index=-100, label_smoothing=0.0, reduction='mean', loss='smooth_l1',
+                 beta=1.0, delta=1.0):
         self.variant = variant
         self.options = nn.CEOptions(weight, ignore_index, label_smoothing, reduction)
         if variant != 'clf' and self.options.active:
             raise ValueError('class weights, ignore_index and label_smoothing belong to the classification loss')
+        self.reg_options = nn.RegOptions(loss, beta, delta, reduction)
+        if variant == 'clf' and (loss, float(beta), float(delta)) != ('smooth_l1', 1.0, 1.0):
+            raise ValueError('loss, beta and delta belong to the regression loss')
 
-    def __call__(self, text_feature, audio_feature, target, model):
+    def __call__(self, text_feature, audio_feature, target, model, weight=None):
+        if self.variant == 'clf' and weight is not None:
+            raise ValueError('row weights belong to the regression loss (the classification loss takes class weights)')
         Wp = model._params['fc_final.0.weight']
         W = Wp.data
         Cc, D = W.shape
@@ -518,6 +526,7 @@ class MyLoss:
         L.gemm(0, 1, B, Cc, Ht, text_feature, Ht, W, D, zt, Cc)
         L.gemm(0, 1, B, Cc, Ha, audio_feature, Ha, W[:, Ht:], D, za, Cc)
         opt = self.options if self.options.active else None
+        reg = None
         if opt is not None:
             t, wide, t_host = opt.labels(target, Cc, dev)
             kind = L.LOSS_CE_LOGITS | wide
@@ -533,6 +542,8 @@ class MyLoss:
             t = torch.as_tensor(np.asarray(target, dtype=np.float32) if not torch.is_tensor(target) else target)
             t = t.to(device=dev, dtype=torch.float32).contiguous().view(B, Cc)
             kind = L.LOSS_SMOOTHL1; norm_local = B * Cc; per_row = Cc
+            if weight is not None or not (self.reg_options.neutral and self.reg_options.loss == 'smooth_l1'):
+                reg = self.reg_options
         rows = torch.empty(B, dtype=torch.float32, device=dev)
         val = torch.empty(1, dtype=torch.float32, device=dev)                       # overwritten by the first dep_reduce_loss
         dzt = torch.empty_like(zt) if train else None
@@ -541,6 +552,11 @@ class MyLoss:
             norm = opt.denominator(t, t_host, Cc, train)                            # one denominator for both halves
             opt.head_loss(kind, zt, t, rows, dzt, norm); opt.reduce(rows, norm, val)
             opt.head_loss(kind, za, t, rows, dza, norm); opt.reduce(rows, norm, val, accumulate=True)
+        elif reg is not None:
+            w_dev, w_host = reg.rows(weight, B, dev)
+            norm = reg.denominator(w_dev, w_host, B, Cc, train)                     # one denominator for both halves
+            reg.head_loss(0, zt, t, w_dev, rows, dzt, norm); reg.reduce(rows, norm, val)
+            reg.head_loss(0, za, t, w_dev, rows, dza, norm); reg.reduce(rows, norm, val, accumulate=True)
         else:
             norm = parallel.loss_count(B, per_row) if train else norm_local
             L.head_loss(kind, zt, t, None, rows, dzt, norm); L.reduce_loss(rows, norm, val)

@@ -454,16 +454,135 @@ class CrossEntropyLoss(_HeadLoss):
                     health=getattr(owner, 'check_health', None), dz=dz)
 
 
-class L1Loss(_HeadLoss):
+class RegOptions:
+    """The regression criteria's form and parameter (dep_head_loss_reg: L1, SmoothL1(beta), Huber(delta), MSE; reduction 'mean') and
+    per-row sample weights (L1Loss / SmoothL1Loss / HuberLoss / MSELoss below, models.MyLoss('reg')): validation, the weights' way to
+    the device, and the choice of the denominator C sum_i w_i that the weighted mean over elements divides by."""
+    FORMS = {'l1': L.REG_L1, 'smooth_l1': L.REG_SMOOTHL1, 'huber': L.REG_HUBER, 'mse': L.REG_MSE}
+
+    def __init__(self, loss='smooth_l1', beta=1.0, delta=1.0, reduction='mean'):
+        if reduction != 'mean':
+            raise ValueError(f"only reduction='mean' is implemented, got {reduction!r}")
+        if loss not in self.FORMS:
+            raise ValueError(f"loss must be one of {sorted(self.FORMS)}, got {loss!r}")
+        beta, delta = float(beta), float(delta)
+        if loss == 'smooth_l1' and not beta >= 0.0:
+            raise ValueError(f'SmoothL1Loss: beta must be non-negative, got {beta!r}')
+        if loss == 'huber' and not delta > 0.0:
+            raise ValueError(f'HuberLoss: delta must be positive, got {delta!r}')
+        if not np.isfinite(beta if loss == 'smooth_l1' else delta if loss == 'huber' else 0.0):
+            raise ValueError(f'{loss}: the parameter must be finite')
+        self.loss = loss
+        self.form = self.FORMS[loss]
+        self.param = beta if loss == 'smooth_l1' else delta if loss == 'huber' else 0.0
+        # the forms dep_head_loss itself computes: without row weights they keep its launches
+        self.neutral = loss == 'l1' or (loss == 'smooth_l1' and beta == 1.0)
+
+    @staticmethod
+    def rows(weight, B, dev):
+        """(device weights, host float64 copy or None) of a criterion call's `weight`: B non-negative finite floats as a sequence, an
+        array or a tensor.  A host-side vector is validated here; a device tensor is the caller's responsibility."""
+        if weight is None:
+            return None, None
+        if torch.is_tensor(weight) and weight.is_cuda:
+            w = weight.reshape(-1)
+            if w.numel() != B:
+                raise ValueError(f'weight has {w.numel()} entries for {B} rows')
+            return w.to(device=dev, dtype=torch.float32).contiguous(), None
+        w = np.asarray(weight.detach().numpy() if torch.is_tensor(weight) else weight, dtype=np.float64).reshape(-1)
+        if w.size != B:
+            raise ValueError(f'weight has {w.size} entries for {B} rows')
+        if not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError('weight must hold finite, non-negative row weights')
+        return torch.from_numpy(w.astype(np.float32)).to(dev), w
+
+    @staticmethod
+    def denominator(w_dev, w_host, B, Cc, train):
+        """What the loss and dz are divided by, in CEOptions.denominator's order: while training a declared weight (accumulated, else
+        -- more than one rank -- global) times C; else the batch's own C sum_i w_i -- a number summed in float64 from host weights, or
+        a device scalar filled by dep_row_weight_sum from device-resident ones (one launch more, no host read); without weights the
+        element count parallel.loss_count declares.  evaluate() (train False) always takes the batch's own."""
+        if train:
+            w = parallel.loss_weight()
+            if w is not None:
+                return w * Cc
+            if w_dev is not None and parallel.world_size() > 1:
+                raise L.DepError("a criterion with row weights under data parallelism needs the global mini-batch's denominator: declare "
+                                 'it with parallel.set_global_weight (or pass row_weight= to _common.train_epoch)')
+        if w_host is not None:
+            den = float(np.float32(Cc * w_host.sum()))
+            if den > 0.0:
+                return den
+            return torch.full((1,), den, dtype=torch.float32, device=w_dev.device)    # every row ignored: NaN (the host `norm` must be > 0)
+        if w_dev is not None:
+            den = torch.empty(1, dtype=torch.float32, device=w_dev.device)
+            L.row_weight_sum(w_dev, Cc, den)
+            return den
+        return parallel.loss_count(B, Cc) if train else B * Cc
+
+    def head_loss(self, relu, z, t_dev, w_dev, rows, dz, norm):
+        L.head_loss_reg(self.form, relu, self.param, z, t_dev, None, rows, dz, norm, w_dev)
+
+    reduce = staticmethod(CEOptions.reduce)
+
+
+class _RegLoss(_HeadLoss):
+    """A regression criterion on the model's ReLU output: criterion(output, target, weight=None), the weighted mean over elements
+    sum_i w_i sum_c l_ic / (C sum_i w_i) (all weights 1: torch's mean).  A row of weight 0 is an ignored row.  The forms
+    dep_head_loss computes (L1, SmoothL1 with beta 1) called without `weight` are _HeadLoss's call -- dep_head_loss + dep_reduce_loss,
+    the launches they always enqueued; everything else is dep_head_loss_reg + dep_reduce_loss / dep_reduce_loss_by."""
+    target_dtype = 'float'
+
+    def __call__(self, output, target, weight=None):
+        opt = self.reg_options
+        if weight is None and opt.neutral:
+            return super().__call__(output, target)
+        owner = output._owner
+        z = output._z
+        B, Cc = z.shape
+        dev = z.device
+        t = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target)
+        t = t.to(device=dev, dtype=torch.float32).contiguous().view(B, Cc)
+        w_dev, w_host = opt.rows(weight, B, dev)
+        train = owner is not None and owner.training
+        norm = opt.denominator(w_dev, w_host, B, Cc, train)
+        rows = torch.empty(B, dtype=torch.float32, device=dev)
+        dz = torch.empty_like(z) if train else None
+        opt.head_loss(1, z, t, w_dev, rows, dz, norm)
+        val = torch.empty(1, dtype=torch.float32, device=dev)         # the reduce overwrites it
+        opt.reduce(rows, norm, val)
+        return Loss(val, (lambda: owner.backward(dz)) if train else None, reduce=train and parallel.world_size() > 1,
+                    health=getattr(owner, 'check_health', None), dz=dz)
+
+
+class L1Loss(_RegLoss):
     """nn.L1Loss on the ReLU output (Regression/audio_bilstm_perm.py:251)."""
     kind = L.LOSS_L1_RELU
-    target_dtype = 'float'
+
+    def __init__(self, reduction='mean'):
+        self.reg_options = RegOptions('l1', reduction=reduction)
 
 
-class SmoothL1Loss(_HeadLoss):
-    """nn.SmoothL1Loss on the ReLU output (Regression/text_bilstm_perm.py:247)."""
+class SmoothL1Loss(_RegLoss):
+    """nn.SmoothL1Loss(beta) on the ReLU output (Regression/text_bilstm_perm.py:247); beta = 0 is L1, as in torch."""
     kind = L.LOSS_SMOOTHL1_RELU
-    target_dtype = 'float'
+
+    def __init__(self, beta=1.0, reduction='mean'):
+        self.reg_options = RegOptions('smooth_l1', beta=beta, reduction=reduction)
+
+
+class HuberLoss(_RegLoss):
+    """nn.HuberLoss(delta) on the ReLU output."""
+
+    def __init__(self, delta=1.0, reduction='mean'):
+        self.reg_options = RegOptions('huber', delta=delta, reduction=reduction)
+
+
+class MSELoss(_RegLoss):
+    """nn.MSELoss on the ReLU output."""
+
+    def __init__(self, reduction='mean'):
+        self.reg_options = RegOptions('mse', reduction=reduction)
 
 
 def empty_shard_step(model, optimizer):

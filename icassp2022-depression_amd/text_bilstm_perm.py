@@ -63,15 +63,20 @@ def train(epoch):
     pred_dev = _common.prediction_buffer(len(idx), model.device)       # zero-filled; every rank writes its own rows
     Y_train = text_targets[idx]
     Y_dev = _common.device_labels(Y_train, model.device)
+    # config['sample_weights']: None, or 'balanced' = n / (2 * size of its group) per row of the two lists iterated here
+    row_weight = _common.sample_row_weight(config, (train_dep_idxs, train_non_idxs))
+    W_dev = None if row_weight is None else _common.device_labels(row_weight, model.device)
     feed = _common.FeatureFeeder(text_features, idx, model.device, role='text_features')       # rows of X_train = text_features[idx], in HBM
 
     def step(a, b, then):
         output = model(feed.rows(a, b, then=then))
-        return criterion(output, Y_dev[a:b].view(-1, 1)), output
+        if W_dev is None:
+            return criterion(output, Y_dev[a:b].view(-1, 1)), output
+        return criterion(output, Y_dev[a:b].view(-1, 1), weight=W_dev[a:b]), output
 
     def after_step(a, b, output):
         _common.store_predictions(pred_dev, a, output)     # this rank's rows; the others' stay zero until the epoch-end SUM
-    total_loss = _common.train_epoch(model, optimizer, len(idx), config['batch_size'], step, after_step)
+    total_loss = _common.train_epoch(model, optimizer, len(idx), config['batch_size'], step, after_step, row_weight=row_weight)
     train_mae, train_rmse = _common.epoch_mae_rmse(Y_train, pred_dev)
     if parallel.rank() == 0:
         print('Train Epoch: {:2d}\t Learning rate: {:.4f}\t Loss: {:.4f}\t MAE: {:.4f}\t RMSE: {:.4f}\n '
@@ -125,7 +130,7 @@ def main(epochs=None):
         parallel.broadcast_params(model)
         optimizer = nn.Adam(model.parameters(), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'),
                             accumulate_steps=config.get('accum_steps', 1))
-        criterion = nn.SmoothL1Loss()
+        criterion = _common.reg_criterion(config, nn.SmoothL1Loss)       # config['loss'] / 'loss_beta' / 'loss_delta'; absent: the reference's
         min_mae = 100; min_rmse = 100
         train_mae = 100
         for ep in range(1, config['epochs'] if epochs is None else epochs):

@@ -395,6 +395,32 @@ int dep_ce_weight_sum(const void* target, int labels_i64, const float* class_wei
 /* dep_reduce_loss with the divisor read from a device float: loss = sum(loss_rows[0..B)) / norm_dev[0]. */
 int dep_reduce_loss_by(const float* loss_rows, int B, const float* norm_dev, float* loss_out, int accumulate, void* stream);
 
+enum { DEP_REG_L1 = 0, DEP_REG_SMOOTHL1 = 1, DEP_REG_HUBER = 2, DEP_REG_MSE = 3 };
+/* The regression criteria with torch's parameters and per-row sample weights, reduction 'mean': one launch, one thread per row.
+ * o = relu ? max(z, 0) : z, d = o - target, a = |d|, per element (torch's CPU formulas, the knees included):
+ *     L1                        l = a                                             dl/do = sgn(d)   (0 at d == 0)
+ *     SMOOTHL1, param = beta    l = a < beta  ? 0.5 d^2 / beta : a - 0.5 beta     dl/do = a < beta  ? d / beta : sgn(d)
+ *     HUBER,    param = delta   l = a < delta ? 0.5 d^2 : delta (a - 0.5 delta)   dl/do = a < delta ? d : delta sgn(d)
+ *     MSE                       l = d^2                                           dl/do = 2 d
+ * beta == 0 is L1, as in torch.  With w_i = row_weight[i] (B floats on the device; NULL = ones):
+ *     loss_rows[i] = w_i sum_c l[i,c]
+ *     dz[i,c]      = w_i dl/do (relu && !(z > 0) ? 0 : 1) / den
+ * den is `norm`, or *norm_dev when norm_dev != NULL (a device float, e.g. dep_row_weight_sum's: no host read).  For the weighted
+ * mean over elements it is C sum_i w_i over the WHOLE global / accumulated batch.  A row whose weight is exactly 0 is an ignored
+ * row, the counterpart of ignore_index: its loss_rows entry and its dz row are exactly 0.0 -- selected, not multiplied, whatever
+ * its target holds (NaN included) -- and its `out` row is still written.  den == 0 on the device gives NaN, as in dep_head_loss_ce.
+ * `out` is written whenever it is given; target may be NULL when dz and loss_rows are NULL (pure forward).
+ * With row_weight == NULL and norm_dev == NULL, L1 and SMOOTHL1 with param == 1 write the bits dep_head_loss writes for
+ * DEP_LOSS_L1_RELU / DEP_LOSS_SMOOTHL1_RELU (relu = 1) and DEP_LOSS_SMOOTHL1 (relu = 0).
+ * DEP_ERR_ARG, before anything is launched: an unknown form, relu not 0 or 1, param NaN or negative, param == 0 for HUBER,
+ * z == NULL, B <= 0, C <= 0 or C > 16, norm <= 0 or NaN with norm_dev == NULL, target == NULL with loss_rows or dz given. */
+int dep_head_loss_reg(int form, int relu, float param, const float* z, const float* target, const float* row_weight,
+                      float* out, float* loss_rows, float* dz, int B, int C, float norm, const float* norm_dev, void* stream);
+/* den_out[0] = scale * sum_i row_weight[i] over B floats (scale > 0; C for the mean over elements): the denominator
+ * dep_head_loss_reg / dep_reduce_loss_by take through their device pointer.  Deterministic single-block tree, the scale applied
+ * once after it. */
+int dep_row_weight_sum(const float* row_weight, int B, float scale, float* den_out, void* stream);
+
 /* The models' MLP head as three launches (one forward, two backward) instead of fifteen:
  *     [Dropout(p)] -> Linear(Hin,H1) -> ReLU -> Dropout(p) -> [Linear(H1,C)]
  * (fc_audio: Classification/audio_gru_whole.py:66-73, Regression/audio_bilstm_perm.py:60-67 -- first_dropout = 1;
