@@ -551,7 +551,8 @@ class Rnn:
         rb = self.lib.dep_rnn_reserve_bytes(C.byref(self.desc))
         wb = self.lib.dep_rnn_workspace_bytes(C.byref(self.desc))
         if rb == 0 or wb == 0:
-            raise DepError(f'bad rnn descriptor: {cell=} {B=} {T=} {F=} {H=} {L=} {dirs=}')
+            why = self.lib.dep_last_error().decode() if cell == CELL_GRU and dirs == 2 else ''      # the size query says which rule a BiGRU broke
+            raise DepError(f'bad rnn descriptor: {cell=} {B=} {T=} {F=} {H=} {L=} {dirs=} {impl=}' + (f': {why}' if 'bidirectional GRU' in why else ''))
         self.reserve = torch.empty(rb // 4, dtype=torch.float32, device=device)
         self.workspace = torch.empty(wb // 4, dtype=torch.float32, device=device)
         self.n_w = 4 * L * dirs

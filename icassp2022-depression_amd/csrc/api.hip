@@ -165,9 +165,21 @@ struct Layout {
     size_t wih_img;                  // workspace: packed W_ih of layer 1 for the fused launches
 };
 
+// A bidirectional GRU runs the tile-MFMA sweeps (gru_*_mfma<JPW, RAG, true>) and nothing else: it has no generic, cluster or fused
+// instances, so the descriptor is good exactly where those sweeps can run.
+bool bigru_ok(const dep_rnn_desc* d) { return (d->impl == 0 || d->impl == 2) && dep_sweep_use_mfma(d->H, d->impl); }
+
+// dep_last_error for a descriptor refused by the rule above (the entry points and the size queries; DEP_OK for any other descriptor)
+int bigru_refusal(const dep_rnn_desc* d, const char* who) {
+    if (!d || d->cell != DEP_CELL_GRU || d->dirs != 2 || d->H <= 0 || bigru_ok(d)) return DEP_OK;
+    dep_set_error("%s: a bidirectional GRU (dirs = 2) runs the tile-MFMA sweeps only: impl must be 0 or 2 and H a multiple of 16 those sweeps can "
+                  "tile (H / 16 = waves x tiles per wave, waves in {1, 2, 4, 8}, tiles <= 4, within the LDS bound: 16 .. 64, 96, 128, 192, 256); got H = %d, impl = %d", who, d->H, d->impl);
+    return DEP_ERR_ARG;
+}
+
 bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     if (!d || d->B <= 0 || d->T <= 0 || d->F <= 0 || d->H <= 0 || d->L < 1 || d->L > MAXL) return false;
-    if (d->cell == DEP_CELL_GRU) { if (d->dirs != 1) return false; }
+    if (d->cell == DEP_CELL_GRU) { if (d->dirs != 1 && !(d->dirs == 2 && bigru_ok(d))) return false; }
     else if (d->cell == DEP_CELL_LSTM) { if (d->dirs != 1 && d->dirs != 2) return false; }
     else return false;
     if (d->dropout_p < 0.f || d->dropout_p >= 1.f) return false;
@@ -190,7 +202,7 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
         lo.ydrop[l] = off; if (lo.drop && l < d->L - 1) off += al(lo.BT * D * H);
         for (int k = 0; k < 4; ++k) lo.sv[l][k] = NOT_KEPT;
         if (lo.keep) {
-            if (d->cell == DEP_CELL_GRU) { for (int k = 0; k < 4; ++k) { lo.sv[l][k] = off; off += al(lo.BT * H); } }
+            if (d->cell == DEP_CELL_GRU) { for (int k = 0; k < 4; ++k) { lo.sv[l][k] = off; off += al(lo.BT * D * H); } }
             else { lo.sv[l][0] = off; off += al(lo.BT * D * 4 * H); lo.sv[l][1] = off; off += al(lo.BT * D * H); lo.sv[l][2] = lo.sv[l][3] = 0; }
         }
         for (size_t dd = 0; dd < D; ++dd) {
@@ -216,7 +228,7 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     lo.nwg = dep_sweep_num_wg(d->B, d->H, d->impl);
     size_t w = 0;
     lo.gi = w; w += al(lo.BT * D * (G + (d->cell == DEP_CELL_GRU && lo.keep ? 1 : 0)) * H);     // GI (fwd) / dGI (bwd; GRU: room for the 4H-wide [dr|dz|dn|dn*r] rows)
-    lo.dghn = w; w += al(lo.BT * H);
+    lo.dghn = w; w += al(lo.BT * (d->cell == DEP_CELL_GRU ? D : 1) * H);      // GRU: (B,T,dirs*H)
     lo.dx[0] = w; w += al(lo.BT * D * H);
     lo.dx[1] = w; w += al(lo.BT * D * H);
     lo.dbpart = w; w += al((size_t)D * lo.nwg * 4 * H);
@@ -245,7 +257,8 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     }
     lo.gemm = w; lo.gemm_bytes = gb; w += al(gb / sizeof(float) + 64);
     // impl: 0 auto (cluster > tile-MFMA > generic), 1 generic, 2 tile-MFMA, 3 cluster (must be supported)
-    const bool cok = d->cell == DEP_CELL_GRU ? dep_cluster_ok(d->cell, d->H, d->B, d->dirs) : dep_cluster_lstm_ok(d->H, d->B, d->dirs);
+    // (a bidirectional GRU is never planned onto the cluster, 16-unit-member or fused kernels: dep_cluster_ok does not look at dirs)
+    const bool cok = d->cell == DEP_CELL_GRU ? d->dirs == 1 && dep_cluster_ok(d->cell, d->H, d->B, d->dirs) : dep_cluster_lstm_ok(d->H, d->B, d->dirs);
     if (d->impl == 3 && !cok) return false;
     lo.cluster = cok && (d->impl == 0 || d->impl == 3);
     lo.xbuf = w; lo.xbuf_bytes = !lo.cluster ? 0 : (d->cell == DEP_CELL_GRU ? dep_cluster_xbuf_bytes(d->cell, d->H, d->B, d->dirs)
@@ -272,7 +285,7 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
 
 extern "C" size_t dep_rnn_reserve_bytes(const dep_rnn_desc* d) {
     Layout lo;
-    if (!make_layout(d, lo)) return 0;
+    if (!make_layout(d, lo)) { (void)bigru_refusal(d, "dep_rnn_reserve_bytes"); return 0; }
     return lo.reserve_floats * sizeof(float);
 }
 extern "C" size_t dep_rnn_workspace_bytes(const dep_rnn_desc* d) {
@@ -468,6 +481,7 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
                             float* pooled, float* h_n, void* reserve, size_t reserve_bytes, void* workspace,
                             size_t workspace_bytes, void* stream) {
     Layout lo;
+    if (const int rf = bigru_refusal(d, "dep_rnn_forward")) return rf;
     DEP_CHECK_ARG(make_layout(d, lo));
     const int mode = dep_get_gemm_mode();
     if (const int rf = ragged_mode_refusal("dep_rnn_forward_varlen", lengths, mode)) return rf;
@@ -655,6 +669,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
                              void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
                              void* stream, const dep_grad_sync* gs) {
     Layout lo;
+    if (const int rf = bigru_refusal(d, "dep_rnn_backward")) return rf;
     DEP_CHECK_ARG(make_layout(d, lo));
     const int mode = dep_get_gemm_mode();
     if (const int rf = ragged_mode_refusal("dep_rnn_backward_varlen", lengths, mode)) return rf;
@@ -865,7 +880,8 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
             } else if (gru) {
                 rc = dep_gemm_internal(1, 0, 2 * H, H, BTr, dg, ldg, yl, D * H, gl[1], H, nullptr, 0.f, T, shift, gws, gwsb, ho, s);
                 if (rc) return rc;
-                rc = dep_gemm_internal(1, 0, H, H, BTr, dghn, p.dg4 ? ldg : H, yl, D * H, gl[1] + (size_t)2 * H * H, H, nullptr,
+                // (the tile sweeps' dghn is (B*T, D*H), direction dd in columns [dd*H, (dd+1)*H); D = 1 unless the GRU is bidirectional)
+                rc = dep_gemm_internal(1, 0, H, H, BTr, dghn + (size_t)dd * H, p.dg4 ? ldg : D * H, yl, D * H, gl[1] + (size_t)2 * H * H, H, nullptr,
                                        0.f, T, shift, gws, gwsb, ho, s);
                 if (rc) return rc;
             } else {

@@ -176,12 +176,12 @@ struct DepProfScope {
 // ---- internal launchers shared across translation units ---------------------------
 struct dep_sweep_args {
     int B, T, H;
-    int cell, dirs;          // GRU: dirs = 1
+    int cell, dirs;          // dirs = 2: both directions in one launch (GRU: the tile-MFMA sweeps only, rnn_sweep.hip)
     int training;
     int impl;
-    // per direction d (LSTM) / single (GRU)
+    // per direction d
     const float* w_hh[2];    // (G*H, H) row-major
-    const float* b_hh[2];    // (G*H)  GRU only (LSTM biases are folded into GI by the GEMM)
+    const float* b_hh[2];    // (G*H)  GRU only, per direction (LSTM biases are folded into GI by the GEMM)
     const float* wp[2];      // packed fragment-order copies (MFMA path), see pack kernels
     int split;               // cluster sweeps: recurrent product on the bf16 matrix cores (3-term split), wp packed to match
     // activations
@@ -189,9 +189,9 @@ struct dep_sweep_args {
     float* y;  int ldy;      // (B,T,ldy) hidden sequence; direction d writes columns [d*H,(d+1)*H)
     float* ydrop;            // same layout: dropout(y) for the next layer, or NULL
     float drop_p; uint64_t seed; uint32_t site;
-    float* pooled; float pool_scale;    // GRU top layer: (B,H) sum_t h_t * scale, or NULL
+    float* pooled; float pool_scale;    // GRU top layer: (B,dirs*H) sum_t y_t * scale, or NULL
     float* h_n;              // (dirs,B,H) final states or NULL
-    // reserve (training): GRU r,z,n,hn each (B,T,H) ; LSTM gates (B,T,dirs*4H) + c (B,T,dirs*H)
+    // reserve (training): GRU r,z,n,hn each (B,T,dirs*H) ; LSTM gates (B,T,dirs*4H) + c (B,T,dirs*H)
     float* sv0; float* sv1; float* sv2; float* sv3;
     const unsigned* only_if;  // cluster forward: run only when this device word is non-zero (fallback behind an exclusive kernel), or NULL
     int sv16;                 // GRU cluster sweeps: sv0..sv2 (r, z, n) are 16-bit fixed point (rnn_cluster_common.h), sv3 (hn) stays fp32
@@ -212,12 +212,12 @@ struct dep_sweep_bwd_args {
     const float* y; int ldy; // forward hidden sequence of this layer (h_{t-1} operand)
     const float* dy; int lddy;           // (B,T,lddy) grad of y (columns [d*H,(d+1)*H) per direction) or NULL
     float drop_p; uint64_t seed; uint32_t site;   // dropout applied to dy on load (p == 0: none)
-    const float* dpooled; float pool_scale;       // GRU top layer or NULL
+    const float* dpooled; float pool_scale;       // GRU top layer (B,dirs*H) or NULL
     const float* dh_n;       // (dirs,B,H) or NULL
     const float* sv0; const float* sv1; const float* sv2; const float* sv3;
     float* dgi;              // (B,T,dirs*G*H) written: grad of the input projection
-    float* dghn;             // GRU: (B,T,H) grad of the n-gate recurrent pre-activation (dn*r)
-    int lddg, lddghn;        // row strides of dgi / dghn (0 = packed: dirs*G*H and H).  The GRU cluster sweep accepts 4H / 4H with
+    float* dghn;             // GRU: (B,T,dirs*H) grad of the n-gate recurrent pre-activation (dn*r)
+    int lddg, lddghn;        // row strides of dgi / dghn (0 = packed: dirs*G*H and dirs*H).  The GRU cluster sweep accepts 4H / 4H with
                              // dghn = dgi + 3H: one (B,T,4H) array [dr | dz | dn | dn*r], so that dW_hh is ONE contraction
     float* dbpart;           // partial bias sums, see dep_sweep_dbpart_floats
     int dbpart_rows;         // number of partial rows provided

@@ -1,7 +1,7 @@
 // Persistent recurrent sweeps for nn.GRU / nn.LSTM (forward and BPTT) on gfx950.
 //
-// One launch walks all T time steps of one layer (both directions of a BiLSTM run side by side
-// in blockIdx.y).  A workgroup owns a tile of 16 utterances (the MFMA N dimension) and the whole
+// One launch walks all T time steps of one layer (both directions of a BiLSTM or a bidirectional GRU
+// run side by side in blockIdx.y; the BiGRU on the tile-MFMA kernels only).  A workgroup owns a tile of 16 utterances (the MFMA N dimension) and the whole
 // recurrent matrix: per step it computes   G^T (gates x 16) = W_hh (gates x H) * h_{t-1}^T (H x 16)
 // with v_mfma_f32_16x16x4_f32 (exact f32, == fmaf chain), W_hh streamed from L2 in a pre-packed
 // MFMA-fragment order (one coalesced 1 KiB load per wave per 16x16 k-chunk), h_{t-1} resident in
@@ -30,9 +30,9 @@ struct FwdP {
     const float* gi; int ldgi;          // (B,T,ldgi), direction d uses columns [d*G*H, (d+1)*G*H)
     float* y; int ldy;                   // (B,T,ldy),  direction d writes columns [d*H, (d+1)*H)
     float* ydrop; float drop_p, drop_scale; uint64_t seed; uint32_t site;
-    float* pooled; float pool_scale;     // (B,H)
+    float* pooled; float pool_scale;     // (B,dirs*H) GRU only, direction d in columns [d*H, (d+1)*H)
     float* h_n;                          // (dirs,B,H)
-    float* sv0; float* sv1; float* sv2; float* sv3;   // GRU: r,z,n,hn (B,T,H) ; LSTM: gates (B,T,dirs*4H), c (B,T,dirs*H)
+    float* sv0; float* sv1; float* sv2; float* sv3;   // GRU: r,z,n,hn (B,T,dirs*H) ; LSTM: gates (B,T,dirs*4H), c (B,T,dirs*H)
     const int* lengths; int pool_mean;   // ragged instances (RAG): row b is live for t < lengths[b]
 };
 
@@ -42,11 +42,11 @@ struct BwdP {
     const float* y; int ldy;
     const float* dy; int lddy;
     float drop_p, drop_scale; uint64_t seed; uint32_t site;
-    const float* dpooled; float pool_scale;
-    const float* dh_n;
+    const float* dpooled; float pool_scale;   // (B,dirs*H) GRU only
+    const float* dh_n;                         // (dirs,B,H)
     const float* sv0; const float* sv1; const float* sv2; const float* sv3;
     float* dgi; int lddg;                // (B,T,lddg) lddg = dirs*G*H
-    float* dghn;                         // GRU (B,T,H)
+    float* dghn;                         // GRU (B,T,dirs*H)
     float* dbpart;                       // [dirs][nwg][G'][H]  G' = 4
     int nwg;
     const int* lengths; int pool_mean;   // ragged instances (RAG)
@@ -104,7 +104,10 @@ __device__ __forceinline__ f32x4 rowsum16(f32x4 v) {
 // Selects, never value * 0: the saved gates / dy of dead positions may be anything.  Every workgroup still runs all T steps.
 // RAG = false is the dense text: the predicate is compiled out.
 // =============================================================================== GRU forward
-template <int JPW, bool RAG = false>
+// BI: the bidirectional instances (grid.y = 2, dir = blockIdx.y): direction 1 sweeps t = T-1 .. 0 on p.d[1], and every array is the
+// direction-interleaved one -- gi (B,T,2*3H), y / dropout(y) / saved gates (B,T,2H), pool (B,2H), h_n (2,B,H).  A ragged row's reverse
+// sweep meets its dead steps first: the state stays 0 through them (the same live select).  BI = false is the unidirectional text.
+template <int JPW, bool RAG = false, bool BI = false>
 __global__ __launch_bounds__(512) void gru_fwd_mfma(FwdP p) {
     // contraction by syntax: see DEP_FP_CONTRACT_NOTE in dep_common.h (why, and how to re-verify the dense instances after a compiler change)
 #pragma clang fp contract(on)
@@ -112,6 +115,8 @@ __global__ __launch_bounds__(512) void gru_fwd_mfma(FwdP p) {
     const int H = p.H, T = p.T, LDH = H + LPAD, KC = H / 16;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int j = lane & 15, q = lane >> 4;
+    const int dir = BI ? (int)blockIdx.y : 0;
+    const int SW = BI ? 2 * H : H;            // row width of the saved gates and the pool
     const int b = blockIdx.x * BT + j;
     const bool valid = b < p.B;
     int len = T;
@@ -119,20 +124,21 @@ __global__ __launch_bounds__(512) void gru_fwd_mfma(FwdP p) {
     float* hs0 = smem; float* hs1 = smem + BT * LDH;
     for (int i = threadIdx.x; i < 2 * BT * LDH; i += blockDim.x) smem[i] = 0.f;
 
-    const f32x4* wp = p.d[0].wp + (size_t)(w * JPW * 3) * KC * 64 + lane;
+    const f32x4* wp = p.d[dir].wp + (size_t)(w * JPW * 3) * KC * 64 + lane;
     f32x4 bh[JPW][3], hprev[JPW], pool[JPW];
 #pragma unroll
     for (int jj = 0; jj < JPW; ++jj) {
         const int col0 = (w * JPW + jj) * 16 + q * 4;
 #pragma unroll
-        for (int g = 0; g < 3; ++g) bh[jj][g] = ld4(p.d[0].b_hh + g * H + col0);
+        for (int g = 0; g < 3; ++g) bh[jj][g] = ld4(p.d[dir].b_hh + g * H + col0);
         hprev[jj] = zero4(); pool[jj] = zero4();
     }
     __syncthreads();
 
-    for (int t = 0; t < T; ++t) {
-        const float* hcur = (t & 1) ? hs1 : hs0;
-        float* hnext = (t & 1) ? hs0 : hs1;
+    for (int s = 0; s < T; ++s) {
+        const int t = (BI && dir) ? T - 1 - s : s;
+        const float* hcur = (s & 1) ? hs1 : hs0;
+        float* hnext = (s & 1) ? hs0 : hs1;
         const size_t row = (size_t)b * T + t;
         f32x4 gi[JPW][3];
 #pragma unroll
@@ -140,7 +146,7 @@ __global__ __launch_bounds__(512) void gru_fwd_mfma(FwdP p) {
             const int col0 = (w * JPW + jj) * 16 + q * 4;
 #pragma unroll
             for (int g = 0; g < 3; ++g)
-                gi[jj][g] = valid ? ld4(p.gi + row * p.ldgi + g * H + col0) : zero4();
+                gi[jj][g] = valid ? ld4(p.gi + row * p.ldgi + dir * 3 * H + g * H + col0) : zero4();
         }
         f32x4 acc[JPW * 3];
 #pragma unroll
@@ -164,11 +170,11 @@ __global__ __launch_bounds__(512) void gru_fwd_mfma(FwdP p) {
             pool[jj] += h;
             st4(hnext + j * LDH + col0, hprev[jj]);
             if (valid) {
-                const size_t o = row * p.ldy + col0;
+                const size_t o = row * p.ldy + dir * H + col0;
                 st4(p.y + o, h);
                 if (p.ydrop) st4(p.ydrop + o, h * dep_dropmask4(p.seed, p.site, o >> 2, p.drop_p, p.drop_scale));
                 if (p.sv0) {
-                    const size_t so = row * H + col0;
+                    const size_t so = row * SW + dir * H + col0;
                     st4(p.sv0 + so, r); st4(p.sv1 + so, z); st4(p.sv2 + so, n); st4(p.sv3 + so, hn);
                 }
             }
@@ -180,19 +186,23 @@ __global__ __launch_bounds__(512) void gru_fwd_mfma(FwdP p) {
         for (int jj = 0; jj < JPW; ++jj) {
             const int col0 = (w * JPW + jj) * 16 + q * 4;
             const float ps = RAG ? dep_ragged_pool_scale(p.pool_mean, len, T, p.pool_scale) : p.pool_scale;
-            if (p.pooled) st4(p.pooled + (size_t)b * H + col0, pool[jj] * ps);
-            if (p.h_n) st4(p.h_n + (size_t)b * H + col0, hprev[jj]);
+            if (p.pooled) st4(p.pooled + (size_t)b * SW + dir * H + col0, pool[jj] * ps);
+            if (p.h_n) st4(p.h_n + ((size_t)dir * p.B + b) * H + col0, hprev[jj]);
         }
     }
 }
 
 // =============================================================================== GRU backward
-template <int JPW, bool RAG = false>
+// BI: as in gru_fwd_mfma.  Direction 1 walks its sweep backwards, t = 0 .. T-1, with h_prev = y[t+1] (none at t = T-1; behind a ragged
+// row's end y is 0); dgi (B,T,2*3H), dghn (B,T,2H), dh_n (2,B,H), dpooled (B,2H), bias partials at row dir*nwg + blockIdx.x.
+template <int JPW, bool RAG = false, bool BI = false>
 __global__ __launch_bounds__(512) void gru_bwd_mfma(BwdP p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H = p.H, T = p.T, G3 = 3 * H, LDG = G3 + LPAD, KC = G3 / 16;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int j = lane & 15, q = lane >> 4;
+    const int dir = BI ? (int)blockIdx.y : 0;
+    const int SW = BI ? 2 * H : H;            // row width of the saved gates, dghn and dpooled
     const int b = blockIdx.x * BT + j;
     const bool valid = b < p.B;
     int len = T;
@@ -200,18 +210,19 @@ __global__ __launch_bounds__(512) void gru_bwd_mfma(BwdP p) {
     const float dps = RAG ? dep_ragged_pool_scale(p.pool_mean, len, T, p.pool_scale) : p.pool_scale;
     float* ds0 = smem; float* ds1 = smem + BT * LDG;
 
-    const f32x4* wp = p.d[0].wp + (size_t)(w * JPW) * KC * 64 + lane;
+    const f32x4* wp = p.d[dir].wp + (size_t)(w * JPW) * KC * 64 + lane;
     f32x4 dhrec[JPW], dbr[JPW], dbz[JPW], dbn[JPW], dbh[JPW], dpl[JPW];
 #pragma unroll
     for (int jj = 0; jj < JPW; ++jj) {
         const int col0 = (w * JPW + jj) * 16 + q * 4;
-        dhrec[jj] = (p.dh_n && valid) ? ld4(p.dh_n + (size_t)b * H + col0) : zero4();
-        dpl[jj] = (p.dpooled && valid) ? ld4(p.dpooled + (size_t)b * H + col0) * dps : zero4();
+        dhrec[jj] = (p.dh_n && valid) ? ld4(p.dh_n + ((size_t)dir * p.B + b) * H + col0) : zero4();
+        dpl[jj] = (p.dpooled && valid) ? ld4(p.dpooled + (size_t)b * SW + dir * H + col0) * dps : zero4();
         dbr[jj] = zero4(); dbz[jj] = zero4(); dbn[jj] = zero4(); dbh[jj] = zero4();
     }
 
-    for (int t = T - 1; t >= 0; --t) {
-        float* dcur = (t & 1) ? ds1 : ds0;
+    for (int s = T - 1; s >= 0; --s) {
+        const int t = (BI && dir) ? T - 1 - s : s;
+        float* dcur = (s & 1) ? ds1 : ds0;
         const size_t row = (size_t)b * T + t;
         f32x4 dzt[JPW];
 #pragma unroll
@@ -219,11 +230,11 @@ __global__ __launch_bounds__(512) void gru_bwd_mfma(BwdP p) {
             const int col0 = (w * JPW + jj) * 16 + q * 4;
             f32x4 r = zero4(), z = zero4(), n = zero4(), hn = zero4(), hp = zero4(), d = dhrec[jj] + dpl[jj];
             if (valid) {
-                const size_t so = row * H + col0;
+                const size_t so = row * SW + dir * H + col0;
                 r = ld4(p.sv0 + so); z = ld4(p.sv1 + so); n = ld4(p.sv2 + so); hn = ld4(p.sv3 + so);
-                if (t > 0) hp = ld4(p.y + (row - 1) * p.ldy + col0);
+                if (s > 0) hp = ld4(p.y + ((BI && dir) ? row + 1 : row - 1) * p.ldy + dir * H + col0);
                 if (p.dy) {
-                    const size_t o = row * p.lddy + col0;
+                    const size_t o = row * p.lddy + dir * H + col0;
                     f32x4 dyv = ld4(p.dy + o);
                     if (p.drop_p > 0.f) dyv *= dep_dropmask4(p.seed, p.site, o >> 2, p.drop_p, p.drop_scale);
                     d += dyv;
@@ -243,9 +254,9 @@ __global__ __launch_bounds__(512) void gru_bwd_mfma(BwdP p) {
             st4(dcur + j * LDG + H + col0, dz);
             st4(dcur + j * LDG + 2 * H + col0, dnr);
             if (valid) {
-                float* g = p.dgi + row * p.lddg;
+                float* g = p.dgi + row * p.lddg + dir * 3 * H;
                 st4(g + col0, dr); st4(g + H + col0, dz); st4(g + 2 * H + col0, dn);
-                st4(p.dghn + row * H + col0, dnr);
+                st4(p.dghn + row * SW + dir * H + col0, dnr);
             }
             dbr[jj] += dr; dbz[jj] += dz; dbn[jj] += dn; dbh[jj] += dnr;
         }
@@ -266,7 +277,7 @@ __global__ __launch_bounds__(512) void gru_bwd_mfma(BwdP p) {
         const int col0 = (w * JPW + jj) * 16 + q * 4;
         const f32x4 s0 = rowsum16(dbr[jj]), s1 = rowsum16(dbz[jj]), s2 = rowsum16(dbn[jj]), s3 = rowsum16(dbh[jj]);
         if (j == 0) {
-            float* o = p.dbpart + (size_t)blockIdx.x * 4 * H;
+            float* o = p.dbpart + ((size_t)dir * p.nwg + blockIdx.x) * 4 * H;
             st4(o + col0, s0); st4(o + H + col0, s1); st4(o + 2 * H + col0, s2); st4(o + 3 * H + col0, s3);
         }
     }
@@ -774,6 +785,28 @@ int dep_pack_whh(const float* w_hh, float* wp, float* wpT, int G, int H, hipStre
         }                                                                                          \
     } while (0)
 
+// the bidirectional GRU instances kern<JPW, RAG, true> (grid.y = 2)
+#define LAUNCH_JPW_BI_CASE(kern, J, RAG, grid, nthr, lds, s, P)                                    \
+    (void)hipFuncSetAttribute((const void*)kern<J, RAG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds)); \
+    DEP_LAUNCH((kern<J, RAG, true>), grid, dim3(nthr), lds, s, P); break
+#define LAUNCH_JPW_BI(kern, grid, nthr, lds, s, P)                                                 \
+    do {                                                                                           \
+        if (P.lengths) {                                                                           \
+            switch (jpw) {                                                                         \
+                case 1: LAUNCH_JPW_BI_CASE(kern, 1, true, grid, nthr, lds, s, P);                  \
+                case 2: LAUNCH_JPW_BI_CASE(kern, 2, true, grid, nthr, lds, s, P);                  \
+                case 3: LAUNCH_JPW_BI_CASE(kern, 3, true, grid, nthr, lds, s, P);                  \
+                default: LAUNCH_JPW_BI_CASE(kern, 4, true, grid, nthr, lds, s, P);                 \
+            }                                                                                      \
+        } else                                                                                     \
+        switch (jpw) {                                                                             \
+            case 1: LAUNCH_JPW_BI_CASE(kern, 1, false, grid, nthr, lds, s, P);                     \
+            case 2: LAUNCH_JPW_BI_CASE(kern, 2, false, grid, nthr, lds, s, P);                     \
+            case 3: LAUNCH_JPW_BI_CASE(kern, 3, false, grid, nthr, lds, s, P);                     \
+            default: LAUNCH_JPW_BI_CASE(kern, 4, false, grid, nthr, lds, s, P);                    \
+        }                                                                                          \
+    } while (0)
+
 int dep_launch_sweep_fwd(const dep_sweep_args& a) {
     const int G = a.cell == DEP_CELL_GRU ? 3 : 4;
     FwdP p{};
@@ -786,12 +819,15 @@ int dep_launch_sweep_fwd(const dep_sweep_args& a) {
     p.sv0 = a.training ? a.sv0 : nullptr; p.sv1 = a.sv1; p.sv2 = a.sv2; p.sv3 = a.sv3;
     p.lengths = a.lengths; p.pool_mean = a.pool_mean;
     DEP_CHECK_ARG(a.y && a.gi);
+    const bool bigru = a.cell == DEP_CELL_GRU && a.dirs == 2;
+    DEP_CHECK_ARG(!bigru || dep_sweep_use_mfma(a.H, a.impl));      // a bidirectional GRU has tile-MFMA instances only
     DepProfScope prof(a.cell == DEP_CELL_GRU ? DEP_PROF_GRU_FWD : DEP_PROF_LSTM_FWD, a.stream);
     if (dep_sweep_use_mfma(a.H, a.impl)) {
         int nw = 0; const int jpw = pick_jpw(a.H, &nw);
         const size_t lds = (size_t)2 * BT * (a.H + LPAD) * sizeof(float);
         dim3 grid(dep_cdiv(a.B, BT), a.dirs);
-        if (a.cell == DEP_CELL_GRU) LAUNCH_JPW(gru_fwd_mfma, grid, nw * 64, lds, a.stream, p);
+        if (bigru) LAUNCH_JPW_BI(gru_fwd_mfma, grid, nw * 64, lds, a.stream, p);
+        else if (a.cell == DEP_CELL_GRU) LAUNCH_JPW(gru_fwd_mfma, grid, nw * 64, lds, a.stream, p);
         else LAUNCH_JPW(lstm_fwd_mfma, grid, nw * 64, lds, a.stream, p);
     } else {
         dim3 grid(a.B, a.dirs);
@@ -821,12 +857,15 @@ int dep_launch_sweep_bwd(const dep_sweep_bwd_args& a) {
     p.lengths = a.lengths; p.pool_mean = a.pool_mean;
     DEP_CHECK_ARG(a.dbpart_rows >= p.nwg * a.dirs);
     DEP_CHECK_ARG(a.sv0 && a.dgi && a.dbpart);
+    const bool bigru = a.cell == DEP_CELL_GRU && a.dirs == 2;
+    DEP_CHECK_ARG(!bigru || dep_sweep_use_mfma(a.H, a.impl));      // a bidirectional GRU has tile-MFMA instances only
     DepProfScope prof(a.cell == DEP_CELL_GRU ? DEP_PROF_GRU_BWD : DEP_PROF_LSTM_BWD, a.stream);
     if (dep_sweep_use_mfma(a.H, a.impl)) {
         int nw = 0; const int jpw = pick_jpw(a.H, &nw);
         const size_t lds = (size_t)2 * BT * (G * a.H + LPAD) * sizeof(float);
         dim3 grid(dep_cdiv(a.B, BT), a.dirs);
-        if (a.cell == DEP_CELL_GRU) LAUNCH_JPW(gru_bwd_mfma, grid, nw * 64, lds, a.stream, p);
+        if (bigru) LAUNCH_JPW_BI(gru_bwd_mfma, grid, nw * 64, lds, a.stream, p);
+        else if (a.cell == DEP_CELL_GRU) LAUNCH_JPW(gru_bwd_mfma, grid, nw * 64, lds, a.stream, p);
         else LAUNCH_JPW(lstm_bwd_mfma, grid, nw * 64, lds, a.stream, p);
     } else {
         dim3 grid(a.B, a.dirs);

@@ -68,19 +68,30 @@ enum { DEP_RUN_EVAL = 0, DEP_RUN_TRAIN = 1, DEP_RUN_DROPOUT_ONLY = 2 };
 
 /* One stacked recurrent network: torch.nn.GRU(F,H,num_layers=L,dropout=p,batch_first=True)
  * (Classification/audio_gru_whole.py:59-60) or torch.nn.LSTM(F,H,num_layers=L,dropout=p,
- * bidirectional=True) (Classification/text_bilstm_whole.py:54-56). */
+ * bidirectional=True) (Classification/text_bilstm_whole.py:54-56).
+ * cell = DEP_CELL_GRU with dirs = 2 is torch.nn.GRU(F,H,num_layers=L,dropout=p,bidirectional=True,batch_first=True): the weight
+ * order below (.._l0, .._l0_reverse, .._l1, ...; weight_ih of layer l > 0 is (3H, 2H)), y = [fwd | rev] columns, h_n ordered
+ * [l0_fwd, l0_rev, l1_fwd, ...] with the reverse entry the state after step 0, pooled / dpooled (B,2H), inter-layer dropout drawn
+ * over the element index of (b, t, col) in the (B,T,2H) array at site DEP_SITE_RNN0 + l like the BiLSTM's.  It runs the
+ * tile-MFMA sweeps and nothing else (see impl). */
 typedef struct {
     int32_t cell;        /* DEP_CELL_GRU | DEP_CELL_LSTM */
     int32_t B, T, F, H;  /* batch, steps, input features, hidden units */
     int32_t L;           /* stacked layers (>=1) */
-    int32_t dirs;        /* 1 (GRU, unidirectional) or 2 (bidirectional LSTM) */
+    int32_t dirs;        /* 1 (unidirectional) or 2 (bidirectional: LSTM at any H; GRU where the tile-MFMA sweeps run, see impl) */
     int32_t training;    /* run mode: DEP_RUN_EVAL | DEP_RUN_TRAIN | DEP_RUN_DROPOUT_ONLY (see above) */
     float   dropout_p;   /* inter-layer dropout probability (applied to layers 0..L-2 outputs) */
     uint64_t seed;       /* Philox key for this call's dropout masks */
-    int32_t pool;        /* GRU only: DEP_POOL_* over T of the top layer (fused in the sweep) */
+    int32_t pool;        /* GRU only: DEP_POOL_* over T of the top layer's y, (B,H*dirs) (fused in the sweep) */
     int32_t impl;        /* 0 auto (cluster > tile-MFMA > generic), 1 generic kernels, 2 one-workgroup-per-tile
                             MFMA kernels, 3 cluster-parallel MFMA kernels (GRU with H in {128,256}, BiLSTM with
-                            H = 128; any B -- batches beyond one co-resident launch run as consecutive chunks) */
+                            H = 128; any B -- batches beyond one co-resident launch run as consecutive chunks).
+                            A bidirectional GRU has tile-MFMA kernels only: impl must be 0 or 2 (both mean those kernels)
+                            and H a multiple of 16 they can tile -- H / 16 = waves x tiles per wave with waves in
+                            {1,2,4,8} and at most 4 tiles per wave, inside the LDS bound: H in {16,32,48,64,96,128,192,256}.
+                            Any other H, impl = 1 and impl = 3 are a bad descriptor (size queries 0, entry points
+                            DEP_ERR_ARG with the rule in dep_last_error); it never takes the cluster, 16-unit-member or
+                            fused two-layer kernels, and dep_rnn_workspace_xbuf_offset is (size_t)-1 for it. */
 } dep_rnn_desc;
 
 size_t dep_rnn_reserve_bytes(const dep_rnn_desc* d);     /* activations kept fwd -> bwd */
@@ -128,7 +139,7 @@ int dep_rnn_get_exclusive(void);
  * `output, (h_n, _) = self.lstm_net(x)` (text_bilstm_whole.py:105).
  *   x      (B,T,F)
  *   y      (B,T,H*dirs) top-layer output, may be NULL when only `pooled` is wanted
- *   pooled (B,H) mean/sum over T of the top layer (GRU, desc.pool != NONE), else NULL
+ *   pooled (B,H*dirs) mean/sum over T of the top layer's y (GRU, desc.pool != NONE; what x.mean(dim=1) / x.sum(dim=1) gives), else NULL
  *   h_n    (L*dirs, B, H) final hidden states ordered [l0_fwd, l0_bwd, l1_fwd, ...], may be NULL
  */
 int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const float* const* weights,
@@ -140,7 +151,7 @@ int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const float* const* w
  * audio_gru_whole.py:190).  Gradients are WRITTEN (not accumulated) to dweights (same order and
  * shapes as weights); dep_grad_accumulate adds them into an accumulator of the caller's.
  *   dy      (B,T,H*dirs) grad of y, or NULL
- *   dpooled (B,H) grad of pooled, or NULL  (the 1/T of a mean pool is applied inside)
+ *   dpooled (B,H*dirs) grad of pooled, or NULL  (the 1/T of a mean pool is applied inside)
  *   dh_n    (L*dirs,B,H) grad of h_n, or NULL
  *   dx      (B,T,F) grad of x, or NULL to skip it (the reference computes it but never uses it)
  */
@@ -169,7 +180,8 @@ int dep_rnn_backward(const dep_rnn_desc* d, const float* x, const float* const* 
  * the reserve holds at dead positions besides the output sequences (saved gates) is unspecified.
  * All three run modes; GEMM modes 0 and 1 (modes 2 / 3 return DEP_ERR_ARG).  Reserve / workspace sizes and offsets are those of the
  * dense call.  A ragged call never runs a kernel without the length predicate: it takes the per-layer sweeps (tile, generic, cluster
- * GRU, cluster BiLSTM), not the fused two-layer GRU launches or the 16-unit-member forward.  A reserve written by a ragged forward is
+ * GRU, cluster BiLSTM), not the fused two-layer GRU launches or the 16-unit-member forward.  A ragged bidirectional GRU takes the ragged
+ * bidirectional instances of the tile-MFMA sweeps (its only kernels), under the same H / impl rule as its dense call.  A reserve written by a ragged forward is
  * consumed by a ragged backward with the SAME lengths; mixing a dense forward with a ragged backward (or the reverse) is the
  * caller's error and is not detected.  lengths == NULL is DEP_ERR_ARG here: the dense call is dep_rnn_forward / dep_rnn_backward. */
 int dep_rnn_forward_varlen(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmark of the dep_rnn operator alone (no head / optimizer): forward and backward of the
-2-layer GRU (cfg2) or BiLSTM (cfg3) stack on synthetic data.   python tools/bench_rnn.py gru|lstm [B T F H]"""
+2-layer GRU (cfg2), BiLSTM (cfg3) or bidirectional GRU stack on synthetic data.   python tools/bench_rnn.py gru|lstm|bigru [B T F H]
+(DEP_IMPL=2 forces the unidirectional GRU onto the tile-MFMA sweeps, the only kernels a bidirectional GRU runs.)"""
 import os
 import sys
 import time
@@ -16,11 +17,12 @@ def main():
     if len(sys.argv) > 5:
         B, T, F, H = map(int, sys.argv[2:6])
     else:
-        B, T, F, H = (512, 300, 256, 256) if cell == 'gru' else (512, 300, 1024, 128)
+        B, T, F, H = (512, 300, 1024, 128) if cell == 'lstm' else (512, 300, 256, 256)
     steps = int(os.environ.get('STEPS', 5))
     dev = torch.device('cuda:0')
+    gru = cell in ('gru', 'bigru')
     dirs = 1 if cell == 'gru' else 2
-    G = 3 if cell == 'gru' else 4
+    G = 3 if gru else 4
     torch.manual_seed(0)
     x = torch.randn(B, T, F, device=dev)
     W = []
@@ -31,13 +33,13 @@ def main():
             W += [(torch.rand(G * H, inp, device=dev) * 2 - 1) * k, (torch.rand(G * H, H, device=dev) * 2 - 1) * k,
                   (torch.rand(G * H, device=dev) * 2 - 1) * k, (torch.rand(G * H, device=dev) * 2 - 1) * k]
     Gd = [torch.empty_like(w) for w in W]
-    rnn = L.Rnn(L.CELL_GRU if cell == 'gru' else L.CELL_LSTM, B, T, F, H, 2, dirs, True, 0.5,
-                L.POOL_MEAN if cell == 'gru' else L.POOL_NONE, dev, impl=int(os.environ.get('DEP_IMPL', 0)))
-    pooled = torch.empty(B, H, device=dev) if cell == 'gru' else None
+    rnn = L.Rnn(L.CELL_GRU if gru else L.CELL_LSTM, B, T, F, H, 2, dirs, True, 0.5,
+                L.POOL_MEAN if gru else L.POOL_NONE, dev, impl=int(os.environ.get('DEP_IMPL', 0)))
+    pooled = torch.empty(B, dirs * H, device=dev) if gru else None
     hn = torch.empty(2 * dirs, B, H, device=dev)
-    dpool = torch.randn(B, H, device=dev) if cell == 'gru' else None
-    dy = None if cell == 'gru' else torch.randn(B, T, 2 * H, device=dev)
-    dhn = None if cell == 'gru' else torch.randn(2 * dirs, B, H, device=dev)
+    dpool = torch.randn(B, dirs * H, device=dev) if gru else None
+    dy = None if gru else torch.randn(B, T, 2 * H, device=dev)
+    dhn = None if gru else torch.randn(2 * dirs, B, H, device=dev)
     dx = torch.empty_like(x)
 
     def fwd(i):

@@ -5,7 +5,7 @@
 
 Both sides compile with build_ext.FLAGS + --cuda-device-only -S in a temporary directory, each with the headers of its own side.
 Per kernel pair: `identical`, or the first differing lines; plus VGPRs, SGPRs, spills, LDS, scratch and kernarg size.  Own symbol,
-.LBB<n>_ function index and __hip_cuid_* are normalised.  --map renames a (demangled) revision-side kernel before pairing.
+.LBB<n>_ function index and __hip_cuid_* are normalised, comments dropped.  --map renames a (demangled) revision-side kernel before pairing.
 --old-stem: the revision side is csrc/<STEM>.hip (a kernel that moved between files); --only keeps the kernels whose name has SUBSTRING.
 """
 import argparse, difflib, os, re, shutil, subprocess, sys, tempfile
@@ -30,7 +30,8 @@ def kernels(tree, stem, tmp):
     for s in syms:
         body = re.search(r'^%s:.*?^\s+\.end_amdhsa_kernel$' % re.escape(s), text, re.M | re.S).group(0)
         body = re.sub(r'\.LBB\d+_', '.LBB_', body.replace(s, '<kernel>'))
-        body = [l for l in re.sub(r'__hip_cuid_\w+', '__hip_cuid', body).split('\n') if not l.lstrip().startswith(';')]
+        body = re.sub(r'[ \t]*;.*$', '', body, flags=re.M)      # comments: loop notes carry the un-normalised function index (BB<n>_<k>)
+        body = [l for l in re.sub(r'__hip_cuid_\w+', '__hip_cuid', body).split('\n') if l.strip()]
         res[names[s]] = (body, {k: re.search(r'%s:\s+(\S+)' % re.escape(k), meta[s]).group(1) for k in RES})
     return res
 
