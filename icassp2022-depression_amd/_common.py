@@ -1,6 +1,8 @@
 """Bits shared by the script-shaped modules: metrics, checkpoint I/O, mini-batch slicing and the training epoch loop,
 permutation augmentation.  (Reference: the duplicated helpers at Classification/audio_gru_whole.py:123-159,
 text_bilstm_whole.py:116-152, fuse_net_whole.py:30-68.)"""
+import contextlib
+import functools
 import itertools
 import os
 
@@ -17,11 +19,69 @@ def save(model, filename):
     the state_dict (name -> CPU tensor) plus the config needed to rebuild the module."""
     save_filename = '{}.pt'.format(filename)
     os.makedirs(os.path.dirname(save_filename) or '.', exist_ok=True)
-    payload = {'state_dict': {k: v.detach().cpu() for k, v in model.state_dict().items()},
-               'class': type(model).__name__, 'variant': getattr(model, 'variant', None)}
+    payload = _model_payload(model)
     if parallel.rank() == 0:
         torch.save(payload, save_filename)
         print('Saved as %s' % save_filename)
+
+
+def _model_payload(model):
+    return {'state_dict': {k: v.detach().cpu() for k, v in model.state_dict().items()},
+            'class': type(model).__name__, 'variant': getattr(model, 'variant', None)}
+
+
+def save_checkpoint(model, optimizer, filename):
+    """`<filename>.pt` = the payload of save() plus 'optimizer': optimizer.state_dict() (step count, moments, and with amsgrad /
+    ema_decay the running maximum and the average): what a stopped run needs to continue with the bits it would have had.  Every
+    entry is a CPU tensor or a plain number, so load_checkpoint reads it with weights_only=True."""
+    save_filename = '{}.pt'.format(filename)
+    os.makedirs(os.path.dirname(save_filename) or '.', exist_ok=True)
+    payload = dict(_model_payload(model), optimizer=optimizer.state_dict())
+    if parallel.rank() == 0:
+        torch.save(payload, save_filename)
+    return save_filename
+
+
+def load_checkpoint(model, optimizer, filename):
+    """Read `<filename>.pt` of save_checkpoint into a model and an optimizer built the way the saved ones were; returns the payload."""
+    payload = torch.load('{}.pt'.format(filename), map_location='cpu', weights_only=True)
+    if 'optimizer' not in payload:
+        raise ValueError('%s.pt holds no optimizer state (written by save(), not save_checkpoint())' % filename)
+    model.load_state_dict(payload['state_dict'])
+    optimizer.load_state_dict(payload['optimizer'])
+    return payload
+
+
+def optim_options(config):
+    """The scripts' two optional config keys as keyword arguments of nn.Adam / nn.AdamW: `amsgrad` (default False) and `ema_decay`
+    (default None; d in [0, 1) keeps an average of the weights that evaluate() then measures and saves).  Both absent or at their
+    defaults: {} -- the optimizer built is the one it always was."""
+    amsgrad, d = config.get('amsgrad', False), config.get('ema_decay')
+    if not isinstance(amsgrad, (bool, np.bool_)):
+        raise ValueError(f'amsgrad must be True or False, got {amsgrad!r}')
+    if d is not None and (isinstance(d, bool) or not isinstance(d, (int, float, np.integer, np.floating)) or not 0.0 <= float(d) < 1.0):
+        raise ValueError(f'ema_decay must be None or a number in [0, 1), got {d!r}')
+    out = {}
+    if amsgrad:
+        out['amsgrad'] = True
+    if d is not None:
+        out['ema_decay'] = float(d)
+    return out
+
+
+def on_averaged_weights(get_optimizer):
+    """Decorator of the scripts' evaluate(): with config['ema_decay'] set the call runs inside optimizer.averaged(), so the metric, the
+    save gate and the saved checkpoint are those of the averaged weights.  get_optimizer() returns the module-global optimizer at
+    call time; one without an average (or none at all) leaves the call as it is."""
+    def wrap(fn):
+        @functools.wraps(fn)
+        def evaluate(*args, **kwargs):
+            opt = get_optimizer()
+            ctx = opt.averaged() if getattr(opt, 'ema_decay', None) is not None else contextlib.nullcontext()
+            with ctx:
+                return fn(*args, **kwargs)
+        return evaluate
+    return wrap
 
 
 class StateDictModule(torch.nn.Module):

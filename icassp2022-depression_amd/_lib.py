@@ -113,6 +113,9 @@ _SIGS = {
                                         C.c_int, C.c_int, _P, C.c_float, C.c_int, _P, _P, _P]),
     'dep_grad_clip_scale': (C.c_int, [C.POINTER(_P), C.POINTER(C.c_long), C.c_int, _P, C.c_float, _P, _P]),
     'dep_grad_accumulate': (C.c_int, [C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_long), C.c_int, C.c_float, C.c_int, _P, _P]),
+    'dep_adam_step_ext': (C.c_int, [_P, _P, _P, _P, C.c_long, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                    C.c_int, C.c_int, _P, _P, C.c_float, C.c_int, _P, _P, _P]),
+    'dep_swap': (C.c_int, [_P, _P, C.c_long, _P]),
     'dep_frame_window': (C.c_int, [_P, C.c_long, C.c_int, C.c_int, C.c_int, _P, _P]),
     'dep_power_spectrum': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
     'dep_log_floor': (C.c_int, [_P, _P, C.c_long, C.c_float, _P]),
@@ -403,6 +406,28 @@ def grad_accumulate(acc_ranges, g_ranges, scale=1.0, first=False, partials=None)
     gptrs, cnts = _range_arrays(g_ranges)
     check(load().dep_grad_accumulate(aptrs, gptrs, cnts, len(g_ranges), float(scale), int(bool(first)), _ptr(partials), stream()),
           'dep_grad_accumulate')
+
+
+class AdamExt(C.Structure):
+    """dep_adam_ext of include/dep_rnn.h."""
+    _fields_ = [('vmax', _P), ('ema', _P), ('ema_decay', C.c_float), ('ema_first', C.c_int)]
+
+
+def adam_step_ext(p, g, m, v, lr, b1, b2, eps, wd, decoupled, step, vmax=None, ema=None, ema_decay=0.0, ema_first=False,
+                  partials=None, max_norm=0.0, skip_nonfinite=False, clip_out=None, stats=None):
+    """dep_adam_step_ext: the Adam / AdamW step of one range with AMSGrad (`vmax`) and / or the fused average of the parameters
+    (`ema`, `ema_decay`, `ema_first`); `partials` selects the clipped form (adam_step_clipped's arguments).  One launch."""
+    ext = AdamExt(_ptr(vmax), _ptr(ema), float(ema_decay), int(bool(ema_first)))
+    check(load().dep_adam_step_ext(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, b1, b2, eps, wd, int(decoupled), int(step),
+                                   C.byref(ext), _ptr(partials), float(max_norm), int(skip_nonfinite), _ptr(clip_out), _ptr(stats),
+                                   stream()), 'dep_adam_step_ext')
+
+
+def swap(a, b):
+    """a <-> b, bit for bit, for two fp32 device tensors of equal size (dep_swap).  One launch."""
+    if a.numel() != b.numel():
+        raise DepError('swap: the two tensors differ in size')
+    check(load().dep_swap(_ptr(f32(a)), _ptr(f32(b)), a.numel(), stream()), 'dep_swap')
 
 
 def fill(t, value):

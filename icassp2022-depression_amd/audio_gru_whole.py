@@ -90,6 +90,7 @@ def train(epoch, train_idxs):
                       100. * correct / n_train))
 
 
+@_common.on_averaged_weights(lambda: optimizer)
 def evaluate(model, test_idxs, fold, train_idxs_tmp, train_idxs):
     """Full-batch evaluation, metrics and the threshold-gated checkpoint (reference lines 204-245)."""
     global max_f1, max_acc, max_prec, max_rec
@@ -157,7 +158,7 @@ def main(fold_files=('train_idxs_0.63_1.npy', 'train_idxs_0.60_2.npy', 'train_id
         model = AudioBiLSTM(config)
         parallel.broadcast_params(model)
         optimizer = nn.AdamW(get_param_group(model), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'),
-                             accumulate_steps=config.get('accum_steps', 1))
+                             accumulate_steps=config.get('accum_steps', 1), **_common.optim_options(config))
         criterion = make_criterion(train_idxs)
         max_f1 = max_acc = max_rec = max_prec = -1
         train_acc = -1

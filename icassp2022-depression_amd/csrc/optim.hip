@@ -1,9 +1,12 @@
 // The optimizer on the device: Adam / AdamW (dep_adam_step), global-norm gradient clipping (dep_grad_sqnorm, dep_adam_step_clipped,
-// dep_grad_clip_scale) and gradient accumulation over micro-batches (dep_grad_accumulate); include/dep_rnn.h.
+// dep_grad_clip_scale), gradient accumulation over micro-batches (dep_grad_accumulate), and AMSGrad plus a fused average of the
+// parameters (dep_adam_step_ext, dep_swap); include/dep_rnn.h.
 //
 // Two equalities hold by construction.  adam_kernel and adam_clipped_kernel both call adam_element, the one Adam expression, so a clip
-// coefficient of one gives the plain step's bits.  grad_sqnorm_kernel and grad_accumulate_kernel are both gn_walk<> over their ranges,
-// so the partial sums the accumulate launch leaves are the ones dep_grad_sqnorm forms from the accumulator.
+// coefficient of one gives the plain step's bits; adam_ext_kernel and adam_clipped_ext_kernel are the same two kernel bodies around
+// adam_element<true>, which adds the running maximum and the average to that expression and repeats none of it.  grad_sqnorm_kernel
+// and grad_accumulate_kernel are both gn_walk<> over their ranges, so the partial sums the accumulate launch leaves are the ones
+// dep_grad_sqnorm forms from the accumulator.
 //
 // The sum of squares is a pure function of the data.  The ranges are read as ONE concatenated array cut into chunks of
 // GN_CHUNK floats; partial slot s holds the sum over chunks s, s + GN_SLOTS, ... in that order, and ONE workgroup owns a slot
@@ -162,41 +165,66 @@ inline AdamBias adam_bias(float lr, float beta1, float beta2, int step) {
     const double bc2 = 1.0 - pow((double)beta2, (double)step);
     return {(float)((double)lr / bc1), (float)(1.0 / sqrt(bc2))};
 }
-// The update of element i, the ONE Adam expression of the library.  The caller loads pv = p[i] and gv = g[i] (adam_clipped_kernel: times
+// What dep_adam_step_ext adds, as the kernels take it: pointers are NULL for a part that is off (uniform over the launch).
+struct AdamExt { float* vmax; float* ema; float ema_w; int ema_first; };   // ema_w = 1 - decay
+// The update of element i, the ONE Adam expression of the library.  The caller loads pv = p[i] and gv = g[i] (the clipped kernels: times
 // the clip coefficient; g * 1.0f is exact, so a coefficient of one gives the plain step's bits) in that order and passes the values.
+// EXT (dep_adam_step_ext): AMSGrad puts max(vmax, v) in v's place under the root; the average follows the stored parameter,
+// ema += w * (p_new - ema) in one fma (p_new == ema: ema + w * 0 keeps ema), or ema = p_new without reading ema when `first`.
+template <bool EXT>
 __device__ __forceinline__ void adam_element(float pv, float gv, float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                              long i, float lr, float b1, float b2, float eps, float wd, int decoupled, float step_size,
-                                             float inv_sqrt_bc2) {
-    if (decoupled) pv *= (1.0f - lr * wd);
+                                             float inv_sqrt_bc2, const AdamExt& x) {
+    // The fused products are written out (fmaf): they are the ones the compiler chose for adam_kernel and adam_clipped_kernel under the
+    // default contraction, where left to itself it fused the OTHER product of m in the EXT instances -- and an AMSGrad step whose
+    // maximum is v itself has to give the plain step's bits.  v is two products and a sum in every instance (tools/isa_diff.py).
+    if (decoupled) pv *= fmaf(-lr, wd, 1.0f);
     else if (wd != 0.f) gv = fmaf(wd, pv, gv);
-    const float mv = b1 * m[i] + (1.0f - b1) * gv;
+    const float mv = fmaf(b1, m[i], (1.0f - b1) * gv);
     const float vv = b2 * v[i] + (1.0f - b2) * gv * gv;
     m[i] = mv; v[i] = vv;
-    const float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
-    p[i] = pv - step_size * (mv / denom);
+    float dv = vv;
+    if (EXT && x.vmax) { dv = fmaxf(x.vmax[i], vv); x.vmax[i] = dv; }
+    const float denom = fmaf(sqrtf(dv), inv_sqrt_bc2, eps);
+    const float pn = fmaf(-step_size, mv / denom, pv);
+    p[i] = pn;
+    if (EXT && x.ema) x.ema[i] = x.ema_first ? pn : fmaf(x.ema_w, pn - x.ema[i], x.ema[i]);
 }
 
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
-                            int decoupled, float step_size, float inv_sqrt_bc2) {
+// the body of the plain kernels: one element per thread
+template <bool EXT>
+__device__ __forceinline__ void adam_plain_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
+                                                int decoupled, float step_size, float inv_sqrt_bc2, const AdamExt& x) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float pv = p[i], gv = g[i];
-    adam_element(pv, gv, p, m, v, i, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2);
+    adam_element<EXT>(pv, gv, p, m, v, i, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2, x);
+}
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                            float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
+                            int decoupled, float step_size, float inv_sqrt_bc2) {
+    adam_plain_body<false>(p, g, m, v, n, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2, AdamExt{});
+}
+__global__ void adam_ext_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
+                                int decoupled, float step_size, float inv_sqrt_bc2, AdamExt x) {
+    adam_plain_body<true>(p, g, m, v, n, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2, x);
 }
 
 constexpr int AC_PER_THREAD = 8;           // elements per thread: the partials are re-summed once per 2048 elements
-__global__ __launch_bounds__(GN_THREADS) void adam_clipped_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                                  float* __restrict__ m, float* __restrict__ v, long n, float lr,
-                                                                  float b1, float b2, float eps, float wd, int decoupled,
-                                                                  float step_size, float inv_sqrt_bc2,
-                                                                  const double* __restrict__ partials, double max_norm,
-                                                                  int skip_nonfinite, float* clip_out, double* stats) {
+// the body of the clipped kernels (GN_THREADS threads)
+template <bool EXT>
+__device__ __forceinline__ void adam_clipped_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                  float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
+                                                  int decoupled, float step_size, float inv_sqrt_bc2,
+                                                  const double* __restrict__ partials, double max_norm, int skip_nonfinite,
+                                                  float* clip_out, double* stats, const AdamExt& x) {
     __shared__ double red[4];
     const ClipCoef c = gn_coef(partials, max_norm, red);
     const bool skipped = skip_nonfinite && !c.finite;
     if (blockIdx.x == 0 && threadIdx.x == 0) gn_report(c, skipped, clip_out, stats);
-    if (skipped) return;                                           // p, m, v untouched
+    if (skipped) return;                                           // p, m, v (and vmax, ema) untouched
     const float coef = c.coef;
     const long base = (long)blockIdx.x * (GN_THREADS * AC_PER_THREAD) + threadIdx.x;
 #pragma unroll
@@ -204,7 +232,37 @@ __global__ __launch_bounds__(GN_THREADS) void adam_clipped_kernel(float* __restr
         const long i = base + (long)k * GN_THREADS;
         if (i >= n) break;
         const float pv = p[i], gv = g[i] * coef;
-        adam_element(pv, gv, p, m, v, i, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2);
+        adam_element<EXT>(pv, gv, p, m, v, i, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2, x);
+    }
+}
+__global__ __launch_bounds__(GN_THREADS) void adam_clipped_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                  float* __restrict__ m, float* __restrict__ v, long n, float lr,
+                                                                  float b1, float b2, float eps, float wd, int decoupled,
+                                                                  float step_size, float inv_sqrt_bc2,
+                                                                  const double* __restrict__ partials, double max_norm,
+                                                                  int skip_nonfinite, float* clip_out, double* stats) {
+    adam_clipped_body<false>(p, g, m, v, n, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2, partials, max_norm, skip_nonfinite,
+                             clip_out, stats, AdamExt{});
+}
+__global__ __launch_bounds__(GN_THREADS) void adam_clipped_ext_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                      float* __restrict__ m, float* __restrict__ v, long n, float lr,
+                                                                      float b1, float b2, float eps, float wd, int decoupled,
+                                                                      float step_size, float inv_sqrt_bc2,
+                                                                      const double* __restrict__ partials, double max_norm,
+                                                                      int skip_nonfinite, float* clip_out, double* stats, AdamExt x) {
+    adam_clipped_body<true>(p, g, m, v, n, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2, partials, max_norm, skip_nonfinite,
+                            clip_out, stats, x);
+}
+
+// a[i] <-> b[i] as 32-bit words (no arithmetic touches them): four per thread where four are left, one by one in the tail
+__global__ __launch_bounds__(GN_THREADS) void swap_kernel(uint32_t* __restrict__ a, uint32_t* __restrict__ b, long n) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const long i = ((long)blockIdx.x * GN_THREADS + threadIdx.x) * 4;
+    if (i + 3 < n) {
+        const u32x4 x = *reinterpret_cast<const u32x4*>(a + i), y = *reinterpret_cast<const u32x4*>(b + i);
+        *reinterpret_cast<u32x4*>(a + i) = y; *reinterpret_cast<u32x4*>(b + i) = x;
+    } else {
+        for (long k = i; k < n; ++k) { const uint32_t x = a[k]; a[k] = b[k]; b[k] = x; }
     }
 }
 
@@ -236,6 +294,11 @@ void set_starts(Ranges& R, const long* counts, int nranges) {
     R.count = nranges;
 }
 // "measure only": max_norm <= 0 or +inf -> 0 for the kernels
+// true when [a, a + n) and [b, b + n) floats share a byte
+inline bool ranges_overlap(const float* a, const float* b, long n) {
+    const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b, bytes = (uintptr_t)n * sizeof(float);
+    return ua < ub + bytes && ub < ua + bytes;
+}
 inline double kernel_max_norm(float max_norm) { return (max_norm > 0.f && max_norm <= 3.402823466e38f) ? (double)max_norm : 0.0; }
 
 }  // namespace
@@ -269,24 +332,80 @@ extern "C" int dep_grad_accumulate(float* const* acc, const float* const* g, con
     return DEP_OK;
 }
 
+// The launches of the three Adam entry points.  x == NULL: the kernels dep_adam_step / dep_adam_step_clipped always launched.
+static int adam_launch(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                       float weight_decay, int decoupled, int step, const AdamExt* x, void* stream) {
+    const AdamBias bc = adam_bias(lr, beta1, beta2, step);
+    if (x)
+        DEP_LAUNCH(adam_ext_kernel, dim3(dep_cdiv(n, 256)), dim3(256), 0, S_, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay,
+                   decoupled, bc.step_size, bc.inv_sqrt_bc2, *x);
+    else
+        DEP_LAUNCH(adam_kernel, dim3(dep_cdiv(n, 256)), dim3(256), 0, S_, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, decoupled,
+                   bc.step_size, bc.inv_sqrt_bc2);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+static int adam_clipped_launch(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                               float weight_decay, int decoupled, int step, const AdamExt* x, const double* partials, float max_norm,
+                               int skip_nonfinite, float* clip_out, double* stats, void* stream) {
+    const AdamBias bc = adam_bias(lr, beta1, beta2, step);
+    const dim3 grid(dep_cdiv(n, GN_THREADS * AC_PER_THREAD));
+    if (x)
+        DEP_LAUNCH(adam_clipped_ext_kernel, grid, dim3(GN_THREADS), 0, S_, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay,
+                   decoupled, bc.step_size, bc.inv_sqrt_bc2, partials, kernel_max_norm(max_norm), skip_nonfinite, clip_out, stats, *x);
+    else
+        DEP_LAUNCH(adam_clipped_kernel, grid, dim3(GN_THREADS), 0, S_, p, g, m, v, n, lr,
+                   beta1, beta2, eps, weight_decay, decoupled, bc.step_size, bc.inv_sqrt_bc2, partials, kernel_max_norm(max_norm),
+                   skip_nonfinite, clip_out, stats);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+
 extern "C" int dep_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                              float eps, float weight_decay, int decoupled, int step, void* stream) {
     DEP_CHECK_ARG(p && g && m && v && n > 0 && step >= 1);
-    const AdamBias bc = adam_bias(lr, beta1, beta2, step);
-    DEP_LAUNCH(adam_kernel, dim3(dep_cdiv(n, 256)), dim3(256), 0, S_, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, decoupled,
-               bc.step_size, bc.inv_sqrt_bc2);
-    DEP_CHECK_LAUNCH();
-    return DEP_OK;
+    return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, decoupled, step, nullptr, stream);
 }
 
 extern "C" int dep_adam_step_clipped(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                                      float eps, float weight_decay, int decoupled, int step, const double* partials,
                                      float max_norm, int skip_nonfinite, float* clip_out, double* stats, void* stream) {
     DEP_CHECK_ARG(p && g && m && v && n > 0 && step >= 1 && partials && max_norm == max_norm);
-    const AdamBias bc = adam_bias(lr, beta1, beta2, step);
-    DEP_LAUNCH(adam_clipped_kernel, dim3(dep_cdiv(n, GN_THREADS * AC_PER_THREAD)), dim3(GN_THREADS), 0, S_, p, g, m, v, n, lr,
-               beta1, beta2, eps, weight_decay, decoupled, bc.step_size, bc.inv_sqrt_bc2, partials, kernel_max_norm(max_norm),
-               skip_nonfinite, clip_out, stats);
+    return adam_clipped_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, decoupled, step, nullptr, partials, max_norm,
+                               skip_nonfinite, clip_out, stats, stream);
+}
+
+extern "C" int dep_adam_step_ext(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, int decoupled, int step, const dep_adam_ext* ext, const double* partials,
+                                 float max_norm, int skip_nonfinite, float* clip_out, double* stats, void* stream) {
+    DEP_CHECK_ARG(p && g && m && v && n > 0 && step >= 1);
+    if (partials) DEP_CHECK_ARG(max_norm == max_norm);
+    AdamExt x{};
+    bool on = false;
+    if (ext && (ext->vmax || ext->ema)) {
+        const float* const others[4] = {p, g, m, v};
+        if (ext->vmax)
+            for (const float* o : others) DEP_CHECK_ARG(!ranges_overlap(ext->vmax, o, n));
+        if (ext->ema) {
+            DEP_CHECK_ARG(ext->ema_decay >= 0.f && ext->ema_decay < 1.f);              // false for a NaN
+            for (const float* o : others) DEP_CHECK_ARG(!ranges_overlap(ext->ema, o, n));
+            if (ext->vmax) DEP_CHECK_ARG(!ranges_overlap(ext->ema, ext->vmax, n));
+        }
+        // a decay of zero is "the average is the parameter": e + 1 * (p - e) rounds twice, the `first` form is exact
+        x = AdamExt{ext->vmax, ext->ema, 1.0f - ext->ema_decay, (ext->ema_first || ext->ema_decay == 0.f) ? 1 : 0};
+        on = true;
+    }
+    // nothing switched on: the launches (and so the bits) of the two entry points above
+    if (partials)
+        return adam_clipped_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, decoupled, step, on ? &x : nullptr, partials,
+                                   max_norm, skip_nonfinite, clip_out, stats, stream);
+    return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, decoupled, step, on ? &x : nullptr, stream);
+}
+
+extern "C" int dep_swap(float* a, float* b, long n, void* stream) {
+    DEP_CHECK_ARG(a && b && n > 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0 && !ranges_overlap(a, b, n));
+    DEP_LAUNCH(swap_kernel, dim3(dep_cdiv(dep_cdiv(n, 4), GN_THREADS)), dim3(GN_THREADS), 0, S_, reinterpret_cast<uint32_t*>(a),
+               reinterpret_cast<uint32_t*>(b), n);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }

@@ -79,7 +79,7 @@ def build(seed=None):
     model = fusion_net(config['text_embed_size'], config['text_hidden_dims'], config['rnn_layers'], config['dropout'],
                        config['num_classes'], config['audio_hidden_dims'], config['audio_embed_size'], seed=seed)
     optimizer = nn.Adam(model.parameters(), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'),
-                        accumulate_steps=config.get('accum_steps', 1))
+                        accumulate_steps=config.get('accum_steps', 1), **_common.optim_options(config))
     criterion = MyLoss(**_common.reg_options(config))       # config['loss'] / 'loss_beta' / 'loss_delta'; absent: the reference's SmoothL1
     return model
 
@@ -111,6 +111,7 @@ def train(model, epoch):
     return train_mae
 
 
+@_common.on_averaged_weights(lambda: optimizer)
 def evaluate(model, fold, train_mae):
     """Reference lines 414-456."""
     global min_mae, min_rmse

@@ -94,7 +94,7 @@ def build(seed=None):
     model = fusion_net(config['text_embed_size'], config['text_hidden_dims'], config['rnn_layers'], config['dropout'],
                        config['num_classes'], config['audio_hidden_dims'], config['audio_embed_size'], seed=seed)
     optimizer = nn.Adam(model.parameters(), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'),
-                        accumulate_steps=config.get('accum_steps', 1))
+                        accumulate_steps=config.get('accum_steps', 1), **_common.optim_options(config))
     criterion = MyLoss()
     return model
 
@@ -124,6 +124,7 @@ def train(epoch, train_idxs):
             100. * correct / n_train))
 
 
+@_common.on_averaged_weights(lambda: optimizer)
 def evaluate(model, test_idxs, fold, train_idxs):
     """Mini-batched evaluation (reference lines 468-520)."""
     global max_train_acc, max_acc, max_f1

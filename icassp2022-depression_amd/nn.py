@@ -16,6 +16,7 @@ by the optimizers exactly like torch skips parameters whose grad is None.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from collections import OrderedDict
 
@@ -604,7 +605,7 @@ class _AdamBase:
     decoupled = False
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=None, max_grad_norm=None, skip_nonfinite=False,
-                 accumulate_steps=1):
+                 accumulate_steps=1, amsgrad=False, ema_decay=None):
         """max_grad_norm: clip the GLOBAL 2-norm of the gradients of all groups to it inside the update (torch's
         clip_grad_norm_(all parameters, max_grad_norm) in front of step(), without its host read; None = no clipping).
         skip_nonfinite: a step whose gradient norm is inf / NaN leaves parameters and moments untouched (it still counts in the bias
@@ -612,8 +613,20 @@ class _AdamBase:
         accumulate_steps: K > 1 makes step() a MICRO-step: it adds the gradients the last backward wrote into a flat accumulator
         per owner module (one dep_grad_accumulate launch over the ranges of all groups) and only every K-th call -- or flush() --
         updates, from the accumulator; clipping and skip_nonfinite then act on the accumulated gradient.  The criteria must divide
-        by the rows of the whole accumulated batch (parallel.set_accumulated_count), not by their own.  1: step() is what it was."""
+        by the rows of the whole accumulated batch (parallel.set_accumulated_count), not by their own.  1: step() is what it was.
+        amsgrad: torch's option -- the running maximum of v takes v's place under the root.
+        ema_decay: d in [0, 1) keeps an average of the parameters, avg += (1 - d) * (p - avg) after every update (torch's
+        AveragedModel with get_ema_multi_avg_fn(d): no bias correction, the first update copies), in one flat buffer per owner module
+        laid out like its parameters; averaged() puts it in the parameters' place.  Either option makes every range's launch a
+        dep_adam_step_ext -- the same number of launches; with both at their defaults the launches are the ones above."""
         params = list(params)
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f'ema_decay must be None or a number in [0, 1), got {ema_decay!r}')
+        self.amsgrad = bool(amsgrad)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self._ext = {}            # id(module) -> (vmax or None, ema or None), made by the first update
+        self._ema_updates = 0     # updates the average has been through
+        self._averaged = False    # inside averaged(): the parameters and the average are exchanged
         if isinstance(accumulate_steps, bool) or not isinstance(accumulate_steps, (int, np.integer)) or accumulate_steps < 1:
             raise ValueError(f'accumulate_steps must be an integer >= 1, got {accumulate_steps!r}')
         self.accumulate_steps = int(accumulate_steps)
@@ -672,6 +685,7 @@ class _AdamBase:
         return spans
 
     def step(self):
+        self._refuse_averaged('step()')
         if self.accumulate_steps > 1:
             return self._micro_step()
         self._step += 1
@@ -695,6 +709,7 @@ class _AdamBase:
             if not have_partials:
                 L.grad_sqnorm([grad_of(o)[s:e] for o, s, e in spans], partials)
             max_norm = 0.0 if self.max_grad_norm is None else self.max_grad_norm          # 0: measure only (skip_nonfinite alone)
+        ext = self._extended()
         first = True
         for g, rs in plan:
             b1, b2 = g['betas']
@@ -702,12 +717,128 @@ class _AdamBase:
                 m, v = self._state_of(owner)
                 args = (owner._flat[s:e], grad_of(owner)[s:e], m[s:e], v[s:e], g['lr'], b1, b2, g['eps'], g['weight_decay'],
                         self.decoupled, self._step)
-                if clip:
+                if ext:
+                    vmax, ema = self._ext_of(owner)
+                    L.adam_step_ext(*args, vmax=None if vmax is None else vmax[s:e], ema=None if ema is None else ema[s:e],
+                                    ema_decay=self.ema_decay or 0.0, ema_first=self._ema_updates == 0,
+                                    partials=partials if clip else None, max_norm=max_norm if clip else 0.0,
+                                    skip_nonfinite=self.skip_nonfinite, clip_out=clip_out if clip and first else None,
+                                    stats=stats if clip and first else None)
+                elif clip:
                     L.adam_step_clipped(*args, partials, max_norm, self.skip_nonfinite, clip_out if first else None,
                                         stats if first else None)
                 else:
                     L.adam_step(*args)
                 first = False
+        if ext:
+            self._ema_updates += 1
+
+    # -- AMSGrad and the average of the parameters (amsgrad, ema_decay) -----------------------------------------------
+    def _extended(self):
+        return self.amsgrad or self.ema_decay is not None
+
+    def _owners(self):
+        """The owner modules, in param_groups order."""
+        return list({id(p.owner): p.owner for g in self.param_groups for p in g['params']}.values())
+
+    def _ext_of(self, owner):
+        """(vmax, ema) of an owner: vmax zeros beside (m, v); ema a flat buffer laid out like owner._flat.  The first update makes the
+        averages of ALL owners, each as a copy of the parameters before that update -- one dep_grad_accumulate launch in its `first`
+        form (acc = g * 1), no ATen kernel.  The copy is what makes the rest simple: a range the optimizer never updates (dead
+        parameters, parameters without a gradient) averages to itself, as AveragedModel's average of a constant does, and the host
+        needs no device word to learn whether the first update was skipped (skip_nonfinite): ema_first goes with the optimizer's
+        first update whatever became of it, and a skipped one leaves average = parameters, which is what the copy put there.  The
+        average then starts at the unchanged parameters instead of at the first update that lands; the two differ by (1 - d) of one
+        step's movement."""
+        if id(owner) not in self._ext:
+            for o in self._owners():
+                vmax = torch.zeros_like(o._flat_grad) if self.amsgrad else None
+                ema = None
+                if self.ema_decay is not None:
+                    ema = torch.empty_like(o._flat)
+                    L.grad_accumulate([ema], [o._flat], 1.0, True, None)
+                self._ext[id(o)] = (vmax, ema)
+        return self._ext[id(owner)]
+
+    def _refuse_averaged(self, what):
+        if self._averaged:
+            raise L.DepError(f'{what} inside averaged(): the parameters hold the average there; leave the context first')
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """with optimizer.averaged(): every owner's parameters and their average are exchanged in place (one dep_swap per owner) and
+        exchanged back on exit, exceptions included.  Inside, model.state_dict(), forward and _common.save see the averaged weights
+        (the models rebuild their packed weight images and the LayerNorm fold from the parameters in every forward: nothing stale
+        survives the exchange).  step(), flush(), state_dict() and a nested averaged() raise DepError inside.  Before the first
+        update the average is the parameters themselves."""
+        if self.ema_decay is None:
+            raise L.DepError('averaged() needs an optimizer built with ema_decay')
+        self._refuse_averaged('averaged()')
+        pairs = [(o, self._ext_of(o)[1]) for o in self._owners()]
+        done = []
+        self._averaged = True
+        try:
+            for o, ema in pairs:
+                L.swap(o._flat, ema)
+                done.append((o, ema))
+            yield self
+        finally:
+            for o, ema in done:
+                L.swap(o._flat, ema)
+            self._averaged = False
+
+    # -- checkpoints ---------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """Everything a resumed run needs to continue with the bits of the uninterrupted one, as CPU tensors and plain numbers: the
+        step count, the options, each group's hyper-parameters, and per owner (param_groups order) m, v and -- where the options
+        ask for them -- vmax, the average and its update count.  Saving in the middle of an accumulation group (pending > 0) is
+        refused, not saved: call it after the group's update or after flush().  The record grad_stats() reads is not part of it."""
+        self._refuse_averaged('state_dict()')
+        if self._pending:
+            raise L.DepError(f'state_dict() in the middle of an accumulation group ({self._pending} micro-steps pending): save after the update or flush()')
+        cpu = lambda t: None if t is None else t.detach().cpu().clone()
+        state = []
+        for o in self._owners():
+            mv, x = self._state.get(id(o)), self._ext.get(id(o), (None, None))
+            state.append({'numel': int(o._flat.numel()), 'm': cpu(mv and mv[0]), 'v': cpu(mv and mv[1]), 'vmax': cpu(x[0]), 'ema': cpu(x[1])})
+        return {'step': self._step, 'ema_updates': self._ema_updates, 'amsgrad': self.amsgrad, 'ema_decay': self.ema_decay,
+                'decoupled': bool(self.decoupled), 'accumulate_steps': self.accumulate_steps,
+                'param_groups': [{'lr': g['lr'], 'betas': tuple(g['betas']), 'eps': g['eps'], 'weight_decay': g['weight_decay'],
+                                  'numel': [int(p.numel) for p in g['params']]} for g in self.param_groups],
+                'state': state}
+
+    def load_state_dict(self, sd):
+        """Into an optimizer built the same way over an identically built model.  The groups' hyper-parameters and ema_decay's value
+        come from `sd` (torch's rule); a difference in amsgrad, in ema_decay present / absent, in Adam / AdamW, or in any size is a ValueError."""
+        self._refuse_averaged('load_state_dict()')
+        if bool(sd['amsgrad']) != self.amsgrad:
+            raise ValueError(f"load_state_dict: amsgrad is {sd['amsgrad']} in the checkpoint, {self.amsgrad} in this optimizer")
+        if (sd['ema_decay'] is None) != (self.ema_decay is None):
+            raise ValueError(f"load_state_dict: ema_decay is {sd['ema_decay']} in the checkpoint, {self.ema_decay} in this optimizer")
+        if bool(sd['decoupled']) != bool(self.decoupled):
+            raise ValueError('load_state_dict: decoupled weight decay (AdamW) in one of checkpoint and optimizer, not in the other')
+        owners = self._owners()
+        sizes = [[int(p.numel) for p in g['params']] for g in self.param_groups]
+        if [g['numel'] for g in sd['param_groups']] != sizes:
+            raise ValueError(f"load_state_dict: parameter group sizes {[g['numel'] for g in sd['param_groups']]} in the checkpoint, {sizes} in this optimizer")
+        if [st['numel'] for st in sd['state']] != [int(o._flat.numel()) for o in owners]:
+            raise ValueError(f"load_state_dict: owner sizes {[st['numel'] for st in sd['state']]} in the checkpoint, "
+                             f'{[int(o._flat.numel()) for o in owners]} in this optimizer')
+        for o, st in zip(owners, sd['state']):
+            for k, like in (('m', o._flat_grad), ('v', o._flat_grad), ('vmax', o._flat_grad), ('ema', o._flat)):
+                if st[k] is not None and st[k].numel() != like.numel():
+                    raise ValueError(f'load_state_dict: {k} has {st[k].numel()} elements in the checkpoint, {like.numel()} in this optimizer')
+        put = lambda t, like: None if t is None else torch.empty_like(like).copy_(t)
+        self._state, self._ext = {}, {}
+        for o, st in zip(owners, sd['state']):
+            if st['m'] is not None:
+                self._state[id(o)] = (put(st['m'], o._flat_grad), put(st['v'], o._flat_grad))
+            if st['vmax'] is not None or st['ema'] is not None:
+                self._ext[id(o)] = (put(st['vmax'], o._flat_grad), put(st['ema'], o._flat))
+        for g, h in zip(self.param_groups, sd['param_groups']):
+            g.update(lr=h['lr'], betas=tuple(h['betas']), eps=h['eps'], weight_decay=h['weight_decay'])
+        self.ema_decay = sd['ema_decay']
+        self._step, self._ema_updates, self._pending = int(sd['step']), int(sd['ema_updates']), 0
 
     # -- accumulation over micro-batches (accumulate_steps > 1) -------------------------------------------------------
     @property
@@ -759,6 +890,7 @@ class _AdamBase:
     def flush(self):
         """Update from a partial group (an epoch whose number of mini-batches is no multiple of accumulate_steps); nothing pending:
         nothing is launched.  Under data parallelism every rank calls it at the same point (it holds the group's one collective)."""
+        self._refuse_averaged('flush()')
         if self._pending:
             self._update_from_accumulator(False)
 

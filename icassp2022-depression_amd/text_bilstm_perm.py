@@ -84,6 +84,7 @@ def train(epoch):
     return train_mae
 
 
+@_common.on_averaged_weights(lambda: optimizer)
 def evaluate(fold, model, train_mae):
     """Reference lines 172-210."""
     global min_mae, min_rmse
@@ -129,7 +130,7 @@ def main(epochs=None):
         model = TextBiLSTM(config)
         parallel.broadcast_params(model)
         optimizer = nn.Adam(model.parameters(), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'),
-                            accumulate_steps=config.get('accum_steps', 1))
+                            accumulate_steps=config.get('accum_steps', 1), **_common.optim_options(config))
         criterion = _common.reg_criterion(config, nn.SmoothL1Loss)       # config['loss'] / 'loss_beta' / 'loss_delta'; absent: the reference's
         min_mae = 100; min_rmse = 100
         train_mae = 100

@@ -508,6 +508,36 @@ int dep_grad_clip_scale(float* const* bufs, const long* counts, int nranges, con
 int dep_grad_accumulate(float* const* acc, const float* const* g, const long* counts, int nranges, float scale, int first,
                         double* partials, void* stream);
 
+/* AMSGrad and a fused average of the parameters (torch.optim.Adam[W](amsgrad=True); torch.optim.swa_utils.AveragedModel with
+ * get_ema_multi_avg_fn(d)), inside the ONE launch per range the optimizer already makes.
+ *   dep_adam_step_ext     : partials == NULL: dep_adam_step (its grid; max_norm, skip_nonfinite, clip_out, stats are ignored).
+ *                           partials != NULL: dep_adam_step_clipped, its contract in every word -- coefficient, measure-only mode,
+ *                           the clip_out / stats record, workgroup 0 as the writer.  `ext` adds, per element and after v is updated:
+ *                               vmax != NULL:  vmax = max(vmax, v) ;  denom = sqrtf(vmax) * inv_sqrt_bc2 + eps
+ *                                              (torch's non-capturable single-tensor path; vmax is zero before step 1)
+ *                               ema  != NULL:  ema = fma(1 - d, p_new - ema, ema)   with d = ema_decay in [0, 1)
+ *                                              (Tensor.lerp_'s form for a weight below one half, no bias correction; p_new == ema
+ *                                              keeps ema).  ema_first != 0, or d == 0: ema = p_new exactly and ema is NOT read (it
+ *                                              may hold anything, NaN included) -- AveragedModel's first update, and the `first`
+ *                                              idiom of dep_grad_accumulate: no initialisation launch.
+ *                           A skipped step (skip_nonfinite, S not finite) leaves p, m, v, vmax and ema untouched bit for bit.
+ *                           ext == NULL, or both pointers NULL: the launches, and so the bits, of dep_adam_step / dep_adam_step_clipped.
+ *   dep_swap              : a[i] <-> b[i] for n floats, as 32-bit words (NaN payloads and signed zeros survive); one launch.  The
+ *                           optimizer's averaged() exchanges a parameter buffer with its average through it, and back.
+ * Nothing allocates or synchronises; refused before any HIP call: what dep_adam_step / dep_adam_step_clipped refuse, ema != NULL
+ * with a NaN ema_decay or one outside [0, 1), vmax or ema overlapping p / g / m / v or each other; dep_swap with NULL, n <= 0, a
+ * pointer that is not 16-byte aligned, or overlapping ranges. */
+typedef struct {
+    float* vmax;       /* AMSGrad: running element-wise maximum of v, n floats, caller-owned, zero before step 1; NULL = off */
+    float* ema;        /* average of p, n floats, caller-owned; NULL = off */
+    float  ema_decay;  /* d in [0, 1) */
+    int    ema_first;  /* != 0: ema is NOT read (it may hold anything, NaN included) and becomes p_new exactly */
+} dep_adam_ext;
+int dep_adam_step_ext(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                      float weight_decay, int decoupled, int step, const dep_adam_ext* ext,
+                      const double* partials, float max_norm, int skip_nonfinite, float* clip_out, double* stats, void* stream);
+int dep_swap(float* a, float* b, long n, void* stream);   /* a[i] <-> b[i], bits exchanged; a, b 16-byte aligned, not overlapping */
+
 /* ------------------------------------------------------------------ feature front-end */
 /* wav2vlad of Classification/audio_features_whole.py:57-72: log-mel spectrogram (librosa.feature.melspectrogram defaults:
  * n_fft 2048, hop 512, periodic Hann, centred frames with reflect padding, power 2, 80 Slaney mel filters) followed by
