@@ -318,6 +318,9 @@ def head_mlp_bwd(dz2, a0, z1, a1, W1, W2, dW1, db1, dW2, db2, dx, dz1, p, seed, 
 
 
 def reduce_loss(loss_rows, norm, loss_out, accumulate=False):
+    """dep_reduce_loss.  norm: a number, or -- as for head_loss_ce / head_loss_reg -- a 1-element fp32 device tensor (reduce_loss_by)."""
+    if torch.is_tensor(norm):
+        return reduce_loss_by(loss_rows, norm, loss_out, accumulate)
     check(load().dep_reduce_loss(_ptr(loss_rows), loss_rows.numel(), float(norm), _ptr(loss_out), int(accumulate),
                                  stream()), 'dep_reduce_loss')
 

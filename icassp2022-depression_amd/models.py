@@ -500,11 +500,15 @@ class MyLoss:
     The classification variant takes torch.nn.CrossEntropyLoss's weight / ignore_index / label_smoothing (nn.CEOptions): both halves
     then run dep_head_loss_ce over ONE shared denominator.  The regression variant takes `loss` ('l1', 'smooth_l1', 'huber', 'mse'),
     `beta`, `delta` (nn.RegOptions) and, on its call, `weight`: B row weights; both plain halves (no ReLU) then run dep_head_loss_reg
-    over ONE shared denominator C sum_i w_i.  All defaults and no weight: the launches it always enqueued."""
+    over ONE shared denominator C sum_i w_i.  All defaults and no weight: the launches it always enqueued.  The target, the
+    denominator and the launches are nn.criterion_call's, on both halves at once; its own are the GEMMs around them."""
+    kind = L.LOSS_CE_LOGITS                     # what nn.criterion_call reads: the halves are logits / plain outputs (no ReLU)
+    relu = 0
 
     def __init__(self, variant='clf', weight=None, ignore_index=-100, label_smoothing=0.0, reduction='mean', loss='smooth_l1',
                  beta=1.0, delta=1.0):
         self.variant = variant
+        self.target_dtype = 'int' if variant == 'clf' else 'float'
         self.options = nn.CEOptions(weight, ignore_index, label_smoothing, reduction)
         if variant != 'clf' and self.options.active:
             raise ValueError('class weights, ignore_index and label_smoothing belong to the classification loss')
@@ -525,50 +529,13 @@ class MyLoss:
         zt = torch.empty(B, Cc, dtype=torch.float32, device=dev); za = torch.empty_like(zt)
         L.gemm(0, 1, B, Cc, Ht, text_feature, Ht, W, D, zt, Cc)
         L.gemm(0, 1, B, Cc, Ha, audio_feature, Ha, W[:, Ht:], D, za, Cc)
-        opt = self.options if self.options.active else None
-        reg = None
-        if opt is not None:
-            t, wide, t_host = opt.labels(target, Cc, dev)
-            kind = L.LOSS_CE_LOGITS | wide
-        elif self.variant == 'clf':
-            t = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target)
-            nn._check_labels(t, Cc)
-            kind = L.LOSS_CE_LOGITS; norm_local = B; per_row = 1
-            if t.dtype == torch.int64:
-                t = t.to(device=dev).contiguous().view(-1); kind |= L.LOSS_LABELS_I64
-            else:
-                t = t.to(device=dev, dtype=torch.int32).contiguous().view(-1)
-        else:
-            t = torch.as_tensor(np.asarray(target, dtype=np.float32) if not torch.is_tensor(target) else target)
-            t = t.to(device=dev, dtype=torch.float32).contiguous().view(B, Cc)
-            kind = L.LOSS_SMOOTHL1; norm_local = B * Cc; per_row = Cc
-            if weight is not None or not (self.reg_options.neutral and self.reg_options.loss == 'smooth_l1'):
-                reg = self.reg_options
-        rows = torch.empty(B, dtype=torch.float32, device=dev)
-        val = torch.empty(1, dtype=torch.float32, device=dev)                       # overwritten by the first dep_reduce_loss
-        dzt = torch.empty_like(zt) if train else None
-        dza = torch.empty_like(za) if train else None
-        if opt is not None:
-            norm = opt.denominator(t, t_host, Cc, train)                            # one denominator for both halves
-            opt.head_loss(kind, zt, t, rows, dzt, norm); opt.reduce(rows, norm, val)
-            opt.head_loss(kind, za, t, rows, dza, norm); opt.reduce(rows, norm, val, accumulate=True)
-        elif reg is not None:
-            w_dev, w_host = reg.rows(weight, B, dev)
-            norm = reg.denominator(w_dev, w_host, B, Cc, train)                     # one denominator for both halves
-            reg.head_loss(0, zt, t, w_dev, rows, dzt, norm); reg.reduce(rows, norm, val)
-            reg.head_loss(0, za, t, w_dev, rows, dza, norm); reg.reduce(rows, norm, val, accumulate=True)
-        else:
-            norm = parallel.loss_count(B, per_row) if train else norm_local
-            L.head_loss(kind, zt, t, None, rows, dzt, norm); L.reduce_loss(rows, norm, val)
-            L.head_loss(kind, za, t, None, rows, dza, norm); L.reduce_loss(rows, norm, val, accumulate=True)
 
-        def bw():
+        def bw(dzt, dza):
             g = Wp._grad
             L.gemm(1, 0, Cc, Ht, B, dzt, Cc, text_feature, Ht, g, D)               # dW[:, :Ht] = dzt^T text
             L.gemm(1, 0, Cc, Ha, B, dza, Cc, audio_feature, Ha, g[:, Ht:], D)      # dW[:, Ht:] = dza^T audio
             model._grad_ready = True
             parallel.finish_grad_sync(model, *model.sync_plan())
-        loss = nn.Loss(val, bw if train else None, reduce=train and parallel.world_size() > 1,
-                       health=getattr(model, 'check_health', None))
-        loss.dz_halves = (dzt, dza)             # dLoss/dz of the text and the audio half (None under evaluate())
+        loss, dzs = nn.criterion_call(self, (zt, za), target, weight, model, train, bw)
+        loss.dz_halves = tuple(dzs)             # dLoss/dz of the text and the audio half (None under evaluate())
         return loss

@@ -310,8 +310,8 @@ def _check_labels(t, num_classes, ignore_index=None):
 
 class CEOptions:
     """torch.nn.CrossEntropyLoss's `weight`, `ignore_index` and `label_smoothing` (reduction 'mean') for the fused CE criteria
-    (CrossEntropyLoss below, models.MyLoss): validation, the device copy of the weights -- uploaded once, here -- and the choice of
-    the denominator sum_i live_i w[y_i] that torch's weighted mean divides by."""
+    (CrossEntropyLoss below, models.MyLoss): validation and the values, with the device copy of the weights -- uploaded once, here.
+    What a call does with them is criterion_call's."""
 
     def __init__(self, weight=None, ignore_index=-100, label_smoothing=0.0, reduction='mean'):
         if reduction != 'mean':
@@ -343,122 +343,11 @@ class CEOptions:
             w = np.ones(int(live.max()) + 1 if live.size else 1)
         return class_row_weight(t, w, self.ignore_index)
 
-    def labels(self, target, num_classes, dev):
-        """(device labels, LOSS_LABELS_I64 or 0, host labels or None) of a criterion call."""
-        if self.weight is not None and self.weight.size != num_classes:
-            raise ValueError(f'weight has {self.weight.size} entries, the model has {num_classes} classes')
-        t = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target).reshape(-1)
-        _check_labels(t, num_classes, self.ignore_index)
-        host = None if t.is_cuda else t
-        if t.dtype == torch.int64:
-            return t.to(device=dev).contiguous(), L.LOSS_LABELS_I64, host
-        return t.to(device=dev, dtype=torch.int32).contiguous(), 0, host
-
-    def denominator(self, t_dev, t_host, num_classes, train):
-        """What the loss and dz are divided by: a declared accumulated weight, else (more than one rank) a declared global weight,
-        else the batch's own -- a number summed in float64 from host labels, or a device scalar filled by dep_ce_weight_sum from
-        device-resident ones (one launch more, no host read).  evaluate() (train False) always takes the batch's own."""
-        if train:
-            w = parallel.loss_weight()
-            if w is not None:
-                return w
-            if parallel.world_size() > 1:
-                raise L.DepError('a criterion with class weights / label smoothing / ignore_index under data parallelism needs the global '
-                                 "mini-batch's denominator: declare it with parallel.set_global_weight (or pass row_weight= to "
-                                 '_common.train_epoch)')
-        if t_host is not None:
-            y = t_host.numpy().astype(np.int64)
-            live = y != self.ignore_index
-            den = float(np.float32(live.sum() if self.weight is None else self.weight[y[live]].sum()))
-            if den > 0.0:
-                return den
-            return torch.full((1,), den, dtype=torch.float32, device=t_dev.device)    # no live row: NaN, as in torch (the host `norm` must be > 0)
-        den = torch.empty(1, dtype=torch.float32, device=t_dev.device)
-        L.ce_weight_sum(t_dev, self.weight_dev, self.ignore_index, num_classes, den)
-        return den
-
-    def head_loss(self, kind, z, t_dev, rows, dz, norm):
-        L.head_loss_ce(kind, z, t_dev, None, rows, dz, norm, self.weight_dev, self.label_smoothing, self.ignore_index)
-
-    @staticmethod
-    def reduce(rows, norm, val, accumulate=False):
-        if torch.is_tensor(norm):
-            L.reduce_loss_by(rows, norm, val, accumulate)
-        else:
-            L.reduce_loss(rows, norm, val, accumulate)
-
-
-class _HeadLoss:
-    """Loss on a model output; the output nonlinearity, the loss and dLoss/dz are one HIP kernel."""
-    kind = None
-    target_dtype = None
-
-    def __call__(self, output, target):
-        owner = output._owner
-        z = output._z
-        B, Cc = z.shape
-        dev = z.device
-        kind = self.kind
-        if self.target_dtype == 'int':
-            t = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target)
-            _check_labels(t, Cc)
-            if t.dtype == torch.int64:                       # torch.long as the reference's loops make them: read in place
-                t = t.to(device=dev).contiguous().view(-1); kind = self.kind | L.LOSS_LABELS_I64
-            else:
-                t = t.to(device=dev, dtype=torch.int32).contiguous().view(-1)
-        else:
-            t = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target)
-            t = t.to(device=dev, dtype=torch.float32).contiguous().view(B, Cc)
-        per_row = 1 if self.target_dtype == 'int' else Cc
-        norm_local = B * per_row
-        train = owner is not None and owner.training
-        # data parallel: every rank normalises by the GLOBAL batch so that summed gradients equal
-        # the reference's batch-mean gradient (ragged shards included); accumulation: by the rows of the whole accumulated batch
-        norm = parallel.loss_count(B, per_row) if train else norm_local
-        rows = torch.empty(B, dtype=torch.float32, device=dev)
-        dz = torch.empty_like(z) if train else None
-        L.head_loss(kind, z, t, None, rows, dz, norm)
-        val = torch.empty(1, dtype=torch.float32, device=dev)         # dep_reduce_loss overwrites it
-        L.reduce_loss(rows, norm, val)
-        return Loss(val, (lambda: owner.backward(dz)) if train else None, reduce=train and parallel.world_size() > 1,
-                    health=getattr(owner, 'check_health', None), dz=dz)
-
-
-class CrossEntropyLoss(_HeadLoss):
-    """nn.CrossEntropyLoss on the model's Softmax output (audio_gru_whole.py:308), with torch's `weight`, `ignore_index` and
-    `label_smoothing` (reduction 'mean').  All defaults: the call is _HeadLoss's -- dep_head_loss + dep_reduce_loss, the launches it
-    always enqueued, and a label -100 is out of range as it always was.  Any option set: dep_head_loss_ce, divided by
-    sum_i live_i w[y_i] (CEOptions.denominator); rows whose label is ignore_index then count for nothing."""
-    kind = L.LOSS_CE_ON_SOFTMAX
-    target_dtype = 'int'
-
-    def __init__(self, weight=None, ignore_index=-100, label_smoothing=0.0, reduction='mean'):
-        self.options = CEOptions(weight, ignore_index, label_smoothing, reduction)
-
-    def __call__(self, output, target):
-        opt = self.options
-        if not opt.active:
-            return super().__call__(output, target)
-        owner = output._owner
-        z = output._z
-        B, Cc = z.shape
-        dev = z.device
-        t, wide, t_host = opt.labels(target, Cc, dev)
-        train = owner is not None and owner.training
-        norm = opt.denominator(t, t_host, Cc, train)
-        rows = torch.empty(B, dtype=torch.float32, device=dev)
-        dz = torch.empty_like(z) if train else None
-        opt.head_loss(self.kind | wide, z, t, rows, dz, norm)
-        val = torch.empty(1, dtype=torch.float32, device=dev)         # the reduce overwrites it
-        opt.reduce(rows, norm, val)
-        return Loss(val, (lambda: owner.backward(dz)) if train else None, reduce=train and parallel.world_size() > 1,
-                    health=getattr(owner, 'check_health', None), dz=dz)
-
 
 class RegOptions:
     """The regression criteria's form and parameter (dep_head_loss_reg: L1, SmoothL1(beta), Huber(delta), MSE; reduction 'mean') and
-    per-row sample weights (L1Loss / SmoothL1Loss / HuberLoss / MSELoss below, models.MyLoss('reg')): validation, the weights' way to
-    the device, and the choice of the denominator C sum_i w_i that the weighted mean over elements divides by."""
+    per-row sample weights (L1Loss / SmoothL1Loss / HuberLoss / MSELoss below, models.MyLoss('reg')): validation, the values, and the
+    weights' way to the device.  What a call does with them is criterion_call's."""
     FORMS = {'l1': L.REG_L1, 'smooth_l1': L.REG_SMOOTHL1, 'huber': L.REG_HUBER, 'mse': L.REG_MSE}
 
     def __init__(self, loss='smooth_l1', beta=1.0, delta=1.0, reduction='mean'):
@@ -497,68 +386,166 @@ class RegOptions:
             raise ValueError('weight must hold finite, non-negative row weights')
         return torch.from_numpy(w.astype(np.float32)).to(dev), w
 
-    @staticmethod
-    def denominator(w_dev, w_host, B, Cc, train):
-        """What the loss and dz are divided by, in CEOptions.denominator's order: while training a declared weight (accumulated, else
-        -- more than one rank -- global) times C; else the batch's own C sum_i w_i -- a number summed in float64 from host weights, or
-        a device scalar filled by dep_row_weight_sum from device-resident ones (one launch more, no host read); without weights the
-        element count parallel.loss_count declares.  evaluate() (train False) always takes the batch's own."""
-        if train:
-            w = parallel.loss_weight()
-            if w is not None:
-                return w * Cc
-            if w_dev is not None and parallel.world_size() > 1:
-                raise L.DepError("a criterion with row weights under data parallelism needs the global mini-batch's denominator: declare "
-                                 'it with parallel.set_global_weight (or pass row_weight= to _common.train_epoch)')
-        if w_host is not None:
-            den = float(np.float32(Cc * w_host.sum()))
-            if den > 0.0:
-                return den
-            return torch.full((1,), den, dtype=torch.float32, device=w_dev.device)    # every row ignored: NaN (the host `norm` must be > 0)
-        if w_dev is not None:
-            den = torch.empty(1, dtype=torch.float32, device=w_dev.device)
+
+# ----------------------------------------------------------------------------- the criteria's one call path
+# A criterion is a declaration: target_dtype ('int': class labels, anything else: values), kind (its dep_head_loss kind), options
+# (CEOptions or None), reg_options (RegOptions or None) and relu.  criterion_call is what every one of them does with a target.
+_PLAIN_REG = {('l1', 1): L.LOSS_L1_RELU, ('smooth_l1', 1): L.LOSS_SMOOTHL1_RELU, ('smooth_l1', 0): L.LOSS_SMOOTHL1}
+
+
+def _plain_kind(crit, weight):
+    """The choice of the entry point: the dep_head_loss kind of a call with everything at its defaults -- the launches it always
+    enqueued -- or None for dep_head_loss_ce (class labels) / dep_head_loss_reg (values).
+        class labels, no option active                                               crit.kind
+        values without reg_options (a bare _HeadLoss subclass)                       crit.kind
+        values without `weight`: L1 or SmoothL1 with beta 1 on relu(z), SmoothL1 with beta 1 on z      _PLAIN_REG
+    Everything else, L1 on z among it, has no plain kind."""
+    if crit.target_dtype == 'int':
+        return None if crit.options is not None and crit.options.active else crit.kind
+    reg = crit.reg_options
+    if reg is None:
+        return crit.kind
+    return _PLAIN_REG.get((reg.loss, crit.relu)) if weight is None and reg.neutral else None
+
+
+def _label_target(target, num_classes, dev, ignore_index):
+    """(device labels, LOSS_LABELS_I64 or 0, host labels or None) of a sequence, an ndarray or a tensor of class indices.  The range is
+    checked on the host copy (ignore_index exempt); torch.long, as the reference's loops make them, is read in place."""
+    t = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target).reshape(-1)
+    _check_labels(t, num_classes, ignore_index)
+    host = None if t.is_cuda else t
+    if t.dtype == torch.int64:
+        return t.to(device=dev).contiguous(), L.LOSS_LABELS_I64, host
+    return t.to(device=dev, dtype=torch.int32).contiguous(), 0, host
+
+
+def _denominator(train, B, Cc, labels, plain, opt, t_dev, t_host, w_dev, w_host):
+    """What the loss and dz of a criterion call are divided by.
+    Unweighted call (`plain`: the dep_head_loss kinds): parallel.loss_count(B, per_row) while training -- the rows of the global /
+    accumulated batch -- else B * per_row; per_row is 1 for class labels and C for the regression means.
+    Weighted call (CE with any option active, label smoothing or ignore_index alone among them; a regression call with `weight`), with
+    scale 1 for CE and C for regression: while training a declared parallel.loss_weight() times scale; else, on more than one rank, a
+    DepError; else the batch's own sum -- from a host copy a number summed in float64 and rounded to float32, or, when that is not
+    positive, a 1-element device tensor holding it (NaN, as in torch: the host `norm` must be > 0); from device-resident labels or
+    weights one dep_ce_weight_sum / dep_row_weight_sum launch into a device scalar (one launch more, no host read).  evaluate()
+    (train False) always takes the batch's own.
+    Quirk, kept: a regression form without a plain kind (MSELoss, say) called WITHOUT `weight` still consults parallel.loss_weight()
+    first while training and only then falls back to the unweighted count; on more than one rank it is not refused."""
+    per_row = scale = 1 if labels else Cc
+    weighted = not plain and (labels or w_dev is not None)
+    if train and not plain:
+        w = parallel.loss_weight()
+        if w is not None:
+            return w * scale
+        if weighted and parallel.world_size() > 1:
+            raise L.DepError(f"a criterion with {'class weights / label smoothing / ignore_index' if labels else 'row weights'} under data "
+                             "parallelism needs the global mini-batch's denominator: declare it with parallel.set_global_weight (or pass "
+                             'row_weight= to _common.train_epoch)')
+    if not weighted:
+        return parallel.loss_count(B, per_row) if train else B * per_row
+    dev = t_dev.device if labels else w_dev.device
+    if labels and t_host is not None:
+        y = t_host.numpy().astype(np.int64)
+        live = y != opt.ignore_index
+        den = live.sum() if opt.weight is None else opt.weight[y[live]].sum()
+    elif w_host is not None:
+        den = Cc * w_host.sum()
+    else:
+        den = torch.empty(1, dtype=torch.float32, device=dev)
+        if labels:
+            L.ce_weight_sum(t_dev, opt.weight_dev, opt.ignore_index, Cc, den)
+        else:
             L.row_weight_sum(w_dev, Cc, den)
-            return den
-        return parallel.loss_count(B, Cc) if train else B * Cc
+        return den
+    den = float(np.float32(den))
+    return den if den > 0.0 else torch.full((1,), den, dtype=torch.float32, device=dev)
 
-    def head_loss(self, relu, z, t_dev, w_dev, rows, dz, norm):
-        L.head_loss_reg(self.form, relu, self.param, z, t_dev, None, rows, dz, norm, w_dev)
 
-    reduce = staticmethod(CEOptions.reduce)
+def criterion_call(crit, zs, target, weight, owner, train, backward):
+    """One criterion call on the pre-activations `zs` -- one (B, C) tensor, or the fusion loss's two halves -- which share the target,
+    the denominator, `rows` and the value: bring the target (and the row weights) to the device, choose the denominator and the entry
+    point, then per z one head-loss launch and one reduce (accumulating after the first).  Returns (Loss, [dLoss/dz per z]); the
+    Loss runs backward(*dzs) when `train`."""
+    B, Cc = zs[0].shape
+    dev = zs[0].device
+    labels = crit.target_dtype == 'int'
+    plain = _plain_kind(crit, weight)
+    opt = reg = t_host = w_dev = w_host = None
+    if labels:
+        if plain is None:
+            opt = crit.options
+            if opt.weight is not None and opt.weight.size != Cc:
+                raise ValueError(f'weight has {opt.weight.size} entries, the model has {Cc} classes')
+        t, wide, t_host = _label_target(target, Cc, dev, None if opt is None else opt.ignore_index)
+    else:
+        t = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target)
+        t = t.to(device=dev, dtype=torch.float32).contiguous().view(B, Cc)
+        wide = 0
+        if plain is None:
+            reg = crit.reg_options
+            w_dev, w_host = reg.rows(weight, B, dev)
+    norm = _denominator(train, B, Cc, labels, plain is not None, opt, t, t_host, w_dev, w_host)
+    rows = torch.empty(B, dtype=torch.float32, device=dev)
+    val = torch.empty(1, dtype=torch.float32, device=dev)             # the first reduce overwrites it
+    dzs = []
+    for z in zs:
+        dz = torch.empty_like(z) if train else None
+        if plain is not None:
+            L.head_loss(plain | wide, z, t, None, rows, dz, norm)
+        elif labels:
+            L.head_loss_ce(crit.kind | wide, z, t, None, rows, dz, norm, opt.weight_dev, opt.label_smoothing, opt.ignore_index)
+        else:
+            L.head_loss_reg(reg.form, crit.relu, reg.param, z, t, None, rows, dz, norm, w_dev)
+        L.reduce_loss(rows, norm, val, bool(dzs))                     # every z after the first adds to the value
+        dzs.append(dz)
+    # data parallel: every rank normalised by the GLOBAL batch, so the value is the local part of the global mean (Loss.item sums them)
+    loss = Loss(val, (lambda: backward(*dzs)) if train else None, reduce=train and parallel.world_size() > 1,
+                health=getattr(owner, 'check_health', None), dz=dzs[0] if len(zs) == 1 else None)
+    return loss, dzs
+
+
+class _HeadLoss:
+    """Loss on a model output; the output nonlinearity, the loss and dLoss/dz are one HIP kernel (criterion_call)."""
+    kind = None
+    target_dtype = None
+    options = None
+    reg_options = None
+    relu = 1
+
+    def __call__(self, output, target):
+        return self._on(output, target, None)
+
+    def _on(self, output, target, weight):
+        owner = output._owner
+        return criterion_call(self, (output._z,), target, weight, owner, owner is not None and owner.training,
+                              lambda dz: owner.backward(dz))[0]
+
+
+class CrossEntropyLoss(_HeadLoss):
+    """nn.CrossEntropyLoss on the model's Softmax output (audio_gru_whole.py:308), with torch's `weight`, `ignore_index` and
+    `label_smoothing` (reduction 'mean').  All defaults: dep_head_loss + dep_reduce_loss, the launches it always enqueued, and a label
+    -100 is out of range as it always was.  Any option set: dep_head_loss_ce, divided by sum_i live_i w[y_i] (_denominator); rows
+    whose label is ignore_index then count for nothing."""
+    kind = L.LOSS_CE_ON_SOFTMAX
+    target_dtype = 'int'
+
+    def __init__(self, weight=None, ignore_index=-100, label_smoothing=0.0, reduction='mean'):
+        self.options = CEOptions(weight, ignore_index, label_smoothing, reduction)
 
 
 class _RegLoss(_HeadLoss):
     """A regression criterion on the model's ReLU output: criterion(output, target, weight=None), the weighted mean over elements
     sum_i w_i sum_c l_ic / (C sum_i w_i) (all weights 1: torch's mean).  A row of weight 0 is an ignored row.  The forms
-    dep_head_loss computes (L1, SmoothL1 with beta 1) called without `weight` are _HeadLoss's call -- dep_head_loss + dep_reduce_loss,
-    the launches they always enqueued; everything else is dep_head_loss_reg + dep_reduce_loss / dep_reduce_loss_by."""
+    dep_head_loss computes (L1, SmoothL1 with beta 1) called without `weight` are dep_head_loss + dep_reduce_loss, the launches they
+    always enqueued; everything else is dep_head_loss_reg + dep_reduce_loss (_plain_kind)."""
     target_dtype = 'float'
 
     def __call__(self, output, target, weight=None):
-        opt = self.reg_options
-        if weight is None and opt.neutral:
-            return super().__call__(output, target)
-        owner = output._owner
-        z = output._z
-        B, Cc = z.shape
-        dev = z.device
-        t = torch.as_tensor(np.asarray(target) if not torch.is_tensor(target) else target)
-        t = t.to(device=dev, dtype=torch.float32).contiguous().view(B, Cc)
-        w_dev, w_host = opt.rows(weight, B, dev)
-        train = owner is not None and owner.training
-        norm = opt.denominator(w_dev, w_host, B, Cc, train)
-        rows = torch.empty(B, dtype=torch.float32, device=dev)
-        dz = torch.empty_like(z) if train else None
-        opt.head_loss(1, z, t, w_dev, rows, dz, norm)
-        val = torch.empty(1, dtype=torch.float32, device=dev)         # the reduce overwrites it
-        opt.reduce(rows, norm, val)
-        return Loss(val, (lambda: owner.backward(dz)) if train else None, reduce=train and parallel.world_size() > 1,
-                    health=getattr(owner, 'check_health', None), dz=dz)
+        return self._on(output, target, weight)
 
 
 class L1Loss(_RegLoss):
     """nn.L1Loss on the ReLU output (Regression/audio_bilstm_perm.py:251)."""
-    kind = L.LOSS_L1_RELU
 
     def __init__(self, reduction='mean'):
         self.reg_options = RegOptions('l1', reduction=reduction)
@@ -566,7 +553,6 @@ class L1Loss(_RegLoss):
 
 class SmoothL1Loss(_RegLoss):
     """nn.SmoothL1Loss(beta) on the ReLU output (Regression/text_bilstm_perm.py:247); beta = 0 is L1, as in torch."""
-    kind = L.LOSS_SMOOTHL1_RELU
 
     def __init__(self, beta=1.0, reduction='mean'):
         self.reg_options = RegOptions('smooth_l1', beta=beta, reduction=reduction)
