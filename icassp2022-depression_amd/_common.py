@@ -53,19 +53,37 @@ def load_checkpoint(model, optimizer, filename):
 
 
 def optim_options(config):
-    """The scripts' two optional config keys as keyword arguments of nn.Adam / nn.AdamW: `amsgrad` (default False) and `ema_decay`
-    (default None; d in [0, 1) keeps an average of the weights that evaluate() then measures and saves).  Both absent or at their
-    defaults: {} -- the optimizer built is the one it always was."""
+    """The scripts' optional config keys as keyword arguments of nn.Adam / nn.AdamW: `amsgrad` (default False), `ema_decay` (default
+    None; d in [0, 1) keeps an average of the weights that evaluate() then measures and saves), and the clipping options
+    `max_grad_value` (default None; c > 0 clamps the gradients' values inside the update), `clip_per_group` (default False; every
+    param group is clipped against its own norm -- a group's own bound goes into the dict get_param_group returns for it, under
+    'max_grad_norm'), `skip_nonfinite` (default False) and `count_skipped` (default True; False needs skip_nonfinite).  All absent
+    or at their defaults: {} -- the optimizer built is the one it always was."""
     amsgrad, d = config.get('amsgrad', False), config.get('ema_decay')
     if not isinstance(amsgrad, (bool, np.bool_)):
         raise ValueError(f'amsgrad must be True or False, got {amsgrad!r}')
-    if d is not None and (isinstance(d, bool) or not isinstance(d, (int, float, np.integer, np.floating)) or not 0.0 <= float(d) < 1.0):
+    number = lambda x: not isinstance(x, bool) and isinstance(x, (int, float, np.integer, np.floating))
+    if d is not None and (not number(d) or not 0.0 <= float(d) < 1.0):
         raise ValueError(f'ema_decay must be None or a number in [0, 1), got {d!r}')
     out = {}
     if amsgrad:
         out['amsgrad'] = True
     if d is not None:
         out['ema_decay'] = float(d)
+    c = config.get('max_grad_value')
+    if c is not None and (not number(c) or not 0.0 < float(c) < float('inf')):
+        raise ValueError(f'max_grad_value must be None or a finite number > 0, got {c!r}')
+    if c is not None:
+        out['max_grad_value'] = float(c)
+    flags = {}
+    for key, default in (('clip_per_group', False), ('skip_nonfinite', False), ('count_skipped', True)):
+        flags[key] = config.get(key, default)
+        if not isinstance(flags[key], (bool, np.bool_)):
+            raise ValueError(f'{key} must be True or False, got {flags[key]!r}')
+        if bool(flags[key]) != default:
+            out[key] = bool(flags[key])
+    if not flags['count_skipped'] and not flags['skip_nonfinite']:
+        raise ValueError('count_skipped=False needs skip_nonfinite=True')
     return out
 
 

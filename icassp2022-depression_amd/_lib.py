@@ -116,6 +116,9 @@ _SIGS = {
     'dep_adam_step_ext': (C.c_int, [_P, _P, _P, _P, C.c_long, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                     C.c_int, C.c_int, _P, _P, C.c_float, C.c_int, _P, _P, _P]),
     'dep_swap': (C.c_int, [_P, _P, C.c_long, _P]),
+    'dep_grad_clip_value': (C.c_int, [C.POINTER(_P), C.POINTER(C.c_long), C.c_int, C.c_float, _P]),
+    'dep_adam_step_opt': (C.c_int, [_P, _P, _P, _P, C.c_long, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                    C.c_int, C.c_int, _P, _P, C.c_float, C.c_int, _P, _P, _P, _P]),
     'dep_frame_window': (C.c_int, [_P, C.c_long, C.c_int, C.c_int, C.c_int, _P, _P]),
     'dep_power_spectrum': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
     'dep_log_floor': (C.c_int, [_P, _P, C.c_long, C.c_float, _P]),
@@ -424,6 +427,35 @@ def adam_step_ext(p, g, m, v, lr, b1, b2, eps, wd, decoupled, step, vmax=None, e
     check(load().dep_adam_step_ext(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, b1, b2, eps, wd, int(decoupled), int(step),
                                    C.byref(ext), _ptr(partials), float(max_norm), int(skip_nonfinite), _ptr(clip_out), _ptr(stats),
                                    stream()), 'dep_adam_step_ext')
+
+
+class AdamOpt(C.Structure):
+    """dep_adam_opt of include/dep_rnn.h."""
+    _fields_ = [('max_grad_value', C.c_float), ('ngroups', C.c_int), ('group', C.c_int), ('group_max_norm', C.POINTER(C.c_float)),
+                ('group_out', _P), ('landed_in', _P), ('landed_out', _P)]
+
+
+def adam_step_opt(p, g, m, v, lr, b1, b2, eps, wd, decoupled, step, vmax=None, ema=None, ema_decay=0.0, ema_first=False,
+                  partials=None, max_norm=0.0, skip_nonfinite=False, clip_out=None, stats=None, max_grad_value=None, ngroups=1, group=0,
+                  group_max_norms=None, group_out=None, landed_in=None, landed_out=None):
+    """dep_adam_step_opt: adam_step_ext's step of one range with the value clamp (`max_grad_value`), a norm per group (`partials` holds
+    `ngroups` slices, this range belongs to `group`, `group_max_norms` a list of the groups' bounds, `group_out` 2 * ngroups fp32 on the
+    device) and the device-side count of landed updates (`landed_in` / `landed_out`: one int32 each on the device).  One launch."""
+    ext = AdamExt(_ptr(vmax), _ptr(ema), float(ema_decay), int(bool(ema_first)))
+    bounds = None if group_max_norms is None else (C.c_float * len(group_max_norms))(*[float(b) for b in group_max_norms])
+    if bounds is not None and len(group_max_norms) != ngroups:
+        raise DepError(f'adam_step_opt: {len(group_max_norms)} bounds for {ngroups} groups')
+    opt = AdamOpt(0.0 if max_grad_value is None else float(max_grad_value), int(ngroups), int(group), bounds, _ptr(group_out),
+                  _ptr(landed_in), _ptr(landed_out))
+    check(load().dep_adam_step_opt(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, b1, b2, eps, wd, int(decoupled), int(step),
+                                   C.byref(ext), _ptr(partials), float(max_norm), int(skip_nonfinite), _ptr(clip_out), _ptr(stats),
+                                   C.byref(opt), stream()), 'dep_adam_step_opt')
+
+
+def grad_clip_value(ranges, clip_value):
+    """g = clamp(g, -clip_value, clip_value) in place over up to 16 contiguous fp32 device tensors (dep_grad_clip_value).  One launch."""
+    ptrs, cnts = _range_arrays(ranges)
+    check(load().dep_grad_clip_value(ptrs, cnts, len(ranges), float(clip_value), stream()), 'dep_grad_clip_value')
 
 
 def swap(a, b):

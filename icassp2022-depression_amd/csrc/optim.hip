@@ -1,10 +1,12 @@
 // The optimizer on the device: Adam / AdamW (dep_adam_step), global-norm gradient clipping (dep_grad_sqnorm, dep_adam_step_clipped,
 // dep_grad_clip_scale), gradient accumulation over micro-batches (dep_grad_accumulate), and AMSGrad plus a fused average of the
-// parameters (dep_adam_step_ext, dep_swap); include/dep_rnn.h.
+// parameters (dep_adam_step_ext, dep_swap), and the value clamp, per-group norms and the device-side count of landed updates
+// (dep_adam_step_opt, dep_grad_clip_value); include/dep_rnn.h.
 //
 // Two equalities hold by construction.  adam_kernel and adam_clipped_kernel both call adam_element, the one Adam expression, so a clip
 // coefficient of one gives the plain step's bits; adam_ext_kernel and adam_clipped_ext_kernel are the same two kernel bodies around
-// adam_element<true>, which adds the running maximum and the average to that expression and repeats none of it.  grad_sqnorm_kernel
+// adam_element<true>, which adds the running maximum and the average to that expression and repeats none of it; adam_opt_kernel and
+// adam_opt_ext_kernel are a third body around the same two instances, whose clamp and coefficients only prepare gv.  grad_sqnorm_kernel
 // and grad_accumulate_kernel are both gn_walk<> over their ranges, so the partial sums the accumulate launch leaves are the ones
 // dep_grad_sqnorm forms from the accumulator.
 //
@@ -133,8 +135,8 @@ __global__ __launch_bounds__(GN_THREADS) void grad_accumulate_kernel(AccumRanges
 //     coef = (float) min(1, max_norm / (norm + 1e-6))          (division in double, ONE rounding to fp32; a NaN quotient stays NaN)
 // max_norm <= 0 ("measure only", +inf arrives here as 0): coef = 1.
 struct ClipCoef { float coef; double norm; bool finite; };
-__device__ __forceinline__ ClipCoef gn_coef(const double* __restrict__ partials, double max_norm, double* red) {
-    const double S = gn_block_sum(partials[threadIdx.x], red);     // blockDim.x == GN_THREADS == GN_SLOTS
+// from S itself: the one place the formula stands (adam_opt_body has S of every group in hand and needs their sum as well)
+__device__ __forceinline__ ClipCoef gn_coef_of(double S, double max_norm) {
     ClipCoef c;
     c.norm = sqrt(S);
     c.finite = S - S == 0.0;                                        // false for inf and NaN
@@ -145,6 +147,9 @@ __device__ __forceinline__ ClipCoef gn_coef(const double* __restrict__ partials,
         c.coef = 1.0f;
     }
     return c;
+}
+__device__ __forceinline__ ClipCoef gn_coef(const double* __restrict__ partials, double max_norm, double* red) {
+    return gn_coef_of(gn_block_sum(partials[threadIdx.x], red), max_norm);     // blockDim.x == GN_THREADS == GN_SLOTS
 }
 // clip_out = [coef, norm, finite, 0]; stats (doubles) = [steps, clipped steps, skipped steps, largest finite norm]
 __device__ __forceinline__ void gn_report(const ClipCoef& c, bool skipped, float* clip_out, double* stats) {
@@ -160,10 +165,23 @@ __device__ __forceinline__ void gn_report(const ClipCoef& c, bool skipped, float
 // ------------------------------------------------------------------------------ Adam / AdamW
 // The bias correction of update `step`, as the kernels take it.
 struct AdamBias { float step_size, inv_sqrt_bc2; };
-inline AdamBias adam_bias(float lr, float beta1, float beta2, int step) {
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+// from the two powers beta1^t and beta2^t (double): each factor is rounded to fp32 once
+__host__ __device__ inline AdamBias adam_bias_of(float lr, double pow1, double pow2) {
+    const double bc1 = 1.0 - pow1;
+    const double bc2 = 1.0 - pow2;
     return {(float)((double)lr / bc1), (float)(1.0 / sqrt(bc2))};
+}
+inline AdamBias adam_bias(float lr, float beta1, float beta2, int step) {
+    return adam_bias_of(lr, pow((double)beta1, (double)step), pow((double)beta2, (double)step));
+}
+// beta^t on the device (the landed count t is known only there): the integer power by squaring, in double.  Neither a device pow nor a
+// running product: a product kept across steps would be one more word of state per (group, beta) pair that a checkpoint has to carry
+// and a skipped step must not touch, and ocml's pow is a few hundred instructions whose last bit is not the host's pow's either.  This
+// is at most 2 * 31 multiplications, each within 2^-53: beta^t within 7e-15 relative, far below the fp32 rounding of the factors.
+__device__ __forceinline__ double ipow(double b, int t) {
+    double r = 1.0;
+    for (; t > 0; t >>= 1) { if (t & 1) r *= b; b *= b; }
+    return r;
 }
 // What dep_adam_step_ext adds, as the kernels take it: pointers are NULL for a part that is off (uniform over the launch).
 struct AdamExt { float* vmax; float* ema; float ema_w; int ema_first; };   // ema_w = 1 - decay
@@ -252,6 +270,106 @@ __global__ __launch_bounds__(GN_THREADS) void adam_clipped_ext_kernel(float* __r
                                                                       int skip_nonfinite, float* clip_out, double* stats, AdamExt x) {
     adam_clipped_body<true>(p, g, m, v, n, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2, partials, max_norm, skip_nonfinite,
                             clip_out, stats, x);
+}
+
+// ------------------------------------------------------------------------------ value clamp, per-group norms, landed count
+constexpr int GN_MAXG = 8;                 // param groups with a norm of their own
+// Tensor.clamp_(-c, c) by comparisons: a NaN fails both and stays, +-inf becomes +-c, -0.0f stays -0.0f
+__device__ __forceinline__ float clamp_value(float x, float c) { return x > c ? c : (x < -c ? -c : x); }
+// What dep_adam_step_opt adds, as the kernels take it (everything uniform over the launch).
+struct AdamOpt {
+    float clamp;                           // > 0: gv = clamp_value(g * coef, clamp); 0: off
+    int ngroups, group;                    // partials holds ngroups slices of GN_SLOTS doubles; this launch updates a range of `group`
+    double max_norm[GN_MAXG];              // kernel_max_norm of every group's bound
+    float* group_out;                      // [coef_g, norm_g] per group, or NULL: written by workgroup 0 (the step's first launch)
+    const int* landed_in;                  // updates landed before this step, or NULL: the bias factors are the host's
+    int* landed_out;                       // where workgroup 0 leaves the count after this step, or NULL; never landed_in
+};
+// The body of dep_adam_step_opt's kernels (GN_THREADS threads, AC_PER_THREAD elements each, as adam_clipped_body).  partials == NULL:
+// coefficient 1, no record.  Otherwise every workgroup sums EVERY group's slice with gn_coef's tree (a __syncthreads between two
+// uses of `red`): its own group's coefficient scales g, "any S_g not finite" skips the whole step, and workgroup 0 writes the record
+// -- the top level as adam_clipped_body writes it, from the smallest coefficient and sqrt(sum of S_g); one group: those ARE
+// gn_coef's values, and the bits of adam_clipped_body follow.  The landed count is read from landed_in by everyone and written to
+// landed_out (another word) by workgroup 0: nothing reads what a workgroup of this launch, or of another launch of the step, writes.
+template <bool EXT>
+__device__ __forceinline__ void adam_opt_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                              float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
+                                              int decoupled, float step_size, float inv_sqrt_bc2,
+                                              const double* __restrict__ partials, int skip_nonfinite, float* clip_out, double* stats,
+                                              const AdamOpt& o, const AdamExt& x) {
+    __shared__ double red[4];
+    const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
+    float coef = 1.0f;
+    bool skipped = false;
+    if (partials) {                                                // uniform over the grid
+        ClipCoef top{1.0f, 0.0, true};
+        double Ssum = 0.0;
+        bool any_nan = false;
+        float nan_coef = 0.f;
+        for (int k = 0; k < o.ngroups; ++k) {
+            if (k) __syncthreads();                                // everyone has read red[] of the previous group
+            const double S = gn_block_sum(partials[(long)k * GN_SLOTS + threadIdx.x], red);
+            const ClipCoef c = gn_coef_of(S, o.max_norm[k]);
+            if (k == o.group) coef = c.coef;
+            if (c.coef != c.coef) { any_nan = true; nan_coef = c.coef; }               // (S NaN, no skip)
+            else if (c.coef < top.coef) top.coef = c.coef;                             // the smallest; none is above 1
+            top.finite = top.finite && c.finite;
+            Ssum += S;
+            if (writer && o.group_out) { o.group_out[2 * k] = c.coef; o.group_out[2 * k + 1] = (float)c.norm; }
+        }
+        top.norm = sqrt(Ssum);
+        skipped = skip_nonfinite && !top.finite;
+        if (writer) {
+            // "clipped" counts a step in which any group's coefficient is below 1; a NaN coefficient of any group then shows in
+            // clip_out[0] whatever the others are (one group: gn_report's own value, NaN < 1 being false there as well)
+            gn_report(top, skipped, clip_out, stats);
+            if (any_nan && clip_out) clip_out[0] = nan_coef;
+        }
+    }
+    if (o.landed_in) {
+        const int landed = *o.landed_in;
+        if (writer && o.landed_out) *o.landed_out = skipped ? landed : landed + 1;
+        if (!skipped) {                                            // this update lands as number landed + 1
+            const AdamBias bc = adam_bias_of(lr, ipow((double)b1, landed + 1), ipow((double)b2, landed + 1));
+            step_size = bc.step_size; inv_sqrt_bc2 = bc.inv_sqrt_bc2;
+        }
+    }
+    if (skipped) return;                                           // p, m, v (and vmax, ema) untouched
+    const float cl = o.clamp;
+    const long base = (long)blockIdx.x * (GN_THREADS * AC_PER_THREAD) + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < AC_PER_THREAD; ++k) {
+        const long i = base + (long)k * GN_THREADS;
+        if (i >= n) break;
+        const float pv = p[i];
+        float gv = g[i] * coef;
+        if (cl > 0.f) gv = clamp_value(gv, cl);
+        adam_element<EXT>(pv, gv, p, m, v, i, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2, x);
+    }
+}
+__global__ __launch_bounds__(GN_THREADS) void adam_opt_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                              float* __restrict__ v, long n, float lr, float b1, float b2, float eps,
+                                                              float wd, int decoupled, float step_size, float inv_sqrt_bc2,
+                                                              const double* __restrict__ partials, int skip_nonfinite,
+                                                              float* clip_out, double* stats, AdamOpt o) {
+    adam_opt_body<false>(p, g, m, v, n, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2, partials, skip_nonfinite, clip_out,
+                         stats, o, AdamExt{});
+}
+__global__ __launch_bounds__(GN_THREADS) void adam_opt_ext_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                  float* __restrict__ m, float* __restrict__ v, long n, float lr,
+                                                                  float b1, float b2, float eps, float wd, int decoupled,
+                                                                  float step_size, float inv_sqrt_bc2,
+                                                                  const double* __restrict__ partials, int skip_nonfinite,
+                                                                  float* clip_out, double* stats, AdamOpt o, AdamExt x) {
+    adam_opt_body<true>(p, g, m, v, n, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2, partials, skip_nonfinite, clip_out,
+                        stats, o, x);
+}
+
+// g = clamp_value(g, c) in place over the ranges, blockIdx.y = range (torch.nn.utils.clip_grad_value_)
+__global__ __launch_bounds__(GN_THREADS) void grad_clip_value_kernel(GradRangesRW R, float c) {
+    float* __restrict__ gp = R.ptr[blockIdx.y];
+    const long n = R.n[blockIdx.y], stride = (long)gridDim.x * GN_THREADS;
+    for (long i = (long)blockIdx.x * GN_THREADS + threadIdx.x; i < n; i += stride) gp[i] = clamp_value(gp[i], c);
 }
 
 // a[i] <-> b[i] as 32-bit words (no arithmetic touches them): four per thread where four are left, one by one in the tail
@@ -375,13 +493,10 @@ extern "C" int dep_adam_step_clipped(float* p, const float* g, float* m, float* 
                                skip_nonfinite, clip_out, stats, stream);
 }
 
-extern "C" int dep_adam_step_ext(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
-                                 float weight_decay, int decoupled, int step, const dep_adam_ext* ext, const double* partials,
-                                 float max_norm, int skip_nonfinite, float* clip_out, double* stats, void* stream) {
-    DEP_CHECK_ARG(p && g && m && v && n > 0 && step >= 1);
-    if (partials) DEP_CHECK_ARG(max_norm == max_norm);
-    AdamExt x{};
-    bool on = false;
+// dep_adam_ext as the kernels take it, after its checks; on = false: nothing of it is switched on
+static int adam_ext_args(const float* p, const float* g, const float* m, const float* v, long n, const dep_adam_ext* ext, AdamExt& x,
+                         bool& on) {
+    on = false;
     if (ext && (ext->vmax || ext->ema)) {
         const float* const others[4] = {p, g, m, v};
         if (ext->vmax)
@@ -395,11 +510,76 @@ extern "C" int dep_adam_step_ext(float* p, const float* g, float* m, float* v, l
         x = AdamExt{ext->vmax, ext->ema, 1.0f - ext->ema_decay, (ext->ema_first || ext->ema_decay == 0.f) ? 1 : 0};
         on = true;
     }
+    return DEP_OK;
+}
+
+extern "C" int dep_adam_step_ext(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, int decoupled, int step, const dep_adam_ext* ext, const double* partials,
+                                 float max_norm, int skip_nonfinite, float* clip_out, double* stats, void* stream) {
+    DEP_CHECK_ARG(p && g && m && v && n > 0 && step >= 1);
+    if (partials) DEP_CHECK_ARG(max_norm == max_norm);
+    AdamExt x{};
+    bool on = false;
+    if (int rc = adam_ext_args(p, g, m, v, n, ext, x, on)) return rc;
     // nothing switched on: the launches (and so the bits) of the two entry points above
     if (partials)
         return adam_clipped_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, decoupled, step, on ? &x : nullptr, partials,
                                    max_norm, skip_nonfinite, clip_out, stats, stream);
     return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, decoupled, step, on ? &x : nullptr, stream);
+}
+
+extern "C" int dep_adam_step_opt(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, int decoupled, int step, const dep_adam_ext* ext, const double* partials,
+                                 float max_norm, int skip_nonfinite, float* clip_out, double* stats, const dep_adam_opt* opt,
+                                 void* stream) {
+    const bool off = !opt || (opt->max_grad_value == 0.f && opt->ngroups == 1 && opt->group == 0 && !opt->group_out &&
+                              !opt->landed_in && !opt->landed_out);
+    if (off)                                                       // dep_adam_step_ext: its checks, its launches, its bits
+        return dep_adam_step_ext(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, decoupled, step, ext, partials, max_norm,
+                                 skip_nonfinite, clip_out, stats, stream);
+    DEP_CHECK_ARG(p && g && m && v && n > 0 && step >= 1);
+    DEP_CHECK_ARG(opt->max_grad_value >= 0.f && opt->max_grad_value <= 3.402823466e38f);      // false for a NaN
+    DEP_CHECK_ARG(opt->ngroups >= 1 && opt->ngroups <= GN_MAXG && opt->group >= 0 && opt->group < opt->ngroups);
+    DEP_CHECK_ARG(opt->ngroups == 1 || (partials && opt->group_max_norm));
+    DEP_CHECK_ARG(!opt->group_out || partials);
+    DEP_CHECK_ARG(!opt->landed_in || (partials && skip_nonfinite));
+    DEP_CHECK_ARG(!opt->landed_out || (opt->landed_in && opt->landed_out != opt->landed_in));
+    AdamOpt o{};
+    o.clamp = opt->max_grad_value; o.ngroups = opt->ngroups; o.group = opt->group;
+    o.group_out = opt->group_out; o.landed_in = opt->landed_in; o.landed_out = opt->landed_out;
+    if (partials) {
+        for (int k = 0; k < o.ngroups; ++k) {
+            const float mx = opt->group_max_norm ? opt->group_max_norm[k] : max_norm;      // (NULL: ngroups == 1, checked above)
+            DEP_CHECK_ARG(mx == mx);
+            o.max_norm[k] = kernel_max_norm(mx);
+        }
+    }
+    AdamExt x{};
+    bool on = false;
+    if (int rc = adam_ext_args(p, g, m, v, n, ext, x, on)) return rc;
+    const AdamBias bc = adam_bias(lr, beta1, beta2, step);          // replaced on the device when landed_in is given
+    const dim3 grid(dep_cdiv(n, GN_THREADS * AC_PER_THREAD));
+    if (on)
+        DEP_LAUNCH(adam_opt_ext_kernel, grid, dim3(GN_THREADS), 0, S_, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, decoupled,
+                   bc.step_size, bc.inv_sqrt_bc2, partials, partials ? skip_nonfinite : 0, clip_out, stats, o, x);
+    else
+        DEP_LAUNCH(adam_opt_kernel, grid, dim3(GN_THREADS), 0, S_, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, decoupled,
+                   bc.step_size, bc.inv_sqrt_bc2, partials, partials ? skip_nonfinite : 0, clip_out, stats, o);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+
+extern "C" int dep_grad_clip_value(float* const* bufs, const long* counts, int nranges, float clip_value, void* stream) {
+    if (int rc = check_ranges(bufs, counts, nranges)) return rc;
+    DEP_CHECK_ARG(clip_value > 0.f && clip_value <= 3.402823466e38f);                          // false for a NaN
+    GradRangesRW R{};
+    long mx = 0;
+    for (int r = 0; r < nranges; ++r) { R.ptr[r] = bufs[r]; R.n[r] = counts[r]; if (counts[r] > mx) mx = counts[r]; }
+    R.count = nranges;
+    int gx = dep_cdiv(mx, GN_THREADS * 4); if (gx > 512) gx = 512;
+    DEP_LAUNCH(grad_clip_value_kernel, dim3(gx, nranges), dim3(GN_THREADS), 0, S_, R, clip_value);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
 }
 
 extern "C" int dep_swap(float* a, float* b, long n, void* stream) {

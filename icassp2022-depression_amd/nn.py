@@ -591,7 +591,7 @@ class _AdamBase:
     decoupled = False
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=None, max_grad_norm=None, skip_nonfinite=False,
-                 accumulate_steps=1, amsgrad=False, ema_decay=None):
+                 accumulate_steps=1, amsgrad=False, ema_decay=None, max_grad_value=None, clip_per_group=False, count_skipped=True):
         """max_grad_norm: clip the GLOBAL 2-norm of the gradients of all groups to it inside the update (torch's
         clip_grad_norm_(all parameters, max_grad_norm) in front of step(), without its host read; None = no clipping).
         skip_nonfinite: a step whose gradient norm is inf / NaN leaves parameters and moments untouched (it still counts in the bias
@@ -604,8 +604,26 @@ class _AdamBase:
         ema_decay: d in [0, 1) keeps an average of the parameters, avg += (1 - d) * (p - avg) after every update (torch's
         AveragedModel with get_ema_multi_avg_fn(d): no bias correction, the first update copies), in one flat buffer per owner module
         laid out like its parameters; averaged() puts it in the parameters' place.  Either option makes every range's launch a
-        dep_adam_step_ext -- the same number of launches; with both at their defaults the launches are the ones above."""
+        dep_adam_step_ext -- the same number of launches; with both at their defaults the launches are the ones above.
+        max_grad_value: c > 0 clamps every element of g * coef to [-c, c] inside the update launch (torch's clip_grad_value_ between
+        clip_grad_norm_ and step(); a NaN stays NaN); on its own it adds no launch and measures no norm.
+        clip_per_group: every param group is clipped against the 2-norm of ITS gradients, bound group['max_grad_norm'] (default: the
+        optimizer's max_grad_norm; None: measured, not clipped) -- one dep_grad_sqnorm per group with a gradient (at most 8), then
+        the one launch per range.  skip_nonfinite stays a decision about the whole step: skipped iff any group's norm is not finite.
+        count_skipped=False (needs skip_nonfinite): a skipped step does not advance the step number of the bias correction, as in
+        the torch loop that calls step() only on a finite norm; the count of landed updates lives on the device (landed_steps()).
+        Any of the three makes every range's launch a dep_adam_step_opt; all at their defaults: the launches above, unchanged."""
         params = list(params)
+        if max_grad_value is not None and not (_is_number(max_grad_value) and 0.0 < float(max_grad_value) < float('inf')):
+            raise ValueError(f'max_grad_value must be None or a finite number > 0, got {max_grad_value!r}')
+        self.max_grad_value = None if max_grad_value is None else float(max_grad_value)
+        self.clip_per_group = bool(clip_per_group)
+        self.count_skipped = bool(count_skipped)
+        if not self.count_skipped and not skip_nonfinite:
+            raise ValueError('count_skipped=False needs skip_nonfinite=True: without it no step is ever skipped')
+        self._clip2 = None        # device side of the new options: (partials of 8 groups, [coef, norm] per group, two landed counts)
+        self._landed_at = 0       # which of the two landed counts the next step reads
+        self._group_slots = []    # param_groups indices of the slices the last per-group step measured
         if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError(f'ema_decay must be None or a number in [0, 1), got {ema_decay!r}')
         self.amsgrad = bool(amsgrad)
@@ -635,7 +653,14 @@ class _AdamBase:
             g['params'] = list(g['params'])
             g.setdefault('lr', lr); g.setdefault('betas', betas); g.setdefault('eps', eps)
             g.setdefault('weight_decay', default_wd)
+            if 'max_grad_norm' in g:
+                if not self.clip_per_group:
+                    raise ValueError("a param group carries 'max_grad_norm' but clip_per_group is False: it would be ignored")
+                if g['max_grad_norm'] is not None and not float(g['max_grad_norm']) >= 0.0:
+                    raise ValueError(f"a group's max_grad_norm must be None or a non-negative number, got {g['max_grad_norm']!r}")
             self.param_groups.append(g)
+        if self.clip_per_group and not self.skip_nonfinite and all(self._bound_of(g) is None for g in self.param_groups):
+            raise ValueError('clip_per_group=True with no max_grad_norm anywhere and skip_nonfinite=False measures norms nobody uses')
         self._step = 0
         self._state = {}          # id(module) -> (m, v)
         if self.accumulate_steps > 1:                      # data parallel: ONE gradient exchange per update, of the accumulator
@@ -660,7 +685,16 @@ class _AdamBase:
         return [(g, _grad_ranges(g['params'])) for g in self.param_groups]
 
     def _clips(self):
-        return self.max_grad_norm is not None or self.skip_nonfinite
+        return self.max_grad_norm is not None or self.skip_nonfinite or self.clip_per_group
+
+    def _bound_of(self, group):
+        """The group's own bound under clip_per_group (None: measured, not clipped)."""
+        b = group.get('max_grad_norm', self.max_grad_norm)
+        return None if b is None else float(b)
+
+    def _options(self):
+        """True when max_grad_value, clip_per_group or count_skipped=False is on: the launches are dep_adam_step_opt's."""
+        return self.max_grad_value is not None or self.clip_per_group or not self.count_skipped
 
     @staticmethod
     def _spans(plan, what):
@@ -676,7 +710,7 @@ class _AdamBase:
             return self._micro_step()
         self._step += 1
         L.order_note('optimizer step')
-        self._update(self._plan(), lambda owner: owner._flat_grad, 'clipping' if self._clips() else None)
+        self._update(self._plan(), lambda owner: owner._flat_grad, 'clipping' if self._clips() and not self.clip_per_group else None)
 
     def _update(self, plan, grad_of, what, have_partials=False):
         """THE update, of every path: one launch per range of `plan`, reading grad_of(owner) -- the owner's _flat_grad or its accumulator.
@@ -689,6 +723,8 @@ class _AdamBase:
         spans = self._spans(plan, what)
         if not spans:
             return
+        if self._options():
+            return self._update_opt(plan, grad_of, have_partials)
         clip = self._clips()
         if clip:
             partials, clip_out, stats = self._clip_buffers(spans[0][0]._flat_grad.device)
@@ -718,6 +754,74 @@ class _AdamBase:
                 first = False
         if ext:
             self._ema_updates += 1
+
+    def _update_opt(self, plan, grad_of, have_partials):
+        """_update with max_grad_value, clip_per_group or count_skipped=False: the same launches in the same order, each a
+        dep_adam_step_opt.  Per group: one dep_grad_sqnorm per group that holds a gradient, in param_groups order, into that group's
+        slice of one buffer (the accumulate launch's partials describe all ranges together and are not asked for), then every launch
+        reads all slices and takes its own group's coefficient.  The landed count: every launch of this step reads one of two device
+        words, the first launch -- the one that writes the record -- leaves the new count in the other, and the next step reads
+        that one; an update that launches nothing does not turn them."""
+        active = [(gi, g, rs) for gi, (g, rs) in enumerate(plan) if rs]
+        dev = active[0][2][0][0]._flat_grad.device
+        clip = self._clips()
+        partials = clip_out = stats = bounds = group_out = landed = None
+        ngroups, max_norm = 1, 0.0
+        if clip:
+            partials, clip_out, stats = self._clip_buffers(dev)
+            max_norm = 0.0 if self.max_grad_norm is None else self.max_grad_norm
+        if self.clip_per_group:
+            ngroups = len(active)
+            if ngroups > _MAX_CLIP_GROUPS:
+                raise L.DepError(f'clip_per_group covers at most {_MAX_CLIP_GROUPS} param groups with a gradient, this optimizer has {ngroups}')
+            for _, _, rs in active:
+                if len(rs) > _MAX_CLIP_RANGES:
+                    raise L.DepError(f'gradient clipping covers at most {_MAX_CLIP_RANGES} contiguous gradient ranges per group, a group has {len(rs)}')
+            partials, group_out, _ = self._clip2_buffers(dev)
+            slots = L.grad_norm_slots()
+            for k, (_, g, rs) in enumerate(active):
+                L.grad_sqnorm([grad_of(o)[s:e] for o, s, e in rs], partials[k * slots:(k + 1) * slots])
+            bounds = [0.0 if self._bound_of(g) is None else self._bound_of(g) for _, g, _ in active]
+            max_norm = bounds[0] if ngroups == 1 else 0.0       # the bounds are the groups' own; the optimizer's is only their default
+            self._group_slots = [gi for gi, _, _ in active]
+        elif clip and not have_partials:
+            L.grad_sqnorm([grad_of(o)[s:e] for o, s, e in self._spans(plan, None)], partials)
+        if not self.count_skipped:
+            landed = self._clip2_buffers(dev)[2]
+        ext = self._extended()
+        first = True
+        for k, (_, g, rs) in enumerate(active):
+            b1, b2 = g['betas']
+            for owner, s, e in rs:
+                m, v = self._state_of(owner)
+                vmax, ema = self._ext_of(owner) if ext else (None, None)
+                at = self._landed_at
+                L.adam_step_opt(owner._flat[s:e], grad_of(owner)[s:e], m[s:e], v[s:e], g['lr'], b1, b2, g['eps'], g['weight_decay'],
+                                self.decoupled, self._step, vmax=None if vmax is None else vmax[s:e], ema=None if ema is None else ema[s:e],
+                                ema_decay=self.ema_decay or 0.0, ema_first=ext and self._ema_updates == 0, partials=partials,
+                                max_norm=max_norm, skip_nonfinite=self.skip_nonfinite, clip_out=clip_out if first else None,
+                                stats=stats if first else None, max_grad_value=self.max_grad_value, ngroups=ngroups,
+                                group=k if self.clip_per_group else 0, group_max_norms=bounds, group_out=group_out if first else None,
+                                landed_in=None if landed is None else landed[at:at + 1],
+                                landed_out=None if landed is None or not first else landed[1 - at:2 - at])
+                first = False
+        if landed is not None:
+            self._landed_at = 1 - self._landed_at
+        if ext:
+            self._ema_updates += 1
+
+    def _clip2_buffers(self, dev):
+        """(partials of _MAX_CLIP_GROUPS groups, [coef, norm] per group, the two landed counts): made by the first step that needs them."""
+        if self._clip2 is None:
+            self._clip2 = (torch.empty(_MAX_CLIP_GROUPS * L.grad_norm_slots(), dtype=torch.float64, device=dev),
+                           torch.zeros(2 * _MAX_CLIP_GROUPS, dtype=torch.float32, device=dev), torch.zeros(2, dtype=torch.int32, device=dev))
+        return self._clip2
+
+    def landed_steps(self):
+        """The number of updates that landed (count_skipped=False): read from the device, a host synchronisation like grad_stats()."""
+        if self.count_skipped:
+            raise L.DepError('landed_steps() needs an optimizer built with count_skipped=False')
+        return 0 if self._clip2 is None else int(self._clip2[2][self._landed_at].item())
 
     # -- AMSGrad and the average of the parameters (amsgrad, ema_decay) -----------------------------------------------
     def _extended(self):
@@ -787,11 +891,14 @@ class _AdamBase:
         for o in self._owners():
             mv, x = self._state.get(id(o)), self._ext.get(id(o), (None, None))
             state.append({'numel': int(o._flat.numel()), 'm': cpu(mv and mv[0]), 'v': cpu(mv and mv[1]), 'vmax': cpu(x[0]), 'ema': cpu(x[1])})
-        return {'step': self._step, 'ema_updates': self._ema_updates, 'amsgrad': self.amsgrad, 'ema_decay': self.ema_decay,
-                'decoupled': bool(self.decoupled), 'accumulate_steps': self.accumulate_steps,
-                'param_groups': [{'lr': g['lr'], 'betas': tuple(g['betas']), 'eps': g['eps'], 'weight_decay': g['weight_decay'],
-                                  'numel': [int(p.numel) for p in g['params']]} for g in self.param_groups],
-                'state': state}
+        sd = {'step': self._step, 'ema_updates': self._ema_updates, 'amsgrad': self.amsgrad, 'ema_decay': self.ema_decay,
+              'decoupled': bool(self.decoupled), 'accumulate_steps': self.accumulate_steps,
+              'param_groups': [{'lr': g['lr'], 'betas': tuple(g['betas']), 'eps': g['eps'], 'weight_decay': g['weight_decay'],
+                                'numel': [int(p.numel) for p in g['params']]} for g in self.param_groups],
+              'state': state}
+        if not self.count_skipped:
+            sd['landed'] = self.landed_steps()          # present when and only when count_skipped is False
+        return sd
 
     def load_state_dict(self, sd):
         """Into an optimizer built the same way over an identically built model.  The groups' hyper-parameters and ema_decay's value
@@ -801,6 +908,8 @@ class _AdamBase:
             raise ValueError(f"load_state_dict: amsgrad is {sd['amsgrad']} in the checkpoint, {self.amsgrad} in this optimizer")
         if (sd['ema_decay'] is None) != (self.ema_decay is None):
             raise ValueError(f"load_state_dict: ema_decay is {sd['ema_decay']} in the checkpoint, {self.ema_decay} in this optimizer")
+        if ('landed' in sd) == self.count_skipped:
+            raise ValueError(f"load_state_dict: count_skipped is {'landed' not in sd} in the checkpoint, {self.count_skipped} in this optimizer")
         if bool(sd['decoupled']) != bool(self.decoupled):
             raise ValueError('load_state_dict: decoupled weight decay (AdamW) in one of checkpoint and optimizer, not in the other')
         owners = self._owners()
@@ -825,6 +934,8 @@ class _AdamBase:
             g.update(lr=h['lr'], betas=tuple(h['betas']), eps=h['eps'], weight_decay=h['weight_decay'])
         self.ema_decay = sd['ema_decay']
         self._step, self._ema_updates, self._pending = int(sd['step']), int(sd['ema_updates']), 0
+        if not self.count_skipped:                       # both words: whichever the next step reads holds the count
+            self._clip2_buffers(owners[0]._flat_grad.device)[2].fill_(int(sd['landed']))
 
     # -- accumulation over micro-batches (accumulate_steps > 1) -------------------------------------------------------
     @property
@@ -866,7 +977,7 @@ class _AdamBase:
                 self._accum[id(owner)] = torch.zeros_like(owner._flat_grad)
         boundary = self._pending + 1 == self.accumulate_steps
         partials = None
-        if boundary and self._clips() and parallel.transport() == 'none':   # (an exchange follows otherwise: the norm is the reduced sums')
+        if boundary and self._clips() and not self.clip_per_group and parallel.transport() == 'none':   # (an exchange follows otherwise: the norm is the reduced sums')
             partials = self._clip_buffers(spans[0][0]._flat_grad.device)[0]
         L.grad_accumulate([self._accum[id(o)][s:e] for o, s, e in spans], [o._flat_grad[s:e] for o, s, e in spans], 1.0, first, partials)
         self._pending += 1
@@ -897,14 +1008,36 @@ class _AdamBase:
         steps / clipped / skipped count optimizer steps (clipped: coefficient < 1; skipped: non-finite norm under skip_nonfinite);
         max_norm is the largest finite gradient norm seen, last_norm / last_coef / last_finite describe the latest step."""
         if self._clip is None:
-            return {'steps': 0, 'clipped': 0, 'skipped': 0, 'max_norm': 0.0, 'last_norm': None, 'last_coef': None, 'last_finite': None}
+            out = {'steps': 0, 'clipped': 0, 'skipped': 0, 'max_norm': 0.0, 'last_norm': None, 'last_coef': None, 'last_finite': None}
+            if self.clip_per_group:
+                out['groups'] = self._group_stats()
+            return out
         _, clip_out, stats = self._clip
         st, co = stats.tolist(), clip_out.tolist()
-        return {'steps': int(st[0]), 'clipped': int(st[1]), 'skipped': int(st[2]), 'max_norm': float(st[3]),
-                'last_norm': float(co[1]), 'last_coef': float(co[0]), 'last_finite': bool(co[2])}
+        out = {'steps': int(st[0]), 'clipped': int(st[1]), 'skipped': int(st[2]), 'max_norm': float(st[3]),
+               'last_norm': float(co[1]), 'last_coef': float(co[0]), 'last_finite': bool(co[2])}
+        if self.clip_per_group:
+            out['groups'] = self._group_stats()
+        return out
+
+    def _group_stats(self):
+        """grad_stats()['groups']: per param group the norm and the coefficient of the latest step (None for a group that held no
+        gradient in it); last_norm / last_coef at the top are then sqrt(sum of S_g) and the smallest coefficient."""
+        out = [{'last_norm': None, 'last_coef': None} for _ in self.param_groups]
+        if self._clip2 is not None:
+            rec = self._clip2[1].tolist()
+            for k, gi in enumerate(self._group_slots):
+                out[gi] = {'last_norm': float(rec[2 * k + 1]), 'last_coef': float(rec[2 * k])}
+        return out
 
 
 _MAX_CLIP_RANGES = 16          # dep_grad_sqnorm takes up to 16 ranges per launch (include/dep_rnn.h)
+_MAX_CLIP_GROUPS = 8           # dep_adam_step_opt reads up to 8 groups' partial sums per launch
+
+
+def _is_number(x):
+    """A real number, not a bool and not a string: the check _common.optim_options applies to the same values."""
+    return not isinstance(x, (bool, np.bool_)) and isinstance(x, (int, float, np.integer, np.floating))
 
 
 def _grad_ranges(params):
@@ -964,6 +1097,23 @@ def clip_grad_norm_(parameters, max_norm):
     L.grad_sqnorm(grads, partials)
     L.grad_clip_scale(grads, partials, float(max_norm), clip_out)
     return GradNorm(clip_out)
+
+
+def clip_grad_value_(parameters, clip_value):
+    """torch.nn.utils.clip_grad_value_(parameters, clip_value) for hand-written loops: clamps the gradients of `parameters` in place to
+    [-clip_value, clip_value] in one launch (dep_grad_clip_value) over their merged ranges; a NaN stays NaN.  Parameters whose grad is
+    None are left out; nothing is launched when none holds a gradient.  Training loops that step with nn.Adam / nn.AdamW pass
+    max_grad_value to the optimizer instead: that clamps inside the update and costs no launch and no pass over the gradients."""
+    if not (_is_number(clip_value) and 0.0 < float(clip_value) < float('inf')):
+        raise ValueError(f'clip_value must be a finite number > 0, got {clip_value!r}')
+    if isinstance(parameters, Parameter):
+        parameters = [parameters]
+    rs = _grad_ranges(list(parameters))
+    if not rs:
+        return
+    if len(rs) > _MAX_CLIP_RANGES:
+        raise L.DepError(f'clip_grad_value_ covers at most {_MAX_CLIP_RANGES} contiguous gradient ranges, got {len(rs)}')
+    L.grad_clip_value([owner._flat_grad[s:e] for owner, s, e in rs], float(clip_value))
 
 
 class Adam(_AdamBase):

@@ -473,7 +473,7 @@ int dep_adam_step(float* p, const float* g, float* m, float* v, long n, float lr
  *                           with ONE rounding to fp32; g is not written.  coef == 1 gives dep_adam_step's bits.  max_norm <= 0
  *                           or +inf: measure only (coef = 1).  skip_nonfinite != 0 and S not finite: p, m, v are left untouched
  *                           bit for bit; the caller's step number still advances, i.e. a skipped step counts in the bias
- *                           correction.  skip_nonfinite == 0: the arithmetic follows (coef = 0 for S = inf, NaN for S = NaN).
+ *                           correction (dep_adam_step_opt's landed count is the form in which it does not).  skip_nonfinite == 0: the arithmetic follows (coef = 0 for S = inf, NaN for S = NaN).
  *                           clip_out (4 floats, or NULL) = [coef, norm, S finite ? 1 : 0, 0].  stats (4 doubles, or NULL), a
  *                           running record: [0] += 1, [1] += 1 if coef < 1, [2] += 1 if the step was skipped, [3] = max([3], norm)
  *                           over finite norms; pass it to ONE launch per optimizer step.  Both are written by workgroup 0.
@@ -537,6 +537,57 @@ int dep_adam_step_ext(float* p, const float* g, float* m, float* v, long n, floa
                       float weight_decay, int decoupled, int step, const dep_adam_ext* ext,
                       const double* partials, float max_norm, int skip_nonfinite, float* clip_out, double* stats, void* stream);
 int dep_swap(float* a, float* b, long n, void* stream);   /* a[i] <-> b[i], bits exchanged; a, b 16-byte aligned, not overlapping */
+
+/* Value clamp (torch.nn.utils.clip_grad_value_), a norm per parameter group, and skipped steps that do not count in the bias
+ * correction (the torch loop that calls step() only when the norm is finite), inside the launches the update already makes.
+ *   dep_grad_clip_value   : g = clamp(g) in place over up to 16 ranges (as dep_grad_clip_scale takes them), one launch, with
+ *                               clamp(x) = x > c ? c : (x < -c ? -c : x)
+ *                           by comparisons, as Tensor.clamp_: a NaN stays NaN, +-inf becomes +-c, -0.0f stays -0.0f.
+ *                           dep_grad_clip_value followed by dep_adam_step gives the bits of dep_adam_step_opt's fused clamp.
+ *   dep_adam_step_opt     : dep_adam_step_ext with `opt`'s three additions; every other argument has dep_adam_step_ext's meaning.
+ *                           opt == NULL, or {0, 1, 0, NULL, NULL, NULL, NULL}: dep_adam_step_ext itself, its launches and its bits.
+ *                           Otherwise ONE launch (partials == NULL too: coefficient 1, no record; max_norm, skip_nonfinite, clip_out
+ *                           and stats are ignored then).
+ *                             max_grad_value c > 0: the update sees clamp(g * coef); g is not written.  Torch's order: the norm is
+ *                               that of the raw gradients, the clamp follows the coefficient, coupled weight decay follows the clamp.
+ *                               A clamp that never binds gives the bits of the same call without it.
+ *                             ngroups G in 1..8, group in [0, G): `partials` holds G slices of dep_grad_norm_slots() doubles, slice k
+ *                               written by a dep_grad_sqnorm over group k's ranges.  Every workgroup sums EVERY slice with the fixed
+ *                               tree of dep_adam_step_clipped and applies its formula with group_max_norm[k] (group_max_norm == NULL,
+ *                               allowed for G == 1 only: with max_norm; otherwise max_norm is not read).  This launch scales g by coef[group].  skip_nonfinite is a decision
+ *                               about the whole step: it is skipped iff ANY S_k is not finite.  clip_out = [smallest coef,
+ *                               sqrt(sum of S_k) formed in double, all finite ? 1 : 0, 0]; stats as in dep_adam_step_clipped with
+ *                               "clipped" = smallest coef < 1; group_out (2 G floats, or NULL) = [coef_k, norm_k] per group, written
+ *                               by workgroup 0 like the other two.  G == 1 gives dep_adam_step_ext's bits, record included.
+ *                             landed_in != NULL (needs partials and skip_nonfinite): one int on the device, the number of updates
+ *                               that landed before this step.  `step` no longer enters the arithmetic: the bias factors are formed
+ *                               on the device in double from t = *landed_in + 1,
+ *                                   step_size = (float)(lr / (1 - beta1^t)) ;  inv_sqrt_bc2 = (float)(1 / sqrt(1 - beta2^t))
+ *                               with the fp32 betas widened and beta^t the integer power by squaring (at most 62 products: within
+ *                               7e-15 of the exact power; it need not have the bits of the host's pow).  landed_out (NULL in all
+ *                               but ONE launch of an optimizer step) receives, from workgroup 0, *landed_in for a skipped step and
+ *                               *landed_in + 1 otherwise.  It must be ANOTHER word than landed_in, because the other launches of
+ *                               the step still read that one: the caller alternates between two words from step to step.  No
+ *                               atomics, no host read; every launch of a step reads the same count.
+ *                           A skipped step leaves p, m, v, vmax, ema and *landed_in untouched bit for bit.
+ * Nothing allocates or synchronises; refused before any HIP call: what dep_adam_step_ext / dep_grad_clip_scale refuse, a clip_value
+ * or max_grad_value that is negative, NaN or infinite (clip_value: zero as well), ngroups outside 1..8, group outside [0, ngroups),
+ * ngroups > 1 without partials or without group_max_norm, a NaN bound, group_out without partials, landed_in without partials and
+ * skip_nonfinite, landed_out without landed_in or equal to it. */
+typedef struct {
+    float        max_grad_value;  /* c > 0: clamp g * coef to [-c, c]; 0 = off */
+    int          ngroups;         /* G in 1..8: slices of dep_grad_norm_slots() doubles in `partials` (1: the global norm) */
+    int          group;           /* the group this range belongs to */
+    const float* group_max_norm;  /* HOST array of G bounds (<= 0 or +inf: measured, not clipped), used whenever given; NULL (G == 1): max_norm */
+    float*       group_out;       /* device, 2 G floats [coef_k, norm_k], or NULL */
+    const int*   landed_in;       /* device, updates landed so far, or NULL: `step` counts as in dep_adam_step */
+    int*         landed_out;      /* device, the count after this step, or NULL; never landed_in */
+} dep_adam_opt;
+int dep_grad_clip_value(float* const* bufs, const long* counts, int nranges, float clip_value, void* stream);
+int dep_adam_step_opt(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                      float weight_decay, int decoupled, int step, const dep_adam_ext* ext,
+                      const double* partials, float max_norm, int skip_nonfinite, float* clip_out, double* stats,
+                      const dep_adam_opt* opt, void* stream);
 
 /* ------------------------------------------------------------------ feature front-end */
 /* wav2vlad of Classification/audio_features_whole.py:57-72: log-mel spectrogram (librosa.feature.melspectrogram defaults:
