@@ -765,7 +765,10 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
         a.dghn = p.dg4 ? a.dgi + 3 * H : W + (second ? lo.dghn2 : lo.dghn);
         a.lddg = p.dg4 ? ldg : 0; a.lddghn = p.dg4 ? ldg : 0;
         a.dbpart = W + (second ? lo.dbpart2 : lo.dbpart); a.dbpart_rows = D * lo.nwg; a.stream = s;
-        a.hdr_slot = l < DEP_HDR_SLOTS ? l : 0; a.hdr_clean = l < DEP_HDR_SLOTS;
+        // one exchange-header slot per layer, all zeroed by the call's one memset; layers past the slots share slot 0 and clear it
+        // themselves.  The backward walks DOWN, so in a stack of more than DEP_HDR_SLOTS layers those layers have used slot 0 by the
+        // time layer 0 comes to it: it is not clean then (flags only grow: stale ones let every wait of the sweep pass at once)
+        a.hdr_slot = l < DEP_HDR_SLOTS ? l : 0; a.hdr_clean = l < DEP_HDR_SLOTS && !(l == 0 && L > DEP_HDR_SLOTS);
         a.dg_pk = pk ? 1 : 0; a.bf16st = p.bf16st ? 1 : 0; a.sv16 = p.sv16 ? 1 : 0;
         a.lengths = lengths; a.pool_mean = d->pool == DEP_POOL_MEAN ? 1 : 0;
         return a;
