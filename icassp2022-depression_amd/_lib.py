@@ -39,6 +39,16 @@ class GradSync(C.Structure):
     _fields_ = [('comm', _P), ('comm_stream', _P), ('range_ptr', _P * 8), ('range_count', C.c_long * 8)]
 
 
+class RnnState(C.Structure):
+    """dep_rnn_state (include/dep_rnn.h): the state a dep_rnn_forward_state call starts from and the cell state it leaves."""
+    _fields_ = [('hx', _P), ('cx', _P), ('c_n', _P)]
+
+
+class RnnStateGrad(C.Structure):
+    """dep_rnn_state_grad (include/dep_rnn.h): the forward's state, the gradient of c_n, and the state gradients written."""
+    _fields_ = [('hx', _P), ('cx', _P), ('dc_n', _P), ('dhx', _P), ('dcx', _P)]
+
+
 _BWD_ARGS = [C.POINTER(RnnDesc), _P, C.POINTER(_P), _P, _P, _P, C.POINTER(_P), _P, _P, C.c_size_t, _P, C.c_size_t, _P]
 _BWD_VARLEN_ARGS = _BWD_ARGS[:2] + [_P] + _BWD_ARGS[2:]          # lengths (device int32) follow x
 _SIGS = {
@@ -59,6 +69,8 @@ _SIGS = {
     'dep_rnn_forward_varlen': (C.c_int, [C.POINTER(RnnDesc), _P, _P, C.POINTER(_P), _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t, _P]),
     'dep_rnn_backward_varlen': (C.c_int, _BWD_VARLEN_ARGS),
     'dep_rnn_backward_overlapped_varlen': (C.c_int, _BWD_VARLEN_ARGS + [C.POINTER(GradSync)]),
+    'dep_rnn_forward_state': (C.c_int, [C.POINTER(RnnDesc), _P, C.POINTER(_P), _P, _P, _P, C.POINTER(RnnState), _P, C.c_size_t, _P, C.c_size_t, _P]),
+    'dep_rnn_backward_state': (C.c_int, _BWD_ARGS[:6] + [C.POINTER(RnnStateGrad)] + _BWD_ARGS[6:] + [C.POINTER(GradSync)]),
     'dep_comm_available': (C.c_int, []),
     'dep_comm_unique_id': (C.c_int, [_P, C.c_size_t]),
     'dep_comm_init': (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, _P, C.c_size_t, C.c_int]),
@@ -663,12 +675,23 @@ class Rnn:
         n = d.B * d.T * d.H * d.dirs
         return self.reserve[off:off + n].view(d.B, d.T, d.H * d.dirs)
 
-    def forward(self, x, weights, seed=0, pooled=None, h_n=None, y=None, lengths=None):
+    def forward(self, x, weights, seed=0, pooled=None, h_n=None, y=None, lengths=None, hx=None, cx=None, c_n=None):
         """lengths: int32 device tensor of B elements -> the ragged call (dep_rnn_forward_varlen: x is padded to T, row b is
-        lengths[b] steps long; padded positions of x must be finite)."""
+        lengths[b] steps long; padded positions of x must be finite).
+        hx, cx, c_n: (L*dirs, B, H) fp32 device tensors ordered like h_n -> dep_rnn_forward_state: the sweeps start from hx (cx) instead
+        of zeros and c_n receives the LSTM's final cell state; h_n may be hx's tensor and c_n cx's (carried in place).  Dense calls on the
+        tile-MFMA / generic sweeps only (include/dep_rnn.h).  With all three None the call is the one made without them."""
         for i, w in enumerate(weights):
             self._warr[i] = w.data_ptr()
         self.desc.seed = seed
+        if hx is not None or cx is not None or c_n is not None:
+            if lengths is not None:
+                raise DepError('Rnn.forward: a recurrent state (hx / cx / c_n) goes with dense calls only, not with lengths')
+            st = RnnState(_ptr(self._state(hx, 'hx')), _ptr(self._state(cx, 'cx')), _ptr(self._state(c_n, 'c_n')))
+            check(self.lib.dep_rnn_forward_state(C.byref(self.desc), _ptr(x), self._warr, _ptr(y), _ptr(pooled), _ptr(h_n), C.byref(st),
+                                                 _ptr(self.reserve), self.reserve.numel() * 4, _ptr(self.workspace),
+                                                 self.workspace.numel() * 4, stream()), 'dep_rnn_forward_state')
+            return
         if lengths is not None:
             check(self.lib.dep_rnn_forward_varlen(C.byref(self.desc), _ptr(x), _ptr(check_lengths(lengths, self.desc.B, self.device)),
                                                   self._warr, _ptr(y), _ptr(pooled), _ptr(h_n), _ptr(self.reserve),
@@ -679,15 +702,37 @@ class Rnn:
                                        _ptr(self.reserve), self.reserve.numel() * 4, _ptr(self.workspace),
                                        self.workspace.numel() * 4, stream()), 'dep_rnn_forward')
 
-    def backward(self, x, weights, dweights, dy=None, dpooled=None, dh_n=None, dx=None, grad_sync=None, lengths=None):
+    def _state(self, t, name):
+        """A state tensor of a *_state call: (L*dirs, B, H) fp32, contiguous, on the device (None stays None)."""
+        if t is None:
+            return None
+        d = self.desc
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() \
+                or t.numel() != d.L * d.dirs * d.B * d.H:
+            raise DepError(f'{name} must be a contiguous fp32 device tensor of shape ({d.L * d.dirs}, {d.B}, {d.H}), got '
+                           f'{tuple(getattr(t, "shape", ()))} {getattr(t, "dtype", type(t))}')
+        return t
+
+    def backward(self, x, weights, dweights, dy=None, dpooled=None, dh_n=None, dx=None, grad_sync=None, lengths=None,
+                 hx=None, cx=None, dc_n=None, dhx=None, dcx=None):
         """grad_sync: a GradSync (data parallel) -> dep_rnn_backward_overlapped: layer l's range of the flat gradient
         buffer is all-reduced on the communication stream beside the weight-gradient GEMMs of the layer below.
-        lengths: the lengths of the ragged forward that wrote the reserve (the *_varlen entry points)."""
+        lengths: the lengths of the ragged forward that wrote the reserve (the *_varlen entry points).
+        hx, cx: the state the forward started from; dc_n: the gradient of c_n; dhx, dcx: receive the gradients of hx / cx (written).
+        Any of them -> dep_rnn_backward_state (dense calls on the tile-MFMA / generic sweeps only, include/dep_rnn.h)."""
         for i, (w, g) in enumerate(zip(weights, dweights)):
             self._warr[i] = w.data_ptr()
             self._garr[i] = g.data_ptr()
         args = (C.byref(self.desc), _ptr(x), self._warr, _ptr(dy), _ptr(dpooled), _ptr(dh_n), self._garr, _ptr(dx),
                 _ptr(self.reserve), self.reserve.numel() * 4, _ptr(self.workspace), self.workspace.numel() * 4, stream())
+        state = {'hx': hx, 'cx': cx, 'dc_n': dc_n, 'dhx': dhx, 'dcx': dcx}
+        if any(v is not None for v in state.values()):
+            if lengths is not None:
+                raise DepError('Rnn.backward: a recurrent state (hx / cx / dc_n / dhx / dcx) goes with dense calls only, not with lengths')
+            st = RnnStateGrad(*[_ptr(self._state(v, k)) for k, v in state.items()])
+            check(self.lib.dep_rnn_backward_state(*args[:6], C.byref(st), *args[6:], None if grad_sync is None else C.byref(grad_sync)),
+                  'dep_rnn_backward_state')
+            return
         if lengths is not None:
             args = args[:2] + (_ptr(check_lengths(lengths, self.desc.B, self.device)),) + args[2:]
             if grad_sync is None:

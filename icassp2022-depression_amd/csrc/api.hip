@@ -475,14 +475,35 @@ int ragged_mode_refusal(const char* who, const int32_t* lengths, int mode) {
     return DEP_ERR_ARG;
 }
 
+// dep_rnn_*_state: a call that brings a state (any member non-NULL) runs where the per-layer sweeps of rnn_sweep.hip run the stack, and
+// the cell state belongs to the LSTM.  Checked before anything is launched (and before any HIP call); DEP_OK for a call without state.
+int state_refusal(const dep_rnn_desc* d, const Layout& lo, const char* who, bool any, bool any_c) {
+    if (!any) return DEP_OK;
+    if (any_c && d->cell != DEP_CELL_LSTM) {
+        dep_set_error("%s: cx, c_n, dc_n and dcx are the LSTM's cell state and its gradients; a GRU takes hx / dhx only", who);
+        return DEP_ERR_ARG;
+    }
+    if (lo.cluster) {
+        dep_set_error("%s: a recurrent state (hx / cx / c_n and their gradients) is taken only where the per-layer tile-MFMA or generic sweeps "
+                      "run the stack, i.e. on a descriptor without a cluster exchange buffer (dep_rnn_workspace_xbuf_offset(d) == (size_t)-1): "
+                      "impl 1 or 2, or impl 0 at a shape without cluster kernels; got cell = %d, H = %d, dirs = %d, impl = %d",
+                      who, d->cell, d->H, d->dirs, d->impl);
+        return DEP_ERR_ARG;
+    }
+    return DEP_OK;
+}
+
 }  // namespace
 
 static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights, float* y,
-                            float* pooled, float* h_n, void* reserve, size_t reserve_bytes, void* workspace,
+                            float* pooled, float* h_n, const dep_rnn_state* state, void* reserve, size_t reserve_bytes, void* workspace,
                             size_t workspace_bytes, void* stream) {
     Layout lo;
     if (const int rf = bigru_refusal(d, "dep_rnn_forward")) return rf;
     DEP_CHECK_ARG(make_layout(d, lo));
+    const dep_rnn_state st = state ? *state : dep_rnn_state{nullptr, nullptr, nullptr};      // NULL and a struct of NULLs are the plain call
+    if (const int rf = state_refusal(d, lo, "dep_rnn_forward_state", st.hx || st.cx || st.c_n, st.cx || st.c_n)) return rf;
+    DEP_CHECK_ARG(!lengths || !(st.hx || st.cx || st.c_n));
     const int mode = dep_get_gemm_mode();
     if (const int rf = ragged_mode_refusal("dep_rnn_forward_varlen", lengths, mode)) return rf;
     const RnnPlan p = make_plan(d, lo, mode, dep_exclusive_on(), lengths != nullptr);
@@ -534,6 +555,10 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
         a.pooled = l == L - 1 ? pooled : nullptr;
         a.pool_scale = pool_scale;
         a.h_n = h_n ? h_n + (size_t)l * D * B * H : nullptr;
+        // layer l's slice of the state arrays, ordered like h_n (a non-NULL member implies the tile / generic sweeps: state_refusal)
+        a.hx = st.hx ? st.hx + (size_t)l * D * B * H : nullptr;
+        a.cx = st.cx ? st.cx + (size_t)l * D * B * H : nullptr;
+        a.c_n = st.c_n ? st.c_n + (size_t)l * D * B * H : nullptr;
         if (lo.keep) { a.sv0 = R + lo.sv[l][0]; a.sv1 = R + lo.sv[l][1]; a.sv2 = R + lo.sv[l][2]; a.sv3 = R + lo.sv[l][3]; }
         a.only_if = only_if; a.stream = s; a.sv16 = p.sv16_fwd ? 1 : 0;
         a.lengths = lengths; a.pool_mean = d->pool == DEP_POOL_MEAN ? 1 : 0;
@@ -654,23 +679,35 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
 extern "C" int dep_rnn_forward(const dep_rnn_desc* d, const float* x, const float* const* weights, float* y,
                                float* pooled, float* h_n, void* reserve, size_t reserve_bytes, void* workspace,
                                size_t workspace_bytes, void* stream) {
-    return rnn_forward_impl(d, x, nullptr, weights, y, pooled, h_n, reserve, reserve_bytes, workspace, workspace_bytes, stream);
+    return rnn_forward_impl(d, x, nullptr, weights, y, pooled, h_n, nullptr, reserve, reserve_bytes, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dep_rnn_forward_state(const dep_rnn_desc* d, const float* x, const float* const* weights, float* y,
+                                     float* pooled, float* h_n, const dep_rnn_state* st, void* reserve, size_t reserve_bytes,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    return rnn_forward_impl(d, x, nullptr, weights, y, pooled, h_n, st, reserve, reserve_bytes, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dep_rnn_forward_varlen(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights,
                                       float* y, float* pooled, float* h_n, void* reserve, size_t reserve_bytes, void* workspace,
                                       size_t workspace_bytes, void* stream) {
     DEP_CHECK_ARG(lengths);
-    return rnn_forward_impl(d, x, lengths, weights, y, pooled, h_n, reserve, reserve_bytes, workspace, workspace_bytes, stream);
+    return rnn_forward_impl(d, x, lengths, weights, y, pooled, h_n, nullptr, reserve, reserve_bytes, workspace, workspace_bytes, stream);
 }
 
 static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights, const float* dy,
-                             const float* dpooled, const float* dh_n, float* const* dweights, float* dx,
+                             const float* dpooled, const float* dh_n, const dep_rnn_state_grad* state, float* const* dweights, float* dx,
                              void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
                              void* stream, const dep_grad_sync* gs) {
     Layout lo;
     if (const int rf = bigru_refusal(d, "dep_rnn_backward")) return rf;
     DEP_CHECK_ARG(make_layout(d, lo));
+    const dep_rnn_state_grad st = state ? *state : dep_rnn_state_grad{nullptr, nullptr, nullptr, nullptr, nullptr};      // NULL and a struct of NULLs are the plain call
+    const bool has_state = st.hx || st.cx || st.dc_n || st.dhx || st.dcx;
+    if (const int rf = state_refusal(d, lo, "dep_rnn_backward_state", has_state, st.cx || st.dc_n || st.dcx)) return rf;
+    DEP_CHECK_ARG(!lengths || !has_state);
+    // the state's dW_hh term reads the gate-gradient rows of one time step as a (B x rows) matrix of row stride T * ldg
+    DEP_CHECK_ARG(!st.hx || (long)d->T * d->dirs * (d->cell == DEP_CELL_GRU ? 3 : 4) * d->H <= 0x7fffffffL);
     const int mode = dep_get_gemm_mode();
     if (const int rf = ragged_mode_refusal("dep_rnn_backward_varlen", lengths, mode)) return rf;
     const RnnPlan p = make_plan(d, lo, mode, dep_exclusive_on(), lengths != nullptr);
@@ -681,7 +718,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
     }
     int rc = reserve_tag_refusal(reserve, p.tag, TAG_DONLY); if (rc) return rc;
     DEP_CHECK_ARG(x && weights && dweights && reserve && workspace);
-    DEP_CHECK_ARG(dy || dpooled || dh_n);
+    DEP_CHECK_ARG(dy || dpooled || dh_n || st.dc_n);
     DEP_CHECK_ARG(!(dpooled && (d->cell != DEP_CELL_GRU || d->pool == DEP_POOL_NONE)));
     if (reserve_bytes < lo.reserve_floats * sizeof(float) || workspace_bytes < lo.ws_floats * sizeof(float)) {
         dep_set_error("dep_rnn_backward: reserve/workspace too small");
@@ -760,6 +797,11 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
         a.dpooled = top ? dpooled : nullptr;
         a.pool_scale = pool_scale;
         a.dh_n = dh_n ? dh_n + (size_t)l * D * B * H : nullptr;
+        {   // layer l's slice of the state arrays, ordered like h_n (a non-NULL member implies the tile / generic sweeps: state_refusal)
+            const size_t so = (size_t)l * D * B * H;
+            a.hx = st.hx ? st.hx + so : nullptr; a.cx = st.cx ? st.cx + so : nullptr; a.dc_n = st.dc_n ? st.dc_n + so : nullptr;
+            a.dhx = st.dhx ? st.dhx + so : nullptr; a.dcx = st.dcx ? st.dcx + so : nullptr;
+        }
         a.sv0 = R + lo.sv[l][0]; a.sv1 = R + lo.sv[l][1]; a.sv2 = R + lo.sv[l][2]; a.sv3 = R + lo.sv[l][3];
         a.dgi = W + (second ? lo.gi2 : lo.gi);
         a.dghn = p.dg4 ? a.dgi + 3 * H : W + (second ? lo.dghn2 : lo.dghn);
@@ -891,6 +933,24 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
                 rc = dep_gemm_internal(1, 0, 4 * H, H, BTr, dg, ldg, yl, D * H, gl[1], H, nullptr, 0.f, T, shift, gws, gwsb, ho, s);
                 if (rc) return rc;
             }
+            if (a.hx) {
+                // The initial state's term, dW_hh += dG[:, t0, :]^T hx: the shifted contractions above give sweep step 0 (t0 = 0; reverse
+                // direction t0 = T-1) a zero h_prev.  Same blocks as above, K = B: op(A) = the gate-gradient rows at t0 (row stride
+                // T * ld), B = this direction's hx slice; added (beta = 1) behind the main contraction, which wrote with beta = 0.
+                // (state_refusal: the tile / generic sweeps ran, so the rows are fp32, D*G*H wide, and the contractions above unpaired.)
+                const float* hxd = a.hx + (size_t)dd * B * H;
+                const size_t t0 = dd == 0 ? 0 : (size_t)T - 1;
+                if (gru) {
+                    rc = dep_gemm_internal(1, 0, 2 * H, H, B, dg + t0 * ldg, T * ldg, hxd, H, gl[1], H, nullptr, 1.f, 0, 0, gws, gwsb, ho, s);
+                    if (rc) return rc;
+                    rc = dep_gemm_internal(1, 0, H, H, B, dghn + (size_t)dd * H + t0 * D * H, T * D * H, hxd, H, gl[1] + (size_t)2 * H * H, H, nullptr,
+                                           1.f, 0, 0, gws, gwsb, ho, s);
+                    if (rc) return rc;
+                } else {
+                    rc = dep_gemm_internal(1, 0, 4 * H, H, B, dg + t0 * ldg, T * ldg, hxd, H, gl[1], H, nullptr, 1.f, 0, 0, gws, gwsb, ho, s);
+                    if (rc) return rc;
+                }
+            }
         }
         // data parallel: layer l's gradients are complete -- their range of the caller's flat gradient buffer goes to RCCL on the
         // communication stream.  Not right away: the collective is enqueued behind the NEXT layer's sweep (see `pending' above),
@@ -911,15 +971,24 @@ extern "C" int dep_rnn_backward(const dep_rnn_desc* d, const float* x, const flo
                                 const float* dpooled, const float* dh_n, float* const* dweights, float* dx,
                                 void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
                                 void* stream) {
-    return rnn_backward_impl(d, x, nullptr, weights, dy, dpooled, dh_n, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
+    return rnn_backward_impl(d, x, nullptr, weights, dy, dpooled, dh_n, nullptr, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
                              stream, nullptr);
+}
+
+extern "C" int dep_rnn_backward_state(const dep_rnn_desc* d, const float* x, const float* const* weights, const float* dy,
+                                      const float* dpooled, const float* dh_n, const dep_rnn_state_grad* st, float* const* dweights, float* dx,
+                                      void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
+                                      void* stream, const dep_grad_sync* gs) {
+    DEP_CHECK_ARG(!gs || (gs->comm && gs->comm_stream && gs->comm_stream != stream));      // (gs given: dep_rnn_backward_overlapped's rule)
+    return rnn_backward_impl(d, x, nullptr, weights, dy, dpooled, dh_n, st, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
+                             stream, gs);
 }
 
 extern "C" int dep_rnn_backward_varlen(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights,
                                        const float* dy, const float* dpooled, const float* dh_n, float* const* dweights, float* dx,
                                        void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes, void* stream) {
     DEP_CHECK_ARG(lengths);
-    return rnn_backward_impl(d, x, lengths, weights, dy, dpooled, dh_n, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
+    return rnn_backward_impl(d, x, lengths, weights, dy, dpooled, dh_n, nullptr, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
                              stream, nullptr);
 }
 
@@ -928,7 +997,7 @@ extern "C" int dep_rnn_backward_overlapped(const dep_rnn_desc* d, const float* x
                                            void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
                                            void* stream, const dep_grad_sync* gs) {
     DEP_CHECK_ARG(gs && gs->comm && gs->comm_stream && gs->comm_stream != stream);
-    return rnn_backward_impl(d, x, nullptr, weights, dy, dpooled, dh_n, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
+    return rnn_backward_impl(d, x, nullptr, weights, dy, dpooled, dh_n, nullptr, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
                              stream, gs);
 }
 
@@ -938,6 +1007,6 @@ extern "C" int dep_rnn_backward_overlapped_varlen(const dep_rnn_desc* d, const f
                                                   size_t workspace_bytes, void* stream, const dep_grad_sync* gs) {
     DEP_CHECK_ARG(lengths);
     DEP_CHECK_ARG(gs && gs->comm && gs->comm_stream && gs->comm_stream != stream);
-    return rnn_backward_impl(d, x, lengths, weights, dy, dpooled, dh_n, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
+    return rnn_backward_impl(d, x, lengths, weights, dy, dpooled, dh_n, nullptr, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
                              stream, gs);
 }

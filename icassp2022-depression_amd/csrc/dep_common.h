@@ -191,6 +191,10 @@ struct dep_sweep_args {
     float drop_p; uint64_t seed; uint32_t site;
     float* pooled; float pool_scale;    // GRU top layer: (B,dirs*H) sum_t y_t * scale, or NULL
     float* h_n;              // (dirs,B,H) final states or NULL
+    // initial state of this layer (dep_rnn_forward_state; rnn_sweep.hip only -- the cluster launchers are never given one)
+    const float* hx;         // (dirs,B,H) h before the sweep's first step, or NULL = zeros; may be h_n's buffer
+    const float* cx;         // LSTM: (dirs,B,H) c before the first step, or NULL = zeros; may be c_n's buffer
+    float* c_n;              // LSTM: (dirs,B,H) c after the last step, or NULL
     // reserve (training): GRU r,z,n,hn each (B,T,dirs*H) ; LSTM gates (B,T,dirs*4H) + c (B,T,dirs*H)
     float* sv0; float* sv1; float* sv2; float* sv3;
     const unsigned* only_if;  // cluster forward: run only when this device word is non-zero (fallback behind an exclusive kernel), or NULL
@@ -214,6 +218,10 @@ struct dep_sweep_bwd_args {
     float drop_p; uint64_t seed; uint32_t site;   // dropout applied to dy on load (p == 0: none)
     const float* dpooled; float pool_scale;       // GRU top layer (B,dirs*H) or NULL
     const float* dh_n;       // (dirs,B,H) or NULL
+    // state of this layer (dep_rnn_backward_state; rnn_sweep.hip only): what the forward started from, and the state gradients
+    const float* hx; const float* cx;     // (dirs,B,H) the forward's initial h / c (LSTM), or NULL = zeros
+    const float* dc_n;       // LSTM: (dirs,B,H) grad of c_n, enters where dh_n enters, or NULL
+    float* dhx; float* dcx;  // (dirs,B,H) grad of hx / cx (LSTM), WRITTEN, or NULL
     const float* sv0; const float* sv1; const float* sv2; const float* sv3;
     float* dgi;              // (B,T,dirs*G*H) written: grad of the input projection
     float* dghn;             // GRU: (B,T,dirs*H) grad of the n-gate recurrent pre-activation (dn*r)

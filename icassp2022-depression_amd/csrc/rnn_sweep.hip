@@ -10,7 +10,9 @@
 //
 // Reference semantics: torch.nn.GRU at Classification/audio_gru_whole.py:59-60,105 and
 // torch.nn.LSTM at Classification/text_bilstm_whole.py:54-56,105 (gate order r,z,n / i,f,g,o,
-// h0 = c0 = 0, inter-layer dropout on the layer output in training mode).
+// h0 = c0 = 0 unless a dep_rnn_*_state call brings them, inter-layer dropout on the layer output in training mode).
+// The state (FwdP / BwdP hx, cx, c_n, dc_n, dhx, dcx) is a set of run-time pointers read once before the step loop; null pointers
+// leave every instance the arithmetic of the stateless call.
 #include "dep_common.h"
 
 namespace {
@@ -34,6 +36,8 @@ struct FwdP {
     float* h_n;                          // (dirs,B,H)
     float* sv0; float* sv1; float* sv2; float* sv3;   // GRU: r,z,n,hn (B,T,dirs*H) ; LSTM: gates (B,T,dirs*4H), c (B,T,dirs*H)
     const int* lengths; int pool_mean;   // ragged instances (RAG): row b is live for t < lengths[b]
+    const float* hx; const float* cx;    // (dirs,B,H) state before the sweep's first step (LSTM: and c), null = zeros; read once, before the step loop
+    float* c_n;                          // LSTM (dirs,B,H) c after the last step, or null
 };
 
 struct BwdP {
@@ -50,6 +54,9 @@ struct BwdP {
     float* dbpart;                       // [dirs][nwg][G'][H]  G' = 4
     int nwg;
     const int* lengths; int pool_mean;   // ragged instances (RAG)
+    const float* hx; const float* cx;    // (dirs,B,H) what the forward started from (h_prev / c_prev of sweep step 0), null = zeros
+    const float* dc_n;                   // LSTM (dirs,B,H), enters where dh_n enters, or null
+    float* dhx; float* dcx;              // (dirs,B,H) the recurrent dh / dc left after the last step of the walk, written, or null
 };
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
@@ -131,7 +138,16 @@ __global__ __launch_bounds__(512) void gru_fwd_mfma(FwdP p) {
         const int col0 = (w * JPW + jj) * 16 + q * 4;
 #pragma unroll
         for (int g = 0; g < 3; ++g) bh[jj][g] = ld4(p.d[dir].b_hh + g * H + col0);
-        hprev[jj] = zero4(); pool[jj] = zero4();
+        // the direction's own slice of hx; rows past B of the last tile read nothing (hx has exactly B rows)
+        hprev[jj] = (p.hx && valid) ? ld4(p.hx + ((size_t)dir * p.B + b) * H + col0) : zero4();
+        pool[jj] = zero4();
+    }
+    if (p.hx) {
+        // the first LDS plane is h before step 0.  The zero fill above wrote the same words from other threads: barrier first.
+        // (p.hx is uniform over the launch.  Every (row, column) of hs0 the matvec reads is stored here, rows past B as zeros.)
+        __syncthreads();
+#pragma unroll
+        for (int jj = 0; jj < JPW; ++jj) st4(hs0 + j * LDH + (w * JPW + jj) * 16 + q * 4, hprev[jj]);
     }
     __syncthreads();
 
@@ -211,11 +227,12 @@ __global__ __launch_bounds__(512) void gru_bwd_mfma(BwdP p) {
     float* ds0 = smem; float* ds1 = smem + BT * LDG;
 
     const f32x4* wp = p.d[dir].wp + (size_t)(w * JPW) * KC * 64 + lane;
-    f32x4 dhrec[JPW], dbr[JPW], dbz[JPW], dbn[JPW], dbh[JPW], dpl[JPW];
+    f32x4 dhrec[JPW], dbr[JPW], dbz[JPW], dbn[JPW], dbh[JPW], dpl[JPW], hx0[JPW];
 #pragma unroll
     for (int jj = 0; jj < JPW; ++jj) {
         const int col0 = (w * JPW + jj) * 16 + q * 4;
         dhrec[jj] = (p.dh_n && valid) ? ld4(p.dh_n + ((size_t)dir * p.B + b) * H + col0) : zero4();
+        hx0[jj] = (p.hx && valid) ? ld4(p.hx + ((size_t)dir * p.B + b) * H + col0) : zero4();      // h_prev of sweep step 0 (t = 0, reverse: t = T-1)
         dpl[jj] = (p.dpooled && valid) ? ld4(p.dpooled + (size_t)b * SW + dir * H + col0) * dps : zero4();
         dbr[jj] = zero4(); dbz[jj] = zero4(); dbn[jj] = zero4(); dbh[jj] = zero4();
     }
@@ -232,7 +249,7 @@ __global__ __launch_bounds__(512) void gru_bwd_mfma(BwdP p) {
             if (valid) {
                 const size_t so = row * SW + dir * H + col0;
                 r = ld4(p.sv0 + so); z = ld4(p.sv1 + so); n = ld4(p.sv2 + so); hn = ld4(p.sv3 + so);
-                if (s > 0) hp = ld4(p.y + ((BI && dir) ? row + 1 : row - 1) * p.ldy + dir * H + col0);
+                hp = s > 0 ? ld4(p.y + ((BI && dir) ? row + 1 : row - 1) * p.ldy + dir * H + col0) : hx0[jj];
                 if (p.dy) {
                     const size_t o = row * p.lddy + dir * H + col0;
                     f32x4 dyv = ld4(p.dy + o);
@@ -271,6 +288,11 @@ __global__ __launch_bounds__(512) void gru_bwd_mfma(BwdP p) {
             else dhrec[jj] = dzt[jj] + acc[jj];
         }
     }
+    // what is carried past sweep step 0, d * z + W_hh^T dG, is the gradient of the initial state
+    if (p.dhx && valid) {
+#pragma unroll
+        for (int jj = 0; jj < JPW; ++jj) st4(p.dhx + ((size_t)dir * p.B + b) * H + (w * JPW + jj) * 16 + q * 4, dhrec[jj]);
+    }
     // bias-gradient partials of this workgroup: dbpart[wg][4][H]  (r, z, n_input, n_hidden)
 #pragma unroll
     for (int jj = 0; jj < JPW; ++jj) {
@@ -303,7 +325,18 @@ __global__ __launch_bounds__(512) void lstm_fwd_mfma(FwdP p) {
     const int ldsg = p.dirs * 4 * H, ldsc = p.dirs * H;
     f32x4 c[JPW], hlast[JPW];
 #pragma unroll
-    for (int jj = 0; jj < JPW; ++jj) { c[jj] = zero4(); hlast[jj] = zero4(); }
+    for (int jj = 0; jj < JPW; ++jj) {
+        // the direction's own slices of hx / cx; rows past B of the last tile read nothing (the state has exactly B rows)
+        const size_t so = ((size_t)dir * p.B + b) * H + (w * JPW + jj) * 16 + q * 4;
+        c[jj] = (p.cx && valid) ? ld4(p.cx + so) : zero4();
+        hlast[jj] = (p.hx && valid) ? ld4(p.hx + so) : zero4();
+    }
+    if (p.hx) {
+        // the first LDS plane is h before step 0; the zero fill above wrote the same words from other threads: barrier first (as in gru_fwd_mfma)
+        __syncthreads();
+#pragma unroll
+        for (int jj = 0; jj < JPW; ++jj) st4(hs0 + j * LDH + (w * JPW + jj) * 16 + q * 4, hlast[jj]);
+    }
     __syncthreads();
 
     for (int s = 0; s < T; ++s) {
@@ -353,11 +386,12 @@ __global__ __launch_bounds__(512) void lstm_fwd_mfma(FwdP p) {
         }
         __syncthreads();
     }
-    if (valid && p.h_n) {
+    if (valid) {
 #pragma unroll
         for (int jj = 0; jj < JPW; ++jj) {
-            const int col0 = (w * JPW + jj) * 16 + q * 4;
-            st4(p.h_n + ((size_t)dir * p.B + b) * H + col0, hlast[jj]);
+            const size_t so = ((size_t)dir * p.B + b) * H + (w * JPW + jj) * 16 + q * 4;
+            if (p.h_n) st4(p.h_n + so, hlast[jj]);
+            if (p.c_n) st4(p.c_n + so, c[jj]);
         }
     }
 }
@@ -382,7 +416,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_mfma(BwdP p) {
     for (int jj = 0; jj < JPW; ++jj) {
         const int col0 = (w * JPW + jj) * 16 + q * 4;
         dhrec[jj] = (p.dh_n && valid) ? ld4(p.dh_n + ((size_t)dir * p.B + b) * H + col0) : zero4();
-        dcrec[jj] = zero4();
+        dcrec[jj] = (p.dc_n && valid) ? ld4(p.dc_n + ((size_t)dir * p.B + b) * H + col0) : zero4();
 #pragma unroll
         for (int g = 0; g < 4; ++g) db[jj][g] = zero4();
     }
@@ -401,6 +435,10 @@ __global__ __launch_bounds__(512) void lstm_bwd_mfma(BwdP p) {
                 if (s > 0) {
                     const size_t rowp = dir ? row + 1 : row - 1;
                     cp = ld4(p.sv1 + rowp * ldsc + dir * H + col0);
+                } else if (p.cx) {
+                    // c_prev of sweep step 0 (t = 0, reverse: t = T-1) is the forward's cx: read once, here, on a branch that is uniform
+                    // over the launch and not taken in any other step (held in registers across the loop it cost the H = 256 sweep 1.6 %)
+                    cp = ld4(p.cx + ((size_t)dir * p.B + b) * H + col0);
                 }
                 if (p.dy) {
                     const size_t o = row * p.lddy + dir * H + col0;
@@ -443,6 +481,15 @@ __global__ __launch_bounds__(512) void lstm_bwd_mfma(BwdP p) {
             else dhrec[jj] = acc[jj];
         }
     }
+    // what is carried past sweep step 0, W_hh^T dG and dc_t * f, are the gradients of the initial state
+    if (valid) {
+#pragma unroll
+        for (int jj = 0; jj < JPW; ++jj) {
+            const size_t so = ((size_t)dir * p.B + b) * H + (w * JPW + jj) * 16 + q * 4;
+            if (p.dhx) st4(p.dhx + so, dhrec[jj]);
+            if (p.dcx) st4(p.dcx + so, dcrec[jj]);
+        }
+    }
 #pragma unroll
     for (int jj = 0; jj < JPW; ++jj) {
         const int col0 = (w * JPW + jj) * 16 + q * 4;
@@ -470,7 +517,7 @@ __global__ __launch_bounds__(GEN_T) void gru_fwd_generic(FwdP p) {
     float* hs = smem;            // [H] h_{t-1}
     float* hnew = smem + H;      // [H]
     const float* W = p.d[0].w; const float* bh = p.d[0].b_hh;
-    for (int i = threadIdx.x; i < H; i += GEN_T) hs[i] = 0.f;
+    for (int i = threadIdx.x; i < H; i += GEN_T) hs[i] = p.hx ? p.hx[(size_t)b * H + i] : 0.f;      // h before step 0
     __syncthreads();
     for (int t = 0; t < T; ++t) {
         const size_t row = (size_t)b * T + t;
@@ -518,9 +565,13 @@ __global__ __launch_bounds__(GEN_T) void gru_bwd_generic(BwdP p) {
     const float dps = RAG ? dep_ragged_pool_scale(p.pool_mean, len, T, p.pool_scale) : p.pool_scale;
     float* dg = smem;            // [3H] dgh of this step
     float* dh = smem + G3;       // [H] recurrent dh
+    float* hx0 = smem + G3 + 2 * H;      // [H] h_prev of step 0 (the forward's hx, or zeros); element i is thread i's own
     float* dbp = p.dbpart + (size_t)b * 4 * H;
     const float* W = p.d[0].w;
-    for (int i = threadIdx.x; i < H; i += GEN_T) dh[i] = p.dh_n ? p.dh_n[(size_t)b * H + i] : 0.f;
+    for (int i = threadIdx.x; i < H; i += GEN_T) {
+        dh[i] = p.dh_n ? p.dh_n[(size_t)b * H + i] : 0.f;
+        hx0[i] = p.hx ? p.hx[(size_t)b * H + i] : 0.f;
+    }
     for (int i = threadIdx.x; i < 4 * H; i += GEN_T) dbp[i] = 0.f;
     __syncthreads();
     for (int t = T - 1; t >= 0; --t) {
@@ -528,7 +579,7 @@ __global__ __launch_bounds__(GEN_T) void gru_bwd_generic(BwdP p) {
         for (int i = threadIdx.x; i < H; i += GEN_T) {
             const size_t so = row * H + i;
             const float r = p.sv0[so], z = p.sv1[so], n = p.sv2[so], hn = p.sv3[so];
-            const float hp = t > 0 ? p.y[(row - 1) * p.ldy + i] : 0.f;
+            const float hp = t > 0 ? p.y[(row - 1) * p.ldy + i] : hx0[i];
             float d = dh[i];
             if (p.dpooled) d += p.dpooled[(size_t)b * H + i] * dps;
             if (p.dy) {
@@ -565,6 +616,8 @@ __global__ __launch_bounds__(GEN_T) void gru_bwd_generic(BwdP p) {
         }
         __syncthreads();
     }
+    // dh past step 0, d * z + W_hh^T dG, is the gradient of the initial state (element i was last written by this thread)
+    if (p.dhx) for (int i = threadIdx.x; i < H; i += GEN_T) p.dhx[(size_t)b * H + i] = dh[i];
 }
 
 template <bool RAG = false>
@@ -575,7 +628,10 @@ __global__ __launch_bounds__(GEN_T) void lstm_fwd_generic(FwdP p) {
     float* hs = smem; float* hnew = smem + H; float* cs = smem + 2 * H;
     const float* W = p.d[dir].w;
     const int ldsg = p.dirs * 4 * H, ldsc = p.dirs * H;
-    for (int i = threadIdx.x; i < H; i += GEN_T) { hs[i] = 0.f; cs[i] = 0.f; }
+    for (int i = threadIdx.x; i < H; i += GEN_T) {      // h, c before the sweep's first step: the direction's own slice
+        const size_t so = ((size_t)dir * p.B + b) * H + i;
+        hs[i] = p.hx ? p.hx[so] : 0.f; cs[i] = p.cx ? p.cx[so] : 0.f;
+    }
     __syncthreads();
     for (int s = 0; s < T; ++s) {
         const int t = dir ? (T - 1 - s) : s;
@@ -619,6 +675,7 @@ __global__ __launch_bounds__(GEN_T) void lstm_fwd_generic(FwdP p) {
         __syncthreads();
     }
     if (p.h_n) for (int i = threadIdx.x; i < H; i += GEN_T) p.h_n[((size_t)dir * p.B + b) * H + i] = hs[i];
+    if (p.c_n) for (int i = threadIdx.x; i < H; i += GEN_T) p.c_n[((size_t)dir * p.B + b) * H + i] = cs[i];
 }
 
 template <bool RAG = false>
@@ -627,12 +684,15 @@ __global__ __launch_bounds__(GEN_T) void lstm_bwd_generic(BwdP p) {
     const int H = p.H, T = p.T, b = blockIdx.x, dir = blockIdx.y, G4 = 4 * H;
     const int len = RAG ? dep_row_len(p.lengths, b, T) : T;
     float* dg = smem; float* dh = smem + G4; float* dc = smem + G4 + H;
+    float* cx0 = smem + G4 + 2 * H;      // [H] c_prev of sweep step 0 (the forward's cx, or zeros); element i is thread i's own
     const float* W = p.d[dir].w;
     const int ldsg = p.dirs * 4 * H, ldsc = p.dirs * H;
     float* dbp = p.dbpart + ((size_t)dir * p.nwg + b) * 4 * H;
     for (int i = threadIdx.x; i < H; i += GEN_T) {
-        dh[i] = p.dh_n ? p.dh_n[((size_t)dir * p.B + b) * H + i] : 0.f;
-        dc[i] = 0.f;
+        const size_t so = ((size_t)dir * p.B + b) * H + i;
+        dh[i] = p.dh_n ? p.dh_n[so] : 0.f;
+        dc[i] = p.dc_n ? p.dc_n[so] : 0.f;
+        cx0[i] = p.cx ? p.cx[so] : 0.f;
     }
     for (int i = threadIdx.x; i < 4 * H; i += GEN_T) dbp[i] = 0.f;
     __syncthreads();
@@ -643,7 +703,7 @@ __global__ __launch_bounds__(GEN_T) void lstm_bwd_generic(BwdP p) {
             const float* gs = p.sv0 + row * ldsg + dir * 4 * H;
             const float ig = gs[i], fg = gs[H + i], gg = gs[2 * H + i], og = gs[3 * H + i];
             const float ct = p.sv1[row * ldsc + dir * H + i];
-            float cp = 0.f;
+            float cp = cx0[i];
             if (s > 0) { const size_t rowp = dir ? row + 1 : row - 1; cp = p.sv1[rowp * ldsc + dir * H + i]; }
             float d = dh[i];
             if (p.dy) {
@@ -679,6 +739,12 @@ __global__ __launch_bounds__(GEN_T) void lstm_bwd_generic(BwdP p) {
             if (!RAG || t < len) dh[i] = sum;      // (dead step: the incoming dh passes through)
         }
         __syncthreads();
+    }
+    // dh / dc past sweep step 0 are the gradients of the initial state (element i of either was last written by this thread)
+    for (int i = threadIdx.x; i < H; i += GEN_T) {
+        const size_t so = ((size_t)dir * p.B + b) * H + i;
+        if (p.dhx) p.dhx[so] = dh[i];
+        if (p.dcx) p.dcx[so] = dc[i];
     }
 }
 
@@ -818,7 +884,10 @@ int dep_launch_sweep_fwd(const dep_sweep_args& a) {
     p.pooled = a.pooled; p.pool_scale = a.pool_scale; p.h_n = a.h_n;
     p.sv0 = a.training ? a.sv0 : nullptr; p.sv1 = a.sv1; p.sv2 = a.sv2; p.sv3 = a.sv3;
     p.lengths = a.lengths; p.pool_mean = a.pool_mean;
+    p.hx = a.hx; p.cx = a.cx; p.c_n = a.c_n;
     DEP_CHECK_ARG(a.y && a.gi);
+    DEP_CHECK_ARG(a.cell == DEP_CELL_LSTM || (!a.cx && !a.c_n));                  // a GRU has no cell state
+    DEP_CHECK_ARG(!a.lengths || (!a.hx && !a.cx && !a.c_n));                      // state goes with dense calls only
     const bool bigru = a.cell == DEP_CELL_GRU && a.dirs == 2;
     DEP_CHECK_ARG(!bigru || dep_sweep_use_mfma(a.H, a.impl));      // a bidirectional GRU has tile-MFMA instances only
     DepProfScope prof(a.cell == DEP_CELL_GRU ? DEP_PROF_GRU_FWD : DEP_PROF_LSTM_FWD, a.stream);
@@ -855,6 +924,9 @@ int dep_launch_sweep_bwd(const dep_sweep_bwd_args& a) {
     p.dgi = a.dgi; p.lddg = a.dirs * G * a.H; p.dghn = a.dghn; p.dbpart = a.dbpart;
     p.nwg = dep_sweep_num_wg(a.B, a.H, a.impl);
     p.lengths = a.lengths; p.pool_mean = a.pool_mean;
+    p.hx = a.hx; p.cx = a.cx; p.dc_n = a.dc_n; p.dhx = a.dhx; p.dcx = a.dcx;
+    DEP_CHECK_ARG(a.cell == DEP_CELL_LSTM || (!a.cx && !a.dc_n && !a.dcx));       // a GRU has no cell state
+    DEP_CHECK_ARG(!a.lengths || (!a.hx && !a.cx && !a.dc_n && !a.dhx && !a.dcx)); // state goes with dense calls only
     DEP_CHECK_ARG(a.dbpart_rows >= p.nwg * a.dirs);
     DEP_CHECK_ARG(a.sv0 && a.dgi && a.dbpart);
     const bool bigru = a.cell == DEP_CELL_GRU && a.dirs == 2;
@@ -869,7 +941,7 @@ int dep_launch_sweep_bwd(const dep_sweep_bwd_args& a) {
         else LAUNCH_JPW(lstm_bwd_mfma, grid, nw * 64, lds, a.stream, p);
     } else {
         dim3 grid(a.B, a.dirs);
-        const size_t lds = (size_t)(G * a.H + 2 * a.H) * sizeof(float);
+        const size_t lds = (size_t)(G * a.H + 3 * a.H) * sizeof(float);      // gate gradients, dh, dc, and h / c before step 0
         if (a.lengths) {
             if (a.cell == DEP_CELL_GRU) DEP_LAUNCH(gru_bwd_generic<true>, grid, dim3(GEN_T), lds, a.stream, p);
             else DEP_LAUNCH(lstm_bwd_generic<true>, grid, dim3(GEN_T), lds, a.stream, p);

@@ -34,8 +34,9 @@ def _rnn_names(prefix, F, H, Lyr, dirs, G):
 class _RnnCache:
     """dep_rnn descriptors + reserve/workspace per (B,T,run mode) so steady-state steps never allocate."""
 
-    def __init__(self, cell, F, H, Lyr, dirs, p, pool, device):
+    def __init__(self, cell, F, H, Lyr, dirs, p, pool, device, impl=0):
         self.args = (cell, F, H, Lyr, dirs, p, pool, device)
+        self.impl = impl             # dep_rnn_desc.impl of every descriptor of this cache
         self.cache = {}
 
     @staticmethod
@@ -58,7 +59,7 @@ class _RnnCache:
             cell, F, H, Lyr, dirs, p, pool, device = self.args
             if len(self.cache) > 6:
                 self.cache.clear()
-            r = L.Rnn(cell, B, T, F, H, Lyr, dirs, training, p if training else 0.0, pool, device)
+            r = L.Rnn(cell, B, T, F, H, Lyr, dirs, training, p if training else 0.0, pool, device, impl=self.impl)
             self.cache[key] = r
         self.last = r
         return r
@@ -154,6 +155,58 @@ class _MLPHead:
         return dx
 
 
+class _AudioStream:
+    """AudioGRU.stream(): chunked scoring of one batch of recordings with the memory of one chunk.  push() runs a chunk through the
+    stack on the per-layer sweeps with the recurrent state carried in place (h_n written over hx, dep_rnn_forward_state) and adds the
+    chunk's sum pool into an accumulator; output() is what model(x) returns for the chunks concatenated along T."""
+
+    def __init__(self, model):
+        self.m = model
+        self.B = None
+        self.T = 0
+        if model.variant == 'clf':                 # LayerNorm's affine folded into layer 0, as encode() does (eval: the weights stand still)
+            P = model._params
+            L.ln_fold_fwd(model._rnn_w[0], model._rnn_w[2], P['ln.weight'].data, P['ln.bias'].data, *model._fold[:2])
+
+    def push(self, chunk):
+        """chunk: (B, Tc, F), host or device; Tc >= 1 and may differ from push to push, B is fixed by the first push."""
+        m = self.m
+        x = m._to_dev(chunk)
+        if x.dim() != 3 or x.shape[1] < 1 or x.shape[2] != m.embedding_size:
+            raise L.DepError(f'stream.push: expected a (B, Tc >= 1, {m.embedding_size}) chunk, got {tuple(x.shape)}')
+        B, Tc, F = x.shape
+        if self.B is None:
+            if B < 1:
+                raise L.DepError('stream.push: an empty batch')
+            self.B = B
+            mk = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=m.device)
+            self.h = mk(m.rnn_layers, B, m.hidden_dims)          # the carried state: zeros before the first chunk
+            self.acc = mk(B, m.hidden_dims)                      # sum over all steps so far of the top layer's output
+            self.part = mk(B, m.hidden_dims)                     # one chunk's sum
+        elif B != self.B:
+            raise L.DepError(f'stream.push: the batch size is fixed by the first push ({self.B}), got {B}')
+        if m.variant == 'clf':                                   # LayerNorm is per row: per chunk, as encode() runs it
+            xn, _ = L.layernorm_fwd(x.view(B * Tc, F), None, None, save=False)
+            weights = m._rnn_w_fold
+        else:
+            xn, weights = x.view(B * Tc, F), m._rnn_w
+        rnn = m._stream_rnns.get(B, Tc, L.RUN_EVAL)
+        rnn.forward(xn, weights, pooled=self.part, h_n=self.h, hx=self.h)
+        L.axpby(self.part, self.acc, 1.0, 1.0)
+        self.T += Tc
+
+    def output(self):
+        m = self.m
+        if self.T == 0:
+            raise L.DepError('stream.output: nothing was pushed')
+        pooled = torch.empty_like(self.acc)
+        L.axpby(self.acc, pooled, 1.0 / self.T if m.variant == 'clf' else 1.0, 0.0)      # the classifier pools by the mean over all steps
+        z = m._head.forward(pooled, 0, False)
+        out = torch.empty_like(z)
+        L.head_loss(L.LOSS_CE_ON_SOFTMAX if m.variant == 'clf' else L.LOSS_L1_RELU, z, None, out, None, None, 1.0)
+        return nn.Output(out, None, z)
+
+
 class AudioGRU(nn.Module):
     def __init__(self, config, variant='clf', seed=None):
         super().__init__()
@@ -199,7 +252,17 @@ class AudioGRU(nn.Module):
             self._rnn_g_fold = [self._fold[2], self._rnn_g[1], self._fold[3]] + self._rnn_g[3:]
         pool = L.POOL_MEAN if variant == 'clf' else L.POOL_SUM
         self._rnns = _RnnCache(L.CELL_GRU, F, H, Lyr, 1, self.dropout, pool, self.device)
+        # stream(): descriptors on the per-layer sweeps, the kernels that take a recurrent state (impl 2: the tile-MFMA sweeps where
+        # they can tile H, the generic sweeps elsewhere -- what impl 1 runs), eval mode, the chunk's SUM as its pool
+        self._stream_rnns = _RnnCache(L.CELL_GRU, F, H, Lyr, 1, self.dropout, L.POOL_SUM, self.device, impl=2)
         self._head = _MLPHead(self, 'fc_audio.1', 'fc_audio.4', self.dropout, True, (L.SITE_FC0, L.SITE_FC1))
+
+    def stream(self):
+        """Chunked scoring with bounded memory (eval mode only): s = model.stream(); s.push(chunk) ...; s.output() is model(x) for
+        the chunks concatenated along T.  See _AudioStream."""
+        if self.training:
+            raise L.DepError('AudioGRU.stream: streaming scores in eval() mode only (no dropout, no backward)')
+        return _AudioStream(self)
 
     def state_dict(self):
         sd = super().state_dict()

@@ -15,7 +15,7 @@
  *   - return 0 on success, negative dep_status on error; dep_last_error() returns a message;
  *   - no allocation happens inside the library: workspace / reserve sizes come from the *_bytes
  *     queries and the caller provides the buffers (16-byte aligned);
- *   - gate order is PyTorch's: GRU r,z,n ; LSTM i,f,g,o ; h0 = c0 = 0 always;
+ *   - gate order is PyTorch's: GRU r,z,n ; LSTM i,f,g,o ; h0 = c0 = 0 unless a *_state call says otherwise;
  *   - batches are dense (all B utterances T steps long) unless an entry point takes `lengths` (the *_varlen calls).
  *   - threads: entry points may be called concurrently from several host threads as long as each call has its own stream,
  *     workspace and reserve (dep_last_error is per thread; the launch-time recorder behind dep_profile_* and the
@@ -250,6 +250,50 @@ int dep_rnn_backward_overlapped_varlen(const dep_rnn_desc* d, const float* x, co
                                        float* const* dweights, float* dx,
                                        void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
                                        void* stream, const dep_grad_sync* gs);
+
+/* ------------------------------------------------------------------ recurrent state in and out -- */
+/* The rest of torch.nn.GRU / torch.nn.LSTM's contract: `output, h_n = gru(x, hx)`, `output, (h_n, c_n) = lstm(x, (hx, cx))` and the
+ * gradients that flow through them.  What it is for: scoring a long recording in chunks of bounded memory (carry h_n -> hx across the
+ * cut), truncated BPTT (a detached state in, its dW_hh contribution kept), exact BPTT across a chunk boundary, learned initial states
+ * and an encoder-to-decoder hand-over (dhx / dcx out, dh_n / dc_n in).
+ *
+ * Layout and NULL
+ *   - every state array is (L*dirs, B, H), ordered like h_n: [l0_fwd, l0_rev, l1_fwd, ...];
+ *   - any pointer may be NULL: for an input (hx, cx, dc_n) that means zeros, for an output (c_n, dhx, dcx) "not wanted";
+ *   - cx, c_n, dc_n, dcx belong to the LSTM: with a GRU a non-NULL one is DEP_ERR_ARG.
+ * Semantics
+ *   - layer l, direction d starts its sweep from hx[l*dirs+d] (and cx[l*dirs+d]); the reverse direction starts at t = T-1 with its own slice;
+ *   - h_n / c_n are the states after the sweep's last step (t = T-1 forward, t = 0 reverse);
+ *   - dhx / dcx are the gradients with respect to hx / cx.  They are WRITTEN, not accumulated;
+ *   - dc_n enters where dh_n enters;
+ *   - the weight gradients include the state's term: dW_hh += dG[:, t0, :]^T hx with t0 = 0 (forward direction) / T-1 (reverse direction);
+ *   - a backward must be given the hx / cx of the forward that wrote the reserve (hx feeds dW_hh and the GRU's dz at step t0, cx the
+ *     LSTM's df at t0).  This is the caller's responsibility, as with `lengths`, and is not detected.
+ * Plain calls
+ *   - st == NULL, or a struct of NULLs, is dep_rnn_forward / dep_rnn_backward (dep_rnn_backward_overlapped when gs is given) on EVERY
+ *     descriptor, cluster and fused ones included: the same launches, the same bits.
+ * Where state is accepted
+ *   - a non-NULL member is accepted exactly where the per-layer tile-MFMA / generic sweeps (rnn_sweep.hip) run the stack: a descriptor
+ *     whose layout has no cluster exchange buffer, dep_rnn_workspace_xbuf_offset(d) == (size_t)-1.  In practice impl 1 or 2, or impl 0
+ *     at a shape without cluster kernels (a bidirectional GRU is always such a descriptor);
+ *   - on any other descriptor the call returns DEP_ERR_ARG before anything is launched, with the rule in dep_last_error.
+ * Scope
+ *   - dense calls only (there is no `lengths` parameter); all three run modes for the forward; the GEMM modes of the dense call;
+ *   - h_n may be the same buffer as hx, and c_n the same as cx: every workgroup reads its rows of the state before the first step
+ *     and writes them after the last (chunked streaming carries the state in place this way);
+ *   - reserve and workspace sizes and every offset are those of dep_rnn_forward / dep_rnn_backward;
+ *   - gs: NULL, or as for dep_rnn_backward_overlapped. */
+typedef struct { const float* hx; const float* cx; float* c_n; } dep_rnn_state;
+typedef struct { const float* hx; const float* cx; const float* dc_n; float* dhx; float* dcx; } dep_rnn_state_grad;
+int dep_rnn_forward_state(const dep_rnn_desc* d, const float* x, const float* const* weights,
+                          float* y, float* pooled, float* h_n, const dep_rnn_state* st,
+                          void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int dep_rnn_backward_state(const dep_rnn_desc* d, const float* x, const float* const* weights,
+                           const float* dy, const float* dpooled, const float* dh_n, const dep_rnn_state_grad* st,
+                           float* const* dweights, float* dx,
+                           void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
+                           void* stream, const dep_grad_sync* gs);
 
 /* ------------------------------------------------------------------ dense --------- */
 /* C[M,N] = opA(A)[M,K] * opB(B)[K,N] + bias[N] + beta*C      (fp32 MFMA, exact f32 products)
