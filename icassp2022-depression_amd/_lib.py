@@ -71,6 +71,9 @@ _SIGS = {
     'dep_rnn_backward_overlapped_varlen': (C.c_int, _BWD_VARLEN_ARGS + [C.POINTER(GradSync)]),
     'dep_rnn_forward_state': (C.c_int, [C.POINTER(RnnDesc), _P, C.POINTER(_P), _P, _P, _P, C.POINTER(RnnState), _P, C.c_size_t, _P, C.c_size_t, _P]),
     'dep_rnn_backward_state': (C.c_int, _BWD_ARGS[:6] + [C.POINTER(RnnStateGrad)] + _BWD_ARGS[6:] + [C.POINTER(GradSync)]),
+    'dep_rnn_forward_state_varlen': (C.c_int, [C.POINTER(RnnDesc), _P, _P, C.POINTER(_P), _P, _P, _P, C.POINTER(RnnState), _P, C.c_size_t, _P,
+                                               C.c_size_t, _P]),
+    'dep_rnn_backward_state_varlen': (C.c_int, _BWD_VARLEN_ARGS[:7] + [C.POINTER(RnnStateGrad)] + _BWD_VARLEN_ARGS[7:] + [C.POINTER(GradSync)]),
     'dep_comm_available': (C.c_int, []),
     'dep_comm_unique_id': (C.c_int, [_P, C.c_size_t]),
     'dep_comm_init': (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, _P, C.c_size_t, C.c_int]),
@@ -150,6 +153,8 @@ _SIGS = {
     'dep_gather_rows': (C.c_int, [_P, _P, _P, C.c_long, C.c_long, _P]),
     'dep_copy2d': (C.c_int, [_P, C.c_long, _P, C.c_long, C.c_long, C.c_long, _P]),
     'dep_argmax_count': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    'dep_stream_accumulate': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    'dep_stream_finish': (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -485,6 +490,18 @@ def axpby(x, y, a, b):
     check(load().dep_axpby(_ptr(x), _ptr(y), x.numel(), float(a), float(b), stream()), 'dep_axpby')
 
 
+def stream_accumulate(part, lengths, acc, totals, Tc):
+    """acc (B,H) += part; totals (B,) int32 += lengths clamped to [0, Tc] (dep_stream_accumulate)."""
+    B, H = acc.shape
+    check(load().dep_stream_accumulate(_ptr(part), _ptr(lengths), _ptr(acc), _ptr(totals), B, H, int(Tc), stream()), 'dep_stream_accumulate')
+
+
+def stream_finish(acc, totals, pooled, mean):
+    """pooled (B,H) = acc / totals per row (a total of 0 gives zeros) when mean, else acc (dep_stream_finish)."""
+    B, H = acc.shape
+    check(load().dep_stream_finish(_ptr(acc), _ptr(totals), _ptr(pooled), B, H, int(bool(mean)), stream()), 'dep_stream_finish')
+
+
 def sigmoid_gate(g, x, y):
     check(load().dep_sigmoid_gate(_ptr(g), _ptr(x), _ptr(y), x.numel(), stream()), 'dep_sigmoid_gate')
 
@@ -686,7 +703,8 @@ class Rnn:
         self.desc.seed = seed
         if hx is not None or cx is not None or c_n is not None:
             if lengths is not None:
-                raise DepError('Rnn.forward: a recurrent state (hx / cx / c_n) goes with dense calls only, not with lengths')
+                raise DepError('Rnn.forward: a recurrent state (hx / cx / c_n) goes with dense calls only, not with lengths; '
+                               'the ragged call with a state is Rnn.forward_state_varlen')
             st = RnnState(_ptr(self._state(hx, 'hx')), _ptr(self._state(cx, 'cx')), _ptr(self._state(c_n, 'c_n')))
             check(self.lib.dep_rnn_forward_state(C.byref(self.desc), _ptr(x), self._warr, _ptr(y), _ptr(pooled), _ptr(h_n), C.byref(st),
                                                  _ptr(self.reserve), self.reserve.numel() * 4, _ptr(self.workspace),
@@ -701,6 +719,38 @@ class Rnn:
         check(self.lib.dep_rnn_forward(C.byref(self.desc), _ptr(x), self._warr, _ptr(y), _ptr(pooled), _ptr(h_n),
                                        _ptr(self.reserve), self.reserve.numel() * 4, _ptr(self.workspace),
                                        self.workspace.numel() * 4, stream()), 'dep_rnn_forward')
+
+    def forward_state_varlen(self, x, weights, lengths, seed=0, pooled=None, h_n=None, y=None, hx=None, cx=None, c_n=None):
+        """dep_rnn_forward_state_varlen: the ragged call (lengths: int32 device tensor of B elements) starting from hx (cx).  Row b is
+        the dense state call on that row alone at T' = lengths[b]; a row of length 0 passes its state through (h_n = hx, c_n = cx).
+        h_n may be hx's tensor and c_n cx's.  With hx, cx and c_n all None it is the plain ragged call."""
+        if lengths is None:
+            raise DepError('Rnn.forward_state_varlen: lengths is required (the dense call with a state is Rnn.forward)')
+        for i, w in enumerate(weights):
+            self._warr[i] = w.data_ptr()
+        self.desc.seed = seed
+        st = RnnState(_ptr(self._state(hx, 'hx')), _ptr(self._state(cx, 'cx')), _ptr(self._state(c_n, 'c_n')))
+        check(self.lib.dep_rnn_forward_state_varlen(C.byref(self.desc), _ptr(x), _ptr(check_lengths(lengths, self.desc.B, self.device)),
+                                                    self._warr, _ptr(y), _ptr(pooled), _ptr(h_n), C.byref(st), _ptr(self.reserve),
+                                                    self.reserve.numel() * 4, _ptr(self.workspace), self.workspace.numel() * 4, stream()),
+              'dep_rnn_forward_state_varlen')
+
+    def backward_state_varlen(self, x, weights, dweights, lengths, dy=None, dpooled=None, dh_n=None, dx=None, grad_sync=None,
+                              hx=None, cx=None, dc_n=None, dhx=None, dcx=None):
+        """dep_rnn_backward_state_varlen: Rnn.backward for a reserve written by forward_state_varlen; lengths, hx and cx are the
+        forward's.  A row of length 0 passes its state gradient through (dhx = dh_n, dcx = dc_n)."""
+        if lengths is None:
+            raise DepError('Rnn.backward_state_varlen: lengths is required (the dense call with a state is Rnn.backward)')
+        for i, (w, g) in enumerate(zip(weights, dweights)):
+            self._warr[i] = w.data_ptr()
+            self._garr[i] = g.data_ptr()
+        state = {'hx': hx, 'cx': cx, 'dc_n': dc_n, 'dhx': dhx, 'dcx': dcx}
+        st = RnnStateGrad(*[_ptr(self._state(v, k)) for k, v in state.items()])
+        check(self.lib.dep_rnn_backward_state_varlen(C.byref(self.desc), _ptr(x), _ptr(check_lengths(lengths, self.desc.B, self.device)),
+                                                     self._warr, _ptr(dy), _ptr(dpooled), _ptr(dh_n), C.byref(st), self._garr, _ptr(dx),
+                                                     _ptr(self.reserve), self.reserve.numel() * 4, _ptr(self.workspace),
+                                                     self.workspace.numel() * 4, stream(), None if grad_sync is None else C.byref(grad_sync)),
+              'dep_rnn_backward_state_varlen')
 
     def _state(self, t, name):
         """A state tensor of a *_state call: (L*dirs, B, H) fp32, contiguous, on the device (None stays None)."""
@@ -728,7 +778,8 @@ class Rnn:
         state = {'hx': hx, 'cx': cx, 'dc_n': dc_n, 'dhx': dhx, 'dcx': dcx}
         if any(v is not None for v in state.values()):
             if lengths is not None:
-                raise DepError('Rnn.backward: a recurrent state (hx / cx / dc_n / dhx / dcx) goes with dense calls only, not with lengths')
+                raise DepError('Rnn.backward: a recurrent state (hx / cx / dc_n / dhx / dcx) goes with dense calls only, not with lengths; '
+                               'the ragged call with a state is Rnn.backward_state_varlen')
             st = RnnStateGrad(*[_ptr(self._state(v, k)) for k, v in state.items()])
             check(self.lib.dep_rnn_backward_state(*args[:6], C.byref(st), *args[6:], None if grad_sync is None else C.byref(grad_sync)),
                   'dep_rnn_backward_state')

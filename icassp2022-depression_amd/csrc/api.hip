@@ -502,8 +502,8 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
     if (const int rf = bigru_refusal(d, "dep_rnn_forward")) return rf;
     DEP_CHECK_ARG(make_layout(d, lo));
     const dep_rnn_state st = state ? *state : dep_rnn_state{nullptr, nullptr, nullptr};      // NULL and a struct of NULLs are the plain call
-    if (const int rf = state_refusal(d, lo, "dep_rnn_forward_state", st.hx || st.cx || st.c_n, st.cx || st.c_n)) return rf;
-    DEP_CHECK_ARG(!lengths || !(st.hx || st.cx || st.c_n));
+    // (state together with lengths is dep_rnn_forward_state_varlen: the ragged instances of rnn_sweep.hip carry the state through dead steps)
+    if (const int rf = state_refusal(d, lo, lengths ? "dep_rnn_forward_state_varlen" : "dep_rnn_forward_state", st.hx || st.cx || st.c_n, st.cx || st.c_n)) return rf;
     const int mode = dep_get_gemm_mode();
     if (const int rf = ragged_mode_refusal("dep_rnn_forward_varlen", lengths, mode)) return rf;
     const RnnPlan p = make_plan(d, lo, mode, dep_exclusive_on(), lengths != nullptr);
@@ -695,6 +695,16 @@ extern "C" int dep_rnn_forward_varlen(const dep_rnn_desc* d, const float* x, con
     return rnn_forward_impl(d, x, lengths, weights, y, pooled, h_n, nullptr, reserve, reserve_bytes, workspace, workspace_bytes, stream);
 }
 
+extern "C" int dep_rnn_forward_state_varlen(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights,
+                                            float* y, float* pooled, float* h_n, const dep_rnn_state* st, void* reserve, size_t reserve_bytes,
+                                            void* workspace, size_t workspace_bytes, void* stream) {
+    if (!lengths) {
+        dep_set_error("dep_rnn_forward_state_varlen: lengths is NULL; the dense call with a state is dep_rnn_forward_state");
+        return DEP_ERR_ARG;
+    }
+    return rnn_forward_impl(d, x, lengths, weights, y, pooled, h_n, st, reserve, reserve_bytes, workspace, workspace_bytes, stream);
+}
+
 static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights, const float* dy,
                              const float* dpooled, const float* dh_n, const dep_rnn_state_grad* state, float* const* dweights, float* dx,
                              void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
@@ -704,10 +714,10 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
     DEP_CHECK_ARG(make_layout(d, lo));
     const dep_rnn_state_grad st = state ? *state : dep_rnn_state_grad{nullptr, nullptr, nullptr, nullptr, nullptr};      // NULL and a struct of NULLs are the plain call
     const bool has_state = st.hx || st.cx || st.dc_n || st.dhx || st.dcx;
-    if (const int rf = state_refusal(d, lo, "dep_rnn_backward_state", has_state, st.cx || st.dc_n || st.dcx)) return rf;
-    DEP_CHECK_ARG(!lengths || !has_state);
-    // the state's dW_hh term reads the gate-gradient rows of one time step as a (B x rows) matrix of row stride T * ldg
-    DEP_CHECK_ARG(!st.hx || (long)d->T * d->dirs * (d->cell == DEP_CELL_GRU ? 3 : 4) * d->H <= 0x7fffffffL);
+    if (const int rf = state_refusal(d, lo, lengths ? "dep_rnn_backward_state_varlen" : "dep_rnn_backward_state", has_state, st.cx || st.dc_n || st.dcx)) return rf;
+    // the dense call's dW_hh state term reads the gate-gradient rows of one time step as a (B x rows) matrix of row stride T * ldg
+    // (a ragged call gathers each row's own step with 64-bit offsets, dep_state_dwhh_ragged: no such bound)
+    DEP_CHECK_ARG(!st.hx || lengths || (long)d->T * d->dirs * (d->cell == DEP_CELL_GRU ? 3 : 4) * d->H <= 0x7fffffffL);
     const int mode = dep_get_gemm_mode();
     if (const int rf = ragged_mode_refusal("dep_rnn_backward_varlen", lengths, mode)) return rf;
     const RnnPlan p = make_plan(d, lo, mode, dep_exclusive_on(), lengths != nullptr);
@@ -940,7 +950,13 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
                 // (state_refusal: the tile / generic sweeps ran, so the rows are fp32, D*G*H wide, and the contractions above unpaired.)
                 const float* hxd = a.hx + (size_t)dd * B * H;
                 const size_t t0 = dd == 0 ? 0 : (size_t)T - 1;
-                if (gru) {
+                if (lengths) {
+                    // ragged: the first sweep step is per row (t0_b = 0; reverse direction len_b - 1, none for an empty row), so the rows
+                    // cannot be one strided GEMM operand: a direct exact-fp32 kernel gathers them (fixed order over b, no workspace)
+                    rc = dep_state_dwhh_ragged(dg, ldg, lengths, B, T, dd, hxd, gru ? 2 * H : 4 * H, H, gl[1], s);
+                    if (rc) return rc;
+                    if (gru) { rc = dep_state_dwhh_ragged(dghn + (size_t)dd * H, D * H, lengths, B, T, dd, hxd, H, H, gl[1] + (size_t)2 * H * H, s); if (rc) return rc; }
+                } else if (gru) {
                     rc = dep_gemm_internal(1, 0, 2 * H, H, B, dg + t0 * ldg, T * ldg, hxd, H, gl[1], H, nullptr, 1.f, 0, 0, gws, gwsb, ho, s);
                     if (rc) return rc;
                     rc = dep_gemm_internal(1, 0, H, H, B, dghn + (size_t)dd * H + t0 * D * H, T * D * H, hxd, H, gl[1] + (size_t)2 * H * H, H, nullptr,
@@ -990,6 +1006,19 @@ extern "C" int dep_rnn_backward_varlen(const dep_rnn_desc* d, const float* x, co
     DEP_CHECK_ARG(lengths);
     return rnn_backward_impl(d, x, lengths, weights, dy, dpooled, dh_n, nullptr, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
                              stream, nullptr);
+}
+
+extern "C" int dep_rnn_backward_state_varlen(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights,
+                                             const float* dy, const float* dpooled, const float* dh_n, const dep_rnn_state_grad* st,
+                                             float* const* dweights, float* dx, void* reserve, size_t reserve_bytes, void* workspace,
+                                             size_t workspace_bytes, void* stream, const dep_grad_sync* gs) {
+    if (!lengths) {
+        dep_set_error("dep_rnn_backward_state_varlen: lengths is NULL; the dense call with a state is dep_rnn_backward_state");
+        return DEP_ERR_ARG;
+    }
+    DEP_CHECK_ARG(!gs || (gs->comm && gs->comm_stream && gs->comm_stream != stream));      // (gs given: dep_rnn_backward_overlapped's rule)
+    return rnn_backward_impl(d, x, lengths, weights, dy, dpooled, dh_n, st, dweights, dx, reserve, reserve_bytes, workspace, workspace_bytes,
+                             stream, gs);
 }
 
 extern "C" int dep_rnn_backward_overlapped(const dep_rnn_desc* d, const float* x, const float* const* weights, const float* dy,

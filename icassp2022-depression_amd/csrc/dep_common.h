@@ -191,7 +191,7 @@ struct dep_sweep_args {
     float drop_p; uint64_t seed; uint32_t site;
     float* pooled; float pool_scale;    // GRU top layer: (B,dirs*H) sum_t y_t * scale, or NULL
     float* h_n;              // (dirs,B,H) final states or NULL
-    // initial state of this layer (dep_rnn_forward_state; rnn_sweep.hip only -- the cluster launchers are never given one)
+    // initial state of this layer (dep_rnn_forward_state[_varlen]; rnn_sweep.hip only -- the cluster launchers are never given one)
     const float* hx;         // (dirs,B,H) h before the sweep's first step, or NULL = zeros; may be h_n's buffer
     const float* cx;         // LSTM: (dirs,B,H) c before the first step, or NULL = zeros; may be c_n's buffer
     float* c_n;              // LSTM: (dirs,B,H) c after the last step, or NULL
@@ -218,7 +218,7 @@ struct dep_sweep_bwd_args {
     float drop_p; uint64_t seed; uint32_t site;   // dropout applied to dy on load (p == 0: none)
     const float* dpooled; float pool_scale;       // GRU top layer (B,dirs*H) or NULL
     const float* dh_n;       // (dirs,B,H) or NULL
-    // state of this layer (dep_rnn_backward_state; rnn_sweep.hip only): what the forward started from, and the state gradients
+    // state of this layer (dep_rnn_backward_state[_varlen]; rnn_sweep.hip only): what the forward started from, and the state gradients
     const float* hx; const float* cx;     // (dirs,B,H) the forward's initial h / c (LSTM), or NULL = zeros
     const float* dc_n;       // LSTM: (dirs,B,H) grad of c_n, enters where dh_n enters, or NULL
     float* dhx; float* dcx;  // (dirs,B,H) grad of hx / cx (LSTM), WRITTEN, or NULL
@@ -250,6 +250,9 @@ size_t dep_pack_floats(int G, int H);               // floats of one packed (G*H
 int dep_pack_whh(const float* w_hh, float* wp, float* wpT, int G, int H, hipStream_t s);
 // bias-gradient finish: sums partial rows
 int dep_finish_db(const dep_sweep_bwd_args& a, float* const* db_ih, float* const* db_hh);
+// ragged state call: dw_hh (M, H) += sum_{b : len_b > 0} dg[b, t0_b, :M]^T hx[b, :], t0_b = 0 or (reverse) len_b - 1; dg rows are lddg wide, T per batch row
+int dep_state_dwhh_ragged(const float* dg, int lddg, const int* lengths, int B, int T, int reverse, const float* hx, int M, int H, float* dw_hh,
+                          hipStream_t s);
 
 // cluster-parallel sweeps (rnn_cluster.hip)
 bool dep_cluster_ok(int cell, int H, int B, int dirs);

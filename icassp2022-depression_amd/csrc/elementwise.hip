@@ -549,6 +549,20 @@ __global__ void loss_accumulate_kernel(const float* loss, const unsigned* status
     if (status) { const double v = (double)*status; if (v > acc[1]) acc[1] = v; }
     if (soft) { const double v = (double)*soft; if (v > acc[2]) acc[2] = v; }
 }
+// chunked scoring of a padded batch (dep_stream_*): one block row per recording, grid.y = b
+__global__ void stream_accumulate_kernel(const float* __restrict__ part, const int* __restrict__ lengths, float* __restrict__ acc,
+                                         int* __restrict__ totals, int H, int Tc) {
+    const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < H) acc[(size_t)b * H + i] += part[(size_t)b * H + i];
+    if (i == 0) totals[b] += dep_row_len(lengths, b, Tc);      // the length as the sweeps clamp it
+}
+__global__ void stream_finish_kernel(const float* __restrict__ acc, const int* __restrict__ totals, float* __restrict__ pooled, int H, int mean) {
+    const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= H) return;
+    const int n = totals[b];
+    const float v = acc[(size_t)b * H + i];
+    pooled[(size_t)b * H + i] = !mean ? v : n > 0 ? v * (1.0f / (float)n) : 0.f;      // (a select: a recording without frames is a row of zeros)
+}
 // first maximum per row (torch.max(1) on the reference's CPU path returns the first index among equals)
 __global__ void argmax_count_kernel(const float* __restrict__ p, const void* __restrict__ labels, int i64, int B, int C,
                                     long long* __restrict__ count, long long* __restrict__ pred) {
@@ -891,6 +905,18 @@ extern "C" int dep_copy2d(const float* src, long lds, float* dst, long ldd, long
 extern "C" int dep_loss_accumulate(const float* loss, const unsigned* status, const unsigned* soft, double* acc, void* stream) {
     DEP_CHECK_ARG(acc && (loss || status || soft));
     DEP_LAUNCH(loss_accumulate_kernel, dim3(1), dim3(64), 0, S_, loss, status, soft, acc);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+extern "C" int dep_stream_accumulate(const float* part, const int32_t* lengths, float* acc, int32_t* totals, int B, int H, int Tc, void* stream) {
+    DEP_CHECK_ARG(part && lengths && acc && totals && B > 0 && B <= 65535 && H > 0 && Tc > 0);
+    DEP_LAUNCH(stream_accumulate_kernel, dim3(nblk(H), B), dim3(256), 0, S_, part, lengths, acc, totals, H, Tc);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+extern "C" int dep_stream_finish(const float* acc, const int32_t* totals, float* pooled, int B, int H, int mean, void* stream) {
+    DEP_CHECK_ARG(acc && totals && pooled && B > 0 && B <= 65535 && H > 0);
+    DEP_LAUNCH(stream_finish_kernel, dim3(nblk(H), B), dim3(256), 0, S_, acc, totals, pooled, H, mean);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }

@@ -109,6 +109,9 @@ __device__ __forceinline__ f32x4 rowsum16(f32x4 v) {
 //   forward : state (h, c) = live ? new : previous ; y[b,t] = live ? h_t : 0 ; the pool takes live steps only ; saved c = live ? c_t : 0
 //   backward: gate gradients of (b,t) = live ? computed : 0 ; dh (dc) carried to the previous step = live ? computed : incoming
 // Selects, never value * 0: the saved gates / dy of dead positions may be anything.  Every workgroup still runs all T steps.
+// With a state (dep_rnn_*_state_varlen) the same selects carry hx / cx through dead steps: a reverse sweep, which meets them first, reaches
+// t = len - 1 with its state, and an empty row hands h, c (backward: dh, dc) through bit for bit.  The backward takes h_prev / c_prev of
+// that first live step from the state, as at sweep step 0, not from the dead position behind it.
 // RAG = false is the dense text: the predicate is compiled out.
 // =============================================================================== GRU forward
 // BI: the bidirectional instances (grid.y = 2, dir = blockIdx.y): direction 1 sweeps t = T-1 .. 0 on p.d[1], and every array is the
@@ -250,6 +253,12 @@ __global__ __launch_bounds__(512) void gru_bwd_mfma(BwdP p) {
                 const size_t so = row * SW + dir * H + col0;
                 r = ld4(p.sv0 + so); z = ld4(p.sv1 + so); n = ld4(p.sv2 + so); hn = ld4(p.sv3 + so);
                 hp = s > 0 ? ld4(p.y + ((BI && dir) ? row + 1 : row - 1) * p.ldy + dir * H + col0) : hx0[jj];
+                // a ragged row's reverse sweep starts at t = len - 1: its h_prev is the state, not the dead position behind it (which holds 0)
+                // Read again from memory, on a branch only that step takes (most waves skip it in most steps): as a per-value select of
+                // hx0 it cost the ragged bidirectional backward 0.7 % at H = 256
+                if constexpr (RAG && BI) {
+                    if (dir && s > 0 && t == len - 1) hp = p.hx ? ld4(p.hx + ((size_t)dir * p.B + b) * H + col0) : zero4();
+                }
                 if (p.dy) {
                     const size_t o = row * p.lddy + dir * H + col0;
                     f32x4 dyv = ld4(p.dy + o);
@@ -432,7 +441,8 @@ __global__ __launch_bounds__(512) void lstm_bwd_mfma(BwdP p) {
                 const float* gs = p.sv0 + row * ldsg + dir * 4 * H + col0;
                 ig = ld4(gs); fg = ld4(gs + H); gg = ld4(gs + 2 * H); og = ld4(gs + 3 * H);
                 ct = ld4(p.sv1 + row * ldsc + dir * H + col0);
-                if (s > 0) {
+                // (RAG: a ragged row's reverse sweep starts at t = len - 1; c_prev of that step is the state too, not the dead position behind it)
+                if (s > 0 && !(RAG && dir && t == len - 1)) {
                     const size_t rowp = dir ? row + 1 : row - 1;
                     cp = ld4(p.sv1 + rowp * ldsc + dir * H + col0);
                 } else if (p.cx) {
@@ -612,7 +622,7 @@ __global__ __launch_bounds__(GEN_T) void gru_bwd_generic(BwdP p) {
         for (int i = threadIdx.x; i < H; i += GEN_T) {
             float s = 0.f;
             for (int k = 0; k < G3; ++k) s = fmaf(dg[k], W[(size_t)k * H + i], s);
-            dh[i] += s;
+            if (!RAG || t < len) dh[i] += s;      // (dead step: the incoming dh passes through bit for bit, -0.0 included)
         }
         __syncthreads();
     }
@@ -704,7 +714,8 @@ __global__ __launch_bounds__(GEN_T) void lstm_bwd_generic(BwdP p) {
             const float ig = gs[i], fg = gs[H + i], gg = gs[2 * H + i], og = gs[3 * H + i];
             const float ct = p.sv1[row * ldsc + dir * H + i];
             float cp = cx0[i];
-            if (s > 0) { const size_t rowp = dir ? row + 1 : row - 1; cp = p.sv1[rowp * ldsc + dir * H + i]; }
+            // (RAG: a ragged row's reverse sweep starts at t = len - 1, whose c_prev is the state as well)
+            if (s > 0 && !(RAG && dir && t == len - 1)) { const size_t rowp = dir ? row + 1 : row - 1; cp = p.sv1[rowp * ldsc + dir * H + i]; }
             float d = dh[i];
             if (p.dy) {
                 const size_t o = row * p.lddy + dir * H + i;
@@ -793,6 +804,35 @@ __global__ void finish_db_kernel(const float* __restrict__ part, int nrows, int 
     } else {
         db_ih[i] = s; db_hh[i] = s;
     }
+}
+
+// =============================================================================== the state's dW_hh term of a ragged call
+// C[m, k] += sum over rows b with len_b > 0 of A[b, t0_b, m] * hx[b, k]   (m < M gate-gradient columns, k < H), t0_b = 0 or, for the
+// reverse direction, len_b - 1: the gate gradients of each row's first sweep step against the state that step started from.  The dense
+// state call forms this with a GEMM over the rows of ONE time step; here the step is per row, so the rows are gathered through LDS.
+// Exact fp32 (fmaf chain), rows added in the order b = 0 .. B-1 by one thread per output element: no atomics, a pure function of the
+// data.  Read-modify-write of C in stream order behind the main contraction, which wrote it with beta = 0.
+constexpr int SDW = 16;      // output tile edge and rows per LDS stage
+__global__ __launch_bounds__(SDW * SDW) void state_dwhh_ragged(const float* __restrict__ A, int lda, const int* __restrict__ lengths, int T, int rev,
+                                                               const float* __restrict__ hx, int B, int M, int H, float* __restrict__ C) {
+    __shared__ float As[SDW][SDW + 1];      // [row][gate-gradient column]
+    __shared__ float Hs[SDW][SDW + 1];      // [row][hidden unit]
+    const int tx = threadIdx.x & (SDW - 1), ty = threadIdx.x / SDW;
+    const int m0 = blockIdx.y * SDW, k0 = blockIdx.x * SDW;
+    float acc = 0.f;
+    for (int b0 = 0; b0 < B; b0 += SDW) {
+        const int b = b0 + ty;
+        const int len = b < B ? dep_row_len(lengths, b, T) : 0;
+        const bool live = len > 0;            // an empty row has no first step: it contributes nothing (a select, never value * 0)
+        const size_t row = (size_t)b * T + (rev ? len - 1 : 0);
+        As[ty][tx] = (live && m0 + tx < M) ? A[row * lda + m0 + tx] : 0.f;
+        Hs[ty][tx] = (live && k0 + tx < H) ? hx[(size_t)b * H + k0 + tx] : 0.f;
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < SDW; ++r) acc = fmaf(As[r][ty], Hs[r][tx], acc);
+        __syncthreads();
+    }
+    if (m0 + ty < M && k0 + tx < H) C[(size_t)(m0 + ty) * H + k0 + tx] += acc;
 }
 
 int pick_jpw(int H, int* nw) {
@@ -887,7 +927,6 @@ int dep_launch_sweep_fwd(const dep_sweep_args& a) {
     p.hx = a.hx; p.cx = a.cx; p.c_n = a.c_n;
     DEP_CHECK_ARG(a.y && a.gi);
     DEP_CHECK_ARG(a.cell == DEP_CELL_LSTM || (!a.cx && !a.c_n));                  // a GRU has no cell state
-    DEP_CHECK_ARG(!a.lengths || (!a.hx && !a.cx && !a.c_n));                      // state goes with dense calls only
     const bool bigru = a.cell == DEP_CELL_GRU && a.dirs == 2;
     DEP_CHECK_ARG(!bigru || dep_sweep_use_mfma(a.H, a.impl));      // a bidirectional GRU has tile-MFMA instances only
     DepProfScope prof(a.cell == DEP_CELL_GRU ? DEP_PROF_GRU_FWD : DEP_PROF_LSTM_FWD, a.stream);
@@ -926,7 +965,6 @@ int dep_launch_sweep_bwd(const dep_sweep_bwd_args& a) {
     p.lengths = a.lengths; p.pool_mean = a.pool_mean;
     p.hx = a.hx; p.cx = a.cx; p.dc_n = a.dc_n; p.dhx = a.dhx; p.dcx = a.dcx;
     DEP_CHECK_ARG(a.cell == DEP_CELL_LSTM || (!a.cx && !a.dc_n && !a.dcx));       // a GRU has no cell state
-    DEP_CHECK_ARG(!a.lengths || (!a.hx && !a.cx && !a.dc_n && !a.dhx && !a.dcx)); // state goes with dense calls only
     DEP_CHECK_ARG(a.dbpart_rows >= p.nwg * a.dirs);
     DEP_CHECK_ARG(a.sv0 && a.dgi && a.dbpart);
     const bool bigru = a.cell == DEP_CELL_GRU && a.dirs == 2;
@@ -948,6 +986,15 @@ int dep_launch_sweep_bwd(const dep_sweep_bwd_args& a) {
         } else if (a.cell == DEP_CELL_GRU) DEP_LAUNCH(gru_bwd_generic<>, grid, dim3(GEN_T), lds, a.stream, p);
         else DEP_LAUNCH(lstm_bwd_generic<>, grid, dim3(GEN_T), lds, a.stream, p);
     }
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+
+int dep_state_dwhh_ragged(const float* dg, int lddg, const int* lengths, int B, int T, int reverse, const float* hx, int M, int H, float* dw_hh,
+                          hipStream_t s) {
+    DEP_CHECK_ARG(dg && lengths && hx && dw_hh && B > 0 && T > 0 && M > 0 && H > 0 && lddg >= M);
+    DEP_LAUNCH(state_dwhh_ragged, dim3(dep_cdiv(H, SDW), dep_cdiv(M, SDW)), dim3(SDW * SDW), 0, s, dg, lddg, lengths, T, reverse ? 1 : 0, hx, B, M, H,
+               dw_hh);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }

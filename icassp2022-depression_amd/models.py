@@ -158,18 +158,25 @@ class _MLPHead:
 class _AudioStream:
     """AudioGRU.stream(): chunked scoring of one batch of recordings with the memory of one chunk.  push() runs a chunk through the
     stack on the per-layer sweeps with the recurrent state carried in place (h_n written over hx, dep_rnn_forward_state) and adds the
-    chunk's sum pool into an accumulator; output() is what model(x) returns for the chunks concatenated along T."""
+    chunk's sum pool into an accumulator; output() is what model(x) returns for the chunks concatenated along T.
+    Recordings of different lengths: push(chunk, lengths) with the live frames of each recording inside the chunk (0 once it has ended)
+    runs the chunk through dep_rnn_forward_state_varlen -- an ended recording's state passes through -- and keeps per-row frame totals on
+    the device; output() is then model(x_padded, lengths=totals).  No host read anywhere."""
 
     def __init__(self, model):
         self.m = model
         self.B = None
         self.T = 0
+        self.totals = None                         # ragged pushes: int32 device vector (B), the frames of each recording so far
         if model.variant == 'clf':                 # LayerNorm's affine folded into layer 0, as encode() does (eval: the weights stand still)
             P = model._params
             L.ln_fold_fwd(model._rnn_w[0], model._rnn_w[2], P['ln.weight'].data, P['ln.bias'].data, *model._fold[:2])
 
-    def push(self, chunk):
-        """chunk: (B, Tc, F), host or device; Tc >= 1 and may differ from push to push, B is fixed by the first push."""
+    def push(self, chunk, lengths=None):
+        """chunk: (B, Tc, F), host or device; Tc >= 1 and may differ from push to push, B is fixed by the first push.
+        lengths: None (every recording has Tc frames in this chunk), or B integers in [0, Tc] -- a host array / sequence or an int32 device
+        tensor: the live frames of each recording inside this chunk, contiguous from the recording's start (the caller's responsibility,
+        as with every `lengths`); a recording that has ended pushes 0 from then on.  A stream takes lengths on every push or on none."""
         m = self.m
         x = m._to_dev(chunk)
         if x.dim() != 3 or x.shape[1] < 1 or x.shape[2] != m.embedding_size:
@@ -183,16 +190,29 @@ class _AudioStream:
             self.h = mk(m.rnn_layers, B, m.hidden_dims)          # the carried state: zeros before the first chunk
             self.acc = mk(B, m.hidden_dims)                      # sum over all steps so far of the top layer's output
             self.part = mk(B, m.hidden_dims)                     # one chunk's sum
+            if lengths is not None:
+                self.totals = torch.zeros(B, dtype=torch.int32, device=m.device)
         elif B != self.B:
             raise L.DepError(f'stream.push: the batch size is fixed by the first push ({self.B}), got {B}')
+        if (lengths is not None) != (self.totals is not None):
+            raise L.DepError('stream.push: a stream takes lengths on every push or on none (the first push decides)')
+        if lengths is not None:
+            if torch.is_tensor(lengths) and lengths.is_cuda:
+                lengths = L.check_lengths(lengths, B, m.device)              # a device vector is read in place: int32, B values
+            else:
+                lengths = _RnnCache.lengths_on(lengths, B, m.device)
         if m.variant == 'clf':                                   # LayerNorm is per row: per chunk, as encode() runs it
             xn, _ = L.layernorm_fwd(x.view(B * Tc, F), None, None, save=False)
             weights = m._rnn_w_fold
         else:
             xn, weights = x.view(B * Tc, F), m._rnn_w
         rnn = m._stream_rnns.get(B, Tc, L.RUN_EVAL)
-        rnn.forward(xn, weights, pooled=self.part, h_n=self.h, hx=self.h)
-        L.axpby(self.part, self.acc, 1.0, 1.0)
+        if lengths is not None:
+            rnn.forward_state_varlen(xn, weights, lengths, pooled=self.part, h_n=self.h, hx=self.h)
+            L.stream_accumulate(self.part, lengths, self.acc, self.totals, Tc)
+        else:
+            rnn.forward(xn, weights, pooled=self.part, h_n=self.h, hx=self.h)
+            L.axpby(self.part, self.acc, 1.0, 1.0)
         self.T += Tc
 
     def output(self):
@@ -200,7 +220,10 @@ class _AudioStream:
         if self.T == 0:
             raise L.DepError('stream.output: nothing was pushed')
         pooled = torch.empty_like(self.acc)
-        L.axpby(self.acc, pooled, 1.0 / self.T if m.variant == 'clf' else 1.0, 0.0)      # the classifier pools by the mean over all steps
+        if self.totals is not None:                # the classifier's mean is over each recording's own frames (none: a row of zeros)
+            L.stream_finish(self.acc, self.totals, pooled, m.variant == 'clf')
+        else:
+            L.axpby(self.acc, pooled, 1.0 / self.T if m.variant == 'clf' else 1.0, 0.0)      # the classifier pools by the mean over all steps
         z = m._head.forward(pooled, 0, False)
         out = torch.empty_like(z)
         L.head_loss(L.LOSS_CE_ON_SOFTMAX if m.variant == 'clf' else L.LOSS_L1_RELU, z, None, out, None, None, 1.0)

@@ -278,7 +278,8 @@ int dep_rnn_backward_overlapped_varlen(const dep_rnn_desc* d, const float* x, co
  *     at a shape without cluster kernels (a bidirectional GRU is always such a descriptor);
  *   - on any other descriptor the call returns DEP_ERR_ARG before anything is launched, with the rule in dep_last_error.
  * Scope
- *   - dense calls only (there is no `lengths` parameter); all three run modes for the forward; the GEMM modes of the dense call;
+ *   - dense calls only (there is no `lengths` parameter: the ragged pair is dep_rnn_*_state_varlen below); all three run modes for the
+ *     forward; the GEMM modes of the dense call;
  *   - h_n may be the same buffer as hx, and c_n the same as cx: every workgroup reads its rows of the state before the first step
  *     and writes them after the last (chunked streaming carries the state in place this way);
  *   - reserve and workspace sizes and every offset are those of dep_rnn_forward / dep_rnn_backward;
@@ -294,6 +295,54 @@ int dep_rnn_backward_state(const dep_rnn_desc* d, const float* x, const float* c
                            float* const* dweights, float* dx,
                            void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
                            void* stream, const dep_grad_sync* gs);
+
+/* Recurrent state together with `lengths`: `gru(pack_padded_sequence(x, lengths, enforce_sorted=False), hx)` as one call.  What it is
+ * for: scoring a padded batch of recordings of different lengths chunk by chunk, and truncated or exact BPTT across a chunk boundary of
+ * a padded batch.  `lengths` is the device array of the *_varlen calls (B int32 values, clamped on the device to [0, T]); the state
+ * structs, their layout and their NULL rules are those of dep_rnn_forward_state / dep_rnn_backward_state above.
+ * Row equivalence
+ *   - row b of every result equals what dep_rnn_forward_state / dep_rnn_backward_state give for that row alone: x[b:b+1, :len_b],
+ *     hx[:, b:b+1], cx[:, b:b+1] (and dh_n[:, b:b+1], dc_n[:, b:b+1]) at T' = len_b.
+ * Padding
+ *   - padded positions (t >= len_b) of every output sequence and of dx are exactly 0.0; pooled follows the varlen rule (sum over
+ *     t < len_b, the mean divides by len_b); dropout draws the dense call's masks (unchanged element index).  The padded positions of x
+ *     must be finite, as for every ragged call.
+ * Directions
+ *   - the forward direction starts from its slice of hx / cx at t = 0; the reverse direction starts from its own slice at t = len_b - 1.
+ * Final states
+ *   - h_n / c_n are the states after the row's last live sweep step (t = len_b - 1 forward, t = 0 reverse); dh_n / dc_n enter there.
+ * len_b = 0: the state passes through
+ *   - h_n[:, b] = hx[:, b] and c_n[:, b] = cx[:, b], bit for bit; dhx[:, b] = dh_n[:, b] and dcx[:, b] = dc_n[:, b], bit for bit (zeros
+ *     for a NULL input); y, pooled and dx of the row are 0 and it contributes to no weight gradient.  This is the rule under which
+ *     chunks compose: a recording that has ended pushes length 0 from then on and its state and state gradient travel through
+ *     unchanged.  With a NULL hx it is the "h_n is 0" rule of the varlen contract.
+ * Weight gradients
+ *   - they include the state's term per row: dW_hh += sum_b dG[b, t0_b, :]^T hx[b] with t0_b = 0 (forward direction) / len_b - 1
+ *     (reverse direction), over the rows with len_b > 0 only.  Exact fp32, summed in the order b = 0 .. B-1, no atomics.
+ * Aliasing and responsibility
+ *   - h_n may be the same buffer as hx and c_n the same as cx, as in the dense state call;
+ *   - the backward must be given the forward's hx / cx AND lengths.  This is the caller's responsibility and is not detected.
+ * Where it is accepted
+ *   - exactly where the dense state call is accepted: a descriptor whose layout has no cluster exchange buffer
+ *     (dep_rnn_workspace_xbuf_offset(d) == (size_t)-1); elsewhere a non-NULL member is DEP_ERR_ARG before anything is launched, with the
+ *     rule in dep_last_error;
+ *   - also refused before any launch: cx / c_n / dc_n / dcx on a GRU, lengths == NULL (the dense call is dep_rnn_*_state), and GEMM
+ *     modes 2 / 3 (as for every ragged call).
+ * All-NULL state
+ *   - st == NULL, or a struct of NULLs, is dep_rnn_forward_varlen / dep_rnn_backward_varlen (dep_rnn_backward_overlapped_varlen when gs
+ *     is given) on every descriptor: the same launches, the same bits.
+ * Unchanged surroundings
+ *   - all three run modes for the forward; gs: NULL, or as for dep_rnn_backward_overlapped; reserve and workspace sizes and every offset
+ *     are those of dep_rnn_forward / dep_rnn_backward; the kernel instances launched are those of the plain ragged call. */
+int dep_rnn_forward_state_varlen(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights,
+                                 float* y, float* pooled, float* h_n, const dep_rnn_state* st,
+                                 void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+int dep_rnn_backward_state_varlen(const dep_rnn_desc* d, const float* x, const int32_t* lengths, const float* const* weights,
+                                  const float* dy, const float* dpooled, const float* dh_n, const dep_rnn_state_grad* st,
+                                  float* const* dweights, float* dx,
+                                  void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
+                                  void* stream, const dep_grad_sync* gs);
 
 /* ------------------------------------------------------------------ dense --------- */
 /* C[M,N] = opA(A)[M,K] * opB(B)[K,N] + bias[N] + beta*C      (fp32 MFMA, exact f32 products)
@@ -696,6 +745,13 @@ int dep_gather_rows(const float* src, const long long* idx, float* dst, long nro
 int dep_copy2d(const float* src, long lds, float* dst, long ldd, long rows, long cols, void* stream);
 int dep_argmax_count(const float* p, const void* labels, int labels_i64, int B, int C, long long* count, long long* pred,
                      void* stream);
+/* Bookkeeping of a chunked scoring run over a padded batch (AudioGRU.stream() with per-chunk lengths), no host read anywhere:
+ *   dep_stream_accumulate : acc[b, :] += part[b, :] (one chunk's sum pool, (B,H)) and totals[b] += min(max(lengths[b], 0), Tc) -- the
+ *                           frames of recording b seen so far; lengths and totals are device int32 vectors of B values;
+ *   dep_stream_finish     : pooled[b, :] = acc[b, :] * (1 / totals[b]) when mean != 0 (a total of 0 gives a row of 0.0: it divides by
+ *                           nothing), acc[b, :] when mean == 0. */
+int dep_stream_accumulate(const float* part, const int32_t* lengths, float* acc, int32_t* totals, int B, int H, int Tc, void* stream);
+int dep_stream_finish(const float* acc, const int32_t* totals, float* pooled, int B, int H, int mean, void* stream);
 
 #ifdef __cplusplus
 }
