@@ -163,6 +163,7 @@ struct Layout {
     bool cluster;                    // cluster-parallel sweeps (rnn_cluster*.hip): the workspace has their exchange buffer
     bool fused2;                     // 2-layer GRU, H = 256: both layers in one launch (rnn_fused2*.hip) where the call's plan allows it
     size_t wih_img;                  // workspace: packed W_ih of layer 1 for the fused launches
+    size_t hxstage;                  // workspace (impl 4 only): B x H floats, a layer's hx copied aside when T = 1 and h_n overlaps it
 };
 
 // A bidirectional GRU runs the tile-MFMA sweeps (gru_*_mfma<JPW, RAG, true>) and nothing else: it has no generic, cluster or fused
@@ -177,8 +178,20 @@ int bigru_refusal(const dep_rnn_desc* d, const char* who) {
     return DEP_ERR_ARG;
 }
 
+// impl = 4, "the per-layer cluster sweeps": the unidirectional GRU where gru_fwd_cluster_r1 / gru_bwd_cluster_r1 have instances.
+bool percluster_ok(const dep_rnn_desc* d) { return d->cell == DEP_CELL_GRU && d->dirs == 1 && dep_cluster_ok(d->cell, d->H, d->B, d->dirs); }
+
+// dep_last_error for an impl = 4 descriptor refused by the rule above (DEP_OK for any other descriptor)
+int percluster_refusal(const dep_rnn_desc* d, const char* who) {
+    if (!d || d->impl != 4 || d->H <= 0 || percluster_ok(d)) return DEP_OK;
+    dep_set_error("%s: impl = 4 (the per-layer cluster sweeps) is a unidirectional GRU with H in {64, 128, 256, 512}: cell must be DEP_CELL_GRU and "
+                  "dirs 1; got cell = %d, H = %d, dirs = %d", who, d->cell, d->H, d->dirs);
+    return DEP_ERR_ARG;
+}
+
 bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     if (!d || d->B <= 0 || d->T <= 0 || d->F <= 0 || d->H <= 0 || d->L < 1 || d->L > MAXL) return false;
+    if (d->impl == 4 && !percluster_ok(d)) return false;
     if (d->cell == DEP_CELL_GRU) { if (d->dirs != 1 && !(d->dirs == 2 && bigru_ok(d))) return false; }
     else if (d->cell == DEP_CELL_LSTM) { if (d->dirs != 1 && d->dirs != 2) return false; }
     else return false;
@@ -256,15 +269,16 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
         if (b3 > gb) gb = b3;
     }
     lo.gemm = w; lo.gemm_bytes = gb; w += al(gb / sizeof(float) + 64);
-    // impl: 0 auto (cluster > tile-MFMA > generic), 1 generic, 2 tile-MFMA, 3 cluster (must be supported)
+    // impl: 0 auto (cluster > tile-MFMA > generic), 1 generic, 2 tile-MFMA, 3 cluster (must be supported), 4 the per-layer cluster
+    // sweeps (GRU, dirs = 1, checked above): the cluster layout without the fused two-layer extras, plus the hx staging area
     // (a bidirectional GRU is never planned onto the cluster, 16-unit-member or fused kernels: dep_cluster_ok does not look at dirs)
     const bool cok = d->cell == DEP_CELL_GRU ? d->dirs == 1 && dep_cluster_ok(d->cell, d->H, d->B, d->dirs) : dep_cluster_lstm_ok(d->H, d->B, d->dirs);
     if (d->impl == 3 && !cok) return false;
-    lo.cluster = cok && (d->impl == 0 || d->impl == 3);
+    lo.cluster = cok && (d->impl == 0 || d->impl == 3 || d->impl == 4);
     lo.xbuf = w; lo.xbuf_bytes = !lo.cluster ? 0 : (d->cell == DEP_CELL_GRU ? dep_cluster_xbuf_bytes(d->cell, d->H, d->B, d->dirs)
                                                                 : dep_cluster_lstm_xbuf_bytes(d->H, d->B, d->dirs));
     if (lo.cluster) lo.nwg = dep_cdiv(d->B, 16);      // the cluster sweeps write one row per tile whatever the tile-MFMA sweep could do at this H
-    lo.fused2 = lo.cluster && dep_fused2_ok(d->cell, d->H, d->L, d->dirs);
+    lo.fused2 = lo.cluster && d->impl != 4 && dep_fused2_ok(d->cell, d->H, d->L, d->dirs);
     if (lo.fused2) {
         size_t fb = dep_fused2_xbuf_bytes(d->B); if (fb > lo.xbuf_bytes) lo.xbuf_bytes = fb;
         if (lo.keep) { fb = dep_fused2_bwd_xbuf_bytes(d->B); if (fb > lo.xbuf_bytes) lo.xbuf_bytes = fb; }
@@ -277,6 +291,7 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
         lo.dghn2 = w; w += al(lo.BT * H);
         lo.dbpart2 = w; w += al((size_t)lo.nwg * 4 * H);
     }
+    lo.hxstage = w; if (d->impl == 4) w += al((size_t)d->B * H);
     lo.ws_floats = w;
     return true;
 }
@@ -285,12 +300,12 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
 
 extern "C" size_t dep_rnn_reserve_bytes(const dep_rnn_desc* d) {
     Layout lo;
-    if (!make_layout(d, lo)) { (void)bigru_refusal(d, "dep_rnn_reserve_bytes"); return 0; }
+    if (!make_layout(d, lo)) { if (!percluster_refusal(d, "dep_rnn_reserve_bytes")) (void)bigru_refusal(d, "dep_rnn_reserve_bytes"); return 0; }
     return lo.reserve_floats * sizeof(float);
 }
 extern "C" size_t dep_rnn_workspace_bytes(const dep_rnn_desc* d) {
     Layout lo;
-    if (!make_layout(d, lo)) return 0;
+    if (!make_layout(d, lo)) { (void)percluster_refusal(d, "dep_rnn_workspace_bytes"); return 0; }
     return lo.ws_floats * sizeof(float);
 }
 // byte offset of layer l's output sequence (B,T,H*dirs) inside the reserve (zero-copy access for the caller)
@@ -389,6 +404,9 @@ struct RnnPlan {
 // tile / generic sweeps, the per-layer cluster GRU sweeps and the cluster BiLSTM sweeps, each of which launches its RAG instance when
 // the sweep arguments carry lengths -- never onto the fused two-layer launches or the 16-unit-member forward (so it enqueues no
 // soft-fallback launches either).  Everything else (images, saved-gate format, PK gate gradients) is decided as for a dense call.
+// impl = 4 (the per-layer cluster sweeps) is planned like a ragged call, dense or not: FWD_CLUSTER_GRU / BWD_CLUSTER_GRU and what follows
+// from them.  Its layout has no fused2 part, and the 16-unit-member kernel does not belong to the descriptor, so the 32-unit-member image
+// and the 16-bit saved gates are chosen as on a shape without that kernel.
 RnnPlan make_plan(const dep_rnn_desc* d, const Layout& lo, int mode, bool excl, bool ragged) {
     const RnnSwitches& sw = dep_rnn_switches();
     const bool gru = d->cell == DEP_CELL_GRU;
@@ -396,7 +414,7 @@ RnnPlan make_plan(const dep_rnn_desc* d, const Layout& lo, int mode, bool excl, 
     p.excl = excl; p.split = mode >= 1;
     const bool csplit = lo.cluster && p.split;
     // the kernels that fill every CU (fused forward, 16-unit members) are not for a shared GPU; the fused BACKWARD does not care
-    const bool cluster16 = lo.cluster && dep_cluster16_ok(d->cell, d->H, d->B);
+    const bool cluster16 = lo.cluster && d->impl != 4 && dep_cluster16_ok(d->cell, d->H, d->B);
     p.fwd = (lo.fused2 && p.split && excl && !ragged) ? FWD_FUSED2 : (cluster16 && excl && !ragged) ? FWD_CLUSTER16
           : !lo.cluster ? FWD_TILE : gru ? FWD_CLUSTER_GRU : FWD_CLUSTER_LSTM;
     p.bwd = (lo.fused2 && sw.fused2_bwd && p.split && dep_fused2_bwd_fits(d->B, d->T) && !ragged) ? BWD_FUSED2
@@ -477,16 +495,25 @@ int ragged_mode_refusal(const char* who, const int32_t* lengths, int mode) {
 
 // dep_rnn_*_state: a call that brings a state (any member non-NULL) runs where the per-layer sweeps of rnn_sweep.hip run the stack, and
 // the cell state belongs to the LSTM.  Checked before anything is launched (and before any HIP call); DEP_OK for a call without state.
-int state_refusal(const dep_rnn_desc* d, const Layout& lo, const char* who, bool any, bool any_c) {
+int state_refusal(const dep_rnn_desc* d, const Layout& lo, const char* who, bool any, bool any_c, bool backward) {
     if (!any) return DEP_OK;
     if (any_c && d->cell != DEP_CELL_LSTM) {
         dep_set_error("%s: cx, c_n, dc_n and dcx are the LSTM's cell state and its gradients; a GRU takes hx / dhx only", who);
         return DEP_ERR_ARG;
     }
+    if (lo.cluster && d->impl == 4) {
+        // the per-layer cluster FORWARD takes hx (gru_fwd_cluster_r1); the cluster backward has neither hx as h_prev of step 0 nor dhx
+        if (!backward && d->training != DEP_RUN_TRAIN) return DEP_OK;
+        dep_set_error("%s: on impl = 4 (the per-layer cluster sweeps) hx is taken by the forward in DEP_RUN_EVAL and DEP_RUN_DROPOUT_ONLY only, the run "
+                      "modes no backward follows: the cluster backward takes no state (no hx term in dW_hh, no dhx).  A DEP_RUN_TRAIN forward with hx "
+                      "and every backward with a state member need impl 1 or 2; got run mode %d, H = %d", who, d->training, d->H);
+        return DEP_ERR_ARG;
+    }
     if (lo.cluster) {
         dep_set_error("%s: a recurrent state (hx / cx / c_n and their gradients) is taken only where the per-layer tile-MFMA or generic sweeps "
                       "run the stack, i.e. on a descriptor without a cluster exchange buffer (dep_rnn_workspace_xbuf_offset(d) == (size_t)-1): "
-                      "impl 1 or 2, or impl 0 at a shape without cluster kernels; got cell = %d, H = %d, dirs = %d, impl = %d",
+                      "impl 1 or 2, or impl 0 at a shape without cluster kernels; got cell = %d, H = %d, dirs = %d, impl = %d.  "
+                      "(A GRU forward that no backward follows takes hx on the per-layer cluster sweeps too: impl = 4.)",
                       who, d->cell, d->H, d->dirs, d->impl);
         return DEP_ERR_ARG;
     }
@@ -499,11 +526,12 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
                             float* pooled, float* h_n, const dep_rnn_state* state, void* reserve, size_t reserve_bytes, void* workspace,
                             size_t workspace_bytes, void* stream) {
     Layout lo;
+    if (const int rf = percluster_refusal(d, "dep_rnn_forward")) return rf;
     if (const int rf = bigru_refusal(d, "dep_rnn_forward")) return rf;
     DEP_CHECK_ARG(make_layout(d, lo));
     const dep_rnn_state st = state ? *state : dep_rnn_state{nullptr, nullptr, nullptr};      // NULL and a struct of NULLs are the plain call
     // (state together with lengths is dep_rnn_forward_state_varlen: the ragged instances of rnn_sweep.hip carry the state through dead steps)
-    if (const int rf = state_refusal(d, lo, lengths ? "dep_rnn_forward_state_varlen" : "dep_rnn_forward_state", st.hx || st.cx || st.c_n, st.cx || st.c_n)) return rf;
+    if (const int rf = state_refusal(d, lo, lengths ? "dep_rnn_forward_state_varlen" : "dep_rnn_forward_state", st.hx || st.cx || st.c_n, st.cx || st.c_n, false)) return rf;
     const int mode = dep_get_gemm_mode();
     if (const int rf = ragged_mode_refusal("dep_rnn_forward_varlen", lengths, mode)) return rf;
     const RnnPlan p = make_plan(d, lo, mode, dep_exclusive_on(), lengths != nullptr);
@@ -555,7 +583,8 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
         a.pooled = l == L - 1 ? pooled : nullptr;
         a.pool_scale = pool_scale;
         a.h_n = h_n ? h_n + (size_t)l * D * B * H : nullptr;
-        // layer l's slice of the state arrays, ordered like h_n (a non-NULL member implies the tile / generic sweeps: state_refusal)
+        // layer l's slice of the state arrays, ordered like h_n (a non-NULL member implies the tile / generic sweeps, or hx on the
+        // per-layer cluster forward of impl 4: state_refusal)
         a.hx = st.hx ? st.hx + (size_t)l * D * B * H : nullptr;
         a.cx = st.cx ? st.cx + (size_t)l * D * B * H : nullptr;
         a.c_n = st.c_n ? st.c_n + (size_t)l * D * B * H : nullptr;
@@ -663,7 +692,16 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
                                    0.f, 0, 0, nullptr, 0, proj, s);
             if (rc) return rc;
         }
-        const dep_sweep_args a = sweep_args(l, nullptr);
+        dep_sweep_args a = sweep_args(l, nullptr);
+        if (p.fwd == FWD_CLUSTER_GRU && a.hx && a.h_n && T == 1 && a.hx < a.h_n + (size_t)B * H && a.h_n < a.hx + (size_t)B * H) {
+            // h_n over hx at T = 1: the sweep has no exchange, so nothing keeps a member's h_n store behind another member's read of that
+            // row of hx.  The kernel reads a copy (T >= 2: every member reads hx before it raises its first flag, and no member stores
+            // h_n before it has seen all of them)
+            if (hipMemcpyAsync(W + lo.hxstage, a.hx, (size_t)B * H * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
+                dep_set_error("dep_rnn_forward_state: staging copy of hx failed"); return DEP_ERR_HIP;
+            }
+            a.hx = W + lo.hxstage;
+        }
         rc = p.fwd == FWD_CLUSTER16 ? dep_launch_cluster16_fwd(a, W + lo.xbuf, lo.xbuf_bytes)
            : p.fwd == FWD_CLUSTER_LSTM ? dep_launch_cluster_lstm_fwd(a, W + lo.xbuf, lo.xbuf_bytes)
            : p.fwd == FWD_CLUSTER_GRU ? dep_launch_cluster_fwd(a, W + lo.xbuf, lo.xbuf_bytes) : dep_launch_sweep_fwd(a);
@@ -710,11 +748,12 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
                              void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
                              void* stream, const dep_grad_sync* gs) {
     Layout lo;
+    if (const int rf = percluster_refusal(d, "dep_rnn_backward")) return rf;
     if (const int rf = bigru_refusal(d, "dep_rnn_backward")) return rf;
     DEP_CHECK_ARG(make_layout(d, lo));
     const dep_rnn_state_grad st = state ? *state : dep_rnn_state_grad{nullptr, nullptr, nullptr, nullptr, nullptr};      // NULL and a struct of NULLs are the plain call
     const bool has_state = st.hx || st.cx || st.dc_n || st.dhx || st.dcx;
-    if (const int rf = state_refusal(d, lo, lengths ? "dep_rnn_backward_state_varlen" : "dep_rnn_backward_state", has_state, st.cx || st.dc_n || st.dcx)) return rf;
+    if (const int rf = state_refusal(d, lo, lengths ? "dep_rnn_backward_state_varlen" : "dep_rnn_backward_state", has_state, st.cx || st.dc_n || st.dcx, true)) return rf;
     // the dense call's dW_hh state term reads the gate-gradient rows of one time step as a (B x rows) matrix of row stride T * ldg
     // (a ragged call gathers each row's own step with 64-bit offsets, dep_state_dwhh_ragged: no such bound)
     DEP_CHECK_ARG(!st.hx || lengths || (long)d->T * d->dirs * (d->cell == DEP_CELL_GRU ? 3 : 4) * d->H <= 0x7fffffffL);

@@ -680,10 +680,15 @@ struct F2 {
     const unsigned* only_if; // run only if this word is set (fallback behind an exclusive forward kernel), or nullptr
     int sv16;                // saved gates r, z, n written as 16-bit fixed point
     const int* lengths; int pool_mean;      // ragged instances (RAG): row b is live for t < lengths[b]; a mean pool divides by lengths[b]
+    const float* hx;         // this layer's (B, H) initial state (dep_rnn_forward_state[_varlen] on impl 4), or nullptr = zeros
 };
 
 // RAG: the ragged-batch instances (dep_rnn_forward_varlen): h = live ? new : previous (what is published, kept and returned as h_n),
 // y / dropout(y) / the pool take live ? h : 0.  Everything about the hand-off is the dense instance's.
+// hx (a run-time pointer, as in rnn_sweep.hip): a global INPUT, so every member fills its LDS copy of the tile's 16 x H block from it in
+// front of the step loop, with no exchange -- as fp32, or (SPLIT) as the two bf16 planes of split_word(hx), the bits a previous step
+// would have published -- and starts hprev from its own two columns.  The loop, the hand-off and every trip count are untouched; a
+// ragged row with len = 0 never leaves hprev, so it returns hx bit for bit.  Rows b >= B of the last tile read nothing and stay 0.
 template <int KCH, bool SPLIT, bool RAG = false>      // SPLIT: 3-term bf16 split of the recurrent product, as in gru_fwd_cluster16
 __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
     // contraction by syntax: see DEP_FP_CONTRACT_NOTE in dep_common.h (why, and how to re-verify the dense instances after a compiler change)
@@ -708,6 +713,31 @@ __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
     unsigned short* hs_lo = hs_hi + BT * LDHB;
     float* red = smem + hs_floats;                    // [4][3][64][4]
     for (int i = tid; i < hs_floats; i += CT) hs[i] = 0.f;
+    if (p.hx) {
+        __syncthreads();                              // (the zero fill walks the planes in another order)
+        const int xshift = __ffs(H) - 1;
+#pragma unroll
+        for (int k = 0; k < KCH / 2; ++k) {           // the gather's piece map: 16-byte piece tid + CT k of the 16 x H block
+            const int i4 = (tid + CT * k) * 4;
+            const int xr = i4 >> xshift, xc = i4 & (H - 1);
+            const int xb = p.b0 + bt * BT + xr;
+            if (xb < p.B) {
+                const float* src = p.hx + (size_t)xb * H + xc;
+                const float2 x01 = ld2(src), x23 = ld2(src + 2);
+                if constexpr (SPLIT) {
+                    const unsigned v0 = split_word(x01.x), v1 = split_word(x01.y), v2 = split_word(x23.x), v3 = split_word(x23.y);
+                    const int o = xr * LDHB + xc;
+                    uint2 hi2, lo2;
+                    hi2.x = (v0 >> 16) | (v1 & 0xffff0000u); hi2.y = (v2 >> 16) | (v3 & 0xffff0000u);
+                    lo2.x = (v0 & 0xffffu) | (v1 << 16);      lo2.y = (v2 & 0xffffu) | (v3 << 16);
+                    *reinterpret_cast<uint2*>(hs_hi + o) = hi2; *reinterpret_cast<uint2*>(hs_lo + o) = lo2;
+                } else {
+                    const f32x4 f = {x01.x, x01.y, x23.x, x23.y};
+                    *reinterpret_cast<f32x4*>(hs + xr * LDH + xc) = f;
+                }
+            }
+        }
+    }
 
     constexpr int KS2 = KCH / 2;                      // 32-wide k-steps per wave (SPLIT)
     f32x4 wr[SPLIT ? 1 : 3][SPLIT ? 1 : KCH];
@@ -732,7 +762,7 @@ __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
     float2 bh[3];
 #pragma unroll
     for (int g = 0; g < 3; ++g) bh[g] = ld2(p.b_hh + g * H + col);
-    float2 hprev = f2(0.f, 0.f), pool = f2(0.f, 0.f);
+    float2 hprev = (p.hx && valid) ? ld2(p.hx + (size_t)b * H + col) : f2(0.f, 0.f), pool = f2(0.f, 0.f);
     const size_t pstride = (size_t)p.nbtp * BT * H;
     const size_t tile_base = (size_t)bt * BT * H;
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.payload, 0, p.payload_bytes, 0x00020000);
@@ -1008,7 +1038,9 @@ int dep_launch_cluster_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf_byte
     p.flags = bind_exchange(p, xbuf, a.hdr_slot, pay);
     p.only_if = a.only_if; p.sv16 = a.training ? a.sv16 : 0;
     p.lengths = a.lengths; p.pool_mean = a.pool_mean;
-    DepProfScope prof(DEP_PROF_GRU_FWD, a.stream, a.only_if == nullptr);      // a conditional fallback launch is not a sweep of the step
+    DEP_CHECK_ARG(!a.hx || (!a.only_if && (reinterpret_cast<uintptr_t>(a.hx) & 7) == 0));      // a state never travels with the fused forward's fallback; 8-byte loads
+    p.hx = a.hx;
+    DepProfScope prof(DEP_PROF_GRU_FWD, a.stream, a.only_if == nullptr);     // a conditional fallback launch is not a sweep of the step
     return launch_chunks(fwd_instance(a.H, a.split, a.lengths != nullptr), g, dim3(CT), p, a.stream, __PRETTY_FUNCTION__,
                          [&](int b0) { return hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); });
 }

@@ -161,10 +161,14 @@ class _AudioStream:
     chunk's sum pool into an accumulator; output() is what model(x) returns for the chunks concatenated along T.
     Recordings of different lengths: push(chunk, lengths) with the live frames of each recording inside the chunk (0 once it has ended)
     runs the chunk through dep_rnn_forward_state_varlen -- an ended recording's state passes through -- and keeps per-row frame totals on
-    the device; output() is then model(x_padded, lengths=totals).  No host read anywhere."""
+    the device; output() is then model(x_padded, lengths=totals).  No host read anywhere.
+    Where the stream's descriptors run the per-layer cluster sweeps (impl 4) every push's status word is folded into a device-side
+    accumulator (dep_loss_accumulate, one launch: each dep_rnn_forward clears the word); check_health() reads it."""
 
-    def __init__(self, model):
+    def __init__(self, model, rnns):
         self.m = model
+        self.rnns = rnns                           # the descriptor cache of this stream's impl
+        self.health = None                         # float64 (3,) on the device once a push ran on a descriptor with a status word
         self.B = None
         self.T = 0
         self.totals = None                         # ragged pushes: int32 device vector (B), the frames of each recording so far
@@ -206,14 +210,27 @@ class _AudioStream:
             weights = m._rnn_w_fold
         else:
             xn, weights = x.view(B * Tc, F), m._rnn_w
-        rnn = m._stream_rnns.get(B, Tc, L.RUN_EVAL)
+        rnn = self.rnns.get(B, Tc, L.RUN_EVAL)
         if lengths is not None:
             rnn.forward_state_varlen(xn, weights, lengths, pooled=self.part, h_n=self.h, hx=self.h)
             L.stream_accumulate(self.part, lengths, self.acc, self.totals, Tc)
         else:
             rnn.forward(xn, weights, pooled=self.part, h_n=self.h, hx=self.h)
             L.axpby(self.part, self.acc, 1.0, 1.0)
+        sw = rnn.status_word()
+        if sw is not None:                         # cluster sweeps: the next push's forward clears the word, so keep its maximum
+            if self.health is None:
+                self.health = torch.zeros(3, dtype=torch.float64, device=m.device)
+            L.loss_accumulate(None, sw, None, self.health)
         self.T += Tc
+
+    def check_health(self):
+        """Synchronises and raises DepError if a cluster sweep of any push so far gave up on a bounded spin (as model.check_health()
+        does for model(x)); nothing to check on the tile-MFMA / generic sweeps."""
+        if self.health is not None and float(self.health[1].item()) != 0:
+            raise L.DepError('stream: a recurrent sweep gave up waiting for a cluster member during a push (status word %d): the GPU was '
+                             'shared with another kernel; model.stream(impl=2) runs the sweeps that need no co-resident workgroups'
+                             % int(self.health[1].item()))
 
     def output(self):
         m = self.m
@@ -275,17 +292,27 @@ class AudioGRU(nn.Module):
             self._rnn_g_fold = [self._fold[2], self._rnn_g[1], self._fold[3]] + self._rnn_g[3:]
         pool = L.POOL_MEAN if variant == 'clf' else L.POOL_SUM
         self._rnns = _RnnCache(L.CELL_GRU, F, H, Lyr, 1, self.dropout, pool, self.device)
-        # stream(): descriptors on the per-layer sweeps, the kernels that take a recurrent state (impl 2: the tile-MFMA sweeps where
-        # they can tile H, the generic sweeps elsewhere -- what impl 1 runs), eval mode, the chunk's SUM as its pool
-        self._stream_rnns = _RnnCache(L.CELL_GRU, F, H, Lyr, 1, self.dropout, L.POOL_SUM, self.device, impl=2)
+        # stream(): descriptors on the per-layer sweeps, the kernels that take a recurrent state, eval mode, the chunk's SUM as its pool.
+        # impl 4 (the per-layer cluster sweeps, W_hh in registers) where that descriptor exists -- its size query is non-zero: H in
+        # {64, 128, 256, 512} -- and impl 2 elsewhere (the tile-MFMA sweeps where they can tile H, the generic sweeps otherwise)
+        probe = L.RnnDesc(L.CELL_GRU, 1, 1, F, H, Lyr, 1, L.RUN_EVAL, 0.0, 0, L.POOL_SUM, L.IMPL_CLUSTER_PER_LAYER)
+        self._stream_impl = L.IMPL_CLUSTER_PER_LAYER if L.load().dep_rnn_workspace_bytes(probe) != 0 else L.IMPL_TILE
+        self._stream_rnns = {}                     # impl -> _RnnCache
         self._head = _MLPHead(self, 'fc_audio.1', 'fc_audio.4', self.dropout, True, (L.SITE_FC0, L.SITE_FC1))
 
-    def stream(self):
+    def stream(self, impl=None):
         """Chunked scoring with bounded memory (eval mode only): s = model.stream(); s.push(chunk) ...; s.output() is model(x) for
-        the chunks concatenated along T.  See _AudioStream."""
+        the chunks concatenated along T.  See _AudioStream.  impl: None = the model's choice (see __init__), or L.IMPL_TILE /
+        L.IMPL_CLUSTER_PER_LAYER to name the sweeps (the latter only where the descriptor exists)."""
         if self.training:
             raise L.DepError('AudioGRU.stream: streaming scores in eval() mode only (no dropout, no backward)')
-        return _AudioStream(self)
+        impl = self._stream_impl if impl is None else int(impl)
+        if impl not in (L.IMPL_TILE, L.IMPL_CLUSTER_PER_LAYER):
+            raise L.DepError(f'AudioGRU.stream: impl must name sweeps that take a recurrent state (2 or 4), got {impl}')
+        if impl not in self._stream_rnns:
+            self._stream_rnns[impl] = _RnnCache(L.CELL_GRU, self.embedding_size, self.hidden_dims, self.rnn_layers, 1, self.dropout,
+                                                L.POOL_SUM, self.device, impl=impl)
+        return _AudioStream(self, self._stream_rnns[impl])
 
     def state_dict(self):
         sd = super().state_dict()

@@ -85,7 +85,15 @@ typedef struct {
     int32_t pool;        /* GRU only: DEP_POOL_* over T of the top layer's y, (B,H*dirs) (fused in the sweep) */
     int32_t impl;        /* 0 auto (cluster > tile-MFMA > generic), 1 generic kernels, 2 one-workgroup-per-tile
                             MFMA kernels, 3 cluster-parallel MFMA kernels (GRU with H in {128,256}, BiLSTM with
-                            H = 128; any B -- batches beyond one co-resident launch run as consecutive chunks).
+                            H = 128; any B -- batches beyond one co-resident launch run as consecutive chunks),
+                            4 the per-layer cluster sweeps: a unidirectional GRU (dirs = 1) with H in {64,128,256,512}, any B, T, L,
+                            every run mode.  The cluster layout without the fused two-layer parts; every call on it, dense or
+                            ragged, runs the plan a ragged call takes on a cluster descriptor -- one co-schedule-tolerant
+                            32-unit-member sweep per layer (gru_fwd_cluster_r1 / gru_bwd_cluster_r1), never the fused two-layer or
+                            16-unit-member launches -- and its forward is the cluster forward that takes hx (dep_rnn_forward_state
+                            below).  dep_rnn_status and dep_rnn_workspace_xbuf_offset work as on impl 3.  Any other cell, dirs or
+                            H with impl = 4 is a bad descriptor (size queries 0, entry points DEP_ERR_ARG, the rule in
+                            dep_last_error).
                             A bidirectional GRU has tile-MFMA kernels only: impl must be 0 or 2 (both mean those kernels)
                             and H a multiple of 16 they can tile -- H / 16 = waves x tiles per wave with waves in
                             {1,2,4,8} and at most 4 tiles per wave, inside the LDS bound: H in {16,32,48,64,96,128,192,256}.
@@ -102,7 +110,7 @@ size_t dep_rnn_reserve_y_offset(const dep_rnn_desc* d, int layer);
 /* Same for the dropped-out copy that feeds layer+1 (DEP_RUN_TRAIN / DEP_RUN_DROPOUT_ONLY with dropout_p > 0 only). */
 size_t dep_rnn_reserve_ydrop_offset(const dep_rnn_desc* d, int layer);
 
-/* Health of the cluster-parallel sweeps that ran on `workspace` since the last dep_rnn_forward (desc.impl 0/3 with a
+/* Health of the cluster-parallel sweeps that ran on `workspace` since the last dep_rnn_forward (desc.impl 0/3/4 with a
  * supported H): they exchange data between workgroups inside one launch with bounded spins; if a spin ever gives up
  * the kernels exit early and this returns DEP_ERR_HIP.  The status is STICKY over a step: dep_rnn_forward clears it once,
  * every later sweep (the other layers, the whole backward) leaves it alone and exits at entry when it is raised, so one
@@ -276,12 +284,21 @@ int dep_rnn_backward_overlapped_varlen(const dep_rnn_desc* d, const float* x, co
  *   - a non-NULL member is accepted exactly where the per-layer tile-MFMA / generic sweeps (rnn_sweep.hip) run the stack: a descriptor
  *     whose layout has no cluster exchange buffer, dep_rnn_workspace_xbuf_offset(d) == (size_t)-1.  In practice impl 1 or 2, or impl 0
  *     at a shape without cluster kernels (a bidirectional GRU is always such a descriptor);
- *   - on any other descriptor the call returns DEP_ERR_ARG before anything is launched, with the rule in dep_last_error.
+ *   - hx alone is also accepted by dep_rnn_forward_state on an impl = 4 descriptor (the per-layer cluster sweeps) in DEP_RUN_EVAL and
+ *     DEP_RUN_DROPOUT_ONLY, the run modes no backward follows: every member of a tile's cluster reads the tile's rows of hx in front
+ *     of its first step.  Still refused there, before anything is launched: hx in DEP_RUN_TRAIN, and any non-NULL member in
+ *     dep_rnn_backward_state -- the cluster backward has neither the hx term of dW_hh nor dhx;
+ *   - on any other descriptor (impl 0 / 3 with cluster kernels) the call returns DEP_ERR_ARG before anything is launched, with the rule
+ *     in dep_last_error.
  * Scope
  *   - dense calls only (there is no `lengths` parameter: the ragged pair is dep_rnn_*_state_varlen below); all three run modes for the
  *     forward; the GEMM modes of the dense call;
  *   - h_n may be the same buffer as hx, and c_n the same as cx: every workgroup reads its rows of the state before the first step
- *     and writes them after the last (chunked streaming carries the state in place this way);
+ *     and writes them after the last (chunked streaming carries the state in place this way).  On impl = 4 a row of hx is read by all
+ *     H / 32 members of its tile: for T >= 2 the hand-off orders every member's read in front of any member's h_n store (a member
+ *     finishes only after all members of its tile raised their first flag); for T = 1 there is no hand-off, so when h_n overlaps hx the
+ *     call first copies the layer's B x H slice of hx into a staging area of its workspace (one device-to-device copy on `stream`)
+ *     and the sweep reads the copy;
  *   - reserve and workspace sizes and every offset are those of dep_rnn_forward / dep_rnn_backward;
  *   - gs: NULL, or as for dep_rnn_backward_overlapped. */
 typedef struct { const float* hx; const float* cx; float* c_n; } dep_rnn_state;
@@ -324,8 +341,10 @@ int dep_rnn_backward_state(const dep_rnn_desc* d, const float* x, const float* c
  *   - the backward must be given the forward's hx / cx AND lengths.  This is the caller's responsibility and is not detected.
  * Where it is accepted
  *   - exactly where the dense state call is accepted: a descriptor whose layout has no cluster exchange buffer
- *     (dep_rnn_workspace_xbuf_offset(d) == (size_t)-1); elsewhere a non-NULL member is DEP_ERR_ARG before anything is launched, with the
- *     rule in dep_last_error;
+ *     (dep_rnn_workspace_xbuf_offset(d) == (size_t)-1), and hx in the forward on an impl = 4 descriptor in DEP_RUN_EVAL /
+ *     DEP_RUN_DROPOUT_ONLY (the ragged instances of the same sweep: a row with len_b = 0 returns hx bit for bit; the T = 1 aliasing
+ *     rule is the dense call's); elsewhere a non-NULL member is DEP_ERR_ARG before anything is launched, with the rule in
+ *     dep_last_error;
  *   - also refused before any launch: cx / c_n / dc_n / dcx on a GRU, lengths == NULL (the dense call is dep_rnn_*_state), and GEMM
  *     modes 2 / 3 (as for every ragged call).
  * All-NULL state
