@@ -146,6 +146,7 @@ _SIGS = {
     'dep_profile_read': (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int]),
     'dep_instance_log_enable': (C.c_int, [C.c_int]),
     'dep_instance_log_read': (C.c_long, [C.c_char_p, C.c_long, C.c_int]),
+    'dep_instance_table_read': (C.c_long, [C.c_char_p, C.c_long]),
     'dep_order_log_enable': (C.c_int, [C.c_int]),
     'dep_order_log_note': (C.c_int, [C.c_char_p]),
     'dep_order_log_read': (C.c_long, [C.c_char_p, C.c_long, C.c_int]),
@@ -816,6 +817,16 @@ def instance_log_read(reset=False):
     buf = C.create_string_buffer(n + 1)
     lib.dep_instance_log_read(buf, n + 1, int(reset))
     return set(l for l in buf.value.decode().split('\n') if l)
+
+
+def instance_table_read():
+    """List of the rows of the cluster families' instance tables, under the texts instance_log_read reports (dep_instance_table_read;
+    needs no GPU)."""
+    lib = load()
+    n = lib.dep_instance_table_read(None, 0)
+    buf = C.create_string_buffer(n + 1)
+    lib.dep_instance_table_read(buf, n + 1)
+    return [l for l in buf.value.decode().split('\n') if l]
 
 
 def profile_enable(on=True):

@@ -137,6 +137,25 @@ extern "C" long dep_instance_log_read(char* buf, long cap, int reset) {
     if (reset) g_ilog.clear();
     return (long)all.size() + 1;
 }
+// Newline-separated texts of every row of the cluster families' instance tables, as launch_chunks logs them (none of them is symbolic,
+// so dep_ilog_note adds nothing to a row's text); buf, cap and the return value as dep_instance_log_read.  Needs no device.
+extern "C" long dep_instance_table_read(char* buf, long cap) {
+    static std::mutex mu;
+    static std::set<std::string> rows;
+    std::lock_guard<std::mutex> lk(mu);
+    if (rows.empty()) {
+        const dep_instance_sink add = [](const char* text) { rows.insert(text); };
+        dep_cluster_gru_instance_texts(add); dep_cluster16_instance_texts(add); dep_cluster_lstm_instance_texts(add);
+        dep_fused2_fwd_instance_texts(add); dep_fused2_bwd_instance_texts(add);
+    }
+    std::string all;
+    for (const auto& s : rows) { all += s; all += '\n'; }
+    if (buf && cap > 0) {
+        const long n = (long)all.size() < cap - 1 ? (long)all.size() : cap - 1;
+        memcpy(buf, all.data(), (size_t)n); buf[n] = 0;
+    }
+    return (long)all.size() + 1;
+}
 
 namespace {
 

@@ -307,6 +307,8 @@ Instance<F16>& fwd16_instance(bool split) {
 
 }  // namespace
 
+void dep_cluster16_instance_texts(dep_instance_sink add) { add(fwd16_instance(false).text); add(fwd16_instance(true).text); }
+
 int dep_pack_cluster16_fwd_split(const float* w_hh, float* out, int H, hipStream_t s) {
     DEP_LAUNCH(pack_cluster16_fwd_split_kernel, dim3(dep_cdiv(pack16_fwd_pieces(H), 256)), dim3(256), 0, s, w_hh, (u32x4*)out, H);
     DEP_CHECK_LAUNCH();

@@ -998,6 +998,15 @@ Instance<P2>& bwd_instance(int H, bool split, bool sv16, bool bf16st, bool rag) 
 }
 }  // namespace
 
+void dep_cluster_gru_instance_texts(dep_instance_sink add) {
+    const int sizes[] = {64, 128, 256, 512};       // dep_cluster_ok
+    for (const int H : sizes)
+        for (int m = 0; m < 16; ++m) {
+            if (m < 4) add(fwd_instance(H, m & 1, m & 2).text);
+            add(bwd_instance(H, m & 1, m & 2, m & 4, m & 8).text);
+        }
+}
+
 // (H x 3H recurrent / input weight) -> forward (bwd[k] = 0) or backward (1) split image, up to 8 jobs in one launch
 int dep_pack_cluster_split_multi(int n, const float* const* src, float* const* dst, const int* bwd, int H, hipStream_t s) {
     DEP_CHECK_ARG(n > 0 && n <= 8 && src && dst && bwd);

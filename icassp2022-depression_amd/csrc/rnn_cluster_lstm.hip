@@ -914,6 +914,10 @@ size_t lstm_fwd_payload_bytes(const ChunkGeometry& g, int H, int dirs) { return 
 
 }  // namespace
 
+void dep_cluster_lstm_instance_texts(dep_instance_sink add) {
+    for (int m = 0; m < 8; ++m) { add(fwd_instance(m & 1, m & 2, m & 4).text); add(bwd_instance(m & 1, m & 2, m & 4).text); }
+}
+
 int dep_pack_cluster_lstm_split(const float* w_hh, float* wp, float* wpT, int H, hipStream_t s) {
     DEP_LAUNCH(pack_lstm_split_kernel, dim3(dep_cdiv(pack_fwd_split_pieces(4, H), 256)), dim3(256), 0, s, w_hh, (u32x4*)wp, (u32x4*)wpT, H);
     DEP_CHECK_LAUNCH();

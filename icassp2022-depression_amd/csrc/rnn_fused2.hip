@@ -551,6 +551,10 @@ size_t fused2_payload_bytes(const ChunkGeometry& g) { return (size_t)4 * g.nbtp_
 // =====================================================================================================================================
 }  // namespace
 
+void dep_fused2_fwd_instance_texts(dep_instance_sink add) {
+    for (int m = 0; m < 16; ++m) add(fwd_instance(m & 1, m & 2, m & 4, m & 8).text);
+}
+
 bool dep_fused2_ok(int cell, int H, int L, int dirs) {
     return dep_rnn_switches().fused2 && cell == DEP_CELL_GRU && H == FH && L == 2 && dirs == 1;
 }

@@ -506,6 +506,10 @@ size_t fused2_bwd_payload_bytes(int nbtp) { return (size_t)nbtp * BNC * (3 * L1_
 
 }  // namespace
 
+void dep_fused2_bwd_instance_texts(dep_instance_sink add) {
+    for (int m = 0; m < 64; ++m) add(bwd_instance(m & 1, m & 2, m & 4, m & 8, m & 16, m & 32).text);
+}
+
 // The fused backward addresses a layer's input arrays (y, dropped y, r, z, n, hn: one stride apart in the reserve) and its 4H-wide gate-gradient image
 // through 32-bit buffer offsets: larger batches take the per-layer sweeps (tile-relative resources) instead.
 bool dep_fused2_bwd_fits(int B, int T) { return (size_t)B * T * BH * sizeof(float) * 8 < 0xfffffff0ull; }

@@ -734,6 +734,11 @@ int dep_profile_read(double* total_ms, int* counts, int ncat);
  * empties the log afterwards.  Process-wide, thread-safe; one relaxed atomic load per launch when off. */
 int dep_instance_log_enable(int on);
 long dep_instance_log_read(char* buf, long cap, int reset);
+/* Every row of the instance tables of the co-resident ("cluster") sweep families -- the per-layer GRU sweeps, the 16-unit-member GRU
+ * forward, the BiLSTM sweeps and the fused two-layer GRU forward / backward -- under the text the launch-instance log records for it,
+ * rows that only an environment switch selects included (tests/test_zz_instance_tables_gpu.py: every row must have been launched by an
+ * oracle-comparing test).  Newline-separated, no duplicates; buf, cap and the return value as dep_instance_log_read.  Needs no GPU. */
+long dep_instance_table_read(char* buf, long cap);
 
 /* Enqueue-order log (test infrastructure of the data-parallel path, tests/test_dp_gpu.py): while enabled, every kernel launch and every
  * collective the library enqueues ("K <kernel>" / "C <what> n=<floats>") is appended IN HOST ENQUEUE ORDER, together with the notes the

@@ -38,6 +38,29 @@ def test_binding_covers_header(built):
     assert sorted(_lib.EXPORTS) == header_symbols()
 
 
+def test_instance_tables_are_enumerated_without_a_gpu(built):
+    """dep_instance_table_read: every row of the cluster families' instance tables under the text the launch-instance log records
+    (tests/test_zz_instance_tables_gpu.py holds the list against what the oracle-comparing tests launched)."""
+    from icassp2022_depression_amd import _lib
+    rows = _lib.instance_table_read()
+    assert rows
+    assert len(rows) == len(set(rows))
+    assert '(gru2_bwd_fused<true, false, true, true>)' in rows        # the name tests/test_step_coverage_gpu.py asserts on
+    assert any('gru2_bwd_fused<true, false, true, true>' in r for r in rows)
+    # every family is there, switch-selected rows included, and a second read gives the same list
+    for name in ('gru_fwd_cluster_r1<2, true>', 'gru_bwd_cluster_r1<8, true, 0>', 'gru_fwd_cluster16<true>', 'lstm_fwd_cluster<true, true, true>',
+                 'lstm_bwd_cluster<true, true>', 'gru2_fwd_fused<true, true, false>', 'gru2_bwd_fused<false, false, true, true, true>'):
+        assert '(%s)' % name in rows, name
+    assert all(r.startswith('(') and r.endswith('>)') for r in rows), rows
+    assert _lib.instance_table_read() == rows
+    lib = _lib.load()                                                  # the return convention of dep_instance_log_read: bytes needed, truncation
+    need = lib.dep_instance_table_read(None, 0)
+    assert need == len('\n'.join(rows)) + 2
+    import ctypes as C
+    buf = C.create_string_buffer(8)
+    assert lib.dep_instance_table_read(buf, 8) == need and buf.value == ('\n'.join(rows))[:7].encode()
+
+
 def test_workspace_queries_run_on_cpu(built):
     import ctypes as C
     from icassp2022_depression_amd import _lib
