@@ -81,8 +81,12 @@ __device__ __forceinline__ unsigned split_word(float x) {
 }
 
 // 16-bit fixed-point storage of the saved GRU gates (round 4, dep_sweep_args.sv16): r, z in (0, 1) as unorm16 (round(x * 65535),
-// |error| <= 7.6e-6), n in (-1, 1) as snorm16 (round(x * 32767), |error| <= 1.5e-5) -- V_CVT_PKNORM_{U,I}16_F32.  Same order as
-// the split products' own error; halves 6H of the 16H saved-gate bytes a step writes in the forward and reads in the backward.
+// |error| <= 7.6e-6), n in (-1, 1) as snorm16 (round(x * 32767), |error| <= 1.5e-5) -- V_CVT_PKNORM_{U,I}16_F32.  Halves 6H of
+// the 16H saved-gate bytes a step writes in the forward and reads in the backward.  The error is ABSOLUTE, and the backward reads z
+// as 1 - z (dn = dh (1 - z) (1 - n^2)): the half-LSB lands relative to 1 - z.  At init-scale gates (z near 0.5) that is 1.5e-5, the
+// order of the split products' own error, and gradients stay within 2e-5 of the fp32-gate ones; with update gates near 1 it is
+// 7.6e-6 / (1 - z) -- 4e-4 at z = 0.98 -- and the weight gradients move by 2e-4 .. 4e-4 of their scale (DEP_SV16=0 keeps fp32 gates;
+// INTEGRATION.md "16-bit saved gates", tests/test_switch_cases_cpu.py).
 __device__ __forceinline__ unsigned pack_unorm2(float a, float b) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pknorm_u16(a, b)); }
 __device__ __forceinline__ unsigned pack_snorm2(float a, float b) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pknorm_i16(a, b)); }
 __device__ __forceinline__ float2 unpack_unorm2(unsigned w) {

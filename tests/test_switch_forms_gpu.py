@@ -34,7 +34,18 @@ figure of every case in lines `switch-forms ...`); "quantised" = against the ora
   DEP_SV16=0        GRU fused stack        plain oracle 6.63e-6
   (the quantisation alone, oracle against oracle on the CPU: BiLSTM 2.5e-5, GRU 2.1e-5 -- tests/test_switch_cases_cpu.py)
   mode 3 against mode 2: a gradient moves by at most 1.2e-3 of its scale in the fused forms, 1.7e-3 on the per-layer backward (bar 1e-2)
-Wall time of a child, 8 to 44 cases: 2.2 to 3.0 s.
+Outside init-scale gates (the regimes of tests/switch_cases.py; same run; worst relerr of any gradient or dx over the regime's cases; E_q = what
+the 16-bit storage alone does to a case, oracle against oracle; the 16-bit forms are held to RTOL + 2 E_q of the case, the fp32-gate forms to RTOL):
+  regime    16-bit GRU gates (default): plain oracle | quantised | E_q             fp32 GRU gates (DEP_SV16=0)
+  memory    1.72e-4 .. 3.95e-4 | 6.31e-5 .. 2.26e-4 | 1.74e-4 .. 3.95e-4            3.79e-6 .. 7.72e-6
+  reset     6.44e-5 .. 1.86e-4 | 3.58e-5 .. 1.31e-4 | 6.40e-5 .. 1.93e-4            5.85e-6 .. 1.14e-5
+  sat       2.16e-5 .. 6.27e-5 | 1.50e-5 .. 5.37e-5 | 1.93e-5 .. 5.15e-5            6.92e-6 .. 3.00e-5
+  drive     2.11e-5 .. 6.43e-5 | 1.46e-5 .. 4.72e-5 | 1.99e-5 .. 4.47e-5            5.18e-6 .. 3.88e-5
+  BiLSTM    DEP_LSTM_SV16=1: memory 2.09e-5 | 8.55e-6 | 1.98e-5, sat 2.74e-5 | 2.43e-5 | 2.87e-5;   default (fp32 gates): memory 3.43e-6, sat 1.19e-5
+  outputs   worst abs on y / h_n / pooled: memory 1.0e-6, reset 7.2e-6, drive 8.0e-5 (h_n of layer 0 at 37 x 20), sat 2.5e-5 at T <= 7 and
+            9.46e-5 at 37 x 20 x 256 without dropout -- with dropout 1.086e-4, past ATOL: the one case left out (switch_cases.LEFT_OUT; the
+            split-precision products' operand format, not the gate phase: tests/test_switch_cases_cpu.py)
+Wall time of a child, 8 to 85 cases: 2.2 to 2.9 s.
 """
 import json
 import os
@@ -126,7 +137,10 @@ def f64(a):
     return np.asarray(a).astype(np.float64)
 
 
-def check_outputs(c, res, ref):
+def check_outputs(c, res, ref, tag=''):
+    if c['regime'] != 'init':                       # (printed before any assertion, like the gradients' figures)
+        print(f'switch-forms {tag} {c["name"]}: outputs, worst abs vs the oracle: ' +
+              ', '.join('%s %.3e' % (k, np.abs(f64(res[k]) - ref[k]).max()) for k in ('y', 'h_n', 'pooled') if k in res))
     assert np.abs(f64(res['y']) - ref['y']).max() < ATOL, 'y'
     assert np.abs(f64(res['h_n']) - ref['h_n']).max() < ATOL, 'h_n'
     if c['cell'] == 'gru':
@@ -238,19 +252,42 @@ def test_the_switch_selected_its_rows(tag, switch_dir):
 
 
 # ----------------------------------------------------------------------------- the default environment: both references
+def storage_error(c, mask):
+    """E_q of a regime case (tests/test_switch_cases_cpu.py): what the 16-bit saved gates alone do to its backward, the oracle fed the
+    quantised gates against the exact oracle, worst relerr over the tensors the case returns.  From the oracle, never from the device."""
+    return S.worst_relerr(c, S.inputs(c), reference(c, mask, quantised=True), reference(c, mask))[0]
+
+
+def check_16bit_regime(tag, c, res, mask):
+    """A regime case on a 16-bit saved-gate form: every gradient and dx against the EXACT oracle under RTOL + 2 E_q(case).  E_q is the
+    storage format's own error at this case; the factor 2 covers a rounding pattern that differs from the oracle's (the device's gates
+    differ from the oracle's by up to 4e-7, which moves about 3 % of the codes) -- the CPU test holds a simulated device to the same bound."""
+    plain = gradient_errors(c, res, reference(c, mask))
+    report(tag, c, plain, gradient_errors(c, res, reference(c, mask, quantised=True)))
+    e_q = storage_error(c, mask)
+    print(f'switch-forms {tag} {c["name"]}: E_q {e_q:.3e}, bound {RTOL + 2 * e_q:.3e}')
+    for n, e in plain:
+        assert e < RTOL + 2 * e_q, (n, e, e_q)
+
+
 @pytest.mark.parametrize('c', S.ENVIRONMENTS['default'][1], ids=ident)
 def test_default_forms_against_the_oracle(c, switch_dir, request):
     """The baseline of the bit-identities below is itself right.  The GRU cases run with 16-bit saved gates by default: they are also
-    held to the oracle backward fed the quantised gates, the reference of the operation they compute (same bar)."""
+    held to the oracle backward fed the quantised gates, the reference of the operation they compute (same bar).  Outside the init
+    regime the 16-bit GRU forms are held to the exact oracle under RTOL + 2 E_q (check_16bit_regime); the BiLSTM saves fp32 gates by
+    default and keeps RTOL against the exact oracle in every regime."""
     res = results('default', switch_dir)[c['name']]
     mask = f64(res['mask']) if c['p'] > 0 else None
     ref = reference(c, mask)
-    check_outputs(c, res, ref)
-    plain = gradient_errors(c, res, ref)
-    quant = gradient_errors(c, res, reference(c, mask, quantised=True)) if c['cell'] == 'gru' else None
-    report('default', c, plain, quant)
-    for n, e in plain + (quant or []):
-        assert e < RTOL, (n, e)
+    check_outputs(c, res, ref, 'default')
+    if c['regime'] != 'init' and c['cell'] == 'gru':
+        check_16bit_regime('default', c, res, mask)
+    else:
+        plain = gradient_errors(c, res, ref)
+        quant = gradient_errors(c, res, reference(c, mask, quantised=True)) if c['cell'] == 'gru' else None
+        report('default', c, plain, quant)
+        for n, e in plain + (quant or []):
+            assert e < RTOL, (n, e)
     record(request, res)
 
 
@@ -260,7 +297,7 @@ def test_fp32_saved_gates_against_the_oracle(c, switch_dir, request):
     res = results('sv16_off', switch_dir)[c['name']]
     base = results('default', switch_dir)[c['name']]
     ref = reference(c, f64(res['mask']) if c['p'] > 0 else None)
-    check_outputs(c, res, ref)
+    check_outputs(c, res, ref, 'DEP_SV16=0')
     errs = gradient_errors(c, res, ref)
     report('DEP_SV16=0', c, errs)
     for n, e in errs:
@@ -275,11 +312,14 @@ def test_16bit_saved_bilstm_gates_against_the_oracle_fed_the_quantised_gates(c, 
     res = results('lstm_sv16', switch_dir)[c['name']]
     base = results('default', switch_dir)[c['name']]
     mask = f64(res['mask']) if c['p'] > 0 else None
-    check_outputs(c, res, reference(c, mask))
-    quant = gradient_errors(c, res, reference(c, mask, quantised=True))
-    report('DEP_LSTM_SV16=1', c, gradient_errors(c, res, reference(c, mask)), quant)       # (the plain oracle: a figure, no bar)
-    for n, e in quant:
-        assert e < RTOL, (n, e)
+    check_outputs(c, res, reference(c, mask), 'DEP_LSTM_SV16=1')
+    if c['regime'] != 'init':
+        check_16bit_regime('DEP_LSTM_SV16=1', c, res, mask)
+    else:
+        quant = gradient_errors(c, res, reference(c, mask, quantised=True))
+        report('DEP_LSTM_SV16=1', c, gradient_errors(c, res, reference(c, mask)), quant)   # (the plain oracle: a figure, no bar)
+        for n, e in quant:
+            assert e < RTOL, (n, e)
     forward_is_bit_identical(res, base)             # SV16 touches the write-out of the saved gates alone (module docstring)
     assert any(not np.array_equal(res[k], base[k]) for k in res if k.startswith('g')), 'the 16-bit gates moved no gradient'
     record(request, res)
