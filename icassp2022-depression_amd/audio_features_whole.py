@@ -59,6 +59,12 @@ def _get_tables(sr, n_fft, n_mels, device):
     return t
 
 
+def frame_count(n, n_fft=2048, hop=512):
+    """Frames of a centred STFT over n samples: the signal is reflect-padded by n_fft // 2 on each side (n_fft - 1 samples in
+    all when n_fft is odd), and a frame starts every `hop` samples while it still ends inside the padded signal."""
+    return 1 + (n + 2 * (n_fft // 2) - n_fft) // hop
+
+
 def log_melspectrogram(wave_data, sr, n_fft=2048, hop=512, n_mels=80, floor=1e-6):
     """np.log(np.maximum(1e-6, librosa.feature.melspectrogram(signal, n_mels=80, sr=sr).T)) -> device tensor (frames, n_mels)."""
     from . import nn
@@ -69,7 +75,7 @@ def log_melspectrogram(wave_data, sr, n_fft=2048, hop=512, n_mels=80, floor=1e-6
         raise L.DepError(f'signal of {n} samples is shorter than the reflect padding ({n_fft // 2})')
     basis, melw = _get_tables(sr, n_fft, n_mels, dev)
     bins = 1 + n_fft // 2
-    nfr = 1 + n // hop
+    nfr = frame_count(n, n_fft, hop)
     lib = L.load()
     frames = torch.empty(nfr, n_fft, dtype=torch.float32, device=dev)
     L.check(lib.dep_frame_window(y.data_ptr(), n, n_fft, hop, nfr, frames.data_ptr(), L.stream()), 'dep_frame_window')

@@ -28,29 +28,40 @@ __global__ void power_kernel(const float* __restrict__ reim, int rows, int bins,
     const int b = (int)(idx % bins);
     const long r = idx / bins;
     const float re = reim[r * ld + b], im = reim[r * ld + bins + b];
-    power[idx] = re * re + im * im;
+    power[idx] = fmaf(re, re, im * im);              // two roundings, not three: within 1 ulp of re^2 + im^2
 }
 
-__global__ void log_floor_kernel(const float* __restrict__ x, float* __restrict__ y, long n, float floor_) {
+// y = log(max(floor, x)) as numpy computes it: a NaN stays a NaN (fmaxf would drop it and return log(floor)).  x == y is allowed
+// (the log-mel path runs in place), so neither pointer is __restrict__.
+__global__ void log_floor_kernel(const float* x, float* y, long n, float floor_) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < n) y[idx] = logf(fmaxf(floor_, x[idx]));
+    if (idx < n) { const float v = x[idx]; y[idx] = logf(v < floor_ ? floor_ : v); }
 }
 
-// softmax over the last axis, C <= 64: one thread per row (C = 16 clusters in the path)
-__global__ void row_softmax_kernel(const float* __restrict__ z, float* __restrict__ p, int rows, int C) {
+// softmax over the last axis, C <= 64: one thread per row (C = 16 clusters in the path).  z == p is allowed (NetVLAD runs it in
+// place: a row is read completely before its first store), so neither pointer is __restrict__.
+__global__ void row_softmax_kernel(const float* z, float* p, int rows, int C) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rows) return;
     const float* zr = z + (size_t)r * C;
     float m = zr[0];
     for (int c = 1; c < C; ++c) m = fmaxf(m, zr[c]);
     float e[64], s = 0.f;
-    for (int c = 0; c < C; ++c) { e[c] = expf(zr[c] - m); s += e[c]; }
+    for (int c = 0; c < C; ++c) {
+        // zr[c] - m rounds by up to 2^-24 |zr[c] - m|, which is that much RELATIVE error in the exponential (5e-6 near the underflow
+        // end); TwoSum recovers the rounding error r exactly and exp(d + r) = exp(d) (1 + r) puts it back
+        const float zc = zr[c], d = zc - m;
+        float ec = expf(d);
+        if (ec > 0.f) { const float t = d - zc; ec = fmaf(ec, (zc - (d - t)) - (m + t), ec); }
+        e[c] = ec; s += ec;
+    }
     const float inv = 1.0f / s;
     for (int c = 0; c < C; ++c) p[(size_t)r * C + c] = e[c] * inv;
 }
 
 // NetVLAD tail: v[f][k] = vkf[k*F + f] - a_sum[k] * w2[f*K + k]; L2-normalise over f per cluster, then over everything
-// (tf.nn.l2_normalize: x * rsqrt(max(sum x^2, 1e-12))); out in (F,K) row-major order.  One workgroup (F*K = 1280 values).
+// (tf.nn.l2_normalize: x * rsqrt(max(sum x^2, 1e-12))); out in (F,K) row-major order.  One workgroup (F*K = 1280 values); every
+// loop strides by the block size, so K may exceed it.
 __global__ void vlad_normalize_kernel(const float* __restrict__ vkf, const float* __restrict__ a_sum, const float* __restrict__ w2,
                                       float* __restrict__ out, int F, int K) {
     extern __shared__ float sm[];                    // [F*K] values, [K] cluster norms, [1] total
@@ -58,7 +69,7 @@ __global__ void vlad_normalize_kernel(const float* __restrict__ vkf, const float
     const int tid = threadIdx.x, n = F * K;
     for (int i = tid; i < n; i += blockDim.x) { const int f = i / K, k = i % K; v[i] = vkf[(size_t)k * F + f] - a_sum[k] * w2[i]; }
     __syncthreads();
-    if (tid < K) { float s = 0.f; for (int f = 0; f < F; ++f) { const float x = v[f * K + tid]; s += x * x; } cn[tid] = rsqrtf(fmaxf(s, 1e-12f)); }
+    for (int k = tid; k < K; k += blockDim.x) { float s = 0.f; for (int f = 0; f < F; ++f) { const float x = v[f * K + k]; s += x * x; } cn[k] = rsqrtf(fmaxf(s, 1e-12f)); }
     __syncthreads();
     for (int i = tid; i < n; i += blockDim.x) v[i] *= cn[i % K];
     __syncthreads();
@@ -71,7 +82,7 @@ __global__ void vlad_normalize_kernel(const float* __restrict__ vkf, const float
 
 extern "C" int dep_frame_window(const float* y, long n, int n_fft, int hop, int n_frames, float* out, void* stream) {
     DEP_CHECK_ARG(y && out && n > n_fft / 2 && n_fft > 0 && hop > 0 && n_frames > 0);
-    DEP_CHECK_ARG((long)(n_frames - 1) * hop + n_fft <= n + n_fft);      // the last frame ends inside the padded signal
+    DEP_CHECK_ARG((long)(n_frames - 1) * hop + n_fft <= n + 2 * (long)(n_fft / 2));   // the last frame ends inside the padded signal (n_fft/2 each side)
     const long tot = (long)n_frames * n_fft;
     DEP_LAUNCH(frame_window_kernel, dim3(dep_cdiv(tot, 256)), dim3(256), 0, (hipStream_t)stream, y, n, n_fft, hop, n_frames, out);
     DEP_CHECK_LAUNCH();
@@ -101,8 +112,10 @@ extern "C" int dep_row_softmax(const float* z, float* p, int rows, int C, void* 
 }
 
 extern "C" int dep_vlad_normalize(const float* vkf, const float* a_sum, const float* w2, float* out, int F, int K, void* stream) {
-    DEP_CHECK_ARG(vkf && a_sum && w2 && out && F > 0 && K > 0 && (size_t)(F * K + K + 1) * sizeof(float) <= 64 * 1024);
-    DEP_LAUNCH(vlad_normalize_kernel, dim3(1), dim3(256), (size_t)(F * K + K + 1) * sizeof(float), (hipStream_t)stream,
+    DEP_CHECK_ARG(vkf && a_sum && w2 && out && F > 0 && K > 0);
+    const long lds_floats = (long)F * K + K + 1;                                      // 64-bit: F * K may not fit an int
+    DEP_CHECK_ARG(lds_floats * (long)sizeof(float) <= 64 * 1024);
+    DEP_LAUNCH(vlad_normalize_kernel, dim3(1), dim3(256), (size_t)lds_floats * sizeof(float), (hipStream_t)stream,
                        vkf, a_sum, w2, out, F, K);
     DEP_CHECK_LAUNCH();
     return DEP_OK;

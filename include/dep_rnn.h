@@ -707,11 +707,22 @@ int dep_adam_step_opt(float* p, const float* g, float* m, float* v, long n, floa
  * loupe_keras.NetVLAD(feature_size 80, cluster_size 16, output_dim 256).  The five contractions run on dep_gemm_f32
  * (windowed frames x [cos | -sin] DFT basis, power x mel filters, frames x cluster weights, assignment^T x frames,
  * VLAD x hidden weights); these entry points are the passes between them.
- *   dep_frame_window   : out (n_frames, n_fft) = reflect-padded y framed at `hop`, times the Hann window
- *   dep_power_spectrum : reim (rows, ld) = [re(0..bins) | im(0..bins)] -> power (rows, bins) = re^2 + im^2
- *   dep_log_floor      : y = log(max(floor, x))                       (np.log(np.maximum(1e-6, melspec)))
- *   dep_row_softmax    : softmax over the last axis, C <= 64          (NetVLAD soft assignment)
- *   dep_vlad_normalize : vkf (K,F) = assignment^T x frames, a_sum (K), w2 (F,K) -> out (F*K) = l2norm_all(l2norm_f(vkf^T - a_sum*w2)) */
+ *   dep_frame_window   : out (n_frames, n_fft) = reflect-padded y framed at `hop`, times the periodic Hann window.  The padding is
+ *                        n_fft/2 samples on each side (integer division, numpy 'reflect'), so n > n_fft/2 and
+ *                        1 <= n_frames <= 1 + (n + 2*(n_fft/2) - n_fft) / hop; one frame more is DEP_ERR_ARG (odd n_fft included)
+ *   dep_power_spectrum : reim (rows, ld) = [re(0..bins) | im(0..bins)], ld >= 2*bins -> power (rows, bins) = re^2 + im^2;
+ *                        (one fma: within 1 ulp); columns from 2*bins on are never read
+ *   dep_log_floor      : y = log(max(floor, x)), floor > 0               (np.log(np.maximum(1e-6, melspec)))
+ *                        with numpy's semantics: a NaN stays a NaN, +inf stays +inf, anything below the floor (0, negative
+ *                        values, denormals, -inf) gives log(floor).  x == y (in place) is allowed
+ *   dep_row_softmax    : softmax over the last axis, 1 <= C <= 64        (NetVLAD soft assignment).  z == p (in place) is allowed.
+ *                        The shift by the row maximum is compensated (exact), so small probabilities keep their relative accuracy:
+ *                        |p - softmax| <= (C + 8) 2^-24 softmax; an entry of -inf gives exactly 0
+ *   dep_vlad_normalize : vkf (K,F) = assignment^T x frames, a_sum (K), w2 (F,K) -> out (F*K) = l2norm_all(l2norm_f(vkf^T - a_sum*w2)),
+ *                        l2norm = x * rsqrt(max(sum x^2, 1e-12)).  One workgroup with the whole tensor in LDS: any K >= 1 (also
+ *                        above the 256 threads of the block), and (F*K + K + 1) * 4 bytes <= 64 KiB, computed in 64 bits;
+ *                        more is DEP_ERR_ARG
+ * A refused call launches nothing and writes nothing. */
 int dep_frame_window(const float* y, long n, int n_fft, int hop, int n_frames, float* out, void* stream);
 int dep_power_spectrum(const float* reim, int rows, int bins, int ld, float* power, void* stream);
 int dep_log_floor(const float* x, float* y, long n, float floor_value, void* stream);
