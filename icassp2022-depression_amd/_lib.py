@@ -17,7 +17,7 @@ POOL_NONE, POOL_MEAN, POOL_SUM = 0, 1, 2
 RUN_EVAL, RUN_TRAIN, RUN_DROPOUT_ONLY = 0, 1, 2
 # dep_rnn_desc.impl (include/dep_rnn.h): auto / generic sweeps / tile-MFMA sweeps / cluster sweeps / the per-layer cluster sweeps (a
 # unidirectional GRU with H in {64, 128, 256, 512}; the cluster descriptor whose forward takes hx in the modes no backward follows)
-IMPL_AUTO, IMPL_GENERIC, IMPL_TILE, IMPL_CLUSTER, IMPL_CLUSTER_PER_LAYER = 0, 1, 2, 3, 4
+IMPL_AUTO, IMPL_GENERIC, IMPL_TILE, IMPL_CLUSTER, IMPL_CLUSTER_PER_LAYER, IMPL_CLUSTER_PER_LAYER_STATE = 0, 1, 2, 3, 4, 5
 LOSS_CE_ON_SOFTMAX, LOSS_L1_RELU, LOSS_SMOOTHL1_RELU, LOSS_CE_LOGITS, LOSS_SMOOTHL1 = 0, 1, 2, 3, 4
 LOSS_LABELS_I64 = 0x100                     # OR into a CE kind: int64 labels read in place
 REG_L1, REG_SMOOTHL1, REG_HUBER, REG_MSE = 0, 1, 2, 3      # dep_head_loss_reg's forms
@@ -644,10 +644,10 @@ class Rnn:
         rb = self.lib.dep_rnn_reserve_bytes(C.byref(self.desc))
         wb = self.lib.dep_rnn_workspace_bytes(C.byref(self.desc))
         if rb == 0 or wb == 0:
-            # the size query says which rule a BiGRU or an impl = 4 descriptor broke
-            why = self.lib.dep_last_error().decode() if (cell == CELL_GRU and dirs == 2) or impl == IMPL_CLUSTER_PER_LAYER else ''
+            # the size query says which rule a BiGRU or an impl = 4 / 5 descriptor broke
+            why = self.lib.dep_last_error().decode() if (cell == CELL_GRU and dirs == 2) or impl in (IMPL_CLUSTER_PER_LAYER, IMPL_CLUSTER_PER_LAYER_STATE) else ''
             raise DepError(f'bad rnn descriptor: {cell=} {B=} {T=} {F=} {H=} {L=} {dirs=} {impl=}' +
-                           (f': {why}' if 'bidirectional GRU' in why or 'impl = 4' in why else ''))
+                           (f': {why}' if 'bidirectional GRU' in why or 'impl = 4' in why or 'impl = 5' in why else ''))
         self.reserve = torch.empty(rb // 4, dtype=torch.float32, device=device)
         self.workspace = torch.empty(wb // 4, dtype=torch.float32, device=device)
         self.n_w = 4 * L * dirs
@@ -703,8 +703,8 @@ class Rnn:
         lengths[b] steps long; padded positions of x must be finite).
         hx, cx, c_n: (L*dirs, B, H) fp32 device tensors ordered like h_n -> dep_rnn_forward_state: the sweeps start from hx (cx) instead
         of zeros and c_n receives the LSTM's final cell state; h_n may be hx's tensor and c_n cx's (carried in place).  Dense calls on the
-        tile-MFMA / generic sweeps, and hx on an impl = IMPL_CLUSTER_PER_LAYER descriptor in RUN_EVAL / RUN_DROPOUT_ONLY
-        (include/dep_rnn.h).  With all three None the call is the one made without them."""
+        tile-MFMA / generic sweeps, hx on an impl = IMPL_CLUSTER_PER_LAYER descriptor in RUN_EVAL / RUN_DROPOUT_ONLY, and hx in every
+        run mode, RUN_TRAIN included, on impl = IMPL_CLUSTER_PER_LAYER_STATE (include/dep_rnn.h).  With all three None the call is the one made without them."""
         for i, w in enumerate(weights):
             self._warr[i] = w.data_ptr()
         self.desc.seed = seed
@@ -730,6 +730,7 @@ class Rnn:
     def forward_state_varlen(self, x, weights, lengths, seed=0, pooled=None, h_n=None, y=None, hx=None, cx=None, c_n=None):
         """dep_rnn_forward_state_varlen: the ragged call (lengths: int32 device tensor of B elements) starting from hx (cx).  Row b is
         the dense state call on that row alone at T' = lengths[b]; a row of length 0 passes its state through (h_n = hx, c_n = cx).
+        On impl = IMPL_CLUSTER_PER_LAYER_STATE the per-layer cluster GRU sweeps take hx in every run mode.
         h_n may be hx's tensor and c_n cx's.  With hx, cx and c_n all None it is the plain ragged call."""
         if lengths is None:
             raise DepError('Rnn.forward_state_varlen: lengths is required (the dense call with a state is Rnn.forward)')
@@ -745,7 +746,8 @@ class Rnn:
     def backward_state_varlen(self, x, weights, dweights, lengths, dy=None, dpooled=None, dh_n=None, dx=None, grad_sync=None,
                               hx=None, cx=None, dc_n=None, dhx=None, dcx=None):
         """dep_rnn_backward_state_varlen: Rnn.backward for a reserve written by forward_state_varlen; lengths, hx and cx are the
-        forward's.  A row of length 0 passes its state gradient through (dhx = dh_n, dcx = dc_n)."""
+        forward's.  A row of length 0 passes its state gradient through (dhx = dh_n, dcx = dc_n).  hx / dhx are also taken on
+        impl = IMPL_CLUSTER_PER_LAYER_STATE (GEMM modes 0 and 1); dhx may be dh_n's tensor."""
         if lengths is None:
             raise DepError('Rnn.backward_state_varlen: lengths is required (the dense call with a state is Rnn.backward)')
         for i, (w, g) in enumerate(zip(weights, dweights)):
@@ -776,7 +778,8 @@ class Rnn:
         buffer is all-reduced on the communication stream beside the weight-gradient GEMMs of the layer below.
         lengths: the lengths of the ragged forward that wrote the reserve (the *_varlen entry points).
         hx, cx: the state the forward started from; dc_n: the gradient of c_n; dhx, dcx: receive the gradients of hx / cx (written).
-        Any of them -> dep_rnn_backward_state (dense calls on the tile-MFMA / generic sweeps only, include/dep_rnn.h)."""
+        Any of them -> dep_rnn_backward_state (dense calls on the tile-MFMA / generic sweeps, and hx / dhx on the per-layer cluster GRU
+        sweeps of impl = IMPL_CLUSTER_PER_LAYER_STATE in GEMM modes 0 and 1, where dhx may be dh_n's tensor; include/dep_rnn.h)."""
         for i, (w, g) in enumerate(zip(weights, dweights)):
             self._warr[i] = w.data_ptr()
             self._garr[i] = g.data_ptr()

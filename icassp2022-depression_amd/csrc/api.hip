@@ -198,19 +198,22 @@ int bigru_refusal(const dep_rnn_desc* d, const char* who) {
 }
 
 // impl = 4, "the per-layer cluster sweeps": the unidirectional GRU where gru_fwd_cluster_r1 / gru_bwd_cluster_r1 have instances.
+// impl = 5, "the per-layer cluster sweeps, state through training": impl = 4 in every respect (descriptors, layout, plan, launches, bits)
+// that also takes hx in a DEP_RUN_TRAIN forward and hx / dhx in the backward state calls (state_refusal).
+bool percluster_impl(const dep_rnn_desc* d) { return d->impl == 4 || d->impl == 5; }
 bool percluster_ok(const dep_rnn_desc* d) { return d->cell == DEP_CELL_GRU && d->dirs == 1 && dep_cluster_ok(d->cell, d->H, d->B, d->dirs); }
 
-// dep_last_error for an impl = 4 descriptor refused by the rule above (DEP_OK for any other descriptor)
+// dep_last_error for an impl = 4 / 5 descriptor refused by the rule above (DEP_OK for any other descriptor)
 int percluster_refusal(const dep_rnn_desc* d, const char* who) {
-    if (!d || d->impl != 4 || d->H <= 0 || percluster_ok(d)) return DEP_OK;
-    dep_set_error("%s: impl = 4 (the per-layer cluster sweeps) is a unidirectional GRU with H in {64, 128, 256, 512}: cell must be DEP_CELL_GRU and "
-                  "dirs 1; got cell = %d, H = %d, dirs = %d", who, d->cell, d->H, d->dirs);
+    if (!d || !percluster_impl(d) || d->H <= 0 || percluster_ok(d)) return DEP_OK;
+    dep_set_error("%s: impl = %d (the per-layer cluster sweeps%s) is a unidirectional GRU with H in {64, 128, 256, 512}: cell must be DEP_CELL_GRU and "
+                  "dirs 1; got cell = %d, H = %d, dirs = %d", who, d->impl, d->impl == 5 ? ", state through training" : "", d->cell, d->H, d->dirs);
     return DEP_ERR_ARG;
 }
 
 bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     if (!d || d->B <= 0 || d->T <= 0 || d->F <= 0 || d->H <= 0 || d->L < 1 || d->L > MAXL) return false;
-    if (d->impl == 4 && !percluster_ok(d)) return false;
+    if (percluster_impl(d) && !percluster_ok(d)) return false;
     if (d->cell == DEP_CELL_GRU) { if (d->dirs != 1 && !(d->dirs == 2 && bigru_ok(d))) return false; }
     else if (d->cell == DEP_CELL_LSTM) { if (d->dirs != 1 && d->dirs != 2) return false; }
     else return false;
@@ -288,16 +291,16 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
         if (b3 > gb) gb = b3;
     }
     lo.gemm = w; lo.gemm_bytes = gb; w += al(gb / sizeof(float) + 64);
-    // impl: 0 auto (cluster > tile-MFMA > generic), 1 generic, 2 tile-MFMA, 3 cluster (must be supported), 4 the per-layer cluster
+    // impl: 0 auto (cluster > tile-MFMA > generic), 1 generic, 2 tile-MFMA, 3 cluster (must be supported), 4 / 5 the per-layer cluster
     // sweeps (GRU, dirs = 1, checked above): the cluster layout without the fused two-layer extras, plus the hx staging area
     // (a bidirectional GRU is never planned onto the cluster, 16-unit-member or fused kernels: dep_cluster_ok does not look at dirs)
     const bool cok = d->cell == DEP_CELL_GRU ? d->dirs == 1 && dep_cluster_ok(d->cell, d->H, d->B, d->dirs) : dep_cluster_lstm_ok(d->H, d->B, d->dirs);
     if (d->impl == 3 && !cok) return false;
-    lo.cluster = cok && (d->impl == 0 || d->impl == 3 || d->impl == 4);
+    lo.cluster = cok && (d->impl == 0 || d->impl == 3 || percluster_impl(d));
     lo.xbuf = w; lo.xbuf_bytes = !lo.cluster ? 0 : (d->cell == DEP_CELL_GRU ? dep_cluster_xbuf_bytes(d->cell, d->H, d->B, d->dirs)
                                                                 : dep_cluster_lstm_xbuf_bytes(d->H, d->B, d->dirs));
     if (lo.cluster) lo.nwg = dep_cdiv(d->B, 16);      // the cluster sweeps write one row per tile whatever the tile-MFMA sweep could do at this H
-    lo.fused2 = lo.cluster && d->impl != 4 && dep_fused2_ok(d->cell, d->H, d->L, d->dirs);
+    lo.fused2 = lo.cluster && !percluster_impl(d) && dep_fused2_ok(d->cell, d->H, d->L, d->dirs);
     if (lo.fused2) {
         size_t fb = dep_fused2_xbuf_bytes(d->B); if (fb > lo.xbuf_bytes) lo.xbuf_bytes = fb;
         if (lo.keep) { fb = dep_fused2_bwd_xbuf_bytes(d->B); if (fb > lo.xbuf_bytes) lo.xbuf_bytes = fb; }
@@ -310,7 +313,7 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
         lo.dghn2 = w; w += al(lo.BT * H);
         lo.dbpart2 = w; w += al((size_t)lo.nwg * 4 * H);
     }
-    lo.hxstage = w; if (d->impl == 4) w += al((size_t)d->B * H);
+    lo.hxstage = w; if (percluster_impl(d)) w += al((size_t)d->B * H);
     lo.ws_floats = w;
     return true;
 }
@@ -423,7 +426,7 @@ struct RnnPlan {
 // tile / generic sweeps, the per-layer cluster GRU sweeps and the cluster BiLSTM sweeps, each of which launches its RAG instance when
 // the sweep arguments carry lengths -- never onto the fused two-layer launches or the 16-unit-member forward (so it enqueues no
 // soft-fallback launches either).  Everything else (images, saved-gate format, PK gate gradients) is decided as for a dense call.
-// impl = 4 (the per-layer cluster sweeps) is planned like a ragged call, dense or not: FWD_CLUSTER_GRU / BWD_CLUSTER_GRU and what follows
+// impl = 4 / 5 (the per-layer cluster sweeps) is planned like a ragged call, dense or not: FWD_CLUSTER_GRU / BWD_CLUSTER_GRU and what follows
 // from them.  Its layout has no fused2 part, and the 16-unit-member kernel does not belong to the descriptor, so the 32-unit-member image
 // and the 16-bit saved gates are chosen as on a shape without that kernel.
 RnnPlan make_plan(const dep_rnn_desc* d, const Layout& lo, int mode, bool excl, bool ragged) {
@@ -433,7 +436,7 @@ RnnPlan make_plan(const dep_rnn_desc* d, const Layout& lo, int mode, bool excl, 
     p.excl = excl; p.split = mode >= 1;
     const bool csplit = lo.cluster && p.split;
     // the kernels that fill every CU (fused forward, 16-unit members) are not for a shared GPU; the fused BACKWARD does not care
-    const bool cluster16 = lo.cluster && d->impl != 4 && dep_cluster16_ok(d->cell, d->H, d->B);
+    const bool cluster16 = lo.cluster && !percluster_impl(d) && dep_cluster16_ok(d->cell, d->H, d->B);
     p.fwd = (lo.fused2 && p.split && excl && !ragged) ? FWD_FUSED2 : (cluster16 && excl && !ragged) ? FWD_CLUSTER16
           : !lo.cluster ? FWD_TILE : gru ? FWD_CLUSTER_GRU : FWD_CLUSTER_LSTM;
     p.bwd = (lo.fused2 && sw.fused2_bwd && p.split && dep_fused2_bwd_fits(d->B, d->T) && !ragged) ? BWD_FUSED2
@@ -514,10 +517,17 @@ int ragged_mode_refusal(const char* who, const int32_t* lengths, int mode) {
 
 // dep_rnn_*_state: a call that brings a state (any member non-NULL) runs where the per-layer sweeps of rnn_sweep.hip run the stack, and
 // the cell state belongs to the LSTM.  Checked before anything is launched (and before any HIP call); DEP_OK for a call without state.
-int state_refusal(const dep_rnn_desc* d, const Layout& lo, const char* who, bool any, bool any_c, bool backward) {
+int state_refusal(const dep_rnn_desc* d, const Layout& lo, const char* who, bool any, bool any_c, bool backward, int mode) {
     if (!any) return DEP_OK;
     if (any_c && d->cell != DEP_CELL_LSTM) {
         dep_set_error("%s: cx, c_n, dc_n and dcx are the LSTM's cell state and its gradients; a GRU takes hx / dhx only", who);
+        return DEP_ERR_ARG;
+    }
+    if (lo.cluster && d->impl == 5) {
+        // state through training: hx in every forward; hx / dhx in the backward (gru_bwd_cluster_r1 takes hx as h_prev of step 0 and stores
+        // the direct term of dhx, rnn_backward_impl adds the two host-side terms).  The bf16-storage / single-product instances get no hx.
+        if (!backward || mode <= 1) return DEP_OK;
+        dep_set_error("%s: a backward with a state (hx / dhx given) on impl = 5 runs in GEMM modes 0 and 1 only; the current mode is %d (dep_set_gemm_mode)", who, mode);
         return DEP_ERR_ARG;
     }
     if (lo.cluster && d->impl == 4) {
@@ -550,7 +560,7 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
     DEP_CHECK_ARG(make_layout(d, lo));
     const dep_rnn_state st = state ? *state : dep_rnn_state{nullptr, nullptr, nullptr};      // NULL and a struct of NULLs are the plain call
     // (state together with lengths is dep_rnn_forward_state_varlen: the ragged instances of rnn_sweep.hip carry the state through dead steps)
-    if (const int rf = state_refusal(d, lo, lengths ? "dep_rnn_forward_state_varlen" : "dep_rnn_forward_state", st.hx || st.cx || st.c_n, st.cx || st.c_n, false)) return rf;
+    if (const int rf = state_refusal(d, lo, lengths ? "dep_rnn_forward_state_varlen" : "dep_rnn_forward_state", st.hx || st.cx || st.c_n, st.cx || st.c_n, false, dep_get_gemm_mode())) return rf;
     const int mode = dep_get_gemm_mode();
     if (const int rf = ragged_mode_refusal("dep_rnn_forward_varlen", lengths, mode)) return rf;
     const RnnPlan p = make_plan(d, lo, mode, dep_exclusive_on(), lengths != nullptr);
@@ -603,7 +613,7 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
         a.pool_scale = pool_scale;
         a.h_n = h_n ? h_n + (size_t)l * D * B * H : nullptr;
         // layer l's slice of the state arrays, ordered like h_n (a non-NULL member implies the tile / generic sweeps, or hx on the
-        // per-layer cluster forward of impl 4: state_refusal)
+        // per-layer cluster forward of impl 4 / 5: state_refusal)
         a.hx = st.hx ? st.hx + (size_t)l * D * B * H : nullptr;
         a.cx = st.cx ? st.cx + (size_t)l * D * B * H : nullptr;
         a.c_n = st.c_n ? st.c_n + (size_t)l * D * B * H : nullptr;
@@ -772,11 +782,13 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
     DEP_CHECK_ARG(make_layout(d, lo));
     const dep_rnn_state_grad st = state ? *state : dep_rnn_state_grad{nullptr, nullptr, nullptr, nullptr, nullptr};      // NULL and a struct of NULLs are the plain call
     const bool has_state = st.hx || st.cx || st.dc_n || st.dhx || st.dcx;
-    if (const int rf = state_refusal(d, lo, lengths ? "dep_rnn_backward_state_varlen" : "dep_rnn_backward_state", has_state, st.cx || st.dc_n || st.dcx, true)) return rf;
+    const int mode = dep_get_gemm_mode();
+    if (const int rf = state_refusal(d, lo, lengths ? "dep_rnn_backward_state_varlen" : "dep_rnn_backward_state", has_state, st.cx || st.dc_n || st.dcx, true, mode)) return rf;
     // the dense call's dW_hh state term reads the gate-gradient rows of one time step as a (B x rows) matrix of row stride T * ldg
     // (a ragged call gathers each row's own step with 64-bit offsets, dep_state_dwhh_ragged: no such bound)
     DEP_CHECK_ARG(!st.hx || lengths || (long)d->T * d->dirs * (d->cell == DEP_CELL_GRU ? 3 : 4) * d->H <= 0x7fffffffL);
-    const int mode = dep_get_gemm_mode();
+    // (the cluster sweeps' rows are 4H wide; the recurrent term of dhx reads the t = 0 rows the same way, dense or ragged)
+    DEP_CHECK_ARG(!(has_state && lo.cluster) || (long)d->T * 4 * d->H <= 0x7fffffffL);
     if (const int rf = ragged_mode_refusal("dep_rnn_backward_varlen", lengths, mode)) return rf;
     const RnnPlan p = make_plan(d, lo, mode, dep_exclusive_on(), lengths != nullptr);
     if (d->training != DEP_RUN_TRAIN) {
@@ -865,7 +877,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
         a.dpooled = top ? dpooled : nullptr;
         a.pool_scale = pool_scale;
         a.dh_n = dh_n ? dh_n + (size_t)l * D * B * H : nullptr;
-        {   // layer l's slice of the state arrays, ordered like h_n (a non-NULL member implies the tile / generic sweeps: state_refusal)
+        {   // layer l's slice of the state arrays, ordered like h_n (a non-NULL member implies the tile / generic sweeps, or hx / dhx on impl 5: state_refusal)
             const size_t so = (size_t)l * D * B * H;
             a.hx = st.hx ? st.hx + so : nullptr; a.cx = st.cx ? st.cx + so : nullptr; a.dc_n = st.dc_n ? st.dc_n + so : nullptr;
             a.dhx = st.dhx ? st.dhx + so : nullptr; a.dcx = st.dcx ? st.dcx + so : nullptr;
@@ -889,7 +901,9 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
         const LayerIn lin = layer_input(d, lo, x, R, l);
         const float* const in = lin.p; const int Kl = lin.K;
         float* dxl = l == 0 ? dx : (fused ? nullptr : W + lo.dx[l & 1]);      // (fused: the gradient entering layer 0 never left the chip)
-        const bool pk = fused ? fused_pk : pk_ok(l, dxl);
+        // a call with a state on the cluster sweeps (impl 5) takes the fp32 gate-gradient rows odd T and H = 512 take: the t = 0 rows are
+        // operands of the hx term of dW_hh and of the recurrent term of dhx below (the contractions are then the unpaired ones)
+        const bool pk = fused ? fused_pk : (pk_ok(l, dxl) && !(has_state && lo.cluster));
         if (p.bf16st && !pk) { dep_set_error(no_pk); return DEP_ERR_ARG; }
         const dep_sweep_bwd_args a = sweep_args(l, pk);
         float* const dgi = a.dgi; float* const dghn = a.dghn;
@@ -1005,19 +1019,21 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
                 // The initial state's term, dW_hh += dG[:, t0, :]^T hx: the shifted contractions above give sweep step 0 (t0 = 0; reverse
                 // direction t0 = T-1) a zero h_prev.  Same blocks as above, K = B: op(A) = the gate-gradient rows at t0 (row stride
                 // T * ld), B = this direction's hx slice; added (beta = 1) behind the main contraction, which wrote with beta = 0.
-                // (state_refusal: the tile / generic sweeps ran, so the rows are fp32, D*G*H wide, and the contractions above unpaired.)
+                // (state_refusal: the tile / generic sweeps ran, or the per-layer cluster sweep of impl 5 with pk = false: the rows are fp32 and
+                // the contractions above unpaired.  Row strides are the sweep's own: the cluster layout's rows are 4H wide, dghn their block 3.)
                 const float* hxd = a.hx + (size_t)dd * B * H;
+                const int ldhn = p.dg4 ? ldg : D * H;
                 const size_t t0 = dd == 0 ? 0 : (size_t)T - 1;
                 if (lengths) {
                     // ragged: the first sweep step is per row (t0_b = 0; reverse direction len_b - 1, none for an empty row), so the rows
                     // cannot be one strided GEMM operand: a direct exact-fp32 kernel gathers them (fixed order over b, no workspace)
                     rc = dep_state_dwhh_ragged(dg, ldg, lengths, B, T, dd, hxd, gru ? 2 * H : 4 * H, H, gl[1], s);
                     if (rc) return rc;
-                    if (gru) { rc = dep_state_dwhh_ragged(dghn + (size_t)dd * H, D * H, lengths, B, T, dd, hxd, H, H, gl[1] + (size_t)2 * H * H, s); if (rc) return rc; }
+                    if (gru) { rc = dep_state_dwhh_ragged(dghn + (size_t)dd * H, ldhn, lengths, B, T, dd, hxd, H, H, gl[1] + (size_t)2 * H * H, s); if (rc) return rc; }
                 } else if (gru) {
                     rc = dep_gemm_internal(1, 0, 2 * H, H, B, dg + t0 * ldg, T * ldg, hxd, H, gl[1], H, nullptr, 1.f, 0, 0, gws, gwsb, ho, s);
                     if (rc) return rc;
-                    rc = dep_gemm_internal(1, 0, H, H, B, dghn + (size_t)dd * H + t0 * D * H, T * D * H, hxd, H, gl[1] + (size_t)2 * H * H, H, nullptr,
+                    rc = dep_gemm_internal(1, 0, H, H, B, dghn + (size_t)dd * H + t0 * ldhn, T * ldhn, hxd, H, gl[1] + (size_t)2 * H * H, H, nullptr,
                                            1.f, 0, 0, gws, gwsb, ho, s);
                     if (rc) return rc;
                 } else {
@@ -1025,6 +1041,18 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
                     if (rc) return rc;
                 }
             }
+        }
+        if (a.dhx && p.bwd == BWD_CLUSTER_GRU) {
+            // The recurrent term of dhx: the sweep stored the direct term d_0 * z_0 (a dead ragged row: its dh_n); the other one,
+            // dG[:, 0, :] W_hh, is a (B x 3H x H) product behind the sweep on the same stream: A = the t = 0 rows (row stride T * ld) of
+            // [dr | dz] and of dn*r, added with beta = 1.  The sweep is unidirectional, so t0 = 0 for dense and ragged alike; a dead row's
+            // gate gradients are 0, so nothing is gathered.
+            const float* whh = weights[(size_t)l * 4 + 1];
+            DepGemmOpts xo; xo.scratch = gws; xo.scratch_bytes = gwsb;
+            rc = dep_gemm_internal(0, 0, B, H, 2 * H, dgi, T * ldg, whh, H, a.dhx, H, nullptr, 1.f, 0, 0, nullptr, 0, xo, s);
+            if (rc) return rc;
+            rc = dep_gemm_internal(0, 0, B, H, H, dghn, T * ldg, whh + (size_t)2 * H * H, H, a.dhx, H, nullptr, 1.f, 0, 0, nullptr, 0, xo, s);
+            if (rc) return rc;
         }
         // data parallel: layer l's gradients are complete -- their range of the caller's flat gradient buffer goes to RCCL on the
         // communication stream.  Not right away: the collective is enqueued behind the NEXT layer's sweep (see `pending' above),

@@ -35,6 +35,12 @@ struct P2 {
     int trall_off;           // debug: LDS offset (32-bit words) of the per-step stamp array
     int dgpk;                // round 4: write the gate gradients as the PK image the bf16x3 GEMMs read without converting (gemm_bf16x3.hip FMT_PK): rows (t even, t+1) of an utterance hold the (hi, lo) bf16 pairs of both steps; burst kernel, 4H-wide layout, T even
     const int* lengths; int pool_mean;      // ragged instances (RAG): row b is live for t < lengths[b]; dpooled of a mean is scaled by 1 / lengths[b]
+    // state (dep_rnn_backward_state[_varlen] on impl 5; run-time pointers like F2::hx, no instance of their own): hx is h_prev of step 0
+    // instead of zeros -- a global input every thread reads at its own units, on a branch only the t = 0 request takes; dhx receives the
+    // direct term of the gradient entering step 0, d_0 * z_0 (a ragged row that never was live: the dh_n it loaded), stored at t == 0 by
+    // the thread that owns the two columns.  The recurrent term dG[:, 0, :] W_hh is added by the host behind the sweep.  dhx may be
+    // dh_n's buffer: the same thread read that address in front of the loop.  Neither touches the exchange, a flag or a trip count.
+    const float* hx; float* dhx;
 };
 
 struct StepIn { float2 r, z, n, hn, hp, dy; };
@@ -172,8 +178,18 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
             } else { s.r = ld2(p.sv0 + so); s.z = ld2(p.sv1 + so); s.n = ld2(p.sv2 + so); }
             s.hn = ld2(p.sv3 + so);
             if (t > 0) s.hp = ld2(p.y + (row - 1) * p.ldy + col);
+            else if (p.hx) s.hp = ld2(p.hx + (size_t)b * H + col);
             if (p.dy) s.dy = ld2(p.dy + row * p.lddy + col);
         }
+    };
+    // dhx at t == 0: the direct term d * z of this thread's two columns (a ragged row that never was live: the dh_n it loaded).  The
+    // product is formed HERE, from a copy of z the optimiser cannot see through: shared with the step loop's dzt it would give that
+    // product a second use, and the loop's fused d * z + s (one v_pk_fma_f32 per step) would become a multiply and an add -- other bits
+    // in every call, with or without state.  A toolchain change: re-run tools/isa_diff.py (profiles/state_cluster_bwd_isa.txt counts the fma).
+    auto store_dhx = [&](float2 d, float2 z) {
+        asm volatile("" : "+v"(z.x), "+v"(z.y));
+        const float2 v = f2(d.x * z.x, d.y * z.y);
+        st2(p.dhx + (size_t)b * H + col, RAG ? dep_sel2(0 < len, v, dhrec) : v);
     };
     StepIn cur, nxt;
     if constexpr (!BURST) load_step(T - 1, cur);
@@ -237,6 +253,8 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
         const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(which == 0 ? rs_in0 : (which == 1 ? rs_in1 : rs_in2), off, 0, 2 /* nt */);
         return make_float2(__uint_as_float(v[0]), __uint_as_float(v[1]));
     };
+    // h_prev of step 0 for the service waves' piece: the caller's hx (plain 16-byte load, outside the tile-relative resources), or zeros
+    auto svc_hx = [&]() -> f32x4 { return p.hx ? *reinterpret_cast<const f32x4*>(p.hx + (size_t)sb * H + scol) : zero4(); };
     // W16 (a std::bool_constant): this wave streams the 16-bit arrays
     auto svc_load1 = [&](auto W16, int k, int i) -> f32x4 {     // input i of this wave for step k
         const int t = T - 1 - k;
@@ -259,7 +277,7 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
                     return sbase2 ? ldnt(2, sbase2 + row * p.lddy + scol) : zero4();
                 } else {
                     if (i == 0) return ldnt(0, sbase0 + row * H + scol);
-                    if (i == 1) return t > 0 ? ldnt(1, sbase1 + (row - 1) * p.ldy + scol) : zero4();
+                    if (i == 1) return t > 0 ? ldnt(1, sbase1 + (row - 1) * p.ldy + scol) : svc_hx();
                     return sbase2 ? ldnt(2, sbase2 + row * p.lddy + scol) : zero4();
                 }
             }
@@ -267,7 +285,7 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
             if (i == 0) return ldnt(0, sbase0 + row * H + scol);
             if (i == 1) return ldnt(1, sbase1 + row * H + scol);
             if (sodd) return sbase2 ? ldnt(2, sbase2 + row * sld2 + scol) : zero4();
-            return t > 0 ? ldnt(2, sbase2 + (row - 1) * sld2 + scol) : zero4();
+            return t > 0 ? ldnt(2, sbase2 + (row - 1) * sld2 + scol) : svc_hx();
         }
     };
     auto svc_issue = [&](auto W16, int k0, int n) {   // inputs of steps k0 .. k0+n-1 -> registers
@@ -468,7 +486,10 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
             }
             dbr.x += dr.x; dbr.y += dr.y; dbz.x += dz.x; dbz.y += dz.y; dbn.x += dn.x; dbn.y += dn.y; dbh.x += dnr.x; dbh.y += dnr.y;
             BSTAMP(1);
-            if (t == 0) { bar_lds(); break; }                // (the service waves' final flush reads obuf behind this barrier)
+            if (t == 0) {
+                if (p.dhx && valid) store_dhx(d, z);
+                bar_lds(); break;                            // (the service waves' final flush reads obuf behind this barrier)
+            }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's six stores are acknowledged
             BSTAMP(2);
             if (lane == 0) { if (fast) st_local(myflag, epoch); else st_agent(myflag, epoch); }
@@ -564,7 +585,10 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
         dbr.x += dr.x; dbr.y += dr.y; dbz.x += dz.x; dbz.y += dz.y; dbn.x += dn.x; dbn.y += dn.y; dbh.x += dnr.x; dbh.y += dnr.y;
         bar_lds();                                   // LDS only: the dgi/dghn stores above stay in flight
         BSTAMP(1);
-        if (t == 0) break;
+        if (t == 0) {
+            if (p.dhx && valid) store_dhx(d, z);
+            break;
+        }
         if constexpr (!BURST) load_step(t - 1, nxt); // independent of the recurrence: in flight under the MFMAs
         f32x4 acc[NTW];
 #pragma unroll
@@ -680,7 +704,7 @@ struct F2 {
     const unsigned* only_if; // run only if this word is set (fallback behind an exclusive forward kernel), or nullptr
     int sv16;                // saved gates r, z, n written as 16-bit fixed point
     const int* lengths; int pool_mean;      // ragged instances (RAG): row b is live for t < lengths[b]; a mean pool divides by lengths[b]
-    const float* hx;         // this layer's (B, H) initial state (dep_rnn_forward_state[_varlen] on impl 4), or nullptr = zeros
+    const float* hx;         // this layer's (B, H) initial state (dep_rnn_forward_state[_varlen] on impl 4 / 5), or nullptr = zeros
 };
 
 // RAG: the ragged-batch instances (dep_rnn_forward_varlen): h = live ? new : previous (what is published, kept and returned as h_n),
@@ -1073,6 +1097,10 @@ int dep_launch_cluster_bwd(const dep_sweep_bwd_args& a, void* xbuf, size_t xbuf_
     p.dgi = a.dgi; p.lddg = a.lddg ? a.lddg : 3 * a.H; p.dghn = a.dghn; p.lddghn = a.lddghn ? a.lddghn : a.H; p.dbpart = a.dbpart;
     p.dgpk = a.dg_pk;
     p.lengths = a.lengths; p.pool_mean = a.pool_mean;
+    p.hx = a.hx; p.dhx = a.dhx;
+    DEP_CHECK_ARG(!a.hx || (reinterpret_cast<uintptr_t>(a.hx) & 15) == 0);      // the service waves read 16-byte pieces of it
+    DEP_CHECK_ARG(!a.dhx || (reinterpret_cast<uintptr_t>(a.dhx) & 7) == 0);
+    DEP_CHECK_ARG(!((a.hx || a.dhx) && a.bf16st));   // the bf16-storage instance takes no state
     DEP_CHECK_ARG(!(a.lengths && a.bf16st));         // no ragged bf16-storage instance
     DEP_CHECK_ARG(!a.sv16 || a.split);               // the 16-bit saved gates exist in split-precision mode only
     DEP_CHECK_ARG(!a.bf16st || (a.H == 256 && a.split && a.sv16 && a.dg_pk));      // bf16-storage mode: H = 256, burst kernel (checked below via dg_pk)

@@ -298,6 +298,14 @@ class AudioGRU(nn.Module):
         probe = L.RnnDesc(L.CELL_GRU, 1, 1, F, H, Lyr, 1, L.RUN_EVAL, 0.0, 0, L.POOL_SUM, L.IMPL_CLUSTER_PER_LAYER)
         self._stream_impl = L.IMPL_CLUSTER_PER_LAYER if L.load().dep_rnn_workspace_bytes(probe) != 0 else L.IMPL_TILE
         self._stream_rnns = {}                     # impl -> _RnnCache
+        # forward_chunked(): the same choice among the sweeps that take a state through TRAINING -- impl 5 (the per-layer cluster sweeps,
+        # state through training) where it exists, impl 2 elsewhere; chunk descriptors pool by the sum, like the stream's
+        probe = L.RnnDesc(L.CELL_GRU, 1, 1, F, H, Lyr, 1, L.RUN_TRAIN, 0.0, 0, L.POOL_SUM, L.IMPL_CLUSTER_PER_LAYER_STATE)
+        self._chunk_impl = L.IMPL_CLUSTER_PER_LAYER_STATE if L.load().dep_rnn_workspace_bytes(probe) != 0 else L.IMPL_TILE
+        self._chunk_rnns = {}                      # impl -> _RnnCache
+        self._chunk_health = None                  # float64 (3,) on the device once a chunk ran on a descriptor with a status word
+        self._chunked = None                       # what forward_chunked() left for backward()
+        self.keep_chunk_states = False             # debugging / tests: backward() keeps each recomputed chunk's h_n in _chunked['h_n_recomputed']
         self._head = _MLPHead(self, 'fc_audio.1', 'fc_audio.4', self.dropout, True, (L.SITE_FC0, L.SITE_FC1))
 
     def stream(self, impl=None):
@@ -331,6 +339,10 @@ class AudioGRU(nn.Module):
 
     def check_health(self):
         self._rnns.check()
+        if self._chunk_health is not None and float(self._chunk_health[1].item()) != 0:
+            raise L.DepError('forward_chunked: a recurrent sweep gave up waiting for a cluster member during a chunk (status word %d): the '
+                             'GPU was shared with another kernel; forward_chunked(impl=2) runs the sweeps that need no co-resident workgroups'
+                             % int(self._chunk_health[1].item()))
 
     def status_words(self):
         w = self._rnns.status_word()
@@ -370,7 +382,135 @@ class AudioGRU(nn.Module):
         kind = L.LOSS_CE_ON_SOFTMAX if self.variant == 'clf' else L.LOSS_L1_RELU
         L.head_loss(kind, z, None, out, None, None, 1.0)
         self._saved = enc
+        self._chunked = None
         return nn.Output(out, self, z)
+
+    def forward_chunked(self, x, chunk_steps, lengths=None, impl=None):
+        """An exact training step over a long recording with the reserve of ONE chunk: the usual nn.Output, so criterion(out, y).backward()
+        and the optimizers work as they are; chunk_steps >= T is one chunk and equals model(x).
+        The forward runs the chunks of chunk_steps frames (the last may be shorter) in RUN_DROPOUT_ONLY -- the train masks bit for bit, no
+        reserve kept -- with the recurrent state carried, keeps every chunk's incoming state hx_k (L, B, H) and its dropout seed, and
+        accumulates the chunks' sum pools as stream() does (LayerNorm per chunk; mean / sum as encode(), per-row totals with lengths:
+        chunk k gets clip(len - k * chunk_steps, 0, chunk)).  backward() then walks the chunks in reverse: re-runs chunk k in RUN_TRAIN
+        from hx_k with its seed, runs the backward state call with the per-frame pool gradient, dh_n = the gradient that left chunk k + 1
+        and dhx written back in place, and adds the chunk's weight gradients into the parameters' (the backward writes with beta = 0).
+        impl: None = the model's choice (IMPL_CLUSTER_PER_LAYER_STATE where that descriptor exists, else IMPL_TILE: 43.4 ms against 364.9 ms
+        at H = F = 256, B = 64, T = 3000 in chunks of 300, profiles/chunked_step_ab.txt), or one of the two, as stream(impl=) names its sweeps.
+        check_health() covers the chunks of the latest step."""
+        if not self.training:
+            raise L.DepError('AudioGRU.forward_chunked: a training step (model.train()); eval-mode chunked scoring is model.stream()')
+        x = self._to_dev(x)
+        if x.dim() != 3 or x.shape[1] < 1 or x.shape[2] != self.embedding_size or int(chunk_steps) < 1:
+            raise L.DepError(f'forward_chunked: expected a (B, T >= 1, {self.embedding_size}) batch and chunk_steps >= 1, got {tuple(x.shape)}, {chunk_steps}')
+        B, T, F = x.shape
+        H, Lyr, chunk = self.hidden_dims, self.rnn_layers, min(int(chunk_steps), T)
+        impl = self._chunk_impl if impl is None else int(impl)
+        if impl not in (L.IMPL_TILE, L.IMPL_CLUSTER_PER_LAYER_STATE):
+            raise L.DepError(f'AudioGRU.forward_chunked: impl must name sweeps that take a state through training (2 or 5), got {impl}')
+        if impl not in self._chunk_rnns:
+            self._chunk_rnns[impl] = _RnnCache(L.CELL_GRU, F, H, Lyr, 1, self.dropout, L.POOL_SUM, self.device, impl=impl)
+        rnns = self._chunk_rnns[impl]
+        lengths = _RnnCache.lengths_on(lengths, B, self.device)
+        clf = self.variant == 'clf'
+        P = self._params
+        if clf:                                    # the weights stand still during the step: one fold for all chunks, forward and recompute
+            L.ln_fold_fwd(self._rnn_w[0], self._rnn_w[2], P['ln.weight'].data, P['ln.bias'].data, *self._fold[:2])
+        weights = self._rnn_w_fold if clf else self._rnn_w
+        mk = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=self.device)
+        h, acc, part = mk(Lyr, B, H), mk(B, H), mk(B, H)
+        totals = torch.zeros(B, dtype=torch.int32, device=self.device) if lengths is not None else None
+        if self._chunk_health is not None:         # a step's health is its own chunks', as model(x)'s status word is that call's
+            self._chunk_health.zero_()
+        cuts, seeds, hxs, lens = [], [], [], []
+        for t0 in range(0, T, chunk):
+            Tc = min(chunk, T - t0)
+            xn = self._chunk_input(x, t0, Tc)
+            lk = None if lengths is None else (lengths - t0).clamp_(0, Tc).to(torch.int32)
+            seed = nn.next_dropout_seed()
+            cuts.append((t0, Tc)); seeds.append(seed); hxs.append(h.clone()); lens.append(lk)
+            rnn = rnns.get(B, Tc, L.RUN_DROPOUT_ONLY)
+            if lk is not None:
+                rnn.forward_state_varlen(xn, weights, lk, seed=seed, pooled=part, h_n=h, hx=h)
+                L.stream_accumulate(part, lk, acc, totals, Tc)
+            else:
+                rnn.forward(xn, weights, seed=seed, pooled=part, h_n=h, hx=h)
+                L.axpby(part, acc, 1.0, 1.0)
+            self._fold_chunk_status(rnn)
+        pooled = torch.empty_like(acc)
+        if totals is not None:
+            L.stream_finish(acc, totals, pooled, clf)
+        else:
+            L.axpby(acc, pooled, 1.0 / T if clf else 1.0, 0.0)
+        z = self._head.forward(pooled, seeds[0], True)
+        out = torch.empty_like(z)
+        L.head_loss(L.LOSS_CE_ON_SOFTMAX if clf else L.LOSS_L1_RELU, z, None, out, None, None, 1.0)
+        self._chunked = dict(x=x, T=T, cuts=cuts, seeds=seeds, hxs=hxs, lens=lens, totals=totals, rnns=rnns, impl=impl, h_end=h)
+        return nn.Output(out, self, z)
+
+    def _chunk_input(self, x, t0, Tc):
+        """Frames [t0, t0 + Tc) of the batch as the (B * Tc, F) array the stack reads: LayerNorm's x-hat for the classifier (per row, so
+        per chunk as encode() runs it on the whole batch)."""
+        B, _, F = x.shape
+        xc = x[:, t0:t0 + Tc].contiguous().view(B * Tc, F)
+        if self.variant == 'clf':
+            xc, _ = L.layernorm_fwd(xc, None, None, save=False)
+        return xc
+
+    def _fold_chunk_status(self, rnn):
+        sw = rnn.status_word()
+        if sw is not None:                         # cluster sweeps: the next chunk's forward clears the word, so keep its maximum
+            if self._chunk_health is None:
+                self._chunk_health = torch.zeros(3, dtype=torch.float64, device=self.device)
+            L.loss_accumulate(None, sw, None, self._chunk_health)
+
+    def _backward_chunked(self, dz):
+        c = self._chunked
+        x, T, rnns, totals = c['x'], c['T'], c['rnns'], c['totals']
+        B = x.shape[0]
+        clf = self.variant == 'clf'
+        P = self._params
+        dpool = self._head.backward(dz)
+        # the gradient of one frame's contribution to the pool (the chunks' descriptors pool by the SUM): the classifier's mean divides
+        # by T, or row by row by the recording's own frames
+        dframe = torch.empty_like(dpool)
+        if totals is not None:
+            L.stream_finish(dpool, totals, dframe, clf)
+        else:
+            L.axpby(dpool, dframe, 1.0 / T if clf else 1.0, 0.0)
+        weights = self._rnn_w_fold if clf else self._rnn_w
+        grads = self._rnn_g_fold if clf else self._rnn_g
+        scratch = [torch.empty_like(g) for g in grads]
+        dh = torch.empty(self.rnn_layers, B, self.hidden_dims, dtype=torch.float32, device=self.device)
+        # (dhx over dh_n in place is the cluster backward's rule; the tile sweeps get two buffers)
+        dh_out = dh if c['impl'] == L.IMPL_CLUSTER_PER_LAYER_STATE else torch.empty_like(dh)
+        K = len(c['cuts'])
+        keep = self.keep_chunk_states
+        c['h_n_recomputed'] = [None] * K if keep else None
+        for k in range(K - 1, -1, -1):
+            t0, Tc = c['cuts'][k]
+            xn = self._chunk_input(x, t0, Tc)
+            rnn = rnns.get(B, Tc, L.RUN_TRAIN)
+            h_n = torch.empty_like(dh) if keep else None
+            dh_n = None if k == K - 1 else dh
+            kw = dict(dpooled=dframe, dh_n=dh_n, dx=None, hx=c['hxs'][k], dhx=dh_out)
+            if c['lens'][k] is not None:
+                rnn.forward_state_varlen(xn, weights, c['lens'][k], seed=c['seeds'][k], h_n=h_n, hx=c['hxs'][k])
+                rnn.backward_state_varlen(xn, weights, scratch, c['lens'][k], **kw)
+            else:
+                rnn.forward(xn, weights, seed=c['seeds'][k], h_n=h_n, hx=c['hxs'][k])
+                rnn.backward(xn, weights, scratch, **kw)
+            self._fold_chunk_status(rnn)
+            if keep:
+                c['h_n_recomputed'][k] = h_n
+            for s, g in zip(scratch, grads):
+                L.axpby(s, g, 1.0, 0.0 if k == K - 1 else 1.0)
+            dh, dh_out = dh_out, dh
+        if clf:
+            L.ln_fold_bwd(self._rnn_w[0], self._fold[2], self._fold[3], P['ln.weight'].data, P['ln.bias'].data,
+                          self._rnn_g[0], self._rnn_g[2], P['ln.weight']._grad, P['ln.bias']._grad)
+        self._grad_ready = True
+        in_call, post = self.sync_plan()           # data parallel: nothing is final inside a chunk's call, every range goes out at the end
+        parallel.finish_grad_sync(self, {}, list(in_call.values()) + list(post))
 
     def sync_plan(self):
         """Flat layout [ln | l0 | l1 | .. | fc_audio]: the top layer's range ends with the head (final before the stack's
@@ -387,6 +527,8 @@ class AudioGRU(nn.Module):
         return in_call, post
 
     def backward(self, dz):
+        if self._chunked is not None:
+            return self._backward_chunked(dz)
         x, xn, rnn, lengths = self._saved
         dpool = self._head.backward(dz)
         P = self._params

@@ -94,6 +94,10 @@ typedef struct {
                             below).  dep_rnn_status and dep_rnn_workspace_xbuf_offset work as on impl 3.  Any other cell, dirs or
                             H with impl = 4 is a bad descriptor (size queries 0, entry points DEP_ERR_ARG, the rule in
                             dep_last_error).
+                            5 the per-layer cluster sweeps, state through training: impl = 4 in every respect -- the same descriptors
+                            exist, the same layout and sizes, the same plan, plain calls launch the same instances and give the same
+                            bits, any other cell, dirs or H is a bad descriptor with the rule naming impl = 5 -- that also takes hx
+                            in a DEP_RUN_TRAIN forward and hx / dhx in dep_rnn_backward_state[_varlen] (the state contract below).
                             A bidirectional GRU has tile-MFMA kernels only: impl must be 0 or 2 (both mean those kernels)
                             and H a multiple of 16 they can tile -- H / 16 = waves x tiles per wave with waves in
                             {1,2,4,8} and at most 4 tiles per wave, inside the LDS bound: H in {16,32,48,64,96,128,192,256}.
@@ -287,7 +291,15 @@ int dep_rnn_backward_overlapped_varlen(const dep_rnn_desc* d, const float* x, co
  *   - hx alone is also accepted by dep_rnn_forward_state on an impl = 4 descriptor (the per-layer cluster sweeps) in DEP_RUN_EVAL and
  *     DEP_RUN_DROPOUT_ONLY, the run modes no backward follows: every member of a tile's cluster reads the tile's rows of hx in front
  *     of its first step.  Still refused there, before anything is launched: hx in DEP_RUN_TRAIN, and any non-NULL member in
- *     dep_rnn_backward_state -- the cluster backward has neither the hx term of dW_hh nor dhx;
+ *     dep_rnn_backward_state -- on impl = 4 the cluster backward takes no state;
+ *   - on an impl = 5 descriptor (the per-layer cluster sweeps, state through training) hx is accepted by the forward in every run
+ *     mode, DEP_RUN_TRAIN included, and hx and dhx by dep_rnn_backward_state: gru_bwd_cluster_r1 takes hx as h_prev of step 0 and
+ *     stores the direct term of dhx (d_0 * z_0) at its last step; the call adds the hx term of dW_hh and the recurrent term of dhx,
+ *     dG[:, 0, :] W_hh, as small contractions behind the sweep on `stream`.  Such a call writes fp32 gate-gradient rows (never the
+ *     pre-split PK image), so its contractions are the unpaired ones; a call without state keeps its plan and its bits.  dhx may be
+ *     dh_n's buffer (the thread that stores a value read that address before the sweep); hx must be 16-byte aligned.  Refused there
+ *     before anything is launched: cx / c_n / dc_n / dcx (a GRU), and a state-bearing backward in GEMM modes 2 / 3 (the bf16-storage
+ *     and single-product instances take no hx);
  *   - on any other descriptor (impl 0 / 3 with cluster kernels) the call returns DEP_ERR_ARG before anything is launched, with the rule
  *     in dep_last_error.
  * Scope
@@ -343,8 +355,9 @@ int dep_rnn_backward_state(const dep_rnn_desc* d, const float* x, const float* c
  *   - exactly where the dense state call is accepted: a descriptor whose layout has no cluster exchange buffer
  *     (dep_rnn_workspace_xbuf_offset(d) == (size_t)-1), and hx in the forward on an impl = 4 descriptor in DEP_RUN_EVAL /
  *     DEP_RUN_DROPOUT_ONLY (the ragged instances of the same sweep: a row with len_b = 0 returns hx bit for bit; the T = 1 aliasing
- *     rule is the dense call's); elsewhere a non-NULL member is DEP_ERR_ARG before anything is launched, with the rule in
- *     dep_last_error;
+ *     rule is the dense call's), and hx in every forward and hx / dhx in the backward on an impl = 5 descriptor (a row with len_b = 0
+ *     never was live: its dhx is the dh_n it was given, bit for bit); elsewhere a non-NULL member is DEP_ERR_ARG before anything is
+ *     launched, with the rule in dep_last_error;
  *   - also refused before any launch: cx / c_n / dc_n / dcx on a GRU, lengths == NULL (the dense call is dep_rnn_*_state), and GEMM
  *     modes 2 / 3 (as for every ragged call).
  * All-NULL state
