@@ -180,9 +180,11 @@ struct Layout {
     bool keep;                       // DEP_RUN_TRAIN: the reserve holds everything the backward reads
     bool donly;                      // DEP_RUN_DROPOUT_ONLY: dropout as in training, the reserve holds what the forward itself reads
     bool cluster;                    // cluster-parallel sweeps (rnn_cluster*.hip): the workspace has their exchange buffer
+    bool cluster_fwd;                // impl 6: the FORWARD alone runs on the cluster (a bidirectional GRU); the workspace has its exchange buffer, and
+                                     // nothing else of `cluster` holds: the backward, its weight images, bias partials and gate gradients are the tile sweeps'
     bool fused2;                     // 2-layer GRU, H = 256: both layers in one launch (rnn_fused2*.hip) where the call's plan allows it
     size_t wih_img;                  // workspace: packed W_ih of layer 1 for the fused launches
-    size_t hxstage;                  // workspace (impl 4 only): B x H floats, a layer's hx copied aside when T = 1 and h_n overlaps it
+    size_t hxstage;                  // workspace (impl 4 / 5 / 6 only): dirs x B x H floats, a layer's hx copied aside when T = 1 and h_n overlaps it
 };
 
 // A bidirectional GRU runs the tile-MFMA sweeps (gru_*_mfma<JPW, RAG, true>) and nothing else: it has no generic, cluster or fused
@@ -191,7 +193,7 @@ bool bigru_ok(const dep_rnn_desc* d) { return (d->impl == 0 || d->impl == 2) && 
 
 // dep_last_error for a descriptor refused by the rule above (the entry points and the size queries; DEP_OK for any other descriptor)
 int bigru_refusal(const dep_rnn_desc* d, const char* who) {
-    if (!d || d->cell != DEP_CELL_GRU || d->dirs != 2 || d->H <= 0 || bigru_ok(d)) return DEP_OK;
+    if (!d || d->cell != DEP_CELL_GRU || d->dirs != 2 || d->H <= 0 || d->impl == 6 || bigru_ok(d)) return DEP_OK;      // (impl 6: bicluster_refusal)
     dep_set_error("%s: a bidirectional GRU (dirs = 2) runs the tile-MFMA sweeps only: impl must be 0 or 2 and H a multiple of 16 those sweeps can "
                   "tile (H / 16 = waves x tiles per wave, waves in {1, 2, 4, 8}, tiles <= 4, within the LDS bound: 16 .. 64, 96, 128, 192, 256); got H = %d, impl = %d", who, d->H, d->impl);
     return DEP_ERR_ARG;
@@ -211,10 +213,25 @@ int percluster_refusal(const dep_rnn_desc* d, const char* who) {
     return DEP_ERR_ARG;
 }
 
+// impl = 6, "the per-layer cluster forward of a bidirectional GRU": gru_fwd_cluster_r1<.., BI = true> runs every forward, both directions
+// of a layer in one launch; the backward is the tile-MFMA BiGRU's (gru_bwd_mfma<.., true>) on the reserve that forward leaves -- the same
+// four fp32 (B,T,2H) saved-gate arrays.  H = 512 has the forward only: the tile sweeps stop at 256, dep_rnn_backward refuses it.
+bool bicluster_impl(const dep_rnn_desc* d) { return d->impl == 6; }
+bool bicluster_ok(const dep_rnn_desc* d) { return d->cell == DEP_CELL_GRU && d->dirs == 2 && dep_cluster_ok(d->cell, d->H, d->B, d->dirs); }
+
+// dep_last_error for an impl = 6 descriptor refused by the rule above (DEP_OK for any other descriptor)
+int bicluster_refusal(const dep_rnn_desc* d, const char* who) {
+    if (!d || !bicluster_impl(d) || d->H <= 0 || bicluster_ok(d)) return DEP_OK;
+    dep_set_error("%s: impl = 6 (the per-layer cluster forward of a bidirectional GRU) is a bidirectional GRU with H in {64, 128, 256, 512}: cell must be "
+                  "DEP_CELL_GRU and dirs 2; got cell = %d, H = %d, dirs = %d", who, d->cell, d->H, d->dirs);
+    return DEP_ERR_ARG;
+}
+
 bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     if (!d || d->B <= 0 || d->T <= 0 || d->F <= 0 || d->H <= 0 || d->L < 1 || d->L > MAXL) return false;
     if (percluster_impl(d) && !percluster_ok(d)) return false;
-    if (d->cell == DEP_CELL_GRU) { if (d->dirs != 1 && !(d->dirs == 2 && bigru_ok(d))) return false; }
+    if (bicluster_impl(d) && !bicluster_ok(d)) return false;
+    if (d->cell == DEP_CELL_GRU) { if (d->dirs != 1 && !(d->dirs == 2 && (bigru_ok(d) || bicluster_impl(d)))) return false; }
     else if (d->cell == DEP_CELL_LSTM) { if (d->dirs != 1 && d->dirs != 2) return false; }
     else return false;
     if (d->dropout_p < 0.f || d->dropout_p >= 1.f) return false;
@@ -297,7 +314,10 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     const bool cok = d->cell == DEP_CELL_GRU ? d->dirs == 1 && dep_cluster_ok(d->cell, d->H, d->B, d->dirs) : dep_cluster_lstm_ok(d->H, d->B, d->dirs);
     if (d->impl == 3 && !cok) return false;
     lo.cluster = cok && (d->impl == 0 || d->impl == 3 || percluster_impl(d));
-    lo.xbuf = w; lo.xbuf_bytes = !lo.cluster ? 0 : (d->cell == DEP_CELL_GRU ? dep_cluster_xbuf_bytes(d->cell, d->H, d->B, d->dirs)
+    // impl 6 (checked above): the bidirectional forward's exchange buffer and the hx staging area, and none of what `cluster` selects
+    lo.cluster_fwd = bicluster_impl(d);
+    lo.xbuf = w; lo.xbuf_bytes = lo.cluster_fwd ? dep_cluster_xbuf_bytes(d->cell, d->H, d->B, d->dirs)
+                               : !lo.cluster ? 0 : (d->cell == DEP_CELL_GRU ? dep_cluster_xbuf_bytes(d->cell, d->H, d->B, d->dirs)
                                                                 : dep_cluster_lstm_xbuf_bytes(d->H, d->B, d->dirs));
     if (lo.cluster) lo.nwg = dep_cdiv(d->B, 16);      // the cluster sweeps write one row per tile whatever the tile-MFMA sweep could do at this H
     lo.fused2 = lo.cluster && !percluster_impl(d) && dep_fused2_ok(d->cell, d->H, d->L, d->dirs);
@@ -313,7 +333,7 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
         lo.dghn2 = w; w += al(lo.BT * H);
         lo.dbpart2 = w; w += al((size_t)lo.nwg * 4 * H);
     }
-    lo.hxstage = w; if (percluster_impl(d)) w += al((size_t)d->B * H);
+    lo.hxstage = w; if (percluster_impl(d) || lo.cluster_fwd) w += al(D * d->B * H);
     lo.ws_floats = w;
     return true;
 }
@@ -322,12 +342,15 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
 
 extern "C" size_t dep_rnn_reserve_bytes(const dep_rnn_desc* d) {
     Layout lo;
-    if (!make_layout(d, lo)) { if (!percluster_refusal(d, "dep_rnn_reserve_bytes")) (void)bigru_refusal(d, "dep_rnn_reserve_bytes"); return 0; }
+    if (!make_layout(d, lo)) {
+        if (!percluster_refusal(d, "dep_rnn_reserve_bytes") && !bicluster_refusal(d, "dep_rnn_reserve_bytes")) (void)bigru_refusal(d, "dep_rnn_reserve_bytes");
+        return 0;
+    }
     return lo.reserve_floats * sizeof(float);
 }
 extern "C" size_t dep_rnn_workspace_bytes(const dep_rnn_desc* d) {
     Layout lo;
-    if (!make_layout(d, lo)) { (void)percluster_refusal(d, "dep_rnn_workspace_bytes"); return 0; }
+    if (!make_layout(d, lo)) { if (!percluster_refusal(d, "dep_rnn_workspace_bytes")) (void)bicluster_refusal(d, "dep_rnn_workspace_bytes"); return 0; }
     return lo.ws_floats * sizeof(float);
 }
 // byte offset of layer l's output sequence (B,T,H*dirs) inside the reserve (zero-copy access for the caller)
@@ -345,7 +368,7 @@ extern "C" size_t dep_rnn_reserve_ydrop_offset(const dep_rnn_desc* d, int layer)
 // Byte offset of the cluster exchange buffer inside the workspace (debug tooling: DEP_TRACE stamps live at +4096).
 extern "C" size_t dep_rnn_workspace_xbuf_offset(const dep_rnn_desc* d) {
     Layout lo;
-    if (!make_layout(d, lo) || !lo.cluster) return (size_t)-1;
+    if (!make_layout(d, lo) || !(lo.cluster || lo.cluster_fwd)) return (size_t)-1;
     return lo.xbuf * sizeof(float);
 }
 
@@ -354,7 +377,7 @@ extern "C" size_t dep_rnn_workspace_xbuf_offset(const dep_rnn_desc* d) {
 extern "C" int dep_rnn_status(const dep_rnn_desc* d, void* workspace, void* stream) {
     Layout lo;
     DEP_CHECK_ARG(make_layout(d, lo) && workspace);
-    if (!lo.cluster) return DEP_OK;
+    if (!(lo.cluster || lo.cluster_fwd)) return DEP_OK;
     unsigned st = 0;
     if (hipMemcpyAsync(&st, (float*)workspace + lo.xbuf, sizeof(st), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
         hipStreamSynchronize((hipStream_t)stream) != hipSuccess) {
@@ -429,19 +452,22 @@ struct RnnPlan {
 // impl = 4 / 5 (the per-layer cluster sweeps) is planned like a ragged call, dense or not: FWD_CLUSTER_GRU / BWD_CLUSTER_GRU and what follows
 // from them.  Its layout has no fused2 part, and the 16-unit-member kernel does not belong to the descriptor, so the 32-unit-member image
 // and the 16-bit saved gates are chosen as on a shape without that kernel.
+// impl = 6 (lo.cluster_fwd): FWD_CLUSTER_GRU on the bidirectional instance, dense or ragged, with each direction's 32-unit-member image (split
+// products) or the fp32 fragment image (exact mode), fp32 saved gates; everything of the backward is the tile BiGRU's of impl = 2 -- BWD_TILE on
+// the wpT image of dep_pack_whh, packed by a DEP_RUN_TRAIN forward in either mode -- because lo.cluster is off.
 RnnPlan make_plan(const dep_rnn_desc* d, const Layout& lo, int mode, bool excl, bool ragged) {
     const RnnSwitches& sw = dep_rnn_switches();
     const bool gru = d->cell == DEP_CELL_GRU;
     RnnPlan p{};
     p.excl = excl; p.split = mode >= 1;
-    const bool csplit = lo.cluster && p.split;
+    const bool csplit = (lo.cluster || lo.cluster_fwd) && p.split;      // the forward's recurrent-weight image is a split-precision one
     // the kernels that fill every CU (fused forward, 16-unit members) are not for a shared GPU; the fused BACKWARD does not care
     const bool cluster16 = lo.cluster && !percluster_impl(d) && dep_cluster16_ok(d->cell, d->H, d->B);
     p.fwd = (lo.fused2 && p.split && excl && !ragged) ? FWD_FUSED2 : (cluster16 && excl && !ragged) ? FWD_CLUSTER16
-          : !lo.cluster ? FWD_TILE : gru ? FWD_CLUSTER_GRU : FWD_CLUSTER_LSTM;
+          : lo.cluster_fwd ? FWD_CLUSTER_GRU : !lo.cluster ? FWD_TILE : gru ? FWD_CLUSTER_GRU : FWD_CLUSTER_LSTM;
     p.bwd = (lo.fused2 && sw.fused2_bwd && p.split && dep_fused2_bwd_fits(d->B, d->T) && !ragged) ? BWD_FUSED2
           : !lo.cluster ? BWD_TILE : gru ? BWD_CLUSTER_GRU : BWD_CLUSTER_LSTM;
-    p.whh_f32 = lo.cluster ? !p.split : dep_sweep_use_mfma(d->H, d->impl);
+    p.whh_f32 = lo.cluster ? !p.split : lo.cluster_fwd ? (!p.split || lo.keep) : dep_sweep_use_mfma(d->H, d->impl);
     p.whh_fwd = !csplit ? WHH_NONE : !gru ? WHH_LSTM_PAIR : p.fwd == FWD_CLUSTER16 ? WHH_SPLIT16 : WHH_SPLIT32;
     p.whh_bwd = (!lo.cluster || !lo.keep || p.whh_fwd == WHH_LSTM_PAIR) ? WHH_NONE : p.split ? WHH_BWD_SPLIT : WHH_BWD_F32;
     // 16-bit saved gates: the kernels that implement them are the fused forward, the 32-unit-member forward and the 32-unit-member
@@ -556,6 +582,7 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
                             size_t workspace_bytes, void* stream) {
     Layout lo;
     if (const int rf = percluster_refusal(d, "dep_rnn_forward")) return rf;
+    if (const int rf = bicluster_refusal(d, "dep_rnn_forward")) return rf;
     if (const int rf = bigru_refusal(d, "dep_rnn_forward")) return rf;
     DEP_CHECK_ARG(make_layout(d, lo));
     const dep_rnn_state st = state ? *state : dep_rnn_state{nullptr, nullptr, nullptr};      // NULL and a struct of NULLs are the plain call
@@ -579,7 +606,7 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
     DepGemmOpts proj; proj.scratch = W + lo.gemm; proj.scratch_bytes = lo.gemm_bytes;
     float* const gi = W + lo.gi;
     int rc;
-    if (lo.cluster) { rc = dep_cluster_reset_status(W + lo.xbuf, s); if (rc) return rc; }
+    if (lo.cluster || lo.cluster_fwd) { rc = dep_cluster_reset_status(W + lo.xbuf, s); if (rc) return rc; }
     if (p.bf16st && (!p.excl || y)) {
         dep_set_error("dep_rnn_forward: bf16-storage mode (dep_set_gemm_mode(3)) runs the exclusive fused forward only (dep_rnn_set_exclusive(1)) "
                       "and has no fp32 copy of the output sequence (y must be NULL)");
@@ -600,7 +627,7 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
     auto sweep_args = [&](int l, const unsigned* only_if) {
         dep_sweep_args a{};
         a.B = B; a.T = T; a.H = H; a.cell = d->cell; a.dirs = D; a.training = d->training; a.impl = d->impl;
-        a.split = (lo.cluster && p.split) ? 1 : 0;
+        a.split = ((lo.cluster || lo.cluster_fwd) && p.split) ? 1 : 0;
         for (int dd = 0; dd < D; ++dd) {
             const float* const* wl = weights + (size_t)(l * D + dd) * 4;
             a.w_hh[dd] = wl[1]; a.b_hh[dd] = wl[3]; a.wp[dd] = R + lo.wp[l][dd];
@@ -722,11 +749,11 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
             if (rc) return rc;
         }
         dep_sweep_args a = sweep_args(l, nullptr);
-        if (p.fwd == FWD_CLUSTER_GRU && a.hx && a.h_n && T == 1 && a.hx < a.h_n + (size_t)B * H && a.h_n < a.hx + (size_t)B * H) {
+        if (p.fwd == FWD_CLUSTER_GRU && a.hx && a.h_n && T == 1 && a.hx < a.h_n + (size_t)D * B * H && a.h_n < a.hx + (size_t)D * B * H) {
             // h_n over hx at T = 1: the sweep has no exchange, so nothing keeps a member's h_n store behind another member's read of that
             // row of hx.  The kernel reads a copy (T >= 2: every member reads hx before it raises its first flag, and no member stores
             // h_n before it has seen all of them)
-            if (hipMemcpyAsync(W + lo.hxstage, a.hx, (size_t)B * H * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
+            if (hipMemcpyAsync(W + lo.hxstage, a.hx, (size_t)D * B * H * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
                 dep_set_error("dep_rnn_forward_state: staging copy of hx failed"); return DEP_ERR_HIP;
             }
             a.hx = W + lo.hxstage;
@@ -778,6 +805,11 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
                              void* stream, const dep_grad_sync* gs) {
     Layout lo;
     if (const int rf = percluster_refusal(d, "dep_rnn_backward")) return rf;
+    if (const int rf = bicluster_refusal(d, "dep_rnn_backward")) return rf;
+    if (d && bicluster_impl(d) && !dep_sweep_use_mfma(d->H, d->impl)) {
+        dep_set_error("dep_rnn_backward: impl = 6 runs the tile-MFMA backward of the bidirectional GRU, which tiles H up to 256; H = %d has the forward only", d->H);
+        return DEP_ERR_ARG;
+    }
     if (const int rf = bigru_refusal(d, "dep_rnn_backward")) return rf;
     DEP_CHECK_ARG(make_layout(d, lo));
     const dep_rnn_state_grad st = state ? *state : dep_rnn_state_grad{nullptr, nullptr, nullptr, nullptr, nullptr};      // NULL and a struct of NULLs are the plain call

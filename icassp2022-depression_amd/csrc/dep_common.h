@@ -176,7 +176,7 @@ struct DepProfScope {
 // ---- internal launchers shared across translation units ---------------------------
 struct dep_sweep_args {
     int B, T, H;
-    int cell, dirs;          // dirs = 2: both directions in one launch (GRU: the tile-MFMA sweeps only, rnn_sweep.hip)
+    int cell, dirs;          // dirs = 2: both directions in one launch (GRU: the tile-MFMA sweeps of rnn_sweep.hip, and dep_launch_cluster_fwd for impl 6)
     int training;
     int impl;
     // per direction d
@@ -191,7 +191,7 @@ struct dep_sweep_args {
     float drop_p; uint64_t seed; uint32_t site;
     float* pooled; float pool_scale;    // GRU top layer: (B,dirs*H) sum_t y_t * scale, or NULL
     float* h_n;              // (dirs,B,H) final states or NULL
-    // initial state of this layer (dep_rnn_forward_state[_varlen]; rnn_sweep.hip, and hx alone on dep_launch_cluster_fwd for an impl 4
+    // initial state of this layer (dep_rnn_forward_state[_varlen]; rnn_sweep.hip, and hx alone on dep_launch_cluster_fwd for an impl 4 / 5 / 6
     // descriptor -- the other cluster launchers are never given one)
     const float* hx;         // (dirs,B,H) h before the sweep's first step, or NULL = zeros; may be h_n's buffer
     const float* cx;         // LSTM: (dirs,B,H) c before the first step, or NULL = zeros; may be c_n's buffer

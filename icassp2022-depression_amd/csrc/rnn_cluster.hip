@@ -76,8 +76,11 @@ bool dep_cluster_ok(int cell, int H, int, int) {      // any batch: the launcher
 // no launcher uses the factor 2 -- both are slack, kept because the number is visible through dep_rnn_workspace_bytes.  The max with
 // the forwards' payloads never binds (both member sizes cut the batch into the same chunks, and the doubled backward payload is
 // 2 * NC times a forward's); it is there to show that the buffer covers the 16-unit-member forward too.
+// dirs = 2 (impl 6): the buffer of the bidirectional forward alone -- the headers and exactly its payload, two parities of the 16 x H block
+// of every (direction, tile) pair of the largest chunk.  No backward, no 16-unit-member forward and no slack share it.
 size_t dep_cluster_xbuf_bytes(int cell, int H, int B, int dirs) {
     if (!dep_cluster_ok(cell, H, B, dirs)) return 0;
+    if (dirs == 2) return PAYLOAD_OFF + gru_fwd_bi_payload_bytes(gru32_bi_geometry(H, B), H);
     const ChunkGeometry g32 = gru32_geometry(H, B), g16 = gru16_geometry(H, B);
     const size_t fwd = std::max(gru_fwd_payload_bytes(g32, H), gru_fwd_payload_bytes(g16, H));
     return PAYLOAD_OFF + std::max(fwd, 8192 + 2 * gru_bwd_payload_bytes(g32, H));

@@ -706,6 +706,10 @@ struct F2 {
     const int* lengths; int pool_mean;      // ragged instances (RAG): row b is live for t < lengths[b]; a mean pool divides by lengths[b]
     const float* hx;         // this layer's (B, H) initial state (dep_rnn_forward_state[_varlen] on impl 4 / 5), or nullptr = zeros
 };
+// The parameters of the bidirectional instances (BI, impl 6): direction 1's W_hh image and b_hh, and the row stride of the saved gates
+// (2H).  A struct of their own, so that the unidirectional instances keep their kernel arguments (and with them their ISA: the implicit
+// arguments sit behind the struct).
+struct F2B : F2 { const f32x4* wp1; const float* b_hh1; int ldsv; };
 
 // RAG: the ragged-batch instances (dep_rnn_forward_varlen): h = live ? new : previous (what is published, kept and returned as h_n),
 // y / dropout(y) / the pool take live ? h : 0.  Everything about the hand-off is the dense instance's.
@@ -713,13 +717,22 @@ struct F2 {
 // front of the step loop, with no exchange -- as fp32, or (SPLIT) as the two bf16 planes of split_word(hx), the bits a previous step
 // would have published -- and starts hprev from its own two columns.  The loop, the hand-off and every trip count are untouched; a
 // ragged row with len = 0 never leaves hprev, so it returns hx bit for bit.  Rows b >= B of the last tile read nothing and stay 0.
-template <int KCH, bool SPLIT, bool RAG = false>      // SPLIT: 3-term bf16 split of the recurrent product, as in gru_fwd_cluster16
-__global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
+// BI: the bidirectional instances (impl 6), as in gru_fwd_mfma.  A cluster is a (direction, tile) PAIR, both directions of a batch chunk in
+// one launch: block = (c * 2 + dir) * nbtp + bt (nbtp, the padded tiles PER DIRECTION, is a multiple of 8: block id -> XCD stays member- and
+// direction-invariant), and the pair dir * nbtp + bt indexes the flag words, the hello words and the payload.  Direction 1 takes wp1 / b_hh1,
+// visits t = T-1-s at sweep step s (epochs, payload parity and the gi prefetch follow s) and every array is the direction-interleaved one:
+// gi (B,T,2*3H), y / dropout(y) (B,T,2H; ldy) and the saved gates (B,T,2H; ldsv), pool (B,2H), hx / h_n (2,B,H).  The dropout draw is the
+// element's index in (B,T,2H), as gru_fwd_mfma draws it.  A ragged row's reverse sweep meets its dead steps first and carries hx (or 0)
+// through them by the same live select.  BI = false is the unidirectional text.
+template <int KCH, bool SPLIT, bool RAG = false, bool BI = false>      // SPLIT: 3-term bf16 split of the recurrent product, as in gru_fwd_cluster16
+__global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(std::conditional_t<BI, F2B, F2> p) {
     // contraction by syntax: see DEP_FP_CONTRACT_NOTE in dep_common.h (why, and how to re-verify the dense instances after a compiler change)
 #pragma clang fp contract(on)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H = p.H, T = p.T, LDH = H + LPAD, KC = H / 16, NC = H / 32;
-    const int c = blockIdx.x / p.nbtp, bt = blockIdx.x % p.nbtp;
+    const int c = BI ? blockIdx.x / (2 * p.nbtp) : blockIdx.x / p.nbtp, bt = blockIdx.x % p.nbtp;
+    const int dir = BI ? (int)(blockIdx.x / p.nbtp) & 1 : 0;
+    const int pt = BI ? dir * p.nbtp + bt : bt;      // the cluster's (direction, tile) pair: flags, hello words, payload
     if (p.b0 + bt * BT >= p.B) return;
     if (ld_agent(p.status) != 0) return;           // an earlier sweep of this step gave up: the status word is sticky until the next dep_rnn_forward
     if (p.only_if && ld_agent(const_cast<unsigned*>(p.only_if)) == 0) return;      // the exclusive kernel in front of us did the work
@@ -737,6 +750,7 @@ __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
     unsigned short* hs_lo = hs_hi + BT * LDHB;
     float* red = smem + hs_floats;                    // [4][3][64][4]
     for (int i = tid; i < hs_floats; i += CT) hs[i] = 0.f;
+    const float* const hxd = BI ? (p.hx ? p.hx + (size_t)dir * p.B * H : nullptr) : p.hx;      // the direction's own slice of hx (2,B,H)
     if (p.hx) {
         __syncthreads();                              // (the zero fill walks the planes in another order)
         const int xshift = __ffs(H) - 1;
@@ -746,7 +760,7 @@ __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
             const int xr = i4 >> xshift, xc = i4 & (H - 1);
             const int xb = p.b0 + bt * BT + xr;
             if (xb < p.B) {
-                const float* src = p.hx + (size_t)xb * H + xc;
+                const float* src = hxd + (size_t)xb * H + xc;
                 const float2 x01 = ld2(src), x23 = ld2(src + 2);
                 if constexpr (SPLIT) {
                     const unsigned v0 = split_word(x01.x), v1 = split_word(x01.y), v2 = split_word(x23.x), v3 = split_word(x23.y);
@@ -766,8 +780,10 @@ __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
     constexpr int KS2 = KCH / 2;                      // 32-wide k-steps per wave (SPLIT)
     f32x4 wr[SPLIT ? 1 : 3][SPLIT ? 1 : KCH];
     u32x4 wq[SPLIT ? 3 : 1][SPLIT ? KS2 : 1][2];      // [gate][k-step][hi, lo]
+    const f32x4* wpd = p.wp; const float* bhd = p.b_hh;      // the direction's own W_hh image and b_hh
+    if constexpr (BI) { if (dir) { wpd = p.wp1; bhd = p.b_hh1; } }
     if constexpr (SPLIT) {
-        const u32x4* wpq = reinterpret_cast<const u32x4*>(p.wp);
+        const u32x4* wpq = reinterpret_cast<const u32x4*>(wpd);
 #pragma unroll
         for (int g = 0; g < 3; ++g)
 #pragma unroll
@@ -780,38 +796,41 @@ __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
         for (int g = 0; g < 3; ++g)
 #pragma unroll
             for (int k = 0; k < KCH; ++k)
-                wr[g][k] = p.wp[(size_t)((jt * 3 + g) * KC + kh * KCH + k) * 64 + lane];
+                wr[g][k] = wpd[(size_t)((jt * 3 + g) * KC + kh * KCH + k) * 64 + lane];
     }
     const int col = jt * 16 + q * 4 + 2 * kh;
+    const int dcol = BI ? dir * H + col : col;        // the column in the direction-interleaved rows of y, dropout(y), the saved gates and the pool
     float2 bh[3];
 #pragma unroll
-    for (int g = 0; g < 3; ++g) bh[g] = ld2(p.b_hh + g * H + col);
-    float2 hprev = (p.hx && valid) ? ld2(p.hx + (size_t)b * H + col) : f2(0.f, 0.f), pool = f2(0.f, 0.f);
-    const size_t pstride = (size_t)p.nbtp * BT * H;
-    const size_t tile_base = (size_t)bt * BT * H;
+    for (int g = 0; g < 3; ++g) bh[g] = ld2(bhd + g * H + col);
+    float2 hprev = (p.hx && valid) ? ld2(hxd + (size_t)b * H + col) : f2(0.f, 0.f), pool = f2(0.f, 0.f);
+    const size_t pstride = (size_t)(BI ? 2 * p.nbtp : p.nbtp) * BT * H;
+    const size_t tile_base = (size_t)pt * BT * H;
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.payload, 0, p.payload_bytes, 0x00020000);
-    unsigned* myflag = p.flags + bt * NC + c;
-    unsigned* tflags = p.flags + bt * NC;
+    unsigned* myflag = p.flags + pt * NC + c;
+    unsigned* tflags = p.flags + pt * NC;
     const int hshift = __ffs(H) - 1;
-    const int sx = p.nofast ? 0 : cluster_same_xcd(p.hello + bt * NC, NC, c, p.status);
+    const int sx = p.nofast ? 0 : cluster_same_xcd(p.hello + pt * NC, NC, c, p.status);
     if (sx < 0) return;
     const bool fast = sx == 1;
+    const float* const gid = BI ? p.gi + dir * 3 * H : p.gi;      // the direction's three gate blocks of the (B,T,2*3H) rows
     float2 gin[3];
 #pragma unroll
     for (int g = 0; g < 3; ++g)
-        gin[g] = valid ? ld2(p.gi + (size_t)b * T * p.ldgi + g * H + col) : f2(0.f, 0.f);
+        gin[g] = valid ? ld2(gid + ((size_t)b * T + ((BI && dir) ? T - 1 : 0)) * p.ldgi + g * H + col) : f2(0.f, 0.f);
     __syncthreads();
 
     long long* tr = (p.trace && blockIdx.x == 0 && tid == 0) ? p.trace : nullptr;
-    for (int t = 0; t < T; ++t) {
+    for (int s = 0; s < T; ++s) {
+        const int t = (BI && dir) ? T - 1 - s : s;
         const size_t row = (size_t)b * T + t;
         DEP_STAMP(0);
         float2 gi[3];
 #pragma unroll
         for (int g = 0; g < 3; ++g) gi[g] = gin[g];
-        if (valid && t + 1 < T) {
+        if (valid && s + 1 < T) {      // the next SWEEP step's row: t + 1, or (reverse) t - 1
 #pragma unroll
-            for (int g = 0; g < 3; ++g) gin[g] = ld2(p.gi + (row + 1) * p.ldgi + g * H + col);
+            for (int g = 0; g < 3; ++g) gin[g] = ld2(gid + ((BI && dir) ? row - 1 : row + 1) * p.ldgi + g * H + col);
         }
         f32x4 acc[3] = {zero4(), zero4(), zero4()};
         if constexpr (SPLIT) {
@@ -872,9 +891,9 @@ __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
             hy = dep_sel2(live, h, f2(0.f, 0.f));
         }
         hprev = h; pool.x += hy.x; pool.y += hy.y;
-        const unsigned epoch = (unsigned)t + 1u;
-        const size_t pbase = (size_t)(t & 1) * pstride + tile_base;
-        const bool more = t + 1 < T;
+        const unsigned epoch = (unsigned)s + 1u;
+        const size_t pbase = (size_t)(s & 1) * pstride + tile_base;
+        const bool more = s + 1 < T;
         DEP_STAMP(3);
         if (more) {       // publish first: it is on the critical path of the other members
             const u64 bits = SPLIT ? ((u64)split_word(h.x) | ((u64)split_word(h.y) << 32))
@@ -887,14 +906,15 @@ __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
             if (tid == 0) { if (fast) st_local(myflag, epoch); else st_agent(myflag, epoch); }
         }
         if (valid) {
-            const size_t o = row * p.ldy + col;
+            const size_t o = row * p.ldy + dcol;
             st2(p.y + o, hy);
             if (p.ydrop) {
                 const f32x4 m = dep_dropmask4(p.seed, p.site, o >> 2, p.drop_p, p.drop_scale);
                 st2(p.ydrop + o, f2(hy.x * (kh ? m[2] : m[0]), hy.y * (kh ? m[3] : m[1])));
             }
             if (p.sv0) {
-                const size_t so = row * H + col;
+                size_t so = row * H + col;
+                if constexpr (BI) so = row * p.ldsv + dcol;
                 if (p.sv16) {
                     *reinterpret_cast<unsigned*>(reinterpret_cast<unsigned short*>(p.sv0) + so) = pack_unorm2(r.x, r.y);
                     *reinterpret_cast<unsigned*>(reinterpret_cast<unsigned short*>(p.sv1) + so) = pack_unorm2(z.x, z.y);
@@ -930,8 +950,8 @@ __global__ __launch_bounds__(CT) void gru_fwd_cluster_r1(F2 p) {
     }
     if (valid) {
         const float ps = RAG ? dep_ragged_pool_scale(p.pool_mean, len, T, p.pool_scale) : p.pool_scale;
-        if (p.pooled) st2(p.pooled + (size_t)b * H + col, f2(pool.x * ps, pool.y * ps));
-        if (p.h_n) st2(p.h_n + (size_t)b * H + col, hprev);
+        if (p.pooled) st2(p.pooled + (BI ? (size_t)b * 2 * H + dcol : (size_t)b * H + col), f2(pool.x * ps, pool.y * ps));
+        if (p.h_n) st2(p.h_n + (BI ? (size_t)dir * p.B + b : (size_t)b) * H + col, hprev);
     }
 }
 
@@ -981,6 +1001,20 @@ Instance<F2>& fwd_instance(int H, bool split, bool rag) {      // KCH = H / 32; 
         { DEP_INSTANCE((gru_fwd_cluster_r1<16, false, true>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<16, true, true>), EXCLUSIVE_LDS) } };
     return (rag ? ragged : rows)[H == 64 ? 0 : H == 128 ? 1 : H == 256 ? 2 : 3][split];
 }
+// ... and the bidirectional instances (impl 6), dense and ragged
+Instance<F2B>& fwd_bi_instance(int H, bool split, bool rag) {
+    static Instance<F2B> bidir[4][2] = {
+        { DEP_INSTANCE((gru_fwd_cluster_r1<2, false, false, true>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<2, true, false, true>), EXCLUSIVE_LDS) },
+        { DEP_INSTANCE((gru_fwd_cluster_r1<4, false, false, true>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<4, true, false, true>), EXCLUSIVE_LDS) },
+        { DEP_INSTANCE((gru_fwd_cluster_r1<8, false, false, true>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<8, true, false, true>), EXCLUSIVE_LDS) },
+        { DEP_INSTANCE((gru_fwd_cluster_r1<16, false, false, true>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<16, true, false, true>), EXCLUSIVE_LDS) } };
+    static Instance<F2B> bidir_ragged[4][2] = {
+        { DEP_INSTANCE((gru_fwd_cluster_r1<2, false, true, true>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<2, true, true, true>), EXCLUSIVE_LDS) },
+        { DEP_INSTANCE((gru_fwd_cluster_r1<4, false, true, true>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<4, true, true, true>), EXCLUSIVE_LDS) },
+        { DEP_INSTANCE((gru_fwd_cluster_r1<8, false, true, true>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<8, true, true, true>), EXCLUSIVE_LDS) },
+        { DEP_INSTANCE((gru_fwd_cluster_r1<16, false, true, true>), EXCLUSIVE_LDS), DEP_INSTANCE((gru_fwd_cluster_r1<16, true, true, true>), EXCLUSIVE_LDS) } };
+    return (rag ? bidir_ragged : bidir)[H == 64 ? 0 : H == 128 ? 1 : H == 256 ? 2 : 3][split];
+}
 
 // NTW = H / 64.  Burst length 4 up to H = 256; H = 512 keeps the round-1 schedule (KB = 0): 192 weight registers per
 // compute wave leave no room for a second wave per SIMD.  H = 256 with split products: the all-gather exchange of the members' gate
@@ -1026,7 +1060,7 @@ void dep_cluster_gru_instance_texts(dep_instance_sink add) {
     const int sizes[] = {64, 128, 256, 512};       // dep_cluster_ok
     for (const int H : sizes)
         for (int m = 0; m < 16; ++m) {
-            if (m < 4) add(fwd_instance(H, m & 1, m & 2).text);
+            if (m < 4) { add(fwd_instance(H, m & 1, m & 2).text); add(fwd_bi_instance(H, m & 1, m & 2).text); }
             add(bwd_instance(H, m & 1, m & 2, m & 4, m & 8).text);
         }
 }
@@ -1057,16 +1091,21 @@ int dep_pack_cluster_bwd_split(const float* w_hh, float* out, int H, hipStream_t
 
 int dep_launch_cluster_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf_bytes) {
     DEP_CHECK_ARG(dep_cluster_ok(a.cell, a.H, a.B, a.dirs) && xbuf && xbuf_bytes >= dep_cluster_xbuf_bytes(a.cell, a.H, a.B, a.dirs));
-    const ChunkGeometry g = gru32_geometry(a.H, a.B);      // one workgroup per CU: 256 / NC tiles per launch, larger batches in chunks
-    F2 p{};
+    DEP_CHECK_ARG(a.dirs == 1 || a.dirs == 2);
+    const bool bi = a.dirs == 2;                           // both directions in one launch: a (direction, tile) pair per cluster
+    // one workgroup per CU: 256 / NC tiles per launch (bidirectional: per direction half as many), larger batches in chunks
+    const ChunkGeometry g = bi ? gru32_bi_geometry(a.H, a.B) : gru32_geometry(a.H, a.B);
+    F2B p{};
     p.B = a.B; p.T = a.T; p.H = a.H;
     p.wp = (const f32x4*)a.wp[0]; p.b_hh = a.b_hh[0];
-    p.gi = a.gi; p.ldgi = 3 * a.H; p.y = a.y; p.ldy = a.ldy;
+    p.wp1 = (const f32x4*)a.wp[1]; p.b_hh1 = a.b_hh[1]; p.ldsv = a.dirs * a.H;
+    DEP_CHECK_ARG(!bi || (a.wp[1] && a.b_hh[1] && !a.only_if && !a.sv16 && a.ldy == 2 * a.H));
+    p.gi = a.gi; p.ldgi = a.dirs * 3 * a.H; p.y = a.y; p.ldy = a.ldy;
     p.ydrop = (a.drop_p > 0.f) ? a.ydrop : nullptr;
     p.drop_p = a.drop_p; p.drop_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f; p.seed = a.seed; p.site = a.site;
     p.pooled = a.pooled; p.pool_scale = a.pool_scale; p.h_n = a.h_n;
     p.sv0 = a.training ? a.sv0 : nullptr; p.sv1 = a.sv1; p.sv2 = a.sv2; p.sv3 = a.sv3;
-    const size_t pay = gru_fwd_payload_bytes(g, a.H);
+    const size_t pay = bi ? gru_fwd_bi_payload_bytes(g, a.H) : gru_fwd_payload_bytes(g, a.H);
     DEP_CHECK_ARG(PAYLOAD_OFF + pay <= xbuf_bytes && g.resident());
     p.flags = bind_exchange(p, xbuf, a.hdr_slot, pay);
     p.only_if = a.only_if; p.sv16 = a.training ? a.sv16 : 0;
@@ -1074,8 +1113,9 @@ int dep_launch_cluster_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf_byte
     DEP_CHECK_ARG(!a.hx || (!a.only_if && (reinterpret_cast<uintptr_t>(a.hx) & 7) == 0));      // a state never travels with the fused forward's fallback; 8-byte loads
     p.hx = a.hx;
     DepProfScope prof(DEP_PROF_GRU_FWD, a.stream, a.only_if == nullptr);     // a conditional fallback launch is not a sweep of the step
-    return launch_chunks(fwd_instance(a.H, a.split, a.lengths != nullptr), g, dim3(CT), p, a.stream, __PRETTY_FUNCTION__,
-                         [&](int b0) { return hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); });
+    const auto prepare = [&](int b0) { return hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); };
+    if (bi) return launch_chunks(fwd_bi_instance(a.H, a.split, a.lengths != nullptr), g, dim3(CT), p, a.stream, __PRETTY_FUNCTION__, prepare);
+    return launch_chunks(fwd_instance(a.H, a.split, a.lengths != nullptr), g, dim3(CT), static_cast<F2&>(p), a.stream, __PRETTY_FUNCTION__, prepare);
 }
 
 // May dep_launch_cluster_bwd write the gate gradients as the PK image (dep_sweep_bwd_args.dg_pk)?  Needs the burst-stream kernel

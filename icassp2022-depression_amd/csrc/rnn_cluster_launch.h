@@ -36,8 +36,13 @@ inline ChunkGeometry chunk_geometry(int members, int per_cu, int cap, int B) {
 // the 16-unit-member forward, two per CU (rnn_cluster16.hip).
 inline ChunkGeometry gru32_geometry(int H, int B) { return chunk_geometry(H / 32, 1, 256, B); }
 inline ChunkGeometry gru16_geometry(int H, int B) { return chunk_geometry(H / 16, 2, 512, B); }
+// The bidirectional forward (gru_fwd_cluster_r1<.., BI = true>, impl 6) runs both directions of a batch chunk in ONE launch: a direction
+// doubles the clusters of a 16-utterance tile, 2 * H / 32 workgroups per tile, so the cap of 256 resident workgroups holds as it is and
+// CH / nbtp count the tiles PER DIRECTION (padded to whole groups of 8, like every chunk).  Its payload is the forward's, per direction.
+inline ChunkGeometry gru32_bi_geometry(int H, int B) { return chunk_geometry(2 * (H / 32), 1, 256, B); }
 // forward: two parities of a tile's 16 x H block of h_t, whatever the member size; backward: two parities of every member's 16 x H partial dh
 inline size_t gru_fwd_payload_bytes(const ChunkGeometry& g, int H) { return (size_t)2 * g.nbtp_max * BT * H * sizeof(float); }
+inline size_t gru_fwd_bi_payload_bytes(const ChunkGeometry& g, int H) { return 2 * gru_fwd_payload_bytes(g, H); }      // g = gru32_bi_geometry
 inline size_t gru_bwd_payload_bytes(const ChunkGeometry& g, int H) { return (size_t)2 * g.nbtp_max * g.members * BT * H * sizeof(float); }
 
 // One launchable template instance: the kernel expression as text (what the launch-instance and order logs record), its address and

@@ -98,12 +98,24 @@ typedef struct {
                             exist, the same layout and sizes, the same plan, plain calls launch the same instances and give the same
                             bits, any other cell, dirs or H is a bad descriptor with the rule naming impl = 5 -- that also takes hx
                             in a DEP_RUN_TRAIN forward and hx / dhx in dep_rnn_backward_state[_varlen] (the state contract below).
-                            A bidirectional GRU has tile-MFMA kernels only: impl must be 0 or 2 (both mean those kernels)
+                            6 the per-layer cluster forward of a bidirectional GRU: cell = DEP_CELL_GRU, dirs = 2, H in {64,128,256,512},
+                            any B, T, L, every run mode.  Every forward on it, dense or ragged, runs one launch of the bidirectional
+                            instance of gru_fwd_cluster_r1 per layer -- both directions of a batch chunk side by side, each
+                            (direction, 16-utterance tile) pair a cluster of H / 32 co-resident workgroups with its W_hh in registers --
+                            and takes hx in all three run modes (slices ordered like h_n, l * 2 + d).  The backward is the tile-MFMA
+                            BiGRU backward of impl = 2, on the reserve that forward leaves (the same fp32 (B,T,2H) saved gates, the same
+                            reserve offsets; hx / dhx as on impl = 2), so dep_rnn_backward[_state][_varlen] needs H <= 256: at H = 512
+                            the descriptor has the forward only and a backward returns DEP_ERR_ARG.  The workspace has a cluster
+                            exchange buffer (dep_rnn_status and dep_rnn_workspace_xbuf_offset work on it) and nothing else of the
+                            cluster layouts.  Any other cell, dirs or H with impl = 6 is a bad descriptor (size queries 0, entry
+                            points DEP_ERR_ARG, the rule in dep_last_error).  Outputs agree with impl = 2 to rounding (fast gate
+                            nonlinearities, split or exact recurrent products as on impl = 4), the dropout masks bit for bit.
+                            A bidirectional GRU otherwise has tile-MFMA kernels only: impl must be 0 or 2 (both mean those kernels)
                             and H a multiple of 16 they can tile -- H / 16 = waves x tiles per wave with waves in
                             {1,2,4,8} and at most 4 tiles per wave, inside the LDS bound: H in {16,32,48,64,96,128,192,256}.
                             Any other H, impl = 1 and impl = 3 are a bad descriptor (size queries 0, entry points
-                            DEP_ERR_ARG with the rule in dep_last_error); it never takes the cluster, 16-unit-member or
-                            fused two-layer kernels, and dep_rnn_workspace_xbuf_offset is (size_t)-1 for it. */
+                            DEP_ERR_ARG with the rule in dep_last_error); on impl 0 / 2 it never takes the cluster, 16-unit-member
+                            or fused two-layer kernels, and dep_rnn_workspace_xbuf_offset is (size_t)-1 for it. */
 } dep_rnn_desc;
 
 size_t dep_rnn_reserve_bytes(const dep_rnn_desc* d);     /* activations kept fwd -> bwd */
@@ -114,7 +126,7 @@ size_t dep_rnn_reserve_y_offset(const dep_rnn_desc* d, int layer);
 /* Same for the dropped-out copy that feeds layer+1 (DEP_RUN_TRAIN / DEP_RUN_DROPOUT_ONLY with dropout_p > 0 only). */
 size_t dep_rnn_reserve_ydrop_offset(const dep_rnn_desc* d, int layer);
 
-/* Health of the cluster-parallel sweeps that ran on `workspace` since the last dep_rnn_forward (desc.impl 0/3/4 with a
+/* Health of the cluster-parallel sweeps that ran on `workspace` since the last dep_rnn_forward (desc.impl 0/3/4/5/6 with a
  * supported H): they exchange data between workgroups inside one launch with bounded spins; if a spin ever gives up
  * the kernels exit early and this returns DEP_ERR_HIP.  The status is STICKY over a step: dep_rnn_forward clears it once,
  * every later sweep (the other layers, the whole backward) leaves it alone and exits at entry when it is raised, so one
@@ -287,7 +299,10 @@ int dep_rnn_backward_overlapped_varlen(const dep_rnn_desc* d, const float* x, co
  * Where state is accepted
  *   - a non-NULL member is accepted exactly where the per-layer tile-MFMA / generic sweeps (rnn_sweep.hip) run the stack: a descriptor
  *     whose layout has no cluster exchange buffer, dep_rnn_workspace_xbuf_offset(d) == (size_t)-1.  In practice impl 1 or 2, or impl 0
- *     at a shape without cluster kernels (a bidirectional GRU is always such a descriptor);
+ *     at a shape without cluster kernels (a bidirectional GRU on impl 0 / 2 is always such a descriptor);
+ *   - on an impl = 6 descriptor (the per-layer cluster forward of a bidirectional GRU) hx is accepted by every forward, in all three run
+ *     modes: each direction's clusters read that direction's slice, (l * 2 + d) like h_n.  hx / dhx in dep_rnn_backward_state go to the
+ *     tile-MFMA backward, which takes them for a bidirectional GRU on impl = 2 already.  cx / c_n / dc_n / dcx are refused (a GRU);
  *   - hx alone is also accepted by dep_rnn_forward_state on an impl = 4 descriptor (the per-layer cluster sweeps) in DEP_RUN_EVAL and
  *     DEP_RUN_DROPOUT_ONLY, the run modes no backward follows: every member of a tile's cluster reads the tile's rows of hx in front
  *     of its first step.  Still refused there, before anything is launched: hx in DEP_RUN_TRAIN, and any non-NULL member in
@@ -310,7 +325,7 @@ int dep_rnn_backward_overlapped_varlen(const dep_rnn_desc* d, const float* x, co
  *     H / 32 members of its tile: for T >= 2 the hand-off orders every member's read in front of any member's h_n store (a member
  *     finishes only after all members of its tile raised their first flag); for T = 1 there is no hand-off, so when h_n overlaps hx the
  *     call first copies the layer's B x H slice of hx into a staging area of its workspace (one device-to-device copy on `stream`)
- *     and the sweep reads the copy;
+ *     and the sweep reads the copy (impl = 6 likewise, with the layer's 2 x B x H slice);
  *   - reserve and workspace sizes and every offset are those of dep_rnn_forward / dep_rnn_backward;
  *   - gs: NULL, or as for dep_rnn_backward_overlapped. */
 typedef struct { const float* hx; const float* cx; float* c_n; } dep_rnn_state;
