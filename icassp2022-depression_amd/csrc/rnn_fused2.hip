@@ -358,6 +358,7 @@ __global__ __launch_bounds__(FTHREADS) void gru2_fwd_fused(FF p) {
             // write the masked planes too.)
         }
         if (grp < 2 && act) {
+            asm volatile("; DEP_REGION gate begin");      // region markers: comments in the -S output (tools/isa_regions.py)
             // branch-free over the two roles: the input-projection term is gi = A + B with
             //   layer 0: A = prefetched projection (gbuf), B = a zero pair ; layer 1: A, B = group 2's two K halves (b_ih inside)
             const int e2 = kh * 128 + lane * 2;           // this lane's pair inside a [2][64][2] fragment block
@@ -436,6 +437,7 @@ __global__ __launch_bounds__(FTHREADS) void gru2_fwd_fused(FF p) {
                     obuf[j * OROW + (ul >> 1) + 5 * OARR] = __uint_as_float(__builtin_bit_cast(unsigned, __builtin_convertvector(dv, b2v)));
                 } else st2(ob + 5 * OARR, hd);
             }
+            asm volatile("; DEP_REGION gate end");
         }
         if (grp < 2 && s == T + 1) break;
         FSTAMP(3);
@@ -457,61 +459,73 @@ __global__ __launch_bounds__(FTHREADS) void gru2_fwd_fused(FF p) {
             FSTAMP(6);
             // gather: h0_s (next layer-0 step; also layer 1's input when there is no dropout) and h1_{s-2} (next layer-1 step)
             const bool need0 = s < T, need2 = s >= 2;    // (h0_{T-1} is still layer 1's last input)
-            u32x4 v[2][2];
-            unsigned mk[2] = {0u, 0u};                    // DROP: the four mask bits of the piece's units (two bytes: pairs col0 / 2, col0 / 2 + 1)
-            for (unsigned spins = 0;; ++spins) {          // until no word is the sentinel
+            // Which blocks a step gathers is a compile-time property of the code that does it: the steady state (both) is one straight
+            // line from the loads to the LDS stores.  As run-time tests inside ONE spin loop, each iteration re-derived the two conditions
+            // on the VALU, and the pieces a fill / drain step leaves unloaded became values carried by the step loop -- sixteen registers
+            // copied in front of the spin loop and sixteen behind it, every step (tools/isa_regions.py).
+            auto gather = [&](auto N0, auto N2) -> bool {
+                constexpr bool n0 = decltype(N0)::value, n2 = decltype(N2)::value;
+                asm volatile("; DEP_REGION gather begin");
+                u32x4 v[2][2];
+                unsigned mk[2] = {0u, 0u};                // DROP: the four mask bits of the piece's units (two bytes: pairs col0 / 2, col0 / 2 + 1)
+                for (unsigned spins = 0;; ++spins) {      // until no word is the sentinel
 #pragma unroll
-            for (int rg = 0; rg < 2; ++rg) {
-                if (rg == 0 ? need0 : need2) {
+                    for (int rg = 0; rg < 2; ++rg) {
+                        if (rg == 0 ? n0 : n2) {
 #pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        v[rg][k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (pbase + (unsigned)(rg * 2) * F_REGION + (unsigned)(tv + 512 * k) * 4) * 4, 0, 16 /* sc1 */);
-                        if (DROP && rg == 0) {
+                            for (int k = 0; k < 2; ++k) {
+                                v[rg][k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (pbase + (unsigned)(rg * 2) * F_REGION + (unsigned)(tv + 512 * k) * 4) * 4, 0, 16 /* sc1 */);
+                                if (DROP && rg == 0) {
+                                    const int i4 = (tv + 512 * k) * 4;
+                                    mk[k] = (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsrc, (pbase + (unsigned)F_REGION) * 4 + (unsigned)((i4 >> 8) * (FH / 2) + ((i4 & (FH - 1)) >> 1)), 0, 16 /* sc1 */);
+                                }
+                            }
+                        }
+                    }
+                    unsigned mx = 0u;                     // max over the requested words: all-ones <=> one of them is still the sentinel
+                    if constexpr (n0) { mx = max(max(max(v[0][0].x, v[0][0].y), max(v[0][0].z, v[0][0].w)), max(max(v[0][1].x, v[0][1].y), max(v[0][1].z, v[0][1].w)));
+                                        if (DROP && ((mk[0] | mk[1]) & 0xfcfcu)) mx = FX_SENT; }
+                    if constexpr (n2) mx = max(mx, max(max(max(v[1][0].x, v[1][0].y), max(v[1][0].z, v[1][0].w)), max(max(v[1][1].x, v[1][1].y), max(v[1][1].z, v[1][1].w))));
+                    if (!__any(mx == FX_SENT)) break;
+                    if (spins > SPIN_LIMIT) { st_agent(p.status, 6); return false; }
+                    if ((spins & 63) == 63 && (ld_agent(p.status) != 0 || (p.soft && ld_agent(p.soft) != 0))) return false;
+                }
+                // The re-arm store of slot (s + 2) % 4 (issued with this step's publish) must be acknowledged before the member's NEXT publish is
+                // issued.  The gather loads' own wait already covers it on gfx9 (loads and stores share vmcnt), so this costs nothing; it is spelled
+                // out so that the protocol does not hang on the compiler's placement of that wait.
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+                for (int rg = 0; rg < 2; ++rg) {
+                    if (rg == 0 ? n0 : n2) {
+                        unsigned short* hi = rg == 0 ? hs0 : hs1;
+#pragma unroll
+                        for (int k = 0; k < 2; ++k) {
                             const int i4 = (tv + 512 * k) * 4;
-                            mk[k] = (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(rsrc, (pbase + (unsigned)F_REGION) * 4 + (unsigned)((i4 >> 8) * (FH / 2) + ((i4 & (FH - 1)) >> 1)), 0, 16 /* sc1 */);
+                            const int o = (i4 >> 8) * FLDHB + (i4 & (FH - 1));
+                            const u32x4 x = v[rg][k];
+                            uint2 hi2, lo2;
+                            // de-interleave the (hi << 16 | lo) words of two units into a hi pair and a lo pair: one byte permute each
+                            hi2.x = __builtin_amdgcn_perm(x.y, x.x, 0x07060302u); hi2.y = __builtin_amdgcn_perm(x.w, x.z, 0x07060302u);
+                            lo2.x = __builtin_amdgcn_perm(x.y, x.x, 0x05040100u); lo2.y = __builtin_amdgcn_perm(x.w, x.z, 0x05040100u);
+                            *reinterpret_cast<uint2*>(hi + o) = hi2; *reinterpret_cast<uint2*>(hi + FPLANE + o) = lo2;
+                            if (DROP && rg == 0) {
+                                // dropout(h0) for group 2: the same planes with the dropped units zeroed (the scale is applied to its sums).
+                                // A mask bit becomes 0 / ~0 by a signed one-bit extract; a permute joins the halves of two units' masks.
+                                const int w = (int)mk[k];
+                                const unsigned m01 = __builtin_amdgcn_perm((unsigned)__builtin_amdgcn_sbfe(w, 1, 1), (unsigned)__builtin_amdgcn_sbfe(w, 0, 1), 0x07060100u);
+                                const unsigned m23 = __builtin_amdgcn_perm((unsigned)__builtin_amdgcn_sbfe(w, 9, 1), (unsigned)__builtin_amdgcn_sbfe(w, 8, 1), 0x07060100u);
+                                uint2 dh, dl;
+                                dh.x = hi2.x & m01; dh.y = hi2.y & m23; dl.x = lo2.x & m01; dl.y = lo2.y & m23;
+                                *reinterpret_cast<uint2*>(hs0d + o) = dh; *reinterpret_cast<uint2*>(hs0d + FPLANE + o) = dl;
+                            }
                         }
                     }
                 }
-            }
-            {
-                unsigned mx = 0u;                         // max over the requested words: all-ones <=> one of them is still the sentinel
-                if (need0) { mx = max(max(max(v[0][0].x, v[0][0].y), max(v[0][0].z, v[0][0].w)), max(max(v[0][1].x, v[0][1].y), max(v[0][1].z, v[0][1].w)));
-                             if (DROP && ((mk[0] | mk[1]) & 0xfcfcu)) mx = FX_SENT; }
-                if (need2) mx = max(mx, max(max(max(v[1][0].x, v[1][0].y), max(v[1][0].z, v[1][0].w)), max(max(v[1][1].x, v[1][1].y), max(v[1][1].z, v[1][1].w))));
-                if (!__any(mx == FX_SENT)) break;
-                if (spins > SPIN_LIMIT) { st_agent(p.status, 6); return; }
-                if ((spins & 63) == 63 && (ld_agent(p.status) != 0 || (p.soft && ld_agent(p.soft) != 0))) return;
-            }
-            }
-            // The re-arm store of slot (s + 2) % 4 (issued with this step's publish) must be acknowledged before the member's NEXT publish is
-            // issued.  The gather loads' own wait already covers it on gfx9 (loads and stores share vmcnt), so this costs nothing; it is spelled
-            // out so that the protocol does not hang on the compiler's placement of that wait.
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int rg = 0; rg < 2; ++rg) {
-                if (rg == 0 ? need0 : need2) {
-                    unsigned short* hi = rg == 0 ? hs0 : hs1;
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const int i4 = (tv + 512 * k) * 4;
-                        const int o = (i4 >> 8) * FLDHB + (i4 & (FH - 1));
-                        const u32x4 x = v[rg][k];
-                        uint2 hi2, lo2;
-                        hi2.x = (x.x >> 16) | (x.y & 0xffff0000u); hi2.y = (x.z >> 16) | (x.w & 0xffff0000u);
-                        lo2.x = (x.x & 0xffffu) | (x.y << 16);      lo2.y = (x.z & 0xffffu) | (x.w << 16);
-                        *reinterpret_cast<uint2*>(hi + o) = hi2; *reinterpret_cast<uint2*>(hi + FPLANE + o) = lo2;
-                        if (DROP && rg == 0) {
-                            // dropout(h0) for group 2: the same planes with the dropped units zeroed (the scale is applied to its sums)
-                            const unsigned w = mk[k];
-                            const unsigned m01 = ((0u - (w & 1u)) & 0xffffu) | ((0u - ((w >> 1) & 1u)) & 0xffff0000u);
-                            const unsigned m23 = ((0u - ((w >> 8) & 1u)) & 0xffffu) | ((0u - ((w >> 9) & 1u)) & 0xffff0000u);
-                            uint2 dh, dl;
-                            dh.x = hi2.x & m01; dh.y = hi2.y & m23; dl.x = lo2.x & m01; dl.y = lo2.y & m23;
-                            *reinterpret_cast<uint2*>(hs0d + o) = dh; *reinterpret_cast<uint2*>(hs0d + FPLANE + o) = dl;
-                        }
-                    }
-                }
-            }
+                asm volatile("; DEP_REGION gather end");
+                return true;
+            };
+            const std::true_type yes{}; const std::false_type no{};
+            if (!(need0 ? (need2 ? gather(yes, yes) : gather(yes, no)) : (need2 ? gather(no, yes) : gather(no, no)))) return;
         }
         FSTAMP(7);
         bar_lds();                                        // groups 0/1: #3 (planes of step s+1 complete) | group 2: #1 of step s+1

@@ -275,6 +275,7 @@ __global__ __launch_bounds__(BTHREADS) void gru2_bwd_fused(FB p) {
         BSTMP(0);
         // ---- gate gradients (groups 0 and 2; identical code, role-dependent LDS bases), published at once
         if (act) {
+            asm volatile("; DEP_REGION gategrad begin");      // region markers: comments in the -S output (tools/isa_regions.py)
             constexpr int GA = gate_arr(SV16);
             const float* il = ibuf + (v % ISL) * IPAR + (grp == 0 ? 0 : iarr_off(HASDY ? 6 : 5, SV16, HASDY, BF));      // this layer's arrays: r, z, n | hn, hp, [dy]
             float2 r, z, n;
@@ -333,6 +334,7 @@ __global__ __launch_bounds__(BTHREADS) void gru2_bwd_fused(FB p) {
                 st2(da, f2(a0.x + dr.x, a0.y + dr.y)); st2(da + IARR, f2(a1.x + dz.x, a1.y + dz.y));
                 st2(da + 2 * IARR, f2(a2.x + dn.x, a2.y + dn.y)); st2(da + 3 * IARR, f2(a3.x + dnr.x, a3.y + dnr.y));
             }
+            asm volatile("; DEP_REGION gategrad end");
         }
         if (v == T + 1) { bar_lds(); break; }             // layer 0's last step (t = 0): nothing left to exchange
         BSTMP(1);
