@@ -182,6 +182,8 @@ struct Layout {
     bool cluster;                    // cluster-parallel sweeps (rnn_cluster*.hip): the workspace has their exchange buffer
     bool cluster_fwd;                // impl 6: the FORWARD alone runs on the cluster (a bidirectional GRU); the workspace has its exchange buffer, and
                                      // nothing else of `cluster` holds: the backward, its weight images, bias partials and gate gradients are the tile sweeps'
+    bool cluster_bwd2;               // impl 7: ... and the BACKWARD too, on the bidirectional instances of gru_bwd_cluster_r1: the exchange buffer covers its
+                                     // payload, the bias partials are one row per (direction, tile), wpT holds the cluster backward's images
     bool fused2;                     // 2-layer GRU, H = 256: both layers in one launch (rnn_fused2*.hip) where the call's plan allows it
     size_t wih_img;                  // workspace: packed W_ih of layer 1 for the fused launches
     size_t hxstage;                  // workspace (impl 4 / 5 / 6 only): dirs x B x H floats, a layer's hx copied aside when T = 1 and h_n overlaps it
@@ -193,7 +195,7 @@ bool bigru_ok(const dep_rnn_desc* d) { return (d->impl == 0 || d->impl == 2) && 
 
 // dep_last_error for a descriptor refused by the rule above (the entry points and the size queries; DEP_OK for any other descriptor)
 int bigru_refusal(const dep_rnn_desc* d, const char* who) {
-    if (!d || d->cell != DEP_CELL_GRU || d->dirs != 2 || d->H <= 0 || d->impl == 6 || bigru_ok(d)) return DEP_OK;      // (impl 6: bicluster_refusal)
+    if (!d || d->cell != DEP_CELL_GRU || d->dirs != 2 || d->H <= 0 || d->impl == 6 || d->impl == 7 || bigru_ok(d)) return DEP_OK;      // (impl 6 / 7: bicluster_refusal)
     dep_set_error("%s: a bidirectional GRU (dirs = 2) runs the tile-MFMA sweeps only: impl must be 0 or 2 and H a multiple of 16 those sweeps can "
                   "tile (H / 16 = waves x tiles per wave, waves in {1, 2, 4, 8}, tiles <= 4, within the LDS bound: 16 .. 64, 96, 128, 192, 256); got H = %d, impl = %d", who, d->H, d->impl);
     return DEP_ERR_ARG;
@@ -216,14 +218,19 @@ int percluster_refusal(const dep_rnn_desc* d, const char* who) {
 // impl = 6, "the per-layer cluster forward of a bidirectional GRU": gru_fwd_cluster_r1<.., BI = true> runs every forward, both directions
 // of a layer in one launch; the backward is the tile-MFMA BiGRU's (gru_bwd_mfma<.., true>) on the reserve that forward leaves -- the same
 // four fp32 (B,T,2H) saved-gate arrays.  H = 512 has the forward only: the tile sweeps stop at 256, dep_rnn_backward refuses it.
-bool bicluster_impl(const dep_rnn_desc* d) { return d->impl == 6; }
+// impl = 7, "the per-layer cluster sweeps of a bidirectional GRU, forward and backward": impl = 6 in every forward (launches, outputs, reserve
+// layout, bit for bit); a DEP_RUN_TRAIN forward packs the cluster backward's image of each direction into wpT, and the backward runs ONE launch
+// per layer of gru_bwd_cluster_r1<.., BI = true>, both directions of a batch chunk side by side, at all four H.  The sweep writes the fp32
+// gate-gradient rows of the tile BiGRU backward, so everything behind it is the code impl 2 / 6 run.
+bool bicluster_impl(const dep_rnn_desc* d) { return d->impl == 6 || d->impl == 7; }
+bool bicluster_train_impl(const dep_rnn_desc* d) { return d->impl == 7; }
 bool bicluster_ok(const dep_rnn_desc* d) { return d->cell == DEP_CELL_GRU && d->dirs == 2 && dep_cluster_ok(d->cell, d->H, d->B, d->dirs); }
 
-// dep_last_error for an impl = 6 descriptor refused by the rule above (DEP_OK for any other descriptor)
+// dep_last_error for an impl = 6 / 7 descriptor refused by the rule above (DEP_OK for any other descriptor)
 int bicluster_refusal(const dep_rnn_desc* d, const char* who) {
     if (!d || !bicluster_impl(d) || d->H <= 0 || bicluster_ok(d)) return DEP_OK;
-    dep_set_error("%s: impl = 6 (the per-layer cluster forward of a bidirectional GRU) is a bidirectional GRU with H in {64, 128, 256, 512}: cell must be "
-                  "DEP_CELL_GRU and dirs 2; got cell = %d, H = %d, dirs = %d", who, d->cell, d->H, d->dirs);
+    dep_set_error("%s: impl = %d (the per-layer cluster %s of a bidirectional GRU) is a bidirectional GRU with H in {64, 128, 256, 512}: cell must be "
+                  "DEP_CELL_GRU and dirs 2; got cell = %d, H = %d, dirs = %d", who, d->impl, d->impl == 7 ? "sweeps, forward and backward," : "forward", d->cell, d->H, d->dirs);
     return DEP_ERR_ARG;
 }
 
@@ -278,6 +285,8 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     // rows of bias-gradient partials: one per 16-utterance tile for the tile-MFMA and the cluster sweeps, one per utterance for
     // the generic sweep.  (Sized for the larger; dep_finish_db sums the rows the sweep that ran has written: dbpart_rows.)
     lo.nwg = dep_sweep_num_wg(d->B, d->H, d->impl);
+    lo.cluster_bwd2 = bicluster_train_impl(d);
+    if (lo.cluster_bwd2) lo.nwg = dep_cdiv(d->B, 16);      // the bidirectional cluster backward: one row per (direction, tile) at every H
     size_t w = 0;
     lo.gi = w; w += al(lo.BT * D * (G + (d->cell == DEP_CELL_GRU && lo.keep ? 1 : 0)) * H);     // GI (fwd) / dGI (bwd; GRU: room for the 4H-wide [dr|dz|dn|dn*r] rows)
     lo.dghn = w; w += al(lo.BT * (d->cell == DEP_CELL_GRU ? D : 1) * H);      // GRU: (B,T,dirs*H)
@@ -316,7 +325,9 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     lo.cluster = cok && (d->impl == 0 || d->impl == 3 || percluster_impl(d));
     // impl 6 (checked above): the bidirectional forward's exchange buffer and the hx staging area, and none of what `cluster` selects
     lo.cluster_fwd = bicluster_impl(d);
-    lo.xbuf = w; lo.xbuf_bytes = lo.cluster_fwd ? dep_cluster_xbuf_bytes(d->cell, d->H, d->B, d->dirs)
+    // impl 7: the larger of the bidirectional forward's buffer and the bidirectional backward's
+    const size_t bixb = !lo.cluster_bwd2 ? 0 : dep_cluster_bwd_bi_xbuf_bytes(d->H, d->B);
+    lo.xbuf = w; lo.xbuf_bytes = lo.cluster_fwd ? (bixb > dep_cluster_xbuf_bytes(d->cell, d->H, d->B, d->dirs) ? bixb : dep_cluster_xbuf_bytes(d->cell, d->H, d->B, d->dirs))
                                : !lo.cluster ? 0 : (d->cell == DEP_CELL_GRU ? dep_cluster_xbuf_bytes(d->cell, d->H, d->B, d->dirs)
                                                                 : dep_cluster_lstm_xbuf_bytes(d->H, d->B, d->dirs));
     if (lo.cluster) lo.nwg = dep_cdiv(d->B, 16);      // the cluster sweeps write one row per tile whatever the tile-MFMA sweep could do at this H
@@ -455,6 +466,10 @@ struct RnnPlan {
 // impl = 6 (lo.cluster_fwd): FWD_CLUSTER_GRU on the bidirectional instance, dense or ragged, with each direction's 32-unit-member image (split
 // products) or the fp32 fragment image (exact mode), fp32 saved gates; everything of the backward is the tile BiGRU's of impl = 2 -- BWD_TILE on
 // the wpT image of dep_pack_whh, packed by a DEP_RUN_TRAIN forward in either mode -- because lo.cluster is off.
+// impl = 7 (lo.cluster_bwd2): impl = 6's forward; BWD_CLUSTER_GRU on the bidirectional instances, dense or ragged, on each direction's cluster
+// backward image in wpT (WHH_BWD_SPLIT in split mode, the member-sliced fp32 image in exact mode) instead of the tile backward's; fp32 saved
+// gates, fp32 gate-gradient rows (pk = false: dg4 is off), the unpaired contractions.  Modes 2 / 3 keep the split instance; the contractions
+// behind the sweep follow the mode on their own (a mode-3 backward is refused by dep_rnn_backward: no PK image to take the hi rows of).
 RnnPlan make_plan(const dep_rnn_desc* d, const Layout& lo, int mode, bool excl, bool ragged) {
     const RnnSwitches& sw = dep_rnn_switches();
     const bool gru = d->cell == DEP_CELL_GRU;
@@ -466,10 +481,10 @@ RnnPlan make_plan(const dep_rnn_desc* d, const Layout& lo, int mode, bool excl, 
     p.fwd = (lo.fused2 && p.split && excl && !ragged) ? FWD_FUSED2 : (cluster16 && excl && !ragged) ? FWD_CLUSTER16
           : lo.cluster_fwd ? FWD_CLUSTER_GRU : !lo.cluster ? FWD_TILE : gru ? FWD_CLUSTER_GRU : FWD_CLUSTER_LSTM;
     p.bwd = (lo.fused2 && sw.fused2_bwd && p.split && dep_fused2_bwd_fits(d->B, d->T) && !ragged) ? BWD_FUSED2
-          : !lo.cluster ? BWD_TILE : gru ? BWD_CLUSTER_GRU : BWD_CLUSTER_LSTM;
-    p.whh_f32 = lo.cluster ? !p.split : lo.cluster_fwd ? (!p.split || lo.keep) : dep_sweep_use_mfma(d->H, d->impl);
+          : lo.cluster_bwd2 ? BWD_CLUSTER_GRU : !lo.cluster ? BWD_TILE : gru ? BWD_CLUSTER_GRU : BWD_CLUSTER_LSTM;
+    p.whh_f32 = lo.cluster ? !p.split : lo.cluster_fwd ? (!p.split || (lo.keep && !lo.cluster_bwd2)) : dep_sweep_use_mfma(d->H, d->impl);
     p.whh_fwd = !csplit ? WHH_NONE : !gru ? WHH_LSTM_PAIR : p.fwd == FWD_CLUSTER16 ? WHH_SPLIT16 : WHH_SPLIT32;
-    p.whh_bwd = (!lo.cluster || !lo.keep || p.whh_fwd == WHH_LSTM_PAIR) ? WHH_NONE : p.split ? WHH_BWD_SPLIT : WHH_BWD_F32;
+    p.whh_bwd = (!(lo.cluster || lo.cluster_bwd2) || !lo.keep || p.whh_fwd == WHH_LSTM_PAIR) ? WHH_NONE : p.split ? WHH_BWD_SPLIT : WHH_BWD_F32;
     // 16-bit saved gates: the kernels that implement them are the fused forward, the 32-unit-member forward and the 32-unit-member
     // backward (burst or not); the 16-unit-member kernels and exact-fp32 mode read / write fp32 gates.  Follows the DESCRIPTOR's
     // cluster16, not whether this call may run that kernel.  An INSTANCE choice: a dropout-only forward launches the instance
@@ -545,6 +560,11 @@ int ragged_mode_refusal(const char* who, const int32_t* lengths, int mode) {
 // the cell state belongs to the LSTM.  Checked before anything is launched (and before any HIP call); DEP_OK for a call without state.
 int state_refusal(const dep_rnn_desc* d, const Layout& lo, const char* who, bool any, bool any_c, bool backward, int mode) {
     if (!any) return DEP_OK;
+    if (any_c && bicluster_train_impl(d)) {
+        dep_set_error("%s: impl = 7 (the per-layer cluster sweeps of a bidirectional GRU) takes hx / dhx only: cx, c_n, dc_n and dcx are the LSTM's cell state "
+                      "and its gradients", who);
+        return DEP_ERR_ARG;
+    }
     if (any_c && d->cell != DEP_CELL_LSTM) {
         dep_set_error("%s: cx, c_n, dc_n and dcx are the LSTM's cell state and its gradients; a GRU takes hx / dhx only", who);
         return DEP_ERR_ARG;
@@ -806,7 +826,12 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
     Layout lo;
     if (const int rf = percluster_refusal(d, "dep_rnn_backward")) return rf;
     if (const int rf = bicluster_refusal(d, "dep_rnn_backward")) return rf;
-    if (d && bicluster_impl(d) && !dep_sweep_use_mfma(d->H, d->impl)) {
+    if (d && bicluster_train_impl(d) && dep_get_gemm_mode() == 3 && bicluster_ok(d)) {
+        dep_set_error("dep_rnn_backward: impl = 7 (the per-layer cluster sweeps of a bidirectional GRU) has no backward in GEMM mode 3: the bidirectional "
+                      "sweep writes fp32 gate-gradient rows, not the PK image whose hi rows that mode reads; modes 0, 1 and 2 run (dep_set_gemm_mode)");
+        return DEP_ERR_ARG;
+    }
+    if (d && d->impl == 6 && !dep_sweep_use_mfma(d->H, d->impl)) {
         dep_set_error("dep_rnn_backward: impl = 6 runs the tile-MFMA backward of the bidirectional GRU, which tiles H up to 256; H = %d has the forward only", d->H);
         return DEP_ERR_ARG;
     }
@@ -821,6 +846,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
     DEP_CHECK_ARG(!st.hx || lengths || (long)d->T * d->dirs * (d->cell == DEP_CELL_GRU ? 3 : 4) * d->H <= 0x7fffffffL);
     // (the cluster sweeps' rows are 4H wide; the recurrent term of dhx reads the t = 0 rows the same way, dense or ragged)
     DEP_CHECK_ARG(!(has_state && lo.cluster) || (long)d->T * 4 * d->H <= 0x7fffffffL);
+    DEP_CHECK_ARG(!(has_state && lo.cluster_bwd2) || (long)d->T * 6 * d->H <= 0x7fffffffL);      // (impl 7: the tile BiGRU's 6H-wide rows)
     if (const int rf = ragged_mode_refusal("dep_rnn_backward_varlen", lengths, mode)) return rf;
     const RnnPlan p = make_plan(d, lo, mode, dep_exclusive_on(), lengths != nullptr);
     if (d->training != DEP_RUN_TRAIN) {
@@ -837,7 +863,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
         return DEP_ERR_WORKSPACE;
     }
     // the cluster kernels must match the images and saved gates dep_rnn_forward left
-    if (lo.cluster) { rc = reserve_tag_refusal(reserve, p.tag, TAG_SPLIT | TAG_BF16ST | TAG_SV16); if (rc) return rc; }
+    if (lo.cluster || lo.cluster_bwd2) { rc = reserve_tag_refusal(reserve, p.tag, TAG_SPLIT | TAG_BF16ST | TAG_SV16); if (rc) return rc; }
     hipStream_t s = (hipStream_t)stream;
     float* R = (float*)reserve; float* W = (float*)workspace;
     const int B = d->B, T = d->T, H = d->H, D = d->dirs, G = lo.G, L = d->L;
@@ -897,7 +923,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
         const bool second = fused && l == 0;                  // (the fused launch left both layers' gate gradients behind)
         dep_sweep_bwd_args a{};
         a.B = B; a.T = T; a.H = H; a.cell = d->cell; a.dirs = D; a.impl = d->impl;
-        a.split = (lo.cluster && p.split) ? 1 : 0;
+        a.split = ((lo.cluster || lo.cluster_bwd2) && p.split) ? 1 : 0;
         for (int dd = 0; dd < D; ++dd) {
             const float* const* wl = weights + (size_t)(l * D + dd) * 4;
             a.w_hh[dd] = wl[1]; a.wpT[dd] = R + lo.wpT[l][dd];
@@ -928,7 +954,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
         return a;
     };
     float* pending_ptr = nullptr; long pending_n = 0;      // data parallel: a finished layer's gradient range waiting for the next sweep to be enqueued
-    if (lo.cluster && !fused) { rc = dep_cluster_reset_flags(W + lo.xbuf, s); if (rc) return rc; }      // every layer's header slot in one memset (the status words stay)
+    if ((lo.cluster || lo.cluster_bwd2) && !fused) { rc = dep_cluster_reset_flags(W + lo.xbuf, s); if (rc) return rc; }      // every layer's header slot in one memset (the status words stay)
     for (int l = L - 1; l >= 0; --l) {
         const LayerIn lin = layer_input(d, lo, x, R, l);
         const float* const in = lin.p; const int Kl = lin.K;
@@ -1074,7 +1100,22 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
                 }
             }
         }
-        if (a.dhx && p.bwd == BWD_CLUSTER_GRU) {
+        if (a.dhx && p.bwd == BWD_CLUSTER_GRU && lo.cluster_bwd2) {
+            // impl 7: the same two products per direction on the tile BiGRU's rows -- direction dd's [dr | dz] in columns [3 dd H, 3 dd H + 2H) of
+            // dgi, its dn*r in columns [dd H, (dd+1) H) of dghn -- at the sweep's LAST step, t = 0 or (direction 1) T-1.  A ragged row whose last
+            // sweep steps of direction 1 were dead has exact zeros there, and its stored dhx already holds the recurrent term (gathered in-kernel
+            // at its first dead step), so one strided product serves dense and ragged.
+            DepGemmOpts xo; xo.scratch = gws; xo.scratch_bytes = gwsb;
+            for (int dd = 0; dd < D; ++dd) {
+                const float* whh = weights[(size_t)(l * D + dd) * 4 + 1];
+                const size_t tl = dd == 0 ? 0 : (size_t)T - 1;
+                float* dhxd = a.dhx + (size_t)dd * B * H;
+                rc = dep_gemm_internal(0, 0, B, H, 2 * H, dgi + (size_t)dd * G * H + tl * ldg, T * ldg, whh, H, dhxd, H, nullptr, 1.f, 0, 0, nullptr, 0, xo, s);
+                if (rc) return rc;
+                rc = dep_gemm_internal(0, 0, B, H, H, dghn + (size_t)dd * H + tl * D * H, T * D * H, whh + (size_t)2 * H * H, H, dhxd, H, nullptr, 1.f, 0, 0, nullptr, 0, xo, s);
+                if (rc) return rc;
+            }
+        } else if (a.dhx && p.bwd == BWD_CLUSTER_GRU) {
             // The recurrent term of dhx: the sweep stored the direct term d_0 * z_0 (a dead ragged row: its dh_n); the other one,
             // dG[:, 0, :] W_hh, is a (B x 3H x H) product behind the sweep on the same stream: A = the t = 0 rows (row stride T * ld) of
             // [dr | dz] and of dn*r, added with beta = 1.  The sweep is unidirectional, so t0 = 0 for dense and ragged alike; a dead row's

@@ -209,7 +209,7 @@ int dep_launch_sweep_fwd(const dep_sweep_args& a);
 
 struct dep_sweep_bwd_args {
     int B, T, H;
-    int cell, dirs;
+    int cell, dirs;          // dirs = 2: both directions in one launch (GRU: the tile-MFMA sweeps of rnn_sweep.hip, and dep_launch_cluster_bwd for impl 7)
     int impl;
     const float* w_hh[2];
     const float* wpT[2];     // packed transposed copies (MFMA path)
@@ -219,7 +219,7 @@ struct dep_sweep_bwd_args {
     float drop_p; uint64_t seed; uint32_t site;   // dropout applied to dy on load (p == 0: none)
     const float* dpooled; float pool_scale;       // GRU top layer (B,dirs*H) or NULL
     const float* dh_n;       // (dirs,B,H) or NULL
-    // state of this layer (dep_rnn_backward_state[_varlen]; rnn_sweep.hip only): what the forward started from, and the state gradients
+    // state of this layer (dep_rnn_backward_state[_varlen]; rnn_sweep.hip, and hx / dhx on dep_launch_cluster_bwd for impl 5 / 7): what the forward started from, and the state gradients
     const float* hx; const float* cx;     // (dirs,B,H) the forward's initial h / c (LSTM), or NULL = zeros
     const float* dc_n;       // LSTM: (dirs,B,H) grad of c_n, enters where dh_n enters, or NULL
     float* dhx; float* dcx;  // (dirs,B,H) grad of hx / cx (LSTM), WRITTEN, or NULL
@@ -258,6 +258,7 @@ int dep_state_dwhh_ragged(const float* dg, int lddg, const int* lengths, int B, 
 // cluster-parallel sweeps (rnn_cluster.hip)
 bool dep_cluster_ok(int cell, int H, int B, int dirs);
 size_t dep_cluster_xbuf_bytes(int cell, int H, int B, int dirs);
+size_t dep_cluster_bwd_bi_xbuf_bytes(int H, int B);      // rnn_cluster_bwd.hip: headers + the bidirectional backward's payload (impl 7; dirs = 2 above is the forward's alone)
 int dep_pack_cluster_bwd(const float* w_hh, float* out, int G, int H, hipStream_t s);
 int dep_launch_cluster_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf_bytes);
 int dep_launch_cluster_bwd(const dep_sweep_bwd_args& a, void* xbuf, size_t xbuf_bytes);

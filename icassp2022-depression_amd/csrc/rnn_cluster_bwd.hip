@@ -42,6 +42,10 @@ struct P2 {
     // dh_n's buffer: the same thread read that address in front of the loop.  Neither touches the exchange, a flag or a trip count.
     const float* hx; float* dhx;
 };
+// The parameters of the bidirectional instances (BI, impl 7), as F2B is the forward's: direction 1's backward weight image, the row stride
+// of the saved gates (2H) and the bias-partial rows per direction (ceil(B / 16): direction d's rows follow direction d-1's).  A struct of
+// their own, so that the unidirectional instances keep their kernel arguments and with them their ISA.
+struct P2B : P2 { const f32x4* wp1; int ldsv; int nbt; };
 
 struct StepIn { float2 r, z, n, hn, hp, dy; };
 
@@ -87,23 +91,41 @@ constexpr size_t burst_lds_bytes_ag(int KB) { return (size_t)(AG_IBUF_F + KB * 6
 // handful of selects in the gate phase: a dead step's gate gradients are 0 (what the members exchange, the write-out and the bias sums
 // see) and its incoming dh passes through to step t-1 unchanged.  Trip counts, epochs, flags, the service waves and the burst write-out
 // are those of the dense instances: every workgroup runs all T steps.
-template <int NTW, bool SPLIT, int KB, bool SV16 = false, bool BF = false, bool AG = false, bool RAG = false>      // output tiles per wave = H/64
-__global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1(P2 p) {
+// BI: the bidirectional instances (impl 7), the geometry of gru_fwd_cluster_r1<.., BI = true>.  A cluster is a (direction, tile) PAIR, both
+// directions of a batch chunk in one launch: block = (c * 2 + dir) * nbtp + bt, and the pair dir * nbtp + bt indexes the flag words, the
+// hello words, the payload and the all-gather blocks.  The loop counter t counts the sweep DOWN in both directions (sweep step k = T-1-t:
+// epochs, payload parity, ring slots, the dirty-step phase and the last-step test t == 0 follow it); the TIME of the step is tm = t for
+// direction 0 and T-1-t for direction 1, whose h_prev is y[b, tm+1] (the last sweep step: its hx slice, or zeros; a ragged row's first
+// live step tm = len-1 likewise: the position behind it holds 0, not the state the forward carried through the dead steps).  Every array
+// is the tile BiGRU's: y, dy, the fp32 saved gates (ldsv) and the dropout index over (B,T,2H) with the direction in columns, dpooled
+// (B,2H), dh_n / hx / dhx (2,B,H), dgi (B T, 6H) and dghn (B T, 2H) as gru_bwd_mfma<.., true> writes them, bias partials [dir][tile].  A
+// ragged row's direction-1 dead steps come LAST: their gate gradients are 0 and dh passes through, so what is stored as dhx then already
+// holds the recurrent term.  Trip counts, epochs, flags and barriers do not know the direction.  BI = false is the unidirectional text.
+template <int NTW, bool SPLIT, int KB, bool SV16 = false, bool BF = false, bool AG = false, bool RAG = false, bool BI = false>      // output tiles per wave = H/64
+__global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1(std::conditional_t<BI, P2B, P2> p) {
     static_assert(!BF || (SV16 && KB > 0), "bf16 storage: 16-bit gates, burst kernel");
+    static_assert(!BI || (!SV16 && !BF), "bidirectional: fp32 saved gates and storage");
     static_assert(!AG || (SPLIT && KB == 4 && NTW == 4), "all-gather exchange: H = 256, split products, burst length 4");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int KS = 96, KCB = KS / 16, LDG = KS + LPAD;
     constexpr int LDGB = KS + 8;                      // bf16 elements per row of a split plane (208-byte rows)
     const int H = p.H, T = p.T, NC = H / 32, NTT = H / 16;
-    const int c = blockIdx.x / p.nbtp, bt = blockIdx.x % p.nbtp;
+    const int c = BI ? blockIdx.x / (2 * p.nbtp) : blockIdx.x / p.nbtp, bt = blockIdx.x % p.nbtp;
+    const int dir = BI ? (int)(blockIdx.x / p.nbtp) & 1 : 0;
+    const int pt = BI ? dir * p.nbtp + bt : bt;      // the cluster's (direction, tile) pair: flags, hello words, payload
     if (p.b0 + bt * BT >= p.B) return;
     if (ld_agent(p.status) != 0) return;           // an earlier sweep of this step gave up: the status word is sticky until the next dep_rnn_forward
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int jl = tid >> 7, lp = (tid >> 1) & 63, half = tid & 1;
     const int j = lp & 15, ul = jl * 16 + (lp >> 4) * 4 + 2 * half;      // unit inside the member's 32
     const int col = 32 * c + ul;
+    const int dcol = BI ? dir * H + col : col;      // the column in the direction-interleaved rows of y, dy, the saved gates and dpooled
     const int b = p.b0 + bt * BT + j;
     const bool valid = b < p.B;
+    // this thread's pair in the (dirs,B,H) state arrays dh_n, hx, dhx (formed where it is used, as the unidirectional text forms it)
+    const auto sat = [&](auto* q) { if constexpr (BI) return q + ((size_t)dir * p.B + b) * H + col; else return q + (size_t)b * H + col; };
+    int ldsv = H;                                    // row stride of the saved gates
+    if constexpr (BI) ldsv = p.ldsv;
     float* dgs = smem;                                                     // [16][LDG] fp32, or (SPLIT) two bf16 planes [16][LDGB]
     unsigned short* dg_hi = reinterpret_cast<unsigned short*>(smem);
     unsigned short* dg_lo = dg_hi + BT * LDGB;
@@ -118,10 +140,12 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
     u32x4 wq[SPLIT ? NTW : 1][SPLIT ? 3 : 1][2];       // [tile][k-step = gate][hi, lo]   (AG: unused, wa below)
     u32x4 wa[AG ? 2 : 1][AG ? 6 : 1][2];               // AG: [own output tile][k-step = (source member 2w + ks/3, gate ks%3)][hi, lo]
     if (!svc) {
+        // the direction's own backward image
+        const auto wsel = [&]() -> const f32x4* { if constexpr (BI) return dir ? p.wp1 : p.wp; else return p.wp; };
         if constexpr (AG) {
             // the SAME packed image as the reduce-scatter kernel's ([K member][output tile][gate][plane][lane]); this member takes the
             // two output tiles of its own 32 columns and, per wave, the K rows of source members 2w, 2w+1
-            const u32x4* wpq = reinterpret_cast<const u32x4*>(p.wp);
+            const u32x4* wpq = reinterpret_cast<const u32x4*>(wsel());
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -130,7 +154,7 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
                     for (int pl = 0; pl < 2; ++pl)
                         wa[i][ks][pl] = wpq[(size_t)((((2 * w + ks / 3) * NTT + 2 * c + i) * 3 + ks % 3) * 2 + pl) * 64 + lane];
         } else if constexpr (SPLIT) {
-            const u32x4* wpq = reinterpret_cast<const u32x4*>(p.wp);
+            const u32x4* wpq = reinterpret_cast<const u32x4*>(wsel());
 #pragma unroll
             for (int i = 0; i < NTW; ++i)
 #pragma unroll
@@ -143,26 +167,31 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
             for (int i = 0; i < NTW; ++i)
 #pragma unroll
                 for (int k = 0; k < KCB; ++k)
-                    wr[i][k] = p.wp[(size_t)((c * NTT + w * NTW + i) * KCB + k) * 64 + lane];
+                    if constexpr (BI) wr[i][k] = wsel()[(size_t)((c * NTT + w * NTW + i) * KCB + k) * 64 + lane];
+                    else wr[i][k] = p.wp[(size_t)((c * NTT + w * NTW + i) * KCB + k) * 64 + lane];
         }
     }
-    float2 dhrec = (p.dh_n && valid && !svc) ? ld2(p.dh_n + (size_t)b * H + col) : f2(0.f, 0.f);
+    float2 dhrec = (p.dh_n && valid && !svc) ? ld2(sat(p.dh_n)) : f2(0.f, 0.f);
     float2 dpl = f2(0.f, 0.f);
     int len = T;
     if constexpr (RAG) len = (valid && !svc) ? dep_row_len(p.lengths, b, T) : 0;
     const float dps = RAG ? dep_ragged_pool_scale(p.pool_mean, len, T, p.pool_scale) : p.pool_scale;
-    if (p.dpooled && valid && !svc) { dpl = ld2(p.dpooled + (size_t)b * H + col); dpl.x *= dps; dpl.y *= dps; }
+    if (p.dpooled && valid && !svc) {
+        if constexpr (BI) dpl = ld2(p.dpooled + (size_t)b * 2 * H + dcol);      // (B,2H)
+        else dpl = ld2(p.dpooled + (size_t)b * H + col);
+        dpl.x *= dps; dpl.y *= dps;
+    }
     float2 dbr = f2(0.f, 0.f), dbz = dbr, dbn = dbr, dbh = dbr;
-    const size_t pstride = (size_t)p.nbtp * NC * BT * H;                   // floats per parity buffer
-    const size_t tile_base = (size_t)bt * NC * BT * H;                     // this tile's [NC][NTT][64][4] block
+    const size_t pstride = (size_t)(BI ? 2 * p.nbtp : p.nbtp) * NC * BT * H;      // floats per parity buffer
+    const size_t tile_base = (size_t)pt * NC * BT * H;                     // this tile's [NC][NTT][64][4] block
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.payload, 0, p.payload_bytes, 0x00020000);
     // per-wave flags: every compute wave raises its OWN epoch flag once its own payload stores are acknowledged (no workgroup barrier
     // in front of the flag); the pollers watch all 4 NC words of the tile
-    unsigned* tflags = p.flags + bt * NC * 4;
+    unsigned* tflags = p.flags + pt * NC * 4;
     unsigned* myflag = tflags + c * 4 + (w & 3);
     const int nflags = NC * 4;
     const int ml = lane & 15, mq = lane >> 4;
-    const int sx = p.nofast ? 0 : cluster_same_xcd(p.hello + bt * NC, NC, c, p.status);
+    const int sx = p.nofast ? 0 : cluster_same_xcd(p.hello + pt * NC, NC, c, p.status);
     if (sx < 0) return;
     const bool fast = sx == 1;
 
@@ -170,16 +199,22 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
         s.r = s.z = s.n = s.hn = s.hp = s.dy = f2(0.f, 0.f);
         if (valid && t >= 0) {
             const size_t row = (size_t)b * T + t;
-            const size_t so = row * H + col;
+            const size_t so = BI ? row * ldsv + dcol : row * H + col;
             if constexpr (SV16) {
                 s.r = unpack_unorm2(*reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned short*>(p.sv0) + so));
                 s.z = unpack_unorm2(*reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned short*>(p.sv1) + so));
                 s.n = unpack_snorm2(*reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned short*>(p.sv2) + so));
             } else { s.r = ld2(p.sv0 + so); s.z = ld2(p.sv1 + so); s.n = ld2(p.sv2 + so); }
             s.hn = ld2(p.sv3 + so);
-            if (t > 0) s.hp = ld2(p.y + (row - 1) * p.ldy + col);
-            else if (p.hx) s.hp = ld2(p.hx + (size_t)b * H + col);
-            if (p.dy) s.dy = ld2(p.dy + row * p.lddy + col);
+            if constexpr (BI) {       // (the sweep's last step, and a ragged row's first live step in direction 1: the state, not a neighbour)
+                const bool inner = dir ? (t < T - 1 && !(RAG && t == len - 1)) : t > 0;
+                if (inner) s.hp = ld2(p.y + (dir ? row + 1 : row - 1) * p.ldy + dcol);
+                else if (p.hx) s.hp = ld2(sat(p.hx));
+            } else {
+                if (t > 0) s.hp = ld2(p.y + (row - 1) * p.ldy + col);
+                else if (p.hx) s.hp = ld2(p.hx + (size_t)b * H + col);
+            }
+            if (p.dy) s.dy = ld2(p.dy + row * p.lddy + dcol);
         }
     };
     // dhx at t == 0: the direct term d * z of this thread's two columns (a ragged row that never was live: the dh_n it loaded).  The
@@ -189,16 +224,19 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
     auto store_dhx = [&](float2 d, float2 z) {
         asm volatile("" : "+v"(z.x), "+v"(z.y));
         const float2 v = f2(d.x * z.x, d.y * z.y);
-        st2(p.dhx + (size_t)b * H + col, RAG ? dep_sel2(0 < len, v, dhrec) : v);
+        st2(sat(p.dhx), RAG ? dep_sel2(((BI && dir) ? T - 1 : 0) < len, v, dhrec) : v);
     };
     StepIn cur, nxt;
-    if constexpr (!BURST) load_step(T - 1, cur);
+    if constexpr (!BURST) load_step((BI && dir) ? 0 : T - 1, cur);
     // ---- service waves.  Step counter k = T-1-t.  Service thread st: piece idx = st + 256 i (i < 3) of a step's 768 input
     // pieces -> array idx / 128, utterance row (idx % 128) / 8, 16-byte piece idx % 8; likewise 512 write-out pieces (i < 2).
     const int st = tid - CT, sarr0 = (st >> 7) & 1, sr = (st >> 3) & 15, sp = st & 7;
     const int sb = p.b0 + bt * BT + sr;
     const bool svalid = sb < p.B;
     const int scol = 32 * c + sp * 4;
+    const int sdcol = BI ? dir * H + scol : scol;     // ... in the direction-interleaved rows
+    int slen = T;                                     // BI, ragged: the service thread's own row (h_prev of its first live step in direction 1)
+    if constexpr (BI && RAG) slen = (svc && svalid) ? dep_row_len(p.lengths, sb, T) : 0;
     const int phi = (bt >> 3) % KBX;                  // the tiles of an XCD (bt = xcd mod 8) take their dirty steps in turn
     f32x4 sreg[KBX][3];
     // wave-uniform array choice (waves 4, 5: arrays 0, 2, 4 = r, n, h_{t-1}; waves 6, 7: 1, 3, 5 = z, hn, dy), made scalar so
@@ -226,15 +264,17 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, (unsigned)((const char*)q - (const char*)base), 0, 2 /* nt */);
     };
     // ... and so do the service waves' one-touch READS (the saved gates, h_{t-1}, dy).
-    const int mld = H > p.ldy ? (H > p.lddy ? H : p.lddy) : (p.ldy > p.lddy ? p.ldy : p.lddy);
+    const int mld0 = H > p.ldy ? (H > p.lddy ? H : p.lddy) : (p.ldy > p.lddy ? p.ldy : p.lddy);
+    const int mld = BI ? (mld0 > ldsv ? mld0 : ldsv) : mld0;
     const unsigned span = (unsigned)((size_t)(BT * T + 1) * mld * 4);        // bounds the tile's rows of every input array (+ the h_{t-1} row in front)
     // bases one row in front of the tile's first row (h_{t-1} of t = 0 is never read; the offset stays non-negative)
     // (the 16-bit arrays of the SV16 wave pair have 2-byte elements: their rows are H / 2 floats apart)
     const bool w16 = SV16 && sodd;
     // byte offset of the tile's first row in each of this wave's three input arrays (element size x row stride)
     const size_t es0 = (w16 || BF) ? 2 : 4, es1 = (w16 || BF) ? 2 : 4, es2 = w16 ? 2 : 4;
-    const size_t rs1 = SV16 ? (sodd ? (size_t)H : (size_t)p.ldy) : (size_t)H, rs2 = SV16 ? (sodd ? (size_t)H : (size_t)p.lddy) : (size_t)sld2;
-    const float* const in0_t = sbase0 ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(sbase0) + trow0 * H * es0) : nullptr;
+    const size_t rs0 = BI ? (size_t)ldsv : (size_t)H;
+    const size_t rs1 = SV16 ? (sodd ? (size_t)H : (size_t)p.ldy) : rs0, rs2 = SV16 ? (sodd ? (size_t)H : (size_t)p.lddy) : (size_t)sld2;
+    const float* const in0_t = sbase0 ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(sbase0) + trow0 * rs0 * es0) : nullptr;
     const float* const in1_t = sbase1 ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(sbase1) + trow0 * rs1 * es1) : nullptr;
     const float* const in2_t = sbase2 ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(sbase2) + trow0 * rs2 * es2) : nullptr;
     __amdgpu_buffer_rsrc_t rs_in0 = __builtin_amdgcn_make_buffer_rsrc((void*)in0_t, 0, span, 0x00020000);
@@ -254,9 +294,19 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
         return make_float2(__uint_as_float(v[0]), __uint_as_float(v[1]));
     };
     // h_prev of step 0 for the service waves' piece: the caller's hx (plain 16-byte load, outside the tile-relative resources), or zeros
-    auto svc_hx = [&]() -> f32x4 { return p.hx ? *reinterpret_cast<const f32x4*>(p.hx + (size_t)sb * H + scol) : zero4(); };
+    auto svc_hx = [&]() -> f32x4 { return p.hx ? *reinterpret_cast<const f32x4*>(p.hx + (BI ? (size_t)dir * p.B + sb : (size_t)sb) * H + scol) : zero4(); };
     // W16 (a std::bool_constant): this wave streams the 16-bit arrays
     auto svc_load1 = [&](auto W16, int k, int i) -> f32x4 {     // input i of this wave for step k
+        if constexpr (BI) {                                   // fp32 arrays only; k counts the sweep, t is the step's time
+            if (!svalid || k >= T) return zero4();
+            const int t = dir ? k : T - 1 - k;
+            const size_t row = (size_t)sb * T + t;
+            if (i == 0) return ldnt(0, sbase0 + row * ldsv + sdcol);
+            if (i == 1) return ldnt(1, sbase1 + row * ldsv + sdcol);
+            if (sodd) return sbase2 ? ldnt(2, sbase2 + row * sld2 + sdcol) : zero4();
+            const bool inner = k < T - 1 && !(RAG && dir && t == slen - 1);
+            return inner ? ldnt(2, sbase2 + (dir ? row + 1 : row - 1) * sld2 + sdcol) : svc_hx();
+        }
         const int t = T - 1 - k;
         if (!svalid || t < 0) return zero4();
         const size_t row = (size_t)sb * T + t;
@@ -325,12 +375,13 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
     auto svc_flush = [&](int k0, int k1) {            // gate gradients of steps k0 .. k1-1: obuf -> dgi (dr, dz, dn), dghn (dn * r)
         if (!svalid) return;
         for (int k = k0 < 0 ? 0 : k0; k < k1; ++k) {
-            const size_t row = (size_t)sb * T + (T - 1 - k);
+            const size_t row = (size_t)sb * T + ((BI && dir) ? k : T - 1 - k);
             const float* o = obuf + (k % OSL) * 4 * SARR + sr * SROW + sp * 4;
+            const int gcol = BI ? dir * 3 * H + scol : scol;      // the direction's three gate blocks of the (B T, 6H) rows
             // arrays sarr0 (dr / dz) and 2 + sarr0 (dn / dn*r)
-            stnt2(rs_dgi, dgi_t, p.dgi + row * p.lddg + (sodd ? H : 0) + scol, ld4(o + (sodd ? SARR : 0)));
-            if (sodd) stnt2(rs_dghn, dghn_t, p.dghn + row * p.lddghn + scol, ld4(o + 3 * SARR));
-            else stnt2(rs_dgi, dgi_t, p.dgi + row * p.lddg + 2 * H + scol, ld4(o + 2 * SARR));
+            stnt2(rs_dgi, dgi_t, p.dgi + row * p.lddg + (sodd ? H : 0) + gcol, ld4(o + (sodd ? SARR : 0)));
+            if (sodd) stnt2(rs_dghn, dghn_t, p.dghn + row * p.lddghn + sdcol, ld4(o + 3 * SARR));
+            else stnt2(rs_dgi, dgi_t, p.dgi + row * p.lddg + 2 * H + gcol, ld4(o + 2 * SARR));
         }
     };
     // PK image (p.dgpk): steps (ka, ka+1), ka even, are rows t_even + 1, t_even (t_even = T-2-ka) of the utterance; physical row
@@ -374,7 +425,7 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
                     // measured the same launch time: the burst occupies the CU's memory pipeline for ~1.3 steps either way.)
                     svc_issue(W16, k + KBX, KBX);
                     if (trs) p.trace[32 + (k - 100) * 4 + 1] = (long long)__builtin_readcyclecounter();
-                    if (p.dgpk) svc_flush_pk(k - KBX - (phi & 1), k - (phi & 1));      // whole pairs: one step later for the tiles with an odd phase
+                    if (!BI && p.dgpk) svc_flush_pk(k - KBX - (phi & 1), k - (phi & 1));      // whole pairs: one step later for the tiles with an odd phase
                     else svc_flush(k - KBX, k);
                 }
                 if (trs) p.trace[32 + (k - 100) * 4 + 2] = (long long)__builtin_readcyclecounter();
@@ -402,7 +453,7 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
                 if (k == T - 1) break;                // (per-wave flags: the compute waves have no drain barrier)
             }
             const int jl2 = (T - 1 + KBX - phi) % KBX;
-            if (p.dgpk) svc_flush_pk(T - 1 - jl2 - (phi & 1), T);      // T is even: the last pair is complete
+            if (!BI && p.dgpk) svc_flush_pk(T - 1 - jl2 - (phi & 1), T);      // T is even: the last pair is complete
             else svc_flush(T - 1 - jl2, T);           // the gate gradients since the last dirty step
         };
         if (svc) {
@@ -419,11 +470,11 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
     // (it depends on nothing but the position), so it never sits on the step's critical path
     const bool masked = p.dy && p.drop_p > 0.f && valid;
     auto draw = [&](int t) {
-        const size_t o = ((size_t)b * T + t) * p.lddy + col;
+        const size_t o = ((size_t)b * T + t) * p.lddy + dcol;
         const f32x4 m = dep_dropmask4(p.seed, p.site, o >> 2, p.drop_p, p.drop_scale);
         return f2(half ? m[2] : m[0], half ? m[3] : m[1]);
     };
-    float2 mk = masked ? draw(T - 1) : f2(1.f, 1.f);
+    float2 mk = masked ? draw((BI && dir) ? 0 : T - 1) : f2(1.f, 1.f);
     // debug stamps (DEP_TRACE=1, tools/trace_bwd.py): buffered in otherwise unused LDS, copied out after the sweep
     long long* trb = (p.trace && blockIdx.x == 0 && tid == 0) ? p.trace : nullptr;
     long long* trlb = reinterpret_cast<long long*>(smem + (AG ? AG_TRACE_F : BURST ? TRACE_F : 8192));
@@ -437,13 +488,14 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
         // (k-group ul / 8, utterance j), word (ul % 8) / 2 -- and a wave's 64 words are 256 contiguous bytes.
         float* red = smem;                                  // [step parity][K quarter = wave][own tile][64 lanes][4]
         const unsigned pw = (unsigned)(half + 2 * ((lp >> 4) & 1) + 4 * j + 64 * (lp >> 5) + 128 * jl);
-        const unsigned par_bytes = (unsigned)p.nbtp * NC * AG_MEMBER_BYTES;
-        const unsigned pub0 = (unsigned)(bt * NC + c) * AG_MEMBER_BYTES + pw * 4;
-        const unsigned ld0 = (unsigned)(bt * NC + 2 * w) * AG_MEMBER_BYTES + lane * 16;     // this wave's 12 blocks are contiguous: members 2w, 2w+1
+        const unsigned par_bytes = (unsigned)(BI ? 2 * p.nbtp : p.nbtp) * NC * AG_MEMBER_BYTES;
+        const unsigned pub0 = (unsigned)(pt * NC + c) * AG_MEMBER_BYTES + pw * 4;
+        const unsigned ld0 = (unsigned)(pt * NC + 2 * w) * AG_MEMBER_BYTES + lane * 16;     // this wave's 12 blocks are contiguous: members 2w, 2w+1
         unsigned* srcflags = tflags + 8 * w;                // the eight per-wave flags of source members 2w, 2w+1
         const int rdo = (jl * 64 + (lp >> 4) * 16 + j) * 4 + 2 * half;      // own pair inside a K quarter's two accumulator tiles
         for (int t = T - 1; t >= 0; --t) {
             const int k = T - 1 - t;
+            const int tm = (BI && dir) ? k : t;              // the step's time (t counts the sweep down)
             BSTAMP(0);
             if (trb && k < 360) trall[k] = (unsigned)__builtin_readcyclecounter();
             const float* ib = ibuf + (k % KBX) * 6 * SARR + j * SROW + ul;
@@ -457,7 +509,7 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
             dzt.x = d.x * z.x; dzt.y = d.y * z.y;
             const float2 drr = dr, dzr = dz, dnrr = dnr;
             if constexpr (RAG) {
-                const bool live = t < len;
+                const bool live = tm < len;
                 const float2 z2 = f2(0.f, 0.f);
                 dn = dep_sel2(live, dn, z2); dz = dep_sel2(live, dz, z2); dr = dep_sel2(live, dr, z2); dnr = dep_sel2(live, dnr, z2);
             }
@@ -466,7 +518,7 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
                 unsigned h0, l0, h1, l1, h2, l2;
                 if constexpr (RAG) {      // the words of the unselected values (rounded as the dense instance rounds them), zeroed for a dead step
                     split_pair(drr.x, drr.y, h0, l0); split_pair(dzr.x, dzr.y, h1, l1); split_pair(dnrr.x, dnrr.y, h2, l2);
-                    if (t >= len) { h0 = l0 = h1 = l1 = h2 = l2 = 0u; }
+                    if (tm >= len) { h0 = l0 = h1 = l1 = h2 = l2 = 0u; }
                 } else {
                     split_pair(dr.x, dr.y, h0, l0); split_pair(dz.x, dz.y, h1, l1); split_pair(dnr.x, dnr.y, h2, l2);
                 }
@@ -508,7 +560,7 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
                 for (int pl = 0; pl < 2; ++pl)
                     gfr[ks][pl] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lo_ + (unsigned)(ks * 2 + pl) * 1024, 0, 16 /* sc1: served by L2 */);
             __builtin_amdgcn_sched_barrier(0);               // all twelve requests first (hipcc otherwise sinks each load next to its MFMAs: twelve round trips in a row)
-            if (masked) mk = draw(t - 1);
+            if (masked) mk = draw((BI && dir) ? tm + 1 : t - 1);
             __builtin_amdgcn_sched_barrier(0);
             f32x4 acc[2] = {zero4(), zero4()};
 #pragma unroll
@@ -530,13 +582,14 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
             float2 s = f2(0.f, 0.f);
 #pragma unroll
             for (int q4 = 0; q4 < 4; ++q4) { const float2 v = ld2(rr + q4 * 512); s.x += v.x; s.y += v.y; }      // fixed order: deterministic
-            if constexpr (RAG) dhrec = dep_sel2(t < len, f2(dzt.x + s.x, dzt.y + s.y), dhrec);      // dead step: the incoming dh passes through
+            if constexpr (RAG) dhrec = dep_sel2(tm < len, f2(dzt.x + s.x, dzt.y + s.y), dhrec);      // dead step: the incoming dh passes through
             else dhrec = f2(dzt.x + s.x, dzt.y + s.y);
             BSTAMP(6);
         }
     } else
     for (int t = T - 1; t >= 0; --t) {
-        const size_t row = (size_t)b * T + t;
+        const int tm = (BI && dir) ? T - 1 - t : t;      // the step's time (t counts the sweep down)
+        const size_t row = (size_t)b * T + tm;
         BSTAMP(0);
         if (trb && T - 1 - t < 360) trall[T - 1 - t] = (unsigned)__builtin_readcyclecounter();
         if constexpr (BURST) {
@@ -555,7 +608,7 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
         dzt.x = d.x * z.x; dzt.y = d.y * z.y;
         const float2 drr = dr, dzr = dz, dnrr = dnr;
         if constexpr (RAG) {
-            const bool live = t < len;
+            const bool live = tm < len;
             const float2 z2 = f2(0.f, 0.f);
             dn = dep_sel2(live, dn, z2); dz = dep_sel2(live, dz, z2); dr = dep_sel2(live, dr, z2); dnr = dep_sel2(live, dnr, z2);
         }
@@ -563,7 +616,7 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
             unsigned h0, l0, h1, l1, h2, l2;
             if constexpr (RAG) {          // the words of the unselected values (rounded as the dense instance rounds them), zeroed for a dead step
                 split_pair(drr.x, drr.y, h0, l0); split_pair(dzr.x, dzr.y, h1, l1); split_pair(dnrr.x, dnrr.y, h2, l2);
-                if (t >= len) { h0 = l0 = h1 = l1 = h2 = l2 = 0u; }
+                if (tm >= len) { h0 = l0 = h1 = l1 = h2 = l2 = 0u; }
             } else {
                 split_pair(dr.x, dr.y, h0, l0); split_pair(dz.x, dz.y, h1, l1); split_pair(dnr.x, dnr.y, h2, l2);
             }
@@ -578,9 +631,9 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
             float* ob = obuf + ((T - 1 - t) % OSL) * 4 * SARR + j * SROW + ul;
             st2(ob, dr); st2(ob + SARR, dz); st2(ob + 2 * SARR, dn); st2(ob + 3 * SARR, dnr);
         } else if (valid) {
-            float* g = p.dgi + row * p.lddg;
+            float* g = p.dgi + row * p.lddg + (BI ? dir * 3 * H : 0);
             st2(g + col, dr); st2(g + H + col, dz); st2(g + 2 * H + col, dn);
-            st2(p.dghn + row * p.lddghn + col, dnr);
+            st2(p.dghn + row * p.lddghn + dcol, dnr);
         }
         dbr.x += dr.x; dbr.y += dr.y; dbz.x += dz.x; dbz.y += dz.y; dbn.x += dn.x; dbn.y += dn.y; dbh.x += dnr.x; dbh.y += dnr.y;
         bar_lds();                                   // LDS only: the dgi/dghn stores above stay in flight
@@ -589,7 +642,7 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
             if (p.dhx && valid) store_dhx(d, z);
             break;
         }
-        if constexpr (!BURST) load_step(t - 1, nxt); // independent of the recurrence: in flight under the MFMAs
+        if constexpr (!BURST) load_step((BI && dir) ? tm + 1 : t - 1, nxt); // independent of the recurrence: in flight under the MFMAs
         f32x4 acc[NTW];
 #pragma unroll
         for (int i = 0; i < NTW; ++i) acc[i] = zero4();
@@ -645,7 +698,7 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
         // flags are among the 4 NC words every wave polls below, which also orders this step's LDS reads before the next
         // step's LDS writes: a sibling raises its flag only after its MFMAs have read the gate-gradient planes)
         if (lane == 0) { if (fast) st_local(myflag, epoch); else st_agent(myflag, epoch); }
-        if (masked) mk = draw(t - 1);                // next step's mask, in the shadow of the wait below
+        if (masked) mk = draw((BI && dir) ? tm + 1 : t - 1);      // next step's mask, in the shadow of the wait below
         BSTAMP(4);
         // wait for every member's flag (one wave polls, relaxed; flags are monotonic)
         // every wave polls the flags itself (no verdict-broadcast barrier); a wave that gives up leaves, the hardware
@@ -661,7 +714,7 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
         for (int m = 0; m < NCM; ++m) part[m] = ld2_agent(src + (size_t)m * NTT * 256);
 #pragma unroll
         for (int m = 0; m < NCM; ++m) { s.x += part[m].x; s.y += part[m].y; }
-        if constexpr (RAG) dhrec = dep_sel2(t < len, f2(dzt.x + s.x, dzt.y + s.y), dhrec);      // dead step: the incoming dh passes through
+        if constexpr (RAG) dhrec = dep_sel2(tm < len, f2(dzt.x + s.x, dzt.y + s.y), dhrec);      // dead step: the incoming dh passes through
         else dhrec = f2(dzt.x + s.x, dzt.y + s.y);
         if constexpr (!BURST) cur = nxt;
         BSTAMP(6);
@@ -679,7 +732,9 @@ __global__ __launch_bounds__(KB ? CT + SVC_THREADS : CT) void gru_bwd_cluster_r1
 #pragma unroll
         for (int m = 2; m <= 16; m <<= 1) { a[k].x += __shfl_xor(a[k].x, m, 64); a[k].y += __shfl_xor(a[k].y, m, 64); }
     if (j == 0) {
-        float* o = p.dbpart + (size_t)(p.b0 / BT + bt) * 4 * H;
+        size_t brow = (size_t)(p.b0 / BT + bt);      // one row of partials per tile (BI: per direction and tile)
+        if constexpr (BI) brow += (size_t)dir * p.nbt;
+        float* o = p.dbpart + brow * 4 * H;
         st2(o + col, a[0]); st2(o + H + col, a[1]); st2(o + 2 * H + col, a[2]); st2(o + 3 * H + col, a[3]);
     }
 }
@@ -1054,13 +1109,30 @@ Instance<P2>& bwd_instance(int H, bool split, bool sv16, bool bf16st, bool rag) 
         default: return h512[form];
     }
 }
+// ... and the bidirectional instances (impl 7), dense and ragged: the unidirectional table's exchange form per H and mode, fp32 saved
+// gates, fp32 gate-gradient rows.  Per H: exact fp32 | split products.
+Instance<P2B>& bwd_bi_instance(int H, bool split, bool rag) {
+    constexpr size_t R1 = EXCLUSIVE_LDS + 2048, AG = burst_lds_bytes_ag(4) + 2048;
+    constexpr size_t BURST = (burst_lds_bytes(4) > EXCLUSIVE_LDS ? burst_lds_bytes(4) : EXCLUSIVE_LDS) + 2048;
+    static Instance<P2B> bidir[4][2] = {
+        { DEP_INSTANCE((gru_bwd_cluster_r1<1, false, 4, false, false, false, false, true>), BURST), DEP_INSTANCE((gru_bwd_cluster_r1<1, true, 4, false, false, false, false, true>), BURST) },
+        { DEP_INSTANCE((gru_bwd_cluster_r1<2, false, 4, false, false, false, false, true>), BURST), DEP_INSTANCE((gru_bwd_cluster_r1<2, true, 4, false, false, false, false, true>), BURST) },
+        { DEP_INSTANCE((gru_bwd_cluster_r1<4, false, 4, false, false, false, false, true>), BURST), DEP_INSTANCE((gru_bwd_cluster_r1<4, true, 4, false, false, true, false, true>), AG) },
+        { DEP_INSTANCE((gru_bwd_cluster_r1<8, false, 0, false, false, false, false, true>), R1), DEP_INSTANCE((gru_bwd_cluster_r1<8, true, 0, false, false, false, false, true>), R1) } };
+    static Instance<P2B> bidir_ragged[4][2] = {
+        { DEP_INSTANCE((gru_bwd_cluster_r1<1, false, 4, false, false, false, true, true>), BURST), DEP_INSTANCE((gru_bwd_cluster_r1<1, true, 4, false, false, false, true, true>), BURST) },
+        { DEP_INSTANCE((gru_bwd_cluster_r1<2, false, 4, false, false, false, true, true>), BURST), DEP_INSTANCE((gru_bwd_cluster_r1<2, true, 4, false, false, false, true, true>), BURST) },
+        { DEP_INSTANCE((gru_bwd_cluster_r1<4, false, 4, false, false, false, true, true>), BURST), DEP_INSTANCE((gru_bwd_cluster_r1<4, true, 4, false, false, true, true, true>), AG) },
+        { DEP_INSTANCE((gru_bwd_cluster_r1<8, false, 0, false, false, false, true, true>), R1), DEP_INSTANCE((gru_bwd_cluster_r1<8, true, 0, false, false, false, true, true>), R1) } };
+    return (rag ? bidir_ragged : bidir)[H == 64 ? 0 : H == 128 ? 1 : H == 256 ? 2 : 3][split];
+}
 }  // namespace
 
 void dep_cluster_gru_instance_texts(dep_instance_sink add) {
     const int sizes[] = {64, 128, 256, 512};       // dep_cluster_ok
     for (const int H : sizes)
         for (int m = 0; m < 16; ++m) {
-            if (m < 4) { add(fwd_instance(H, m & 1, m & 2).text); add(fwd_bi_instance(H, m & 1, m & 2).text); }
+            if (m < 4) { add(fwd_instance(H, m & 1, m & 2).text); add(fwd_bi_instance(H, m & 1, m & 2).text); add(bwd_bi_instance(H, m & 1, m & 2).text); }
             add(bwd_instance(H, m & 1, m & 2, m & 4, m & 8).text);
         }
 }
@@ -1122,19 +1194,33 @@ int dep_launch_cluster_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf_byte
 // (its service waves' flush forms the pairs), i.e. H <= 256, and whole step pairs.
 bool dep_cluster_bwd_pk_ok(int H, int T) { return H <= 256 && T % 2 == 0; }
 
+// dirs = 2 (impl 7): the bidirectional instances, both directions of a batch chunk in one launch -- the forward's pair geometry, the
+// backward's payload per (direction, tile) pair.  They have fp32 saved gates and fp32 gate-gradient rows only.
+size_t dep_cluster_bwd_bi_xbuf_bytes(int H, int B) {
+    if (!dep_cluster_ok(DEP_CELL_GRU, H, B, 2)) return 0;
+    return PAYLOAD_OFF + gru_bwd_payload_bytes(gru32_bi_geometry(H, B), H);
+}
+
 int dep_launch_cluster_bwd(const dep_sweep_bwd_args& a, void* xbuf, size_t xbuf_bytes) {
-    DEP_CHECK_ARG(dep_cluster_ok(a.cell, a.H, a.B, a.dirs) && xbuf && xbuf_bytes >= dep_cluster_xbuf_bytes(a.cell, a.H, a.B, a.dirs));
-    const ChunkGeometry g = gru32_geometry(a.H, a.B);
+    DEP_CHECK_ARG(a.dirs == 1 || a.dirs == 2);
+    const bool bi = a.dirs == 2;
+    DEP_CHECK_ARG(dep_cluster_ok(a.cell, a.H, a.B, a.dirs) && xbuf &&
+                  xbuf_bytes >= (bi ? dep_cluster_bwd_bi_xbuf_bytes(a.H, a.B) : dep_cluster_xbuf_bytes(a.cell, a.H, a.B, a.dirs)));
+    DEP_CHECK_ARG(!bi || (!a.dg_pk && !a.sv16 && !a.bf16st));      // refused before any launch
+    const ChunkGeometry g = bi ? gru32_bi_geometry(a.H, a.B) : gru32_geometry(a.H, a.B);
     const int nbt = dep_cdiv(a.B, BT);
-    P2 p{};
+    P2B p{};
     p.B = a.B; p.T = a.T; p.H = a.H;
     p.wp = (const f32x4*)a.wpT[0];
+    p.wp1 = (const f32x4*)a.wpT[1]; p.ldsv = a.dirs * a.H; p.nbt = nbt;
+    DEP_CHECK_ARG(!bi || (a.wpT[1] && a.ldy == 2 * a.H && a.lddy == 2 * a.H));
     p.y = a.y; p.ldy = a.ldy; p.dy = a.dy; p.lddy = a.lddy;
     p.drop_p = a.dy ? a.drop_p : 0.f; p.drop_scale = a.drop_p > 0.f ? 1.0f / (1.0f - a.drop_p) : 1.0f;
     p.seed = a.seed; p.site = a.site;
     p.dpooled = a.dpooled; p.pool_scale = a.pool_scale; p.dh_n = a.dh_n;
     p.sv0 = a.sv0; p.sv1 = a.sv1; p.sv2 = a.sv2; p.sv3 = a.sv3;
-    p.dgi = a.dgi; p.lddg = a.lddg ? a.lddg : 3 * a.H; p.dghn = a.dghn; p.lddghn = a.lddghn ? a.lddghn : a.H; p.dbpart = a.dbpart;
+    p.dgi = a.dgi; p.lddg = a.lddg ? a.lddg : a.dirs * 3 * a.H; p.dghn = a.dghn; p.lddghn = a.lddghn ? a.lddghn : a.dirs * a.H; p.dbpart = a.dbpart;
+    DEP_CHECK_ARG(!bi || (p.lddg >= 6 * a.H && p.lddghn >= 2 * a.H));
     p.dgpk = a.dg_pk;
     p.lengths = a.lengths; p.pool_mean = a.pool_mean;
     p.hx = a.hx; p.dhx = a.dhx;
@@ -1144,19 +1230,24 @@ int dep_launch_cluster_bwd(const dep_sweep_bwd_args& a, void* xbuf, size_t xbuf_
     DEP_CHECK_ARG(!(a.lengths && a.bf16st));         // no ragged bf16-storage instance
     DEP_CHECK_ARG(!a.sv16 || a.split);               // the 16-bit saved gates exist in split-precision mode only
     DEP_CHECK_ARG(!a.bf16st || (a.H == 256 && a.split && a.sv16 && a.dg_pk));      // bf16-storage mode: H = 256, burst kernel (checked below via dg_pk)
-    DEP_CHECK_ARG(a.dbpart_rows >= nbt);
-    const size_t pay = gru_bwd_payload_bytes(g, a.H);
+    DEP_CHECK_ARG(a.dbpart_rows >= a.dirs * nbt);
+    const size_t pay = gru_bwd_payload_bytes(g, a.H);      // (the pair geometry counts both directions' members)
     DEP_CHECK_ARG(PAYLOAD_OFF + pay <= xbuf_bytes && g.resident());
     p.flags = bind_exchange(p, xbuf, a.hdr_slot, pay);
     DepProfScope prof(DEP_PROF_GRU_BWD, a.stream);
     // (one tile's rows of the widest array must fit a 32-bit buffer offset)
     { const int mxl = p.lddg > p.lddy ? p.lddg : p.lddy; DEP_CHECK_ARG((size_t)(BT * a.T + 1) * (mxl > p.ldy ? mxl : p.ldy) * 4 < 0xffffffffull); }
     const int kb = bwd_burst(a.H);
+    const auto prepare = [&](int b0) { return hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); };
+    if (bi) {
+        Instance<P2B>& k2 = bwd_bi_instance(a.H, a.split, a.lengths != nullptr);
+        p.trall_off = (int)((k2.lds - 2048) / 4);
+        return launch_chunks(k2, g, dim3(kb ? CT + SVC_THREADS : CT), p, a.stream, __PRETTY_FUNCTION__, prepare);
+    }
     Instance<P2>& k = bwd_instance(a.H, a.split, a.sv16, a.bf16st, a.lengths != nullptr);
     p.trall_off = (int)((k.lds - 2048) / 4);
     if (p.dgpk) {       // the PK image needs the burst kernel's flush, the 4H-wide rows and whole step pairs (dep_cluster_bwd_pk_ok)
         DEP_CHECK_ARG(kb == 4 && a.split && a.T % 2 == 0 && a.lddg == 4 * a.H && a.lddghn == 4 * a.H && a.dghn == a.dgi + 3 * a.H);
     }
-    return launch_chunks(k, g, dim3(kb ? CT + SVC_THREADS : CT), p, a.stream, __PRETTY_FUNCTION__,
-                         [&](int b0) { return hdr_prepare(xbuf, a.hdr_slot, a.hdr_clean && b0 == 0, a.stream); });
+    return launch_chunks(k, g, dim3(kb ? CT + SVC_THREADS : CT), static_cast<P2&>(p), a.stream, __PRETTY_FUNCTION__, prepare);
 }

@@ -110,6 +110,23 @@ typedef struct {
                             cluster layouts.  Any other cell, dirs or H with impl = 6 is a bad descriptor (size queries 0, entry
                             points DEP_ERR_ARG, the rule in dep_last_error).  Outputs agree with impl = 2 to rounding (fast gate
                             nonlinearities, split or exact recurrent products as on impl = 4), the dropout masks bit for bit.
+                            7 the per-layer cluster sweeps of a bidirectional GRU, forward and backward: impl = 6 in every forward -- the
+                            same descriptors exist, the same launches, outputs and dropout masks bit for bit, the same reserve size and
+                            offsets -- whose dep_rnn_backward[_state][_varlen] (and _overlapped) runs one launch per layer of the
+                            bidirectional instance of gru_bwd_cluster_r1: both directions of a batch chunk side by side, each
+                            (direction, 16-utterance tile) pair a cluster of H / 32 co-resident workgroups with its W_hh slice in
+                            registers, at H in {64,128,256,512} -- H = 512 trains here -- any B, T, L, dense and ragged.  A
+                            DEP_RUN_TRAIN forward packs the cluster backward's weight image of each direction where impl = 6 packs the
+                            tile backward's, so a reserve goes with the impl that wrote it.  The sweep writes the fp32 gate-gradient
+                            rows of the tile BiGRU backward ((B T, 6H) and (B T, 2H)), and everything behind it -- bias sums, the
+                            direction-stacked dX and dW_ih, the per-direction dW_hh -- is the code impl 2 / 6 run; gradients agree with
+                            impl = 6 to rounding.  Saved gates are fp32; there is no 16-bit or bf16 storage and no PK gate-gradient
+                            image.  GEMM modes: 0 and 1 for every call; a dense backward also runs in mode 2 (the split-product sweep
+                            instance, single-product contractions behind it); a backward in mode 3 is refused (its contractions read
+                            the hi rows of a PK image this sweep does not write), and a ragged call in modes 2 / 3 as on every plan.
+                            hx / dhx go through the backward at all four H; cx / c_n / dc_n / dcx are refused with the rule naming
+                            impl = 7, as is any other cell, dirs or H.  The workspace is at least impl = 6's: its exchange buffer also
+                            covers the backward's payload (dep_rnn_status and dep_rnn_workspace_xbuf_offset work as on impl = 6).
                             A bidirectional GRU otherwise has tile-MFMA kernels only: impl must be 0 or 2 (both mean those kernels)
                             and H a multiple of 16 they can tile -- H / 16 = waves x tiles per wave with waves in
                             {1,2,4,8} and at most 4 tiles per wave, inside the LDS bound: H in {16,32,48,64,96,128,192,256}.
@@ -126,7 +143,7 @@ size_t dep_rnn_reserve_y_offset(const dep_rnn_desc* d, int layer);
 /* Same for the dropped-out copy that feeds layer+1 (DEP_RUN_TRAIN / DEP_RUN_DROPOUT_ONLY with dropout_p > 0 only). */
 size_t dep_rnn_reserve_ydrop_offset(const dep_rnn_desc* d, int layer);
 
-/* Health of the cluster-parallel sweeps that ran on `workspace` since the last dep_rnn_forward (desc.impl 0/3/4/5/6 with a
+/* Health of the cluster-parallel sweeps that ran on `workspace` since the last dep_rnn_forward (desc.impl 0/3/4/5/6/7 with a
  * supported H): they exchange data between workgroups inside one launch with bounded spins; if a spin ever gives up
  * the kernels exit early and this returns DEP_ERR_HIP.  The status is STICKY over a step: dep_rnn_forward clears it once,
  * every later sweep (the other layers, the whole backward) leaves it alone and exits at entry when it is raised, so one
@@ -303,6 +320,14 @@ int dep_rnn_backward_overlapped_varlen(const dep_rnn_desc* d, const float* x, co
  *   - on an impl = 6 descriptor (the per-layer cluster forward of a bidirectional GRU) hx is accepted by every forward, in all three run
  *     modes: each direction's clusters read that direction's slice, (l * 2 + d) like h_n.  hx / dhx in dep_rnn_backward_state go to the
  *     tile-MFMA backward, which takes them for a bidirectional GRU on impl = 2 already.  cx / c_n / dc_n / dcx are refused (a GRU);
+ *   - on an impl = 7 descriptor (the per-layer cluster sweeps of a bidirectional GRU, forward and backward) the forward takes hx as
+ *     on impl = 6, and dep_rnn_backward_state[_varlen] takes hx and dhx at H in {64,128,256,512}, dense and ragged, in every GEMM mode
+ *     the backward runs in: the bidirectional gru_bwd_cluster_r1 takes a direction's hx slice as h_prev of that direction's last
+ *     sweep step (t = 0; reverse direction t = T-1, or a ragged row's t = len_b - 1) and stores the direct term of dhx there; the call
+ *     adds the hx term of dW_hh and, per direction, the recurrent term dG[:, t_last, :] W_hh (t_last = 0 / T-1) behind the sweep on
+ *     `stream`.  A ragged row whose reverse sweep ends in dead steps has zero gate gradients at t_last and its stored dhx is already
+ *     complete; a row of length 0 gets dhx = dh_n.  dhx may be dh_n's buffer; hx must be 16-byte aligned.  cx / c_n / dc_n / dcx are
+ *     refused with the rule naming impl = 7;
  *   - hx alone is also accepted by dep_rnn_forward_state on an impl = 4 descriptor (the per-layer cluster sweeps) in DEP_RUN_EVAL and
  *     DEP_RUN_DROPOUT_ONLY, the run modes no backward follows: every member of a tile's cluster reads the tile's rows of hx in front
  *     of its first step.  Still refused there, before anything is launched: hx in DEP_RUN_TRAIN, and any non-NULL member in

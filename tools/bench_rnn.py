@@ -3,8 +3,9 @@
 2-layer GRU (cfg2), BiLSTM (cfg3) or bidirectional GRU stack on synthetic data.
     python tools/bench_rnn.py gru|lstm|bigru [B T F H] [--impl N] [--eval]
 --impl N (or DEP_IMPL=N): dep_rnn_desc.impl.  2 forces the unidirectional GRU onto the tile-MFMA sweeps, which a bidirectional GRU runs on
-impl 0 / 2 anyway; `bigru --impl 6` times the per-layer cluster forward of the bidirectional GRU (the backward stays the tile-MFMA one).
---eval: the DEP_RUN_EVAL forward alone (no dropout, no reserve for a backward, no backward): the only timing an H = 512 BiGRU has."""
+impl 0 / 2 anyway; `bigru --impl 6` times the per-layer cluster forward of the bidirectional GRU (the backward stays the tile-MFMA one),
+`bigru --impl 7` the same forward with the bidirectional cluster backward behind it (the only BiGRU backward at H = 512).
+--eval: the DEP_RUN_EVAL forward alone (no dropout, no reserve for a backward, no backward): the only timing an H = 512 BiGRU has on impl 6."""
 import os
 import sys
 import time
