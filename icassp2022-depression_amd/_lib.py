@@ -102,6 +102,9 @@ _SIGS = {
     'dep_layernorm_fwd': (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P]),
     'dep_ln_fold_fwd': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
     'dep_ln_fold_bwd': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
+    'dep_ln_fold_fwd_multi': (C.c_int, [C.POINTER(_P), C.POINTER(_P), _P, _P, C.POINTER(_P), C.POINTER(_P), C.c_int, C.c_int, C.c_int, _P]),
+    'dep_ln_fold_bwd_multi': (C.c_int, [C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P, C.POINTER(_P), C.POINTER(_P), _P, _P,
+                                        C.c_int, C.c_int, C.c_int, _P]),
     'dep_layernorm_bwd_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int]),
     'dep_layernorm_bwd': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, _P, C.c_size_t, _P]),
     'dep_attn_fwd': (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
@@ -282,6 +285,37 @@ def ln_fold_bwd(W, dWf, dbf, gamma, beta, dW, db, dgamma, dbeta):
     J, F = W.shape
     check(load().dep_ln_fold_bwd(_ptr(W), _ptr(dWf), _ptr(dbf), _ptr(gamma), _ptr(beta), _ptr(dW), _ptr(db), _ptr(dgamma),
                                  _ptr(dbeta), J, F, stream()), 'dep_ln_fold_bwd')
+
+
+def _fold_pieces(what, lists, vectors, F):
+    """The host pointer arrays of a several-map fold: every list holds one contiguous fp32 device tensor per piece, (J, F) or (J); the
+    LayerNorm vectors hold F elements."""
+    n = len(lists[0][1])
+    if any(v.numel() != F for v in vectors):
+        raise DepError(f'{what}: gamma, beta and their gradients must hold F = {F} elements')
+    arrs = []
+    for name, ts, shape in lists:
+        if len(ts) != n or any(tuple(t.shape) != shape for t in ts):
+            raise DepError(f'{what}: {name} must hold {n} tensors of shape {shape}, got {[tuple(t.shape) for t in ts]}')
+        arrs.append((_P * n)(*[_ptr(f32(t)) for t in ts]))
+    return n, arrs
+
+
+def ln_fold_fwd_multi(Ws, bs, gamma, beta, Wfs, bfs):
+    """dep_ln_fold_fwd_multi: Wf_k = W_k*gamma, bf_k = b_k + W_k beta for the 1 or 2 maps of the lists, in one launch."""
+    J, F = Ws[0].shape
+    n, (W, b, Wf, bf) = _fold_pieces('ln_fold_fwd_multi', (('W', Ws, (J, F)), ('b', bs, (J,)), ('Wf', Wfs, (J, F)), ('bf', bfs, (J,))),
+                                     (gamma, beta), F)
+    check(load().dep_ln_fold_fwd_multi(W, b, _ptr(gamma), _ptr(beta), Wf, bf, n, J, F, stream()), 'dep_ln_fold_fwd_multi')
+
+
+def ln_fold_bwd_multi(Ws, dWfs, dbfs, gamma, beta, dWs, dbs, dgamma, dbeta):
+    """dep_ln_fold_bwd_multi: dW_k, db_k per map and dgamma / dbeta summed over the maps in a fixed order (written), in one launch."""
+    J, F = Ws[0].shape
+    n, (W, dWf, dbf, dW, db) = _fold_pieces('ln_fold_bwd_multi', (('W', Ws, (J, F)), ('dWf', dWfs, (J, F)), ('dbf', dbfs, (J,)),
+                                                                    ('dW', dWs, (J, F)), ('db', dbs, (J,))), (gamma, beta, dgamma, dbeta), F)
+    check(load().dep_ln_fold_bwd_multi(W, dWf, dbf, _ptr(gamma), _ptr(beta), dW, db, _ptr(dgamma), _ptr(dbeta), n, J, F, stream()),
+          'dep_ln_fold_bwd_multi')
 
 
 def layernorm_bwd(dy2d, x2d, gamma, mr, dgamma, dbeta, want_dx=False):

@@ -143,6 +143,68 @@ __global__ __launch_bounds__(1024) void ln_fold_bwd_kernel(const float* __restri
     if (blockIdx.x == 0) for (int j = threadIdx.x; j < J; j += 1024) db[j] = q[j];
 }
 
+// The fold for several maps that read the same LayerNorm (dep_ln_fold_fwd_multi / dep_ln_fold_bwd_multi: the two first-layer
+// maps of a bidirectional stack).  The pieces' device pointers travel in the kernel arguments, as the optimizer's ranges do.
+constexpr int LF_MAXP = 2;
+struct FoldFwdPieces { const float* W[LF_MAXP]; const float* b[LF_MAXP]; float* Wf[LF_MAXP]; float* bf[LF_MAXP]; };
+struct FoldBwdPieces { const float* W[LF_MAXP]; const float* P[LF_MAXP]; const float* q[LF_MAXP]; float* dW[LF_MAXP]; float* db[LF_MAXP]; };
+// forward: ln_fold_fwd_kernel's wave per row, blockIdx.y = the piece -- the same chain and the same butterfly per row
+__global__ __launch_bounds__(256) void ln_fold_fwd_multi_kernel(FoldFwdPieces R, const float* __restrict__ gamma,
+                                                                const float* __restrict__ beta, int J, int F) {
+    const int lane = threadIdx.x & 63;
+    const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= J) return;
+    const bool k = blockIdx.y != 0;
+    const float* W = k ? R.W[1] : R.W[0];
+    float* Wf = k ? R.Wf[1] : R.Wf[0];
+    float s = 0.f;
+    for (int f = lane; f < F; f += 64) {
+        const float w = W[(size_t)j * F + f];
+        Wf[(size_t)j * F + f] = w * gamma[f];
+        s = fmaf(w, beta[f], s);
+    }
+    s = wave_sum(s);
+    if (lane == 0) (k ? R.bf[1] : R.bf[0])[j] = (k ? R.b[1] : R.b[0])[j] + s;
+}
+// backward: ln_fold_bwd_kernel's walk and tree once per piece, piece 0 first; dgamma / dbeta = piece 0's tree sum, then piece 1's
+// added to it once.  A fixed order, no atomics; one piece leaves exactly ln_fold_bwd_kernel's bits.
+__global__ __launch_bounds__(1024) void ln_fold_bwd_multi_kernel(FoldBwdPieces R, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, float* __restrict__ dgamma,
+                                                                 float* __restrict__ dbeta, int npieces, int J, int F) {
+    __shared__ float red[2][LFR][LFC];
+    const int c = threadIdx.x % LFC, rg = threadIdx.x / LFC;
+    const int f = blockIdx.x * LFC + c;
+    float total = 0.f;
+#pragma unroll
+    for (int k = 0; k < LF_MAXP; ++k) {
+        if (k >= npieces) break;
+        const float* W = R.W[k]; const float* P = R.P[k]; const float* q = R.q[k];
+        float* dW = R.dW[k]; float* db = R.db[k];
+        float dg = 0.f, dbt = 0.f;
+        if (f < F) {
+            const float g = gamma[f], bt = beta[f];
+#pragma unroll 4
+            for (int j = rg; j < J; j += LFR) {
+                const float w = W[(size_t)j * F + f], pj = P[(size_t)j * F + f], qj = q[j];
+                dW[(size_t)j * F + f] = fmaf(pj, g, qj * bt);
+                dg = fmaf(pj, w, dg);
+                dbt = fmaf(w, qj, dbt);
+            }
+        }
+        if (k) __syncthreads();                                    // the tree of the piece before has been read
+        red[0][rg][c] = dg; red[1][rg][c] = dbt;
+        __syncthreads();
+        if (rg < 2 && f < F) {
+            float a = 0.f;
+#pragma unroll 8
+            for (int r = 0; r < LFR; ++r) a += red[rg][r][c];
+            total = k ? total + a : a;
+        }
+        if (blockIdx.x == 0) for (int j = threadIdx.x; j < J; j += 1024) db[j] = q[j];
+    }
+    if (rg < 2 && f < F) (rg == 0 ? dgamma : dbeta)[f] = total;
+}
+
 // partial[blk][2][F]: per-block column sums of dy*xhat and dy over the block's row range
 __global__ __launch_bounds__(256) void ln_bwd_param_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                            const float* __restrict__ mr, float* __restrict__ partial,
@@ -717,6 +779,33 @@ extern "C" int dep_ln_fold_bwd(const float* W, const float* dWf, const float* db
                                float* dW, float* db, float* dgamma, float* dbeta, int J, int F, void* stream) {
     DEP_CHECK_ARG(W && dWf && dbf && gamma && beta && dW && db && dgamma && dbeta && J > 0 && F > 0);
     DEP_LAUNCH(ln_fold_bwd_kernel, dim3(dep_cdiv(F, LFC)), dim3(1024), 0, S_, W, dWf, dbf, gamma, beta, dW, db, dgamma, dbeta, J, F);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+
+extern "C" int dep_ln_fold_fwd_multi(const float* const* W, const float* const* b, const float* gamma, const float* beta,
+                                     float* const* Wf, float* const* bf, int npieces, int J, int F, void* stream) {
+    DEP_CHECK_ARG(W && b && gamma && beta && Wf && bf && npieces >= 1 && npieces <= LF_MAXP && J > 0 && F > 0);
+    FoldFwdPieces R{};
+    for (int k = 0; k < npieces; ++k) {
+        DEP_CHECK_ARG(W[k] && b[k] && Wf[k] && bf[k]);
+        R.W[k] = W[k]; R.b[k] = b[k]; R.Wf[k] = Wf[k]; R.bf[k] = bf[k];
+    }
+    DEP_LAUNCH(ln_fold_fwd_multi_kernel, dim3(dep_cdiv(J, 4), npieces), dim3(256), 0, S_, R, gamma, beta, J, F);
+    DEP_CHECK_LAUNCH();
+    return DEP_OK;
+}
+
+extern "C" int dep_ln_fold_bwd_multi(const float* const* W, const float* const* dWf, const float* const* dbf, const float* gamma,
+                                     const float* beta, float* const* dW, float* const* db, float* dgamma, float* dbeta,
+                                     int npieces, int J, int F, void* stream) {
+    DEP_CHECK_ARG(W && dWf && dbf && gamma && beta && dW && db && dgamma && dbeta && npieces >= 1 && npieces <= LF_MAXP && J > 0 && F > 0);
+    FoldBwdPieces R{};
+    for (int k = 0; k < npieces; ++k) {
+        DEP_CHECK_ARG(W[k] && dWf[k] && dbf[k] && dW[k] && db[k]);
+        R.W[k] = W[k]; R.P[k] = dWf[k]; R.q[k] = dbf[k]; R.dW[k] = dW[k]; R.db[k] = db[k];
+    }
+    DEP_LAUNCH(ln_fold_bwd_multi_kernel, dim3(dep_cdiv(F, LFC)), dim3(1024), 0, S_, R, gamma, beta, dgamma, dbeta, npieces, J, F);
     DEP_CHECK_LAUNCH();
     return DEP_OK;
 }

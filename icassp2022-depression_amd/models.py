@@ -1,7 +1,8 @@
 """The three model families of the hot path, each a forward + explicit backward over libdep_rnn.so.
 
   AudioGRU   -- `AudioBiLSTM` of Classification/audio_gru_whole.py:24-108 (variant 'clf': LayerNorm,
-                mean pool, Softmax) and Regression/audio_bilstm_perm.py:45-127 ('reg': no LN, sum pool, ReLU)
+                mean pool, Softmax) and Regression/audio_bilstm_perm.py:45-127 ('reg': no LN, sum pool, ReLU);
+                config['bidirectional'] = True: [LN] -> BiGRU -> attention_net_with_w(output, h_n) in place of the pool
   TextBiLSTM -- Classification/text_bilstm_whole.py:23-114 ('clf') / Regression/text_bilstm_perm.py:37-124 ('reg')
   FusionNet  -- `fusion_net` + `MyLoss` of Classification/fuse_net_whole.py:245-395 ('clf') and
                 Regression/fuse_net.py:224-366 ('reg')
@@ -254,15 +255,17 @@ class AudioGRU(nn.Module):
         self.num_classes = config['num_classes']; self.learning_rate = config['learning_rate']
         self.dropout = float(config['dropout']); self.hidden_dims = H = config['hidden_dims']
         self.rnn_layers = Lyr = config['rnn_layers']; self.embedding_size = F = config['embedding_size']
-        self.bidirectional = config.get('bidirectional', False)
-        if self.bidirectional:
-            raise L.DepError('AudioBiLSTM: the reference runs a unidirectional GRU (bidirectional=False)')
+        self.bidirectional = bi = bool(config.get('bidirectional', False))
+        if bi:
+            # ln -> BiGRU -> attention_net_with_w(output, h_n) -> fc_audio: the one bidirectional forward the reference class can express
+            # without changing the shape of a parameter; fails here, by name, for a width no bidirectional sweep runs
+            self._bi_impl = self._bidirectional_impl(F, H, Lyr)
         gen = nn.make_generator(seed)
         init = {}
-        # definition order of the reference (named_parameters order)
-        self._add('attention_layer.0.weight', (H, H), live=False); self._add('attention_layer.0.bias', (H,), live=False)
+        # definition order of the reference (named_parameters order); the attention pair is live in the bidirectional model alone
+        self._add('attention_layer.0.weight', (H, H), live=bi); self._add('attention_layer.0.bias', (H,), live=bi)
         init.update(nn.default_linear_init('attention_layer.0.weight', 'attention_layer.0.bias', H, H, gen))
-        rn = _rnn_names('lstm_net_audio', F, H, Lyr, 1, 3)
+        rn = _rnn_names('lstm_net_audio', F, H, Lyr, 2 if bi else 1, 3)
         for n, s in rn:
             self._add(n, s)
         init.update(nn.default_rnn_init(rn, H, gen))
@@ -282,6 +285,22 @@ class AudioGRU(nn.Module):
         self._finalize(init)
         self._rnn_w = [self._params[n].data for n, _ in rn]
         self._rnn_g = [self._params[n]._grad for n, _ in rn]
+        if bi:
+            self._chunk_health = self._chunked = None            # (what check_health() and backward() look at; never set here)
+            self._head = _MLPHead(self, 'fc_audio.1', 'fc_audio.4', self.dropout, True, (L.SITE_FC0, L.SITE_FC1))
+            if variant == 'clf':
+                # the fold as below, for the two first-layer maps (entries 0 / 2 and 4 / 6 of the weight list) in one launch each way:
+                # dep_ln_fold_bwd_multi sums dgamma / dbeta over both directions
+                mk = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+                mat, vec = (lambda: [mk(3 * H, F), mk(3 * H, F)]), (lambda: [mk(3 * H), mk(3 * H)])
+                self._fold2 = Wf, bf, dWf, dbf = mat(), vec(), mat(), vec()          # one per direction
+                self._rnn_w_fold = list(self._rnn_w); self._rnn_g_fold = list(self._rnn_g)
+                for d in (0, 1):
+                    self._rnn_w_fold[4 * d], self._rnn_w_fold[4 * d + 2] = Wf[d], bf[d]
+                    self._rnn_g_fold[4 * d], self._rnn_g_fold[4 * d + 2] = dWf[d], dbf[d]
+            # eval and train on the same impl: a reserve goes with the impl that wrote it
+            self._rnns = _RnnCache(L.CELL_GRU, F, H, Lyr, 2, self.dropout, L.POOL_NONE, self.device, impl=self._bi_impl)
+            return
         if variant == 'clf':
             # LayerNorm's affine is folded into gru.weight_ih_l0 / bias_ih_l0 (dep_ln_fold_*): the stack runs on x-hat
             # with the folded pair and hands back their gradients, from which dW, db, dgamma, dbeta follow exactly --
@@ -308,10 +327,32 @@ class AudioGRU(nn.Module):
         self.keep_chunk_states = False             # debugging / tests: backward() keeps each recomputed chunk's h_n in _chunked['h_n_recomputed']
         self._head = _MLPHead(self, 'fc_audio.1', 'fc_audio.4', self.dropout, True, (L.SITE_FC0, L.SITE_FC1))
 
+    @staticmethod
+    def _bidirectional_impl(F, H, Lyr):
+        """The sweeps of the bidirectional model: impl 7 (the per-layer cluster sweeps of a bidirectional GRU, forward and backward)
+        where that descriptor exists -- its size query is non-zero -- else impl 2 where the tile-MFMA sweeps can tile H; else a
+        DepError.  What impl 7 refuses later (a backward in GEMM mode 3, a ragged call in modes 2 / 3) is raised with the library's
+        own message: the plan never changes silently."""
+        def exists(impl):
+            probe = L.RnnDesc(L.CELL_GRU, 1, 1, F, H, Lyr, 2, L.RUN_TRAIN, 0.0, 0, L.POOL_NONE, impl)
+            return L.load().dep_rnn_workspace_bytes(probe) != 0
+        if exists(L.IMPL_CLUSTER_BIGRU_TRAIN):
+            return L.IMPL_CLUSTER_BIGRU_TRAIN
+        if exists(L.IMPL_TILE):
+            return L.IMPL_TILE
+        raise L.DepError(f'AudioBiLSTM(bidirectional=True): no bidirectional GRU sweep runs hidden_dims = {H}: the per-layer cluster sweeps '
+                         'take 64, 128, 256 and 512, the tile-MFMA sweeps 16, 32, 48, 96 and 192')
+
+    def _refuse_chunks(self, what):
+        if self.bidirectional:
+            raise L.DepError(f'AudioGRU.{what}: a bidirectional encoder cannot be cut into chunks -- the reverse direction starts at the '
+                             'last frame, so no chunk is final before the recording ends; model(x) scores the whole recording')
+
     def stream(self, impl=None):
         """Chunked scoring with bounded memory (eval mode only): s = model.stream(); s.push(chunk) ...; s.output() is model(x) for
         the chunks concatenated along T.  See _AudioStream.  impl: None = the model's choice (see __init__), or L.IMPL_TILE /
         L.IMPL_CLUSTER_PER_LAYER to name the sweeps (the latter only where the descriptor exists)."""
+        self._refuse_chunks('stream')
         if self.training:
             raise L.DepError('AudioGRU.stream: streaming scores in eval() mode only (no dropout, no backward)')
         impl = self._stream_impl if impl is None else int(impl)
@@ -356,6 +397,8 @@ class AudioGRU(nn.Module):
     def encode(self, x, training, seed, lengths=None):
         """lengths: int32 device vector (B), the utterances' own lengths inside the padded batch (None: dense).  The padding
         must be finite (pad_ragged pads with zeros; LayerNorm maps a zero row to a zero row)."""
+        if self.bidirectional:
+            return self._encode_bidirectional(x, training, seed, lengths)
         B, T, F = x.shape
         P = self._params
         if self.variant == 'clf':
@@ -369,9 +412,30 @@ class AudioGRU(nn.Module):
         rnn.forward(xn, weights, seed=seed, pooled=pooled, lengths=lengths)
         return pooled, (x, xn, rnn, lengths)
 
+    def _encode_bidirectional(self, x, training, seed, lengths):
+        """x-hat (clf) -> BiGRU stack (no pool, h_n wanted) -> attention_net_with_w over the top sequence, read in place: the halves
+        of the output summed, attention over the row's own steps, the final states of all layers and directions summed into the
+        query.  A row of length 0 has ctx = 0."""
+        B, T, F = x.shape
+        P = self._params
+        if self.variant == 'clf':
+            xn, _ = L.layernorm_fwd(x.view(B * T, F), None, None, save=False)
+            w = self._rnn_w
+            L.ln_fold_fwd_multi([w[0], w[4]], [w[2], w[6]], P['ln.weight'].data, P['ln.bias'].data, *self._fold2[:2])
+            weights = self._rnn_w_fold
+        else:
+            xn, weights = x.view(B * T, F), self._rnn_w
+        rnn = self._rnns.get(B, T, training)
+        h_n = torch.empty(2 * self.rnn_layers, B, self.hidden_dims, dtype=torch.float32, device=self.device)
+        rnn.forward(xn, weights, seed=seed, h_n=h_n, lengths=lengths)
+        out = rnn.layer_output()
+        ctx, att = L.attn_fwd(out, h_n, P['attention_layer.0.weight'].data, P['attention_layer.0.bias'].data, lengths=lengths)
+        return ctx, (x, xn, rnn, lengths, out, att)
+
     def forward(self, x, lengths=None):
         """lengths: the ragged call -- x is padded to its longest utterance, row b is lengths[b] steps long (mean / sum pool over
-        its own steps); see _common.pad_ragged."""
+        its own steps; bidirectional: the reverse direction starts at its last step, the attention runs over its own steps); see
+        _common.pad_ragged."""
         x = self._to_dev(x)
         lengths = _RnnCache.lengths_on(lengths, x.shape[0], self.device)
         training = self.training
@@ -383,6 +447,8 @@ class AudioGRU(nn.Module):
         L.head_loss(kind, z, None, out, None, None, 1.0)
         self._saved = enc
         self._chunked = None
+        if self.bidirectional:
+            self.last_alpha = enc[5][0]
         return nn.Output(out, self, z)
 
     def forward_chunked(self, x, chunk_steps, lengths=None, impl=None):
@@ -397,6 +463,7 @@ class AudioGRU(nn.Module):
         impl: None = the model's choice (IMPL_CLUSTER_PER_LAYER_STATE where that descriptor exists, else IMPL_TILE: 43.4 ms against 364.9 ms
         at H = F = 256, B = 64, T = 3000 in chunks of 300, profiles/chunked_step_ab.txt), or one of the two, as stream(impl=) names its sweeps.
         check_health() covers the chunks of the latest step."""
+        self._refuse_chunks('forward_chunked')
         if not self.training:
             raise L.DepError('AudioGRU.forward_chunked: a training step (model.train()); eval-mode chunked scoring is model.stream()')
         x = self._to_dev(x)
@@ -518,6 +585,18 @@ class AudioGRU(nn.Module):
         sits right in front of it -- ONE contiguous range, so a 2-layer step is two all-reduces."""
         Lyr, px = self.rnn_layers, 'lstm_net_audio'
         in_call, post = {}, []
+        if self.bidirectional:
+            # [ln | attention | l0 (both directions) | l1 .. | fc_audio]: the attention pair sits in front of layer 0 and goes with it,
+            # as in TextBiLSTM.sync_plan; the classifier's layer 0 waits for dep_ln_fold_bwd_multi, so there LayerNorm pair, attention
+            # pair and layer 0 are ONE contiguous range reduced after the backward.  The head rides with the top layer.
+            for l in range(Lyr):
+                first = 'attention_layer.0.weight' if l == 0 else f'{px}.weight_ih_l{l}'
+                last = 'fc_audio.4.bias' if l == Lyr - 1 else f'{px}.bias_hh_l{l}_reverse'
+                if l == 0 and self.variant == 'clf':
+                    post.append(self._span('ln.weight', last))
+                else:
+                    in_call[l] = self._span(first, last)
+            return in_call, post
         for l in range(Lyr):
             first, last = f'{px}.weight_ih_l{l}', ('fc_audio.4.bias' if l == Lyr - 1 else f'{px}.bias_hh_l{l}')
             if l == 0 and self.variant == 'clf':
@@ -529,6 +608,8 @@ class AudioGRU(nn.Module):
     def backward(self, dz):
         if self._chunked is not None:
             return self._backward_chunked(dz)
+        if self.bidirectional:
+            return self._backward_bidirectional(dz)
         x, xn, rnn, lengths = self._saved
         dpool = self._head.backward(dz)
         P = self._params
@@ -540,6 +621,24 @@ class AudioGRU(nn.Module):
                           self._rnn_g[0], self._rnn_g[2], P['ln.weight']._grad, P['ln.bias']._grad)
         else:
             rnn.backward(xn, self._rnn_w, self._rnn_g, dpooled=dpool, dx=None, grad_sync=gs, lengths=lengths)
+        self._grad_ready = True
+        parallel.finish_grad_sync(self, in_call, post)
+
+    def _backward_bidirectional(self, dz):
+        x, xn, rnn, lengths, out, att = self._saved
+        P = self._params
+        dctx = self._head.backward(dz)
+        dout, dh_n = L.attn_bwd(dctx, out, P['attention_layer.0.weight'].data, att, 2 * self.rnn_layers,
+                                P['attention_layer.0.weight']._grad, P['attention_layer.0.bias']._grad, lengths=lengths)
+        in_call, post = self.sync_plan()
+        gs = parallel.make_grad_sync(self, in_call)
+        if self.variant == 'clf':
+            rnn.backward(xn, self._rnn_w_fold, self._rnn_g_fold, dy=dout, dh_n=dh_n, dx=None, grad_sync=gs, lengths=lengths)
+            w, g = self._rnn_w, self._rnn_g
+            L.ln_fold_bwd_multi([w[0], w[4]], self._fold2[2], self._fold2[3], P['ln.weight'].data, P['ln.bias'].data,
+                                [g[0], g[4]], [g[2], g[6]], P['ln.weight']._grad, P['ln.bias']._grad)
+        else:
+            rnn.backward(xn, self._rnn_w, self._rnn_g, dy=dout, dh_n=dh_n, dx=None, grad_sync=gs, lengths=lengths)
         self._grad_ready = True
         parallel.finish_grad_sync(self, in_call, post)
 

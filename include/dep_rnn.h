@@ -485,6 +485,19 @@ int dep_ln_fold_fwd(const float* W, const float* b, const float* gamma, const fl
                     float* Wf, float* bf, int J, int F, void* stream);
 int dep_ln_fold_bwd(const float* W, const float* dWf, const float* dbf, const float* gamma, const float* beta,
                     float* dW, float* db, float* dgamma, float* dbeta, int J, int F, void* stream);
+/* The fold for npieces in {1, 2} maps W_k (J,F), b_k (J) that consume the SAME LayerNorm (weight_ih_l0 and weight_ih_l0_reverse of
+ * a bidirectional stack).  W, b, Wf, bf, dWf, dbf, dW, db are HOST arrays of npieces device pointers (read during the call, as
+ * dep_grad_sqnorm reads its ranges); gamma, beta, dgamma, dbeta are device vectors (F).  One launch each.
+ *   forward : Wf_k = W_k*gamma, bf_k = b_k + W_k beta
+ *   backward: dW_k = dWf_k*gamma + dbf_k beta^T, db_k = dbf_k, and -- WRITTEN, not added --
+ *             dgamma[f] = sum_k sum_j dWf_k[j,f] W_k[j,f], dbeta[f] = sum_k sum_j W_k[j,f] dbf_k[j]
+ *             in a fixed order: piece 0's sum, then piece 1's, added once; no atomics, the same bits on every run.
+ * npieces == 1 gives the bits of dep_ln_fold_fwd / dep_ln_fold_bwd.  Arguments are checked before any HIP call. */
+int dep_ln_fold_fwd_multi(const float* const* W, const float* const* b, const float* gamma, const float* beta,
+                          float* const* Wf, float* const* bf, int npieces, int J, int F, void* stream);
+int dep_ln_fold_bwd_multi(const float* const* W, const float* const* dWf, const float* const* dbf, const float* gamma,
+                          const float* beta, float* const* dW, float* const* db, float* dgamma, float* dbeta,
+                          int npieces, int J, int F, void* stream);
 /* dgamma/dbeta are written; dx may be NULL (the reference never consumes it).
  * workspace: dep_layernorm_bwd_workspace_bytes. */
 size_t dep_layernorm_bwd_workspace_bytes(int rows, int F);
