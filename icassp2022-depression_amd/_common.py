@@ -434,11 +434,40 @@ def train_epoch(model, optimizer, n_rows, batch_size, step, after_step=None, row
     return total.item()
 
 
-def fusion_forward(model, rows):
+def fusion_forward(model, rows, lengths=None):
     """pretrained_feature -> cat(text, audio) -> head of the fusion loops (fuse_net_whole.py:441-448): `rows` is what
-    fusion_net.pretrained_feature takes, PairFeeder rows or a list slice of pairs.  Returns (text_feature, audio_feature, output)."""
-    text_feature, audio_feature = model.pretrained_feature(rows)
+    fusion_net.pretrained_feature takes, PairFeeder rows or a list slice of pairs; `lengths` the (audio_lengths, text_lengths) of a
+    ragged batch (PairFeeder.lengths_rows), None for a dense one.  Returns (text_feature, audio_feature, output)."""
+    text_feature, audio_feature = model.pretrained_feature(rows) if lengths is None else model.pretrained_feature(rows, lengths=lengths)
     return text_feature, audio_feature, model(concat_features(text_feature, audio_feature))
+
+
+def fusion_audio_state(model, audio_state_dict, listed):
+    """What the fusion scripts' transplant() loads from an audio checkpoint.  A unidirectional model and checkpoint: the `listed`
+    keys, as the reference lists them.  A model built with audio_bidirectional=True: every `lstm_net_audio.*` key of the checkpoint,
+    `_reverse` ones included, the checkpoint's `attention_layer.0.*` under the fusion model's `attention_layer_audio.0.*`, and the
+    listed keys that are not the stack's.  A unidirectional checkpoint offered to a bidirectional model, or the reverse, is a
+    DepError naming the first key without a counterpart: strict=False would leave random reverse weights."""
+    bi = bool(getattr(model, 'audio_bidirectional', False))
+    rev = [k for k in audio_state_dict if k.startswith('lstm_net_audio.') and k.endswith('_reverse')]
+    if not bi:
+        if rev:
+            raise L.DepError(f'transplant: the audio checkpoint is bidirectional ({rev[0]} has no counterpart in this model): build the '
+                             "fusion model with audio_bidirectional=True (config['audio_bidirectional'])")
+        return {k: audio_state_dict[k] for k in listed}
+    want = [k for k in model.state_dict() if k.startswith('lstm_net_audio.')]
+    out = {}
+    for k in want:
+        if k not in audio_state_dict:
+            raise L.DepError(f'transplant: the fusion model is bidirectional in its audio branch and the audio checkpoint has no {k}: '
+                             "it is a unidirectional checkpoint (config['bidirectional'] = False)")
+        out[k] = audio_state_dict[k]
+    for k in ('weight', 'bias'):
+        if f'attention_layer.0.{k}' not in audio_state_dict:
+            raise L.DepError(f'transplant: the audio checkpoint has no attention_layer.0.{k} for attention_layer_audio.0.{k}')
+        out[f'attention_layer_audio.0.{k}'] = audio_state_dict[f'attention_layer.0.{k}']
+    out.update({k: audio_state_dict[k] for k in listed if not k.startswith('lstm_net_audio.')})
+    return out
 
 
 def mae_rmse(y, pred):
@@ -639,14 +668,21 @@ class PairFeeder:
     """The fusion scripts' list of [audio_i, text_i] pairs (fuse_net_whole.py:27, grown by append in the fold loop) as two
     HBM-resident fp32 tensors, stacked and uploaded once per (list object, length); rows(a, b) = the (audio, text) tensors of
     idxs[a:b], which `fusion_net.pretrained_feature` accepts in place of the list slice.  Lists whose items differ in shape keep
-    the per-batch path (rows() then returns the list slice itself)."""
+    the per-batch path (rows() then returns the list slice itself).
+    ragged=True: the items may differ in length, audio_i (Ta_i, Fa) and text_i (Tt_i, Ft).  Each modality is padded once with
+    pad_ragged, the two int32 length vectors of `idxs` stay on the device, rows(a, b) are the padded tensors and lengths_rows(a, b)
+    the (audio_lengths, text_lengths) views that go with them -- `pretrained_feature(rows, lengths=...)`."""
 
-    def __init__(self, pairs, idxs, device):
+    def __init__(self, pairs, idxs, device, ragged=False):
         self.pairs = pairs
         self.idxs = [int(i) for i in idxs]
         self.device = device
         self.ok = False
+        self.len_dev = None
         n = len(pairs)
+        if ragged:
+            self._init_ragged(n)
+            return
         if n == 0:
             return
         hit = _dev_cache.get('fuse_pairs')
@@ -676,6 +712,39 @@ class PairFeeder:
             _dev_cache['fuse_pairs'] = (pairs, key, (self.Xa, self.Xt))
         self.idx_dev = torch.as_tensor(np.asarray(self.idxs, dtype=np.int64), device=device)
         self.ok = True
+
+    def _init_ragged(self, n):
+        if n == 0:
+            raise ValueError('PairFeeder(ragged=True): no pairs')
+        if any(i < 0 or i >= n for i in self.idxs):       # the device gather does not range-check
+            raise IndexError(f'pair index out of bounds for a list of {n} pairs')
+        shapes = tuple((np.shape(e[0]), np.shape(e[1])) for e in self.pairs)
+        def probe(e):
+            a, t = np.asarray(e[0]).reshape(-1), np.asarray(e[1]).reshape(-1)
+            return (float(a[0]) + float(a[a.size // 2]) if a.size else 0.0) + (float(t[0]) + float(t[t.size // 2]) if t.size else 0.0)
+        # the key covers what the padded arrays are made of: every item's shape (so every length), and the dense feeder's probes
+        key = (n, shapes, str(self.device), float(np.asarray(self.pairs[0][0], dtype=np.float64).sum() + np.asarray(self.pairs[-1][1], dtype=np.float64).sum()),
+               float(sum(probe(e) for e in self.pairs)))
+        hit = _dev_cache.get('fuse_pairs_ragged')
+        if hit is not None and hit[0] is self.pairs and hit[1] == key:
+            self.Xa, self.Xt, la, lt = hit[2]
+        else:
+            xa, la = pad_ragged([e[0] for e in self.pairs])
+            xt, lt = pad_ragged([e[1] for e in self.pairs])
+            if (xa.size + xt.size) * 4 > float(os.environ.get('DEP_FEATURES_HBM_GB', '64')) * 2 ** 30:
+                raise ValueError('PairFeeder(ragged=True): the padded pair arrays exceed DEP_FEATURES_HBM_GB; a ragged corpus has no streamed path')
+            self.Xa, self.Xt = torch.from_numpy(xa).to(self.device), torch.from_numpy(xt).to(self.device)
+            _dev_cache['fuse_pairs_ragged'] = (self.pairs, key, (self.Xa, self.Xt, la, lt))
+        sel = np.asarray(self.idxs, dtype=np.int64)
+        self.idx_dev = torch.as_tensor(sel, device=self.device)
+        # gathered once, on the host: lengths_rows is then always a pair of views
+        self.len_dev = (torch.as_tensor(np.ascontiguousarray(la[sel], dtype=np.int32), device=self.device),
+                        torch.as_tensor(np.ascontiguousarray(lt[sel], dtype=np.int32), device=self.device))
+        self.ok = True
+
+    def lengths_rows(self, a, b):
+        """(audio_lengths, text_lengths) of rows(a, b), int32 device views (no gather, no host synchronisation); None for a dense feeder."""
+        return None if self.len_dev is None else (self.len_dev[0][a:b], self.len_dev[1][a:b])
 
     def rows(self, a, b):
         if not self.ok:

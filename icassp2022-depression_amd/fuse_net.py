@@ -35,6 +35,7 @@ config = {
     'text_hidden_dims': 128,
     'cuda': False,
     'lambda': 1e-2,
+    'audio_bidirectional': False,      # True: the audio branch is the bidirectional AudioBiLSTM's encoder (BiGRU + attention)
 }
 
 model = None
@@ -64,9 +65,9 @@ def load_features(root=None):
 
 class fusion_net(models.FusionNet):
     def __init__(self, text_embed_size, text_hidden_dims, rnn_layers, dropout, num_classes,
-                 audio_hidden_dims, audio_embed_size, seed=None):
+                 audio_hidden_dims, audio_embed_size, seed=None, audio_bidirectional=False):
         super().__init__(text_embed_size, text_hidden_dims, rnn_layers, dropout, num_classes, audio_hidden_dims,
-                         audio_embed_size, variant='reg', seed=seed)
+                         audio_embed_size, variant='reg', seed=seed, audio_bidirectional=audio_bidirectional)
 
 
 class MyLoss(models.MyLoss):
@@ -77,7 +78,8 @@ class MyLoss(models.MyLoss):
 def build(seed=None):
     global model, optimizer, criterion
     model = fusion_net(config['text_embed_size'], config['text_hidden_dims'], config['rnn_layers'], config['dropout'],
-                       config['num_classes'], config['audio_hidden_dims'], config['audio_embed_size'], seed=seed)
+                       config['num_classes'], config['audio_hidden_dims'], config['audio_embed_size'], seed=seed,
+                       audio_bidirectional=config.get('audio_bidirectional', False))
     optimizer = nn.Adam(model.parameters(), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'),
                         accumulate_steps=config.get('accum_steps', 1), **_common.optim_options(config))
     criterion = MyLoss(**_common.reg_options(config))       # config['loss'] / 'loss_beta' / 'loss_delta'; absent: the reference's SmoothL1
@@ -90,13 +92,13 @@ def train(model, epoch):
     idx = list(train_dep_idxs) + list(train_non_idxs)
     pred_dev = _common.prediction_buffer(len(idx), model.device)       # zero-filled; every rank writes its own rows
     Y_train = [fuse_targets[i] for i in idx]
-    feed = _common.PairFeeder(fuse_features, idx, model.device)
+    feed = _common.PairFeeder(fuse_features, idx, model.device, ragged=config.get('ragged', False))
     # config['sample_weights']: None, or 'balanced' = n / (2 * size of its group) per row of the two lists iterated here
     row_weight = _common.sample_row_weight(config, (train_dep_idxs, train_non_idxs))
     W_dev = None if row_weight is None else _common.device_labels(row_weight, model.device)
 
     def step(a, b, then):
-        text_feature, audio_feature, output = _common.fusion_forward(model, feed.rows(a, b))
+        text_feature, audio_feature, output = _common.fusion_forward(model, feed.rows(a, b), feed.lengths_rows(a, b))
         if W_dev is None:
             return criterion(text_feature, audio_feature, Y_train[a:b], model), output
         return criterion(text_feature, audio_feature, Y_train[a:b], model, weight=W_dev[a:b]), output
@@ -120,9 +122,9 @@ def evaluate(model, fold, train_mae):
     pred = np.array([])
     idx = list(test_dep_idxs) + list(test_non_idxs)
     Y_test = [fuse_targets[i] for i in idx]
-    feed = _common.PairFeeder(fuse_features, idx, model.device)
+    feed = _common.PairFeeder(fuse_features, idx, model.device, ragged=config.get('ragged', False))
     for lo, hi in _common.minibatches(len(idx), config['batch_size']):
-        text_feature, audio_feature, output = _common.fusion_forward(model, feed.rows(lo, hi))
+        text_feature, audio_feature, output = _common.fusion_forward(model, feed.rows(lo, hi), feed.lengths_rows(lo, hi))
         loss = criterion(text_feature, audio_feature, Y_test[lo:hi], model)
         pred = np.hstack((pred, output.data.flatten().cpu().numpy()))
         total_loss += loss.item()
@@ -169,13 +171,13 @@ def evaluate_text(model):
 
 def transplant(model, text_state_dict, audio_state_dict):
     """Reference lines 562-583 (no `ln` here; every parameter keeps requires_grad=True, yet only
-    fc_final.0.weight is reached by the loss)."""
+    fc_final.0.weight is reached by the loss).  audio_bidirectional: as fuse_net_whole.transplant (_common.fusion_audio_state)."""
     audio_keys = ['lstm_net_audio.weight_ih_l0', 'lstm_net_audio.weight_hh_l0', 'lstm_net_audio.bias_ih_l0',
                   'lstm_net_audio.bias_hh_l0', 'lstm_net_audio.weight_ih_l1', 'lstm_net_audio.weight_hh_l1',
                   'lstm_net_audio.bias_ih_l1', 'lstm_net_audio.bias_hh_l1', 'fc_audio.1.weight', 'fc_audio.1.bias',
                   'fc_audio.4.weight', 'fc_audio.4.bias']
     model.load_state_dict(text_state_dict, strict=False)
-    model.load_state_dict({k: audio_state_dict[k] for k in audio_keys}, strict=False)
+    model.load_state_dict(_common.fusion_audio_state(model, audio_state_dict, audio_keys), strict=False)
     for param in model.parameters():
         param.requires_grad = True
 

@@ -33,6 +33,7 @@ config = {
     'text_hidden_dims': 128,
     'cuda': False,
     'lambda': 1e-5,
+    'audio_bidirectional': False,      # True: the audio branch is the bidirectional AudioBiLSTM's encoder (BiGRU + attention)
 }
 
 model = None
@@ -70,9 +71,9 @@ class fusion_net(models.FusionNet):
     """Reference lines 245-374."""
 
     def __init__(self, text_embed_size, text_hidden_dims, rnn_layers, dropout, num_classes,
-                 audio_hidden_dims, audio_embed_size, seed=None):
+                 audio_hidden_dims, audio_embed_size, seed=None, audio_bidirectional=False):
         super().__init__(text_embed_size, text_hidden_dims, rnn_layers, dropout, num_classes, audio_hidden_dims,
-                         audio_embed_size, variant='clf', seed=seed)
+                         audio_embed_size, variant='clf', seed=seed, audio_bidirectional=audio_bidirectional)
 
 
 class MyLoss(models.MyLoss):
@@ -92,7 +93,8 @@ def build(seed=None):
     """The module-level construction the reference performs at import (lines 413-419)."""
     global model, optimizer, criterion
     model = fusion_net(config['text_embed_size'], config['text_hidden_dims'], config['rnn_layers'], config['dropout'],
-                       config['num_classes'], config['audio_hidden_dims'], config['audio_embed_size'], seed=seed)
+                       config['num_classes'], config['audio_hidden_dims'], config['audio_embed_size'], seed=seed,
+                       audio_bidirectional=config.get('audio_bidirectional', False))
     optimizer = nn.Adam(model.parameters(), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'),
                         accumulate_steps=config.get('accum_steps', 1), **_common.optim_options(config))
     criterion = MyLoss()
@@ -107,10 +109,10 @@ def train(epoch, train_idxs):
     n_train = len(train_idxs)
     Y_train = [fuse_targets[idx] for idx in train_idxs]
     Y_dev = _common.device_labels(np.asarray(Y_train), model.device, config['num_classes'])
-    feed = _common.PairFeeder(fuse_features, train_idxs, model.device)       # the pairs X_train = [fuse_features[i] ...], in HBM
+    feed = _common.PairFeeder(fuse_features, train_idxs, model.device, ragged=config.get('ragged', False))       # the pairs X_train = [fuse_features[i] ...], in HBM
 
     def step(a, b, then):
-        text_feature, audio_feature, output = _common.fusion_forward(model, feed.rows(a, b))
+        text_feature, audio_feature, output = _common.fusion_forward(model, feed.rows(a, b), feed.lengths_rows(a, b))
         _common.count_correct(output, Y_dev[a:b], correct_dev)
         return criterion(text_feature, audio_feature, Y_train[a:b], model), output
     total_loss = _common.train_epoch(model, optimizer, n_train, config['batch_size'], step,
@@ -132,9 +134,9 @@ def evaluate(model, test_idxs, fold, train_idxs):
     total_loss = 0
     Y_test = [fuse_targets[idx] for idx in test_idxs]
     pred_dev = torch.empty(len(Y_test), 1, dtype=torch.int64, device=model.device)      # every mini-batch's arg-max lands here
-    feed = _common.PairFeeder(fuse_features, test_idxs, model.device)
+    feed = _common.PairFeeder(fuse_features, test_idxs, model.device, ragged=config.get('ragged', False))
     for lo, hi in _common.minibatches(len(Y_test), config['batch_size']):
-        text_feature, audio_feature, output = _common.fusion_forward(model, feed.rows(lo, hi))
+        text_feature, audio_feature, output = _common.fusion_forward(model, feed.rows(lo, hi), feed.lengths_rows(lo, hi))
         loss = criterion(text_feature, audio_feature, Y_test[lo:hi], model)
         _common.predict(output, out=pred_dev[lo:hi])
         total_loss += loss.item()
@@ -156,13 +158,15 @@ def transplant(model, text_state_dict, audio_state_dict):
     """The name-based weight transplant of reference lines 566-588: every key of the text checkpoint that
     exists in fusion_net is taken (strict=False: e.g. `fc_out.0.*` of a text_bilstm_whole checkpoint has
     no counterpart and is dropped -- SURVEY 2.1 quirk 5), then the listed audio keys (`fc_audio.4.*` is
-    listed but has no counterpart and is dropped too)."""
+    listed but has no counterpart and is dropped too).  A model built with audio_bidirectional=True takes a bidirectional audio
+    checkpoint: every `lstm_net_audio.*` key, and its `attention_layer.0.*` as `attention_layer_audio.0.*`
+    (_common.fusion_audio_state; a checkpoint of the other kind is a DepError)."""
     audio_keys = ['lstm_net_audio.weight_ih_l0', 'lstm_net_audio.weight_hh_l0', 'lstm_net_audio.bias_ih_l0',
                   'lstm_net_audio.bias_hh_l0', 'lstm_net_audio.weight_ih_l1', 'lstm_net_audio.weight_hh_l1',
                   'lstm_net_audio.bias_ih_l1', 'lstm_net_audio.bias_hh_l1', 'fc_audio.1.weight', 'fc_audio.1.bias',
                   'fc_audio.4.weight', 'fc_audio.4.bias', 'ln.weight', 'ln.bias']
     model.load_state_dict(text_state_dict, strict=False)
-    model.load_state_dict({k: audio_state_dict[k] for k in audio_keys}, strict=False)
+    model.load_state_dict(_common.fusion_audio_state(model, audio_state_dict, audio_keys), strict=False)
     for param in model.parameters():
         param.requires_grad = False
     model.fc_final[0].weight.requires_grad = True

@@ -130,9 +130,15 @@ def check_fusion_classifier(root, idxs_paths=('train_idxs_0.63_1.npy', 'train_id
     m.load_features(root)
     folds = [np.load(os.path.join(m.prefix, 'Features/TextWhole', f), allow_pickle=True) for f in idxs_paths]
     c = m.config
-    models = [_load_into(m.fusion_net(c['text_embed_size'], c['text_hidden_dims'], c['rnn_layers'], c['dropout'], c['num_classes'],
-                                      c['audio_hidden_dims'], c['audio_embed_size']),
-                         os.path.join(m.prefix, 'Model/ClassificationWhole/Fuse', f)) for f in model_paths]
+
+    def load(f):        # a checkpoint with `_reverse` audio keys was saved by a model built with audio_bidirectional=True
+        sd = _common.load_checkpoint_state_dict(os.path.join(m.prefix, 'Model/ClassificationWhole/Fuse', f))
+        bi = any(k.startswith('lstm_net_audio.') and k.endswith('_reverse') for k in sd)
+        model = m.fusion_net(c['text_embed_size'], c['text_hidden_dims'], c['rnn_layers'], c['dropout'], c['num_classes'],
+                             c['audio_hidden_dims'], c['audio_embed_size'], audio_bidirectional=bi)
+        model.load_state_dict(sd, strict=True)
+        return model
+    models = [load(f) for f in model_paths]
     ps, rs, fs, _ = check_fusion_folds(models, folds, c['batch_size'])
     return _mean_report(ps, rs, fs)
 

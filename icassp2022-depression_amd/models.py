@@ -741,12 +741,18 @@ class TextBiLSTM(nn.Module):
 
 class FusionNet(nn.Module):
     """Frozen audio-GRU + text-BiLSTM encoders -> concat(text, audio) -> Linear(no bias) head.
-    Only `fc_final.0.weight` trains (fuse_net_whole.py:590-593); the encoders run forward only."""
+    Only `fc_final.0.weight` trains (fuse_net_whole.py:590-593); the encoders run forward only.
+    audio_bidirectional: the audio branch is the frozen encoder of the bidirectional AudioGRU -- [LayerNorm] -> BiGRU ->
+    attention_net_with_w(output, h_n) -> fc_audio.1 -- with `lstm_net_audio.*_reverse` keys and the attention pair under
+    `attention_layer_audio.0.*` (the reference's fusion class gives `attention_layer.0.*` to the text attention)."""
 
     def __init__(self, text_embed_size, text_hidden_dims, rnn_layers, dropout, num_classes, audio_hidden_dims,
-                 audio_embed_size, variant='clf', seed=None):
+                 audio_embed_size, variant='clf', seed=None, audio_bidirectional=False):
         super().__init__()
         self.variant = variant
+        self.audio_bidirectional = bi = bool(audio_bidirectional)
+        if bi:          # the sweeps AudioGRU chooses for this width; a DepError by name where no bidirectional sweep runs it
+            self._bi_impl = AudioGRU._bidirectional_impl(audio_embed_size, audio_hidden_dims, rnn_layers)
         self.text_embed_size = Ft = text_embed_size; self.audio_embed_size = Fa = audio_embed_size
         self.text_hidden_dims = Ht = text_hidden_dims; self.audio_hidden_dims = Ha = audio_hidden_dims
         self.rnn_layers = Lyr = rnn_layers; self.dropout = float(dropout); self.num_classes = num_classes
@@ -765,10 +771,12 @@ class FusionNet(nn.Module):
             self._add(n, s, live=False)
         init.update(nn.default_rnn_init(rt, Ht, gen))
         lin('fc_out.1.weight', 'fc_out.1.bias', Ht, Ht, False)
-        ra = _rnn_names('lstm_net_audio', Fa, Ha, Lyr, 1, 3)
+        ra = _rnn_names('lstm_net_audio', Fa, Ha, Lyr, 2 if bi else 1, 3)
         for n, s in ra:
             self._add(n, s, live=False)
         init.update(nn.default_rnn_init(ra, Ha, gen))
+        if bi:
+            lin('attention_layer_audio.0.weight', 'attention_layer_audio.0.bias', Ha, Ha, False)
         lin('fc_audio.1.weight', 'fc_audio.1.bias', Ha, Ha, False)
         if variant == 'clf':
             self._add('ln.weight', (Fa,), live=False); self._add('ln.bias', (Fa,), live=False)
@@ -779,7 +787,10 @@ class FusionNet(nn.Module):
         self._wt = [self._params[n].data for n, _ in rt]
         self._wa = [self._params[n].data for n, _ in ra]
         self._rnn_t = _RnnCache(L.CELL_LSTM, Ft, Ht, Lyr, 2, self.dropout, L.POOL_NONE, self.device)
-        self._rnn_a = _RnnCache(L.CELL_GRU, Fa, Ha, Lyr, 1, self.dropout, L.POOL_SUM, self.device)
+        if bi:
+            self._rnn_a = _RnnCache(L.CELL_GRU, Fa, Ha, Lyr, 2, self.dropout, L.POOL_NONE, self.device, impl=self._bi_impl)
+        else:
+            self._rnn_a = _RnnCache(L.CELL_GRU, Fa, Ha, Lyr, 1, self.dropout, L.POOL_SUM, self.device)
         self.fc_final = [self._params['fc_final.0.weight']]       # `model.fc_final[0].weight`-style access
         self._params['fc_final.0.weight'].weight = self._params['fc_final.0.weight']
 
@@ -799,10 +810,21 @@ class FusionNet(nn.Module):
         xa = np.stack([np.asarray(e[0]) for e in x]); xt = np.stack([np.asarray(e[1]) for e in x])
         return self._to_dev(xa), self._to_dev(xt)
 
-    def pretrained_feature(self, x):
+    def pretrained_feature(self, x, lengths=None):
         """fusion_net.pretrained_feature (fuse_net_whole.py:336-366): no gradients; Dropout stays active in
-        train() mode exactly as in the reference."""
+        train() mode exactly as in the reference.
+        lengths: (audio_lengths, text_lengths) of a ragged batch -- each None or B integers (a host sequence or an int32 device
+        vector): x is padded (_common.pad_ragged), row b of a modality is its own lengths[b] steps long.  The reverse sweeps start
+        at a row's last step, both attentions and the unidirectional audio pool run over its own steps; a row of length 0 has
+        context / pool 0, and the head is applied to that zero vector."""
         xa, xt = self._split(x)
+        if lengths is None:
+            la = lt = None
+        else:
+            if not isinstance(lengths, (tuple, list)) or len(lengths) != 2:
+                raise L.DepError('pretrained_feature: lengths is the pair (audio_lengths, text_lengths), each None or B integers')
+            la = _RnnCache.lengths_on(lengths[0], xa.shape[0], self.device)
+            lt = _RnnCache.lengths_on(lengths[1], xt.shape[0], self.device)
         training = self.training
         seed = nn.next_dropout_seed() if training else 0
         p = self.dropout if training else 0.0
@@ -813,8 +835,8 @@ class FusionNet(nn.Module):
         # text encoder
         rnn = self._rnn_t.get(B, T, mode)
         h_n = torch.empty(2 * self.rnn_layers, B, self.text_hidden_dims, dtype=torch.float32, device=self.device)
-        rnn.forward(xt, self._wt, seed=seed, h_n=h_n)
-        ctx, _ = L.attn_fwd(rnn.layer_output(), h_n, P['attention_layer.0.weight'].data, P['attention_layer.0.bias'].data)
+        rnn.forward(xt, self._wt, seed=seed, h_n=h_n, lengths=lt)
+        ctx, _ = L.attn_fwd(rnn.layer_output(), h_n, P['attention_layer.0.weight'].data, P['attention_layer.0.bias'].data, lengths=lt)
         tf = _mlp_feature(ctx, P['fc_out.1.weight'].data, P['fc_out.1.bias'].data, p, seed, (L.SITE_FC0, L.SITE_FC1))
         # audio encoder
         Ba, Ta, Fa = xa.shape
@@ -823,8 +845,15 @@ class FusionNet(nn.Module):
         else:
             xn = xa.view(Ba * Ta, Fa)
         rna = self._rnn_a.get(Ba, Ta, mode)
-        pooled = torch.empty(Ba, self.audio_hidden_dims, dtype=torch.float32, device=self.device)
-        rna.forward(xn, self._wa, seed=seed + 1, pooled=pooled)
+        if self.audio_bidirectional:
+            # nothing trains, so no LayerNorm fold: the affine above and the raw weights; the top sequence is read in place
+            h_na = torch.empty(2 * self.rnn_layers, Ba, self.audio_hidden_dims, dtype=torch.float32, device=self.device)
+            rna.forward(xn, self._wa, seed=seed + 1, h_n=h_na, lengths=la)
+            pooled, _ = L.attn_fwd(rna.layer_output(), h_na, P['attention_layer_audio.0.weight'].data,
+                                   P['attention_layer_audio.0.bias'].data, lengths=la)
+        else:
+            pooled = torch.empty(Ba, self.audio_hidden_dims, dtype=torch.float32, device=self.device)
+            rna.forward(xn, self._wa, seed=seed + 1, pooled=pooled, lengths=la)
         af = _mlp_feature(pooled, P['fc_audio.1.weight'].data, P['fc_audio.1.bias'].data, p, seed, (L.SITE_FC2, L.SITE_FC3))
         return tf, af
 
