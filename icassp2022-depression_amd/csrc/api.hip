@@ -146,7 +146,7 @@ extern "C" long dep_instance_table_read(char* buf, long cap) {
     if (rows.empty()) {
         const dep_instance_sink add = [](const char* text) { rows.insert(text); };
         dep_cluster_gru_instance_texts(add); dep_cluster16_instance_texts(add); dep_cluster_lstm_instance_texts(add);
-        dep_fused2_fwd_instance_texts(add); dep_fused2_bwd_instance_texts(add);
+        dep_fused2_fwd_instance_texts(add); dep_fused2_bwd_instance_texts(add); dep_local_lstm_instance_texts(add);
     }
     std::string all;
     for (const auto& s : rows) { all += s; all += '\n'; }
@@ -187,6 +187,7 @@ struct Layout {
     bool fused2;                     // 2-layer GRU, H = 256: both layers in one launch (rnn_fused2*.hip) where the call's plan allows it
     size_t wih_img;                  // workspace: packed W_ih of layer 1 for the fused launches
     size_t hxstage;                  // workspace (impl 4 / 5 / 6 only): dirs x B x H floats, a layer's hx copied aside when T = 1 and h_n overlaps it
+    bool local_lstm;                 // impl 8: every forward on lstm_fwd_local (rnn_local_lstm.hip); no exchange buffer, nothing of `cluster` holds
 };
 
 // A bidirectional GRU runs the tile-MFMA sweeps (gru_*_mfma<JPW, RAG, true>) and nothing else: it has no generic, cluster or fused
@@ -234,8 +235,27 @@ int bicluster_refusal(const dep_rnn_desc* d, const char* who) {
     return DEP_ERR_ARG;
 }
 
+// impl = 8, "the exchange-free per-layer LSTM forward": lstm_fwd_local runs every forward, one workgroup per (direction, 16-utterance tile)
+// with the whole W_hh of its direction in registers -- no exchange buffer, no co-residency, any batch in one launch.  Forward only: the run
+// modes no backward follows (DEP_RUN_EVAL, DEP_RUN_DROPOUT_ONLY), LSTM, H = 128, dirs 1 or 2.  It takes hx, cx and c_n, dense and ragged.
+bool local_impl(const dep_rnn_desc* d) { return d->impl == 8; }
+bool local_ok(const dep_rnn_desc* d) {
+    return dep_local_lstm_ok(d->cell, d->H, d->dirs) && (d->training == DEP_RUN_EVAL || d->training == DEP_RUN_DROPOUT_ONLY) && d->L >= 1 && d->L <= MAXL;
+}
+
+// dep_last_error for an impl = 8 descriptor refused by the rule above (DEP_OK for any other descriptor)
+int local_refusal(const dep_rnn_desc* d, const char* who) {
+    if (!d || !local_impl(d) || local_ok(d)) return DEP_OK;
+    dep_set_error("%s: impl = 8 (the exchange-free per-layer LSTM forward) is a forward-only LSTM with H = 128: cell must be DEP_CELL_LSTM, dirs 1 or 2, "
+                  "L 1 .. %d and the run mode DEP_RUN_EVAL or DEP_RUN_DROPOUT_ONLY (DEP_RUN_TRAIN needs a backward, which it does not have); "
+                  "got cell = %d, H = %d, dirs = %d, L = %d, run mode = %d", who, MAXL, d->cell, d->H, d->dirs, d->L, d->training);
+    return DEP_ERR_ARG;
+}
+
 bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     if (!d || d->B <= 0 || d->T <= 0 || d->F <= 0 || d->H <= 0 || d->L < 1 || d->L > MAXL) return false;
+    if (local_impl(d) && !local_ok(d)) return false;
+    lo.local_lstm = local_impl(d);
     if (percluster_impl(d) && !percluster_ok(d)) return false;
     if (bicluster_impl(d) && !bicluster_ok(d)) return false;
     if (d->cell == DEP_CELL_GRU) { if (d->dirs != 1 && !(d->dirs == 2 && (bigru_ok(d) || bicluster_impl(d)))) return false; }
@@ -322,7 +342,7 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     // (a bidirectional GRU is never planned onto the cluster, 16-unit-member or fused kernels: dep_cluster_ok does not look at dirs)
     const bool cok = d->cell == DEP_CELL_GRU ? d->dirs == 1 && dep_cluster_ok(d->cell, d->H, d->B, d->dirs) : dep_cluster_lstm_ok(d->H, d->B, d->dirs);
     if (d->impl == 3 && !cok) return false;
-    lo.cluster = cok && (d->impl == 0 || d->impl == 3 || percluster_impl(d));
+    lo.cluster = cok && (d->impl == 0 || d->impl == 3 || percluster_impl(d));      // (impl 8: none of the cluster parts)
     // impl 6 (checked above): the bidirectional forward's exchange buffer and the hx staging area, and none of what `cluster` selects
     lo.cluster_fwd = bicluster_impl(d);
     // impl 7: the larger of the bidirectional forward's buffer and the bidirectional backward's
@@ -354,14 +374,18 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
 extern "C" size_t dep_rnn_reserve_bytes(const dep_rnn_desc* d) {
     Layout lo;
     if (!make_layout(d, lo)) {
-        if (!percluster_refusal(d, "dep_rnn_reserve_bytes") && !bicluster_refusal(d, "dep_rnn_reserve_bytes")) (void)bigru_refusal(d, "dep_rnn_reserve_bytes");
+        if (!percluster_refusal(d, "dep_rnn_reserve_bytes") && !bicluster_refusal(d, "dep_rnn_reserve_bytes") && !local_refusal(d, "dep_rnn_reserve_bytes"))
+            (void)bigru_refusal(d, "dep_rnn_reserve_bytes");
         return 0;
     }
     return lo.reserve_floats * sizeof(float);
 }
 extern "C" size_t dep_rnn_workspace_bytes(const dep_rnn_desc* d) {
     Layout lo;
-    if (!make_layout(d, lo)) { if (!percluster_refusal(d, "dep_rnn_workspace_bytes")) (void)bicluster_refusal(d, "dep_rnn_workspace_bytes"); return 0; }
+    if (!make_layout(d, lo)) {
+        if (!percluster_refusal(d, "dep_rnn_workspace_bytes") && !bicluster_refusal(d, "dep_rnn_workspace_bytes")) (void)local_refusal(d, "dep_rnn_workspace_bytes");
+        return 0;
+    }
     return lo.ws_floats * sizeof(float);
 }
 // byte offset of layer l's output sequence (B,T,H*dirs) inside the reserve (zero-copy access for the caller)
@@ -433,6 +457,7 @@ enum FwdKernel { FWD_FUSED2,          // both GRU layers in one launch, the per-
                  FWD_CLUSTER16,       // GRU, 16-unit members (rnn_cluster16.hip)
                  FWD_CLUSTER_GRU,     // GRU, 32-unit members (rnn_cluster.hip)
                  FWD_CLUSTER_LSTM,    // (Bi)LSTM cluster (rnn_cluster_lstm.hip)
+                 FWD_LOCAL_LSTM,      // (Bi)LSTM, one workgroup per (direction, tile), no exchange (rnn_local_lstm.hip; impl 8)
                  FWD_TILE };          // tile-MFMA / generic sweep (rnn_sweep.hip picks by impl and H)
 enum BwdKernel { BWD_FUSED2, BWD_CLUSTER_GRU, BWD_CLUSTER_LSTM, BWD_TILE };
 // the split-precision recurrent-weight images (the fp32 fragment images of dep_pack_whh are RnnPlan::whh_f32)
@@ -470,19 +495,21 @@ struct RnnPlan {
 // backward image in wpT (WHH_BWD_SPLIT in split mode, the member-sliced fp32 image in exact mode) instead of the tile backward's; fp32 saved
 // gates, fp32 gate-gradient rows (pk = false: dg4 is off), the unpaired contractions.  Modes 2 / 3 keep the split instance; the contractions
 // behind the sweep follow the mode on their own (a mode-3 backward is refused by dep_rnn_backward: no PK image to take the hi rows of).
+// impl = 8 (lo.local_lstm): FWD_LOCAL_LSTM, dense or ragged, whatever `excl` says: the split instance on the forward image of
+// pack_lstm_split_kernel in modes 1 / 2 / 3, the exact instance on the fp32 fragment image in mode 0.  No backward is ever planned on it.
 RnnPlan make_plan(const dep_rnn_desc* d, const Layout& lo, int mode, bool excl, bool ragged) {
     const RnnSwitches& sw = dep_rnn_switches();
     const bool gru = d->cell == DEP_CELL_GRU;
     RnnPlan p{};
     p.excl = excl; p.split = mode >= 1;
-    const bool csplit = (lo.cluster || lo.cluster_fwd) && p.split;      // the forward's recurrent-weight image is a split-precision one
+    const bool csplit = (lo.cluster || lo.cluster_fwd || lo.local_lstm) && p.split;      // the forward's recurrent-weight image is a split-precision one
     // the kernels that fill every CU (fused forward, 16-unit members) are not for a shared GPU; the fused BACKWARD does not care
     const bool cluster16 = lo.cluster && !percluster_impl(d) && dep_cluster16_ok(d->cell, d->H, d->B);
     p.fwd = (lo.fused2 && p.split && excl && !ragged) ? FWD_FUSED2 : (cluster16 && excl && !ragged) ? FWD_CLUSTER16
-          : lo.cluster_fwd ? FWD_CLUSTER_GRU : !lo.cluster ? FWD_TILE : gru ? FWD_CLUSTER_GRU : FWD_CLUSTER_LSTM;
+          : lo.cluster_fwd ? FWD_CLUSTER_GRU : lo.local_lstm ? FWD_LOCAL_LSTM : !lo.cluster ? FWD_TILE : gru ? FWD_CLUSTER_GRU : FWD_CLUSTER_LSTM;
     p.bwd = (lo.fused2 && sw.fused2_bwd && p.split && dep_fused2_bwd_fits(d->B, d->T) && !ragged) ? BWD_FUSED2
           : lo.cluster_bwd2 ? BWD_CLUSTER_GRU : !lo.cluster ? BWD_TILE : gru ? BWD_CLUSTER_GRU : BWD_CLUSTER_LSTM;
-    p.whh_f32 = lo.cluster ? !p.split : lo.cluster_fwd ? (!p.split || (lo.keep && !lo.cluster_bwd2)) : dep_sweep_use_mfma(d->H, d->impl);
+    p.whh_f32 = (lo.cluster || lo.local_lstm) ? !p.split : lo.cluster_fwd ? (!p.split || (lo.keep && !lo.cluster_bwd2)) : dep_sweep_use_mfma(d->H, d->impl);
     p.whh_fwd = !csplit ? WHH_NONE : !gru ? WHH_LSTM_PAIR : p.fwd == FWD_CLUSTER16 ? WHH_SPLIT16 : WHH_SPLIT32;
     p.whh_bwd = (!(lo.cluster || lo.cluster_bwd2) || !lo.keep || p.whh_fwd == WHH_LSTM_PAIR) ? WHH_NONE : p.split ? WHH_BWD_SPLIT : WHH_BWD_F32;
     // 16-bit saved gates: the kernels that implement them are the fused forward, the 32-unit-member forward and the 32-unit-member
@@ -496,7 +523,7 @@ RnnPlan make_plan(const dep_rnn_desc* d, const Layout& lo, int mode, bool excl, 
     // stack has the variant -- the fused 2-layer GRU forward and the burst backward with the 4H-wide gate-gradient rows.  Other
     // stacks run mode 3 exactly like mode 2 (single bf16 products, fp32 storage).
     p.bf16st = mode == 3 && lo.keep && p.sv16 && lo.fused2 && p.dg4 && d->T % 2 == 0 && dep_cluster_bwd_pk_ok(d->H, d->T);
-    p.pk = sw.dgi_pk && csplit && lo.BT % 2 == 0 &&
+    p.pk = sw.dgi_pk && csplit && !lo.local_lstm && lo.BT % 2 == 0 &&
            (gru ? p.dg4 && d->T % 2 == 0 && (p.bwd == BWD_FUSED2 || dep_cluster_bwd_pk_ok(d->H, d->T)) : d->dirs == 2 && dep_cluster_lstm_bwd_pk_ok(d->T));
     p.pk_fmt = (p.bf16st || mode >= 2) ? FMT_PKH : FMT_PK;
     p.dw_pair = p.dg4 && mode == 1;      // (the other precision modes never pair: they keep the single launches' target)
@@ -603,6 +630,7 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
     Layout lo;
     if (const int rf = percluster_refusal(d, "dep_rnn_forward")) return rf;
     if (const int rf = bicluster_refusal(d, "dep_rnn_forward")) return rf;
+    if (const int rf = local_refusal(d, "dep_rnn_forward")) return rf;
     if (const int rf = bigru_refusal(d, "dep_rnn_forward")) return rf;
     DEP_CHECK_ARG(make_layout(d, lo));
     const dep_rnn_state st = state ? *state : dep_rnn_state{nullptr, nullptr, nullptr};      // NULL and a struct of NULLs are the plain call
@@ -647,13 +675,13 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
     auto sweep_args = [&](int l, const unsigned* only_if) {
         dep_sweep_args a{};
         a.B = B; a.T = T; a.H = H; a.cell = d->cell; a.dirs = D; a.training = d->training; a.impl = d->impl;
-        a.split = ((lo.cluster || lo.cluster_fwd) && p.split) ? 1 : 0;
+        a.split = ((lo.cluster || lo.cluster_fwd || lo.local_lstm) && p.split) ? 1 : 0;
         for (int dd = 0; dd < D; ++dd) {
             const float* const* wl = weights + (size_t)(l * D + dd) * 4;
             a.w_hh[dd] = wl[1]; a.b_hh[dd] = wl[3]; a.wp[dd] = R + lo.wp[l][dd];
         }
         const bool dropl = lo.drop && l < L - 1;
-        a.gi = gi; a.y = yout(l, p.fwd == FWD_CLUSTER_LSTM && dropl); a.ldy = D * H;
+        a.gi = gi; a.y = yout(l, (p.fwd == FWD_CLUSTER_LSTM || p.fwd == FWD_LOCAL_LSTM) && dropl); a.ldy = D * H;
         a.ydrop = dropl ? R + lo.ydrop[l] : nullptr;
         a.drop_p = dropl ? d->dropout_p : 0.f; a.seed = d->seed; a.site = DEP_SITE_RNN0 + l;
         a.pooled = l == L - 1 ? pooled : nullptr;
@@ -741,7 +769,7 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
             DEP_CHECK_ARG(wl[0] && wl[1] && wl[2] && wl[3]);
             // recurrent weight images in MFMA fragment order (precision / clustering decide the format: RnnPlan)
             float* const wp = R + lo.wp[l][dd]; float* const wpT = lo.wpT[l][dd] == NOT_KEPT ? nullptr : R + lo.wpT[l][dd];
-            if (p.whh_f32) { rc = dep_pack_whh(wl[1], wp, wpT, G, H, s); if (rc) return rc; }
+            if (p.whh_f32) { rc = dep_pack_whh(wl[1], wp, lo.local_lstm ? nullptr : wpT, G, H, s); if (rc) return rc; }
             rc = p.whh_fwd == WHH_LSTM_PAIR ? dep_pack_cluster_lstm_split(wl[1], wp, lo.keep ? wpT : nullptr, H, s)
                : p.whh_fwd == WHH_SPLIT16 ? dep_pack_cluster16_fwd_split(wl[1], wp, H, s)
                : p.whh_fwd == WHH_SPLIT32 ? dep_pack_cluster_fwd_split(wl[1], wp, H, s) : DEP_OK;
@@ -780,6 +808,7 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
         }
         rc = p.fwd == FWD_CLUSTER16 ? dep_launch_cluster16_fwd(a, W + lo.xbuf, lo.xbuf_bytes)
            : p.fwd == FWD_CLUSTER_LSTM ? dep_launch_cluster_lstm_fwd(a, W + lo.xbuf, lo.xbuf_bytes)
+           : p.fwd == FWD_LOCAL_LSTM ? dep_launch_local_lstm_fwd(a)
            : p.fwd == FWD_CLUSTER_GRU ? dep_launch_cluster_fwd(a, W + lo.xbuf, lo.xbuf_bytes) : dep_launch_sweep_fwd(a);
         if (rc) return rc;
     }
@@ -826,6 +855,12 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
     Layout lo;
     if (const int rf = percluster_refusal(d, "dep_rnn_backward")) return rf;
     if (const int rf = bicluster_refusal(d, "dep_rnn_backward")) return rf;
+    if (d && local_impl(d)) {
+        if (const int rf = local_refusal(d, "dep_rnn_backward")) return rf;
+        dep_set_error("dep_rnn_backward: impl = 8 (the exchange-free per-layer LSTM forward) has no backward: its forwards run in DEP_RUN_EVAL and "
+                      "DEP_RUN_DROPOUT_ONLY and save no gates; train on impl 0 .. 3");
+        return DEP_ERR_ARG;
+    }
     if (d && bicluster_train_impl(d) && dep_get_gemm_mode() == 3 && bicluster_ok(d)) {
         dep_set_error("dep_rnn_backward: impl = 7 (the per-layer cluster sweeps of a bidirectional GRU) has no backward in GEMM mode 3: the bidirectional "
                       "sweep writes fp32 gate-gradient rows, not the PK image whose hi rows that mode reads; modes 0, 1 and 2 run (dep_set_gemm_mode)");

@@ -324,6 +324,9 @@ int dep_attn2_bwd(const float* dctx, const float* out, const float* alpha, const
 int dep_pack_cluster_fwd_split(const float* w_hh, float* out, int H, hipStream_t s);
 int dep_pack_cluster_lstm_split(const float* w_hh, float* wp, float* wpT, int H, hipStream_t s);
 int dep_launch_cluster16_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf_bytes);
+// rnn_local_lstm.hip: the exchange-free LSTM forward (impl 8; takes a.hx, a.cx, a.c_n and a.lengths, any batch in one launch)
+bool dep_local_lstm_ok(int cell, int H, int dirs);
+int dep_launch_local_lstm_fwd(const dep_sweep_args& a);
 // dep_instance_table_read: each cluster-family file hands `add` the text of every row its selection functions can return (it calls
 // them over their whole argument domain; duplicates are the caller's to drop).  Host only, no device call.
 typedef void (*dep_instance_sink)(const char* text);
@@ -332,6 +335,7 @@ void dep_cluster16_instance_texts(dep_instance_sink add);         // rnn_cluster
 void dep_cluster_lstm_instance_texts(dep_instance_sink add);      // rnn_cluster_lstm.hip
 void dep_fused2_fwd_instance_texts(dep_instance_sink add);        // rnn_fused2.hip
 void dep_fused2_bwd_instance_texts(dep_instance_sink add);        // rnn_fused2_bwd.hip
+void dep_local_lstm_instance_texts(dep_instance_sink add);        // rnn_local_lstm.hip
 
 int dep_gemm_internal(int transA, int transB, int M, int N, int K, const float* A, int lda,
                       const float* B, int ldb, float* C, int ldc, const float* bias, float beta,

@@ -36,6 +36,7 @@ config = {
     'cuda': False,
     'lambda': 1e-2,
     'audio_bidirectional': False,      # True: the audio branch is the bidirectional AudioBiLSTM's encoder (BiGRU + attention)
+    'text_impl': None,                 # 8: the frozen text BiLSTM runs the exchange-free forward (needs no CUs to itself); None: the cluster sweeps
 }
 
 model = None
@@ -65,9 +66,10 @@ def load_features(root=None):
 
 class fusion_net(models.FusionNet):
     def __init__(self, text_embed_size, text_hidden_dims, rnn_layers, dropout, num_classes,
-                 audio_hidden_dims, audio_embed_size, seed=None, audio_bidirectional=False):
+                 audio_hidden_dims, audio_embed_size, seed=None, audio_bidirectional=False, text_impl=None):
         super().__init__(text_embed_size, text_hidden_dims, rnn_layers, dropout, num_classes, audio_hidden_dims,
-                         audio_embed_size, variant='reg', seed=seed, audio_bidirectional=audio_bidirectional)
+                         audio_embed_size, variant='reg', seed=seed, audio_bidirectional=audio_bidirectional,
+                         text_impl=text_impl)
 
 
 class MyLoss(models.MyLoss):
@@ -79,7 +81,7 @@ def build(seed=None):
     global model, optimizer, criterion
     model = fusion_net(config['text_embed_size'], config['text_hidden_dims'], config['rnn_layers'], config['dropout'],
                        config['num_classes'], config['audio_hidden_dims'], config['audio_embed_size'], seed=seed,
-                       audio_bidirectional=config.get('audio_bidirectional', False))
+                       audio_bidirectional=config.get('audio_bidirectional', False), text_impl=config.get('text_impl'))
     optimizer = nn.Adam(model.parameters(), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'),
                         accumulate_steps=config.get('accum_steps', 1), **_common.optim_options(config))
     criterion = MyLoss(**_common.reg_options(config))       # config['loss'] / 'loss_beta' / 'loss_delta'; absent: the reference's SmoothL1

@@ -34,6 +34,7 @@ config = {
     'cuda': False,
     'lambda': 1e-5,
     'audio_bidirectional': False,      # True: the audio branch is the bidirectional AudioBiLSTM's encoder (BiGRU + attention)
+    'text_impl': None,                 # 8: the frozen text BiLSTM runs the exchange-free forward (needs no CUs to itself); None: the cluster sweeps
 }
 
 model = None
@@ -71,9 +72,10 @@ class fusion_net(models.FusionNet):
     """Reference lines 245-374."""
 
     def __init__(self, text_embed_size, text_hidden_dims, rnn_layers, dropout, num_classes,
-                 audio_hidden_dims, audio_embed_size, seed=None, audio_bidirectional=False):
+                 audio_hidden_dims, audio_embed_size, seed=None, audio_bidirectional=False, text_impl=None):
         super().__init__(text_embed_size, text_hidden_dims, rnn_layers, dropout, num_classes, audio_hidden_dims,
-                         audio_embed_size, variant='clf', seed=seed, audio_bidirectional=audio_bidirectional)
+                         audio_embed_size, variant='clf', seed=seed, audio_bidirectional=audio_bidirectional,
+                         text_impl=text_impl)
 
 
 class MyLoss(models.MyLoss):
@@ -94,7 +96,7 @@ def build(seed=None):
     global model, optimizer, criterion
     model = fusion_net(config['text_embed_size'], config['text_hidden_dims'], config['rnn_layers'], config['dropout'],
                        config['num_classes'], config['audio_hidden_dims'], config['audio_embed_size'], seed=seed,
-                       audio_bidirectional=config.get('audio_bidirectional', False))
+                       audio_bidirectional=config.get('audio_bidirectional', False), text_impl=config.get('text_impl'))
     optimizer = nn.Adam(model.parameters(), lr=config['learning_rate'], max_grad_norm=config.get('max_grad_norm'),
                         accumulate_steps=config.get('accum_steps', 1), **_common.optim_options(config))
     criterion = MyLoss()

@@ -32,6 +32,20 @@ def _rnn_names(prefix, F, H, Lyr, dirs, G):
     return out
 
 
+def _local_lstm_choice(value, what, F, H, Lyr):
+    """A model's choice of forward-only text sweeps: None -> impl 0 (the default plan: the cluster BiLSTM where it exists), 8 ->
+    L.IMPL_LOCAL_LSTM, the exchange-free forward that needs no co-resident workgroups (H = 128).  Anything else is a DepError."""
+    if value is None:
+        return L.IMPL_AUTO
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or int(value) != L.IMPL_LOCAL_LSTM:
+        raise L.DepError(f'{what}: None (the default sweeps) or {L.IMPL_LOCAL_LSTM} (the exchange-free LSTM forward), got {value!r}')
+    probe = L.RnnDesc(L.CELL_LSTM, 1, 1, F, H, Lyr, 2, L.RUN_EVAL, 0.0, 0, L.POOL_NONE, L.IMPL_LOCAL_LSTM)
+    lib = L.load()
+    if lib.dep_rnn_workspace_bytes(probe) == 0:
+        raise L.DepError(f'{what} = {L.IMPL_LOCAL_LSTM}: ' + lib.dep_last_error().decode())
+    return L.IMPL_LOCAL_LSTM
+
+
 class _RnnCache:
     """dep_rnn descriptors + reserve/workspace per (B,T,run mode) so steady-state steps never allocate."""
 
@@ -674,6 +688,9 @@ class TextBiLSTM(nn.Module):
         self._rnn_w = [self._params[n].data for n, _ in rn]
         self._rnn_g = [self._params[n]._grad for n, _ in rn]
         self._rnns = _RnnCache(L.CELL_LSTM, F, H, Lyr, 2, self.dropout, L.POOL_NONE, self.device)
+        # config['eval_impl'] = 8: a forward in eval() mode runs the exchange-free LSTM forward (no backward follows it); training keeps its cache
+        eval_impl = _local_lstm_choice(config.get('eval_impl'), "TextBiLSTM: config['eval_impl']", F, H, Lyr)
+        self._eval_rnns = None if eval_impl == L.IMPL_AUTO else _RnnCache(L.CELL_LSTM, F, H, Lyr, 2, self.dropout, L.POOL_NONE, self.device, impl=eval_impl)
         self._head = _MLPHead(self, self._fc[0], self._fc[1], self.dropout, variant == 'reg', (L.SITE_FC0, L.SITE_FC1))
 
     def check_health(self):
@@ -701,7 +718,8 @@ class TextBiLSTM(nn.Module):
     def encode(self, x, training, seed, lengths=None):
         B, T, F = x.shape
         P = self._params
-        rnn = self._rnns.get(B, T, training)
+        rnns = self._eval_rnns if (self._eval_rnns is not None and int(training) == L.RUN_EVAL) else self._rnns
+        rnn = rnns.get(B, T, training)
         h_n = torch.empty(2 * self.rnn_layers, B, self.hidden_dims, dtype=torch.float32, device=self.device)
         rnn.forward(x, self._rnn_w, seed=seed, h_n=h_n, lengths=lengths)
         out = rnn.layer_output()
@@ -728,6 +746,9 @@ class TextBiLSTM(nn.Module):
 
     def backward(self, dz):
         x, rnn, out, att, lengths = self._saved
+        if rnn.desc.impl == L.IMPL_LOCAL_LSTM:
+            raise L.DepError("TextBiLSTM.backward: the last forward ran in eval() mode on config['eval_impl'] = 8, the exchange-free LSTM "
+                             'forward, which saves no gates and has no backward; call train() and run the forward again')
         P = self._params
         dctx = self._head.backward(dz)
         dout, dh_n = L.attn_bwd(dctx, out, P['attention_layer.0.weight'].data, att, 2 * self.rnn_layers,
@@ -747,9 +768,11 @@ class FusionNet(nn.Module):
     `attention_layer_audio.0.*` (the reference's fusion class gives `attention_layer.0.*` to the text attention)."""
 
     def __init__(self, text_embed_size, text_hidden_dims, rnn_layers, dropout, num_classes, audio_hidden_dims,
-                 audio_embed_size, variant='clf', seed=None, audio_bidirectional=False):
+                 audio_embed_size, variant='clf', seed=None, audio_bidirectional=False, text_impl=None):
         super().__init__()
         self.variant = variant
+        # text_impl = 8: the frozen text BiLSTM on the exchange-free forward (same parameters, same state dict); None: the default plan
+        self.text_impl = _local_lstm_choice(text_impl, 'FusionNet: text_impl', text_embed_size, text_hidden_dims, rnn_layers)
         self.audio_bidirectional = bi = bool(audio_bidirectional)
         if bi:          # the sweeps AudioGRU chooses for this width; a DepError by name where no bidirectional sweep runs it
             self._bi_impl = AudioGRU._bidirectional_impl(audio_embed_size, audio_hidden_dims, rnn_layers)
@@ -786,7 +809,7 @@ class FusionNet(nn.Module):
         self._finalize(init)
         self._wt = [self._params[n].data for n, _ in rt]
         self._wa = [self._params[n].data for n, _ in ra]
-        self._rnn_t = _RnnCache(L.CELL_LSTM, Ft, Ht, Lyr, 2, self.dropout, L.POOL_NONE, self.device)
+        self._rnn_t = _RnnCache(L.CELL_LSTM, Ft, Ht, Lyr, 2, self.dropout, L.POOL_NONE, self.device, impl=self.text_impl)
         if bi:
             self._rnn_a = _RnnCache(L.CELL_GRU, Fa, Ha, Lyr, 2, self.dropout, L.POOL_NONE, self.device, impl=self._bi_impl)
         else:

@@ -127,6 +127,18 @@ typedef struct {
                             hx / dhx go through the backward at all four H; cx / c_n / dc_n / dcx are refused with the rule naming
                             impl = 7, as is any other cell, dirs or H.  The workspace is at least impl = 6's: its exchange buffer also
                             covers the backward's payload (dep_rnn_status and dep_rnn_workspace_xbuf_offset work as on impl = 6).
+                            8 the exchange-free per-layer LSTM forward: an LSTM (cell = DEP_CELL_LSTM) with H = 128, dirs 1 or 2, any B,
+                            T, F and L, in DEP_RUN_EVAL and DEP_RUN_DROPOUT_ONLY -- the run modes no backward follows.  Every forward,
+                            dense or ragged, runs one projection GEMM and ONE launch of lstm_fwd_local per layer: a workgroup owns a
+                            (direction, 16-utterance tile) and the whole W_hh of its direction, so nothing is exchanged between
+                            workgroups -- the sweep needs no co-residency, runs the same beside other streams or processes
+                            (dep_rnn_set_exclusive has no effect on it), covers any B in one launch and cannot give up: there is no
+                            exchange buffer (dep_rnn_workspace_xbuf_offset is (size_t)-1) and dep_rnn_status is always DEP_OK.  It
+                            takes hx, cx and c_n (dep_rnn_forward_state[_varlen] below).  The reserve offsets of y / dropout(y) are
+                            those of impl = 3; outputs agree with impl = 3 to rounding, the dropout masks bit for bit.  GEMM mode 0
+                            runs the exact-fp32 instance, modes 1 / 2 / 3 the three-term split instance (a ragged call in modes
+                            2 / 3 is refused as on every plan).  DEP_RUN_TRAIN, any other cell or H, and every backward entry point
+                            are refused (size queries 0, entry points DEP_ERR_ARG) with the rule naming impl = 8 in dep_last_error.
                             A bidirectional GRU otherwise has tile-MFMA kernels only: impl must be 0 or 2 (both mean those kernels)
                             and H a multiple of 16 they can tile -- H / 16 = waves x tiles per wave with waves in
                             {1,2,4,8} and at most 4 tiles per wave, inside the LDS bound: H in {16,32,48,64,96,128,192,256}.
@@ -340,6 +352,10 @@ int dep_rnn_backward_overlapped_varlen(const dep_rnn_desc* d, const float* x, co
  *     dh_n's buffer (the thread that stores a value read that address before the sweep); hx must be 16-byte aligned.  Refused there
  *     before anything is launched: cx / c_n / dc_n / dcx (a GRU), and a state-bearing backward in GEMM modes 2 / 3 (the bf16-storage
  *     and single-product instances take no hx);
+ *   - on an impl = 8 descriptor (the exchange-free per-layer LSTM forward) hx, cx and c_n are accepted by dep_rnn_forward_state and
+ *     dep_rnn_forward_state_varlen: a workgroup loads its tile's rows of the direction's hx / cx slice in front of its first step and
+ *     stores h_n / c_n behind its last, so h_n may be hx's buffer and c_n cx's at every T; a ragged row of length 0 returns its state
+ *     bit for bit.  It has no backward, so every dep_rnn_backward* call is refused with the rule naming impl = 8;
  *   - on any other descriptor (impl 0 / 3 with cluster kernels) the call returns DEP_ERR_ARG before anything is launched, with the rule
  *     in dep_last_error.
  * Scope
