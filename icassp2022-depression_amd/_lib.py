@@ -25,6 +25,9 @@ IMPL_CLUSTER_BIGRU = 6
 IMPL_CLUSTER_BIGRU_TRAIN = 7
 # the exchange-free per-layer LSTM forward (LSTM, H = 128, RUN_EVAL / RUN_DROPOUT_ONLY; no exchange buffer, takes hx / cx / c_n, no backward)
 IMPL_LOCAL_LSTM = 8
+# the exchange-free per-layer LSTM sweeps, forward and backward (LSTM, H = 128, every run mode; IMPL_LOCAL_LSTM's forwards, plus a saving
+# RUN_TRAIN forward and a backward that take hx / cx / c_n / dh_n / dc_n / dhx / dcx, dense and ragged, in GEMM modes 0 and 1)
+IMPL_LOCAL_LSTM_TRAIN = 9
 LOSS_CE_ON_SOFTMAX, LOSS_L1_RELU, LOSS_SMOOTHL1_RELU, LOSS_CE_LOGITS, LOSS_SMOOTHL1 = 0, 1, 2, 3, 4
 LOSS_LABELS_I64 = 0x100                     # OR into a CE kind: int64 labels read in place
 REG_L1, REG_SMOOTHL1, REG_HUBER, REG_MSE = 0, 1, 2, 3      # dep_head_loss_reg's forms
@@ -685,10 +688,10 @@ class Rnn:
         rb = self.lib.dep_rnn_reserve_bytes(C.byref(self.desc))
         wb = self.lib.dep_rnn_workspace_bytes(C.byref(self.desc))
         if rb == 0 or wb == 0:
-            # the size query says which rule a BiGRU or an impl = 4 / 5 / 6 / 7 / 8 descriptor broke
-            why = self.lib.dep_last_error().decode() if (cell == CELL_GRU and dirs == 2) or impl in (IMPL_CLUSTER_PER_LAYER, IMPL_CLUSTER_PER_LAYER_STATE, IMPL_CLUSTER_BIGRU, IMPL_CLUSTER_BIGRU_TRAIN, IMPL_LOCAL_LSTM) else ''
+            # the size query says which rule a BiGRU or an impl = 4 / 5 / 6 / 7 / 8 / 9 descriptor broke
+            why = self.lib.dep_last_error().decode() if (cell == CELL_GRU and dirs == 2) or impl in (IMPL_CLUSTER_PER_LAYER, IMPL_CLUSTER_PER_LAYER_STATE, IMPL_CLUSTER_BIGRU, IMPL_CLUSTER_BIGRU_TRAIN, IMPL_LOCAL_LSTM, IMPL_LOCAL_LSTM_TRAIN) else ''
             raise DepError(f'bad rnn descriptor: {cell=} {B=} {T=} {F=} {H=} {L=} {dirs=} {impl=}' +
-                           (f': {why}' if 'bidirectional GRU' in why or 'impl = 4' in why or 'impl = 5' in why or 'impl = 6' in why or 'impl = 7' in why or 'impl = 8' in why else ''))
+                           (f': {why}' if 'bidirectional GRU' in why or 'impl = 4' in why or 'impl = 5' in why or 'impl = 6' in why or 'impl = 7' in why or 'impl = 8' in why or 'impl = 9' in why else ''))
         self.reserve = torch.empty(rb // 4, dtype=torch.float32, device=device)
         self.workspace = torch.empty(wb // 4, dtype=torch.float32, device=device)
         self.n_w = 4 * L * dirs
@@ -821,7 +824,8 @@ class Rnn:
         lengths: the lengths of the ragged forward that wrote the reserve (the *_varlen entry points).
         hx, cx: the state the forward started from; dc_n: the gradient of c_n; dhx, dcx: receive the gradients of hx / cx (written).
         Any of them -> dep_rnn_backward_state (dense calls on the tile-MFMA / generic sweeps, and hx / dhx on the per-layer cluster GRU
-        sweeps of impl = IMPL_CLUSTER_PER_LAYER_STATE in GEMM modes 0 and 1, where dhx may be dh_n's tensor; include/dep_rnn.h)."""
+        sweeps of impl = IMPL_CLUSTER_PER_LAYER_STATE in GEMM modes 0 and 1, where dhx may be dh_n's tensor; every member on
+        impl = IMPL_LOCAL_LSTM_TRAIN, where dhx / dcx may be the tensors of dh_n / dc_n; include/dep_rnn.h)."""
         for i, (w, g) in enumerate(zip(weights, dweights)):
             self._warr[i] = w.data_ptr()
             self._garr[i] = g.data_ptr()

@@ -187,7 +187,8 @@ struct Layout {
     bool fused2;                     // 2-layer GRU, H = 256: both layers in one launch (rnn_fused2*.hip) where the call's plan allows it
     size_t wih_img;                  // workspace: packed W_ih of layer 1 for the fused launches
     size_t hxstage;                  // workspace (impl 4 / 5 / 6 only): dirs x B x H floats, a layer's hx copied aside when T = 1 and h_n overlaps it
-    bool local_lstm;                 // impl 8: every forward on lstm_fwd_local (rnn_local_lstm.hip); no exchange buffer, nothing of `cluster` holds
+    bool local_lstm;                 // impl 8 / 9: every forward on lstm_fwd_local (rnn_local_lstm.hip); no exchange buffer, nothing of `cluster` holds
+    bool local_train;                // impl 9: ... a DEP_RUN_TRAIN forward on its saving instance, the backward on lstm_bwd_local; wpT holds that sweep's image
 };
 
 // A bidirectional GRU runs the tile-MFMA sweeps (gru_*_mfma<JPW, RAG, true>) and nothing else: it has no generic, cluster or fused
@@ -252,10 +253,40 @@ int local_refusal(const dep_rnn_desc* d, const char* who) {
     return DEP_ERR_ARG;
 }
 
+// impl = 9, "the exchange-free per-layer LSTM sweeps, forward and backward": impl = 8 in every forward no backward follows (the same
+// lstm_fwd_local instances, the same bits), plus DEP_RUN_TRAIN: that forward runs lstm_fwd_save_local, which also stores the fp32 activated
+// gates and c where the layout keeps the LSTM's saved gates, and packs the backward's W_hh image beside the forward's; every backward entry
+// point runs ONE launch of lstm_bwd_local per layer, which writes the fp32 gate-gradient rows (ldg = dirs*4H) and one dbpart row per
+// (direction, tile), so everything behind the sweep is the unpaired code the tile sweeps run.  It takes every state member, dense and ragged.
+bool local_train_impl(const dep_rnn_desc* d) { return d->impl == 9; }
+bool local_train_ok(const dep_rnn_desc* d) {
+    return dep_local_lstm_ok(d->cell, d->H, d->dirs) && d->L >= 1 && d->L <= MAXL &&
+           (d->training == DEP_RUN_EVAL || d->training == DEP_RUN_TRAIN || d->training == DEP_RUN_DROPOUT_ONLY);
+}
+
+// dep_last_error for an impl = 9 descriptor refused by the rule above (DEP_OK for any other descriptor)
+int local_train_refusal(const dep_rnn_desc* d, const char* who) {
+    if (!d || !local_train_impl(d) || local_train_ok(d)) return DEP_OK;
+    dep_set_error("%s: impl = 9 (the exchange-free per-layer LSTM sweeps, forward and backward) is an LSTM with H = 128: cell must be DEP_CELL_LSTM, "
+                  "dirs 1 or 2, L 1 .. %d and the run mode DEP_RUN_EVAL, DEP_RUN_TRAIN or DEP_RUN_DROPOUT_ONLY; "
+                  "got cell = %d, H = %d, dirs = %d, L = %d, run mode = %d", who, MAXL, d->cell, d->H, d->dirs, d->L, d->training);
+    return DEP_ERR_ARG;
+}
+
+// impl = 9 trains in the parity modes only: the saving forward and the backward have no single-product instances
+int local_train_mode_refusal(const dep_rnn_desc* d, const char* who, int mode) {
+    if (!local_train_impl(d) || mode <= 1) return DEP_OK;
+    dep_set_error("%s: impl = 9 (the exchange-free per-layer LSTM sweeps, forward and backward) runs its DEP_RUN_TRAIN forward and its backward in GEMM "
+                  "modes 0 and 1 only; the current mode is %d (dep_set_gemm_mode).  Its DEP_RUN_EVAL and DEP_RUN_DROPOUT_ONLY forwards run in all four", who, mode);
+    return DEP_ERR_ARG;
+}
+
 bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     if (!d || d->B <= 0 || d->T <= 0 || d->F <= 0 || d->H <= 0 || d->L < 1 || d->L > MAXL) return false;
     if (local_impl(d) && !local_ok(d)) return false;
-    lo.local_lstm = local_impl(d);
+    if (local_train_impl(d) && !local_train_ok(d)) return false;
+    lo.local_train = local_train_impl(d);
+    lo.local_lstm = local_impl(d) || lo.local_train;
     if (percluster_impl(d) && !percluster_ok(d)) return false;
     if (bicluster_impl(d) && !bicluster_ok(d)) return false;
     if (d->cell == DEP_CELL_GRU) { if (d->dirs != 1 && !(d->dirs == 2 && (bigru_ok(d) || bicluster_impl(d)))) return false; }
@@ -307,6 +338,7 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     lo.nwg = dep_sweep_num_wg(d->B, d->H, d->impl);
     lo.cluster_bwd2 = bicluster_train_impl(d);
     if (lo.cluster_bwd2) lo.nwg = dep_cdiv(d->B, 16);      // the bidirectional cluster backward: one row per (direction, tile) at every H
+    if (lo.local_train) lo.nwg = dep_cdiv(d->B, 16);       // lstm_bwd_local: likewise
     size_t w = 0;
     lo.gi = w; w += al(lo.BT * D * (G + (d->cell == DEP_CELL_GRU && lo.keep ? 1 : 0)) * H);     // GI (fwd) / dGI (bwd; GRU: room for the 4H-wide [dr|dz|dn|dn*r] rows)
     lo.dghn = w; w += al(lo.BT * (d->cell == DEP_CELL_GRU ? D : 1) * H);      // GRU: (B,T,dirs*H)
@@ -342,7 +374,7 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
     // (a bidirectional GRU is never planned onto the cluster, 16-unit-member or fused kernels: dep_cluster_ok does not look at dirs)
     const bool cok = d->cell == DEP_CELL_GRU ? d->dirs == 1 && dep_cluster_ok(d->cell, d->H, d->B, d->dirs) : dep_cluster_lstm_ok(d->H, d->B, d->dirs);
     if (d->impl == 3 && !cok) return false;
-    lo.cluster = cok && (d->impl == 0 || d->impl == 3 || percluster_impl(d));      // (impl 8: none of the cluster parts)
+    lo.cluster = cok && (d->impl == 0 || d->impl == 3 || percluster_impl(d));      // (impl 8 / 9: none of the cluster parts)
     // impl 6 (checked above): the bidirectional forward's exchange buffer and the hx staging area, and none of what `cluster` selects
     lo.cluster_fwd = bicluster_impl(d);
     // impl 7: the larger of the bidirectional forward's buffer and the bidirectional backward's
@@ -374,7 +406,8 @@ bool make_layout(const dep_rnn_desc* d, Layout& lo) {
 extern "C" size_t dep_rnn_reserve_bytes(const dep_rnn_desc* d) {
     Layout lo;
     if (!make_layout(d, lo)) {
-        if (!percluster_refusal(d, "dep_rnn_reserve_bytes") && !bicluster_refusal(d, "dep_rnn_reserve_bytes") && !local_refusal(d, "dep_rnn_reserve_bytes"))
+        if (!percluster_refusal(d, "dep_rnn_reserve_bytes") && !bicluster_refusal(d, "dep_rnn_reserve_bytes") && !local_refusal(d, "dep_rnn_reserve_bytes") &&
+            !local_train_refusal(d, "dep_rnn_reserve_bytes"))
             (void)bigru_refusal(d, "dep_rnn_reserve_bytes");
         return 0;
     }
@@ -383,7 +416,8 @@ extern "C" size_t dep_rnn_reserve_bytes(const dep_rnn_desc* d) {
 extern "C" size_t dep_rnn_workspace_bytes(const dep_rnn_desc* d) {
     Layout lo;
     if (!make_layout(d, lo)) {
-        if (!percluster_refusal(d, "dep_rnn_workspace_bytes") && !bicluster_refusal(d, "dep_rnn_workspace_bytes")) (void)local_refusal(d, "dep_rnn_workspace_bytes");
+        if (!percluster_refusal(d, "dep_rnn_workspace_bytes") && !bicluster_refusal(d, "dep_rnn_workspace_bytes") && !local_refusal(d, "dep_rnn_workspace_bytes"))
+            (void)local_train_refusal(d, "dep_rnn_workspace_bytes");
         return 0;
     }
     return lo.ws_floats * sizeof(float);
@@ -457,9 +491,11 @@ enum FwdKernel { FWD_FUSED2,          // both GRU layers in one launch, the per-
                  FWD_CLUSTER16,       // GRU, 16-unit members (rnn_cluster16.hip)
                  FWD_CLUSTER_GRU,     // GRU, 32-unit members (rnn_cluster.hip)
                  FWD_CLUSTER_LSTM,    // (Bi)LSTM cluster (rnn_cluster_lstm.hip)
-                 FWD_LOCAL_LSTM,      // (Bi)LSTM, one workgroup per (direction, tile), no exchange (rnn_local_lstm.hip; impl 8)
+                 FWD_LOCAL_LSTM,      // (Bi)LSTM, one workgroup per (direction, tile), no exchange (rnn_local_lstm.hip; impl 8 / 9)
                  FWD_TILE };          // tile-MFMA / generic sweep (rnn_sweep.hip picks by impl and H)
-enum BwdKernel { BWD_FUSED2, BWD_CLUSTER_GRU, BWD_CLUSTER_LSTM, BWD_TILE };
+enum BwdKernel { BWD_FUSED2, BWD_CLUSTER_GRU, BWD_CLUSTER_LSTM,
+                 BWD_LOCAL_LSTM,      // (Bi)LSTM, one workgroup per (direction, tile), no exchange (lstm_bwd_local, rnn_local_lstm.hip; impl 9)
+                 BWD_TILE };
 // the split-precision recurrent-weight images (the fp32 fragment images of dep_pack_whh are RnnPlan::whh_f32)
 enum WhhImage { WHH_NONE, WHH_SPLIT16, WHH_SPLIT32, WHH_LSTM_PAIR /* forward and backward image in one launch */, WHH_BWD_SPLIT, WHH_BWD_F32 /* fp32, member-sliced */ };
 // What a forward leaves behind in its reserve: dep_rnn_backward must run kernels of the same kind (reserve_tag_refusal).
@@ -497,6 +533,10 @@ struct RnnPlan {
 // behind the sweep follow the mode on their own (a mode-3 backward is refused by dep_rnn_backward: no PK image to take the hi rows of).
 // impl = 8 (lo.local_lstm): FWD_LOCAL_LSTM, dense or ragged, whatever `excl` says: the split instance on the forward image of
 // pack_lstm_split_kernel in modes 1 / 2 / 3, the exact instance on the fp32 fragment image in mode 0.  No backward is ever planned on it.
+// impl = 9 (lo.local_train): impl = 8's plan, and BWD_LOCAL_LSTM, dense or ragged.  A DEP_RUN_TRAIN forward packs both images of a direction:
+// WHH_LSTM_PAIR (one launch of pack_lstm_split_kernel with `bwd` set) in split mode, the two fp32 fragment images of dep_pack_whh in mode 0.
+// fp32 saved gates (sv16 off), fp32 gate-gradient rows (pk off, dg4 off), the unpaired contractions.  Modes 2 / 3 are refused for the training
+// forward and the backward (local_train_mode_refusal) before anything is launched.
 RnnPlan make_plan(const dep_rnn_desc* d, const Layout& lo, int mode, bool excl, bool ragged) {
     const RnnSwitches& sw = dep_rnn_switches();
     const bool gru = d->cell == DEP_CELL_GRU;
@@ -508,7 +548,7 @@ RnnPlan make_plan(const dep_rnn_desc* d, const Layout& lo, int mode, bool excl, 
     p.fwd = (lo.fused2 && p.split && excl && !ragged) ? FWD_FUSED2 : (cluster16 && excl && !ragged) ? FWD_CLUSTER16
           : lo.cluster_fwd ? FWD_CLUSTER_GRU : lo.local_lstm ? FWD_LOCAL_LSTM : !lo.cluster ? FWD_TILE : gru ? FWD_CLUSTER_GRU : FWD_CLUSTER_LSTM;
     p.bwd = (lo.fused2 && sw.fused2_bwd && p.split && dep_fused2_bwd_fits(d->B, d->T) && !ragged) ? BWD_FUSED2
-          : lo.cluster_bwd2 ? BWD_CLUSTER_GRU : !lo.cluster ? BWD_TILE : gru ? BWD_CLUSTER_GRU : BWD_CLUSTER_LSTM;
+          : lo.cluster_bwd2 ? BWD_CLUSTER_GRU : lo.local_train ? BWD_LOCAL_LSTM : !lo.cluster ? BWD_TILE : gru ? BWD_CLUSTER_GRU : BWD_CLUSTER_LSTM;
     p.whh_f32 = (lo.cluster || lo.local_lstm) ? !p.split : lo.cluster_fwd ? (!p.split || (lo.keep && !lo.cluster_bwd2)) : dep_sweep_use_mfma(d->H, d->impl);
     p.whh_fwd = !csplit ? WHH_NONE : !gru ? WHH_LSTM_PAIR : p.fwd == FWD_CLUSTER16 ? WHH_SPLIT16 : WHH_SPLIT32;
     p.whh_bwd = (!(lo.cluster || lo.cluster_bwd2) || !lo.keep || p.whh_fwd == WHH_LSTM_PAIR) ? WHH_NONE : p.split ? WHH_BWD_SPLIT : WHH_BWD_F32;
@@ -585,6 +625,9 @@ int ragged_mode_refusal(const char* who, const int32_t* lengths, int mode) {
 
 // dep_rnn_*_state: a call that brings a state (any member non-NULL) runs where the per-layer sweeps of rnn_sweep.hip run the stack, and
 // the cell state belongs to the LSTM.  Checked before anything is launched (and before any HIP call); DEP_OK for a call without state.
+// impl = 8 and impl = 9 have no exchange buffer (lo.cluster is off), so they pass: impl 8's forwards take hx / cx / c_n, and impl 9 takes every
+// member in every forward and backward -- lstm_bwd_local owns the whole W_hh, so dhx / dcx are what it carries past its last step and there is
+// no host-side recurrent term; the hx term of dW_hh is the code behind the sweep.
 int state_refusal(const dep_rnn_desc* d, const Layout& lo, const char* who, bool any, bool any_c, bool backward, int mode) {
     if (!any) return DEP_OK;
     if (any_c && bicluster_train_impl(d)) {
@@ -631,12 +674,14 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
     if (const int rf = percluster_refusal(d, "dep_rnn_forward")) return rf;
     if (const int rf = bicluster_refusal(d, "dep_rnn_forward")) return rf;
     if (const int rf = local_refusal(d, "dep_rnn_forward")) return rf;
+    if (const int rf = local_train_refusal(d, "dep_rnn_forward")) return rf;
     if (const int rf = bigru_refusal(d, "dep_rnn_forward")) return rf;
     DEP_CHECK_ARG(make_layout(d, lo));
     const dep_rnn_state st = state ? *state : dep_rnn_state{nullptr, nullptr, nullptr};      // NULL and a struct of NULLs are the plain call
     // (state together with lengths is dep_rnn_forward_state_varlen: the ragged instances of rnn_sweep.hip carry the state through dead steps)
     if (const int rf = state_refusal(d, lo, lengths ? "dep_rnn_forward_state_varlen" : "dep_rnn_forward_state", st.hx || st.cx || st.c_n, st.cx || st.c_n, false, dep_get_gemm_mode())) return rf;
     const int mode = dep_get_gemm_mode();
+    if (lo.keep) { if (const int rf = local_train_mode_refusal(d, "dep_rnn_forward", mode)) return rf; }
     if (const int rf = ragged_mode_refusal("dep_rnn_forward_varlen", lengths, mode)) return rf;
     const RnnPlan p = make_plan(d, lo, mode, dep_exclusive_on(), lengths != nullptr);
     DEP_CHECK_ARG(x && weights && reserve && workspace);
@@ -769,7 +814,8 @@ static int rnn_forward_impl(const dep_rnn_desc* d, const float* x, const int32_t
             DEP_CHECK_ARG(wl[0] && wl[1] && wl[2] && wl[3]);
             // recurrent weight images in MFMA fragment order (precision / clustering decide the format: RnnPlan)
             float* const wp = R + lo.wp[l][dd]; float* const wpT = lo.wpT[l][dd] == NOT_KEPT ? nullptr : R + lo.wpT[l][dd];
-            if (p.whh_f32) { rc = dep_pack_whh(wl[1], wp, lo.local_lstm ? nullptr : wpT, G, H, s); if (rc) return rc; }
+            // (impl 8 / 9: the transposed image is the backward's, packed only by the forward a backward follows)
+            if (p.whh_f32) { rc = dep_pack_whh(wl[1], wp, (lo.local_lstm && !(lo.local_train && lo.keep)) ? nullptr : wpT, G, H, s); if (rc) return rc; }
             rc = p.whh_fwd == WHH_LSTM_PAIR ? dep_pack_cluster_lstm_split(wl[1], wp, lo.keep ? wpT : nullptr, H, s)
                : p.whh_fwd == WHH_SPLIT16 ? dep_pack_cluster16_fwd_split(wl[1], wp, H, s)
                : p.whh_fwd == WHH_SPLIT32 ? dep_pack_cluster_fwd_split(wl[1], wp, H, s) : DEP_OK;
@@ -870,6 +916,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
         dep_set_error("dep_rnn_backward: impl = 6 runs the tile-MFMA backward of the bidirectional GRU, which tiles H up to 256; H = %d has the forward only", d->H);
         return DEP_ERR_ARG;
     }
+    if (const int rf = local_train_refusal(d, "dep_rnn_backward")) return rf;
     if (const int rf = bigru_refusal(d, "dep_rnn_backward")) return rf;
     DEP_CHECK_ARG(make_layout(d, lo));
     const dep_rnn_state_grad st = state ? *state : dep_rnn_state_grad{nullptr, nullptr, nullptr, nullptr, nullptr};      // NULL and a struct of NULLs are the plain call
@@ -882,6 +929,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
     // (the cluster sweeps' rows are 4H wide; the recurrent term of dhx reads the t = 0 rows the same way, dense or ragged)
     DEP_CHECK_ARG(!(has_state && lo.cluster) || (long)d->T * 4 * d->H <= 0x7fffffffL);
     DEP_CHECK_ARG(!(has_state && lo.cluster_bwd2) || (long)d->T * 6 * d->H <= 0x7fffffffL);      // (impl 7: the tile BiGRU's 6H-wide rows)
+    if (lo.keep) { if (const int rf = local_train_mode_refusal(d, "dep_rnn_backward", mode)) return rf; }      // (another run mode: the message below)
     if (const int rf = ragged_mode_refusal("dep_rnn_backward_varlen", lengths, mode)) return rf;
     const RnnPlan p = make_plan(d, lo, mode, dep_exclusive_on(), lengths != nullptr);
     if (d->training != DEP_RUN_TRAIN) {
@@ -898,7 +946,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
         return DEP_ERR_WORKSPACE;
     }
     // the cluster kernels must match the images and saved gates dep_rnn_forward left
-    if (lo.cluster || lo.cluster_bwd2) { rc = reserve_tag_refusal(reserve, p.tag, TAG_SPLIT | TAG_BF16ST | TAG_SV16); if (rc) return rc; }
+    if (lo.cluster || lo.cluster_bwd2 || lo.local_train) { rc = reserve_tag_refusal(reserve, p.tag, TAG_SPLIT | TAG_BF16ST | TAG_SV16); if (rc) return rc; }
     hipStream_t s = (hipStream_t)stream;
     float* R = (float*)reserve; float* W = (float*)workspace;
     const int B = d->B, T = d->T, H = d->H, D = d->dirs, G = lo.G, L = d->L;
@@ -958,7 +1006,7 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
         const bool second = fused && l == 0;                  // (the fused launch left both layers' gate gradients behind)
         dep_sweep_bwd_args a{};
         a.B = B; a.T = T; a.H = H; a.cell = d->cell; a.dirs = D; a.impl = d->impl;
-        a.split = ((lo.cluster || lo.cluster_bwd2) && p.split) ? 1 : 0;
+        a.split = ((lo.cluster || lo.cluster_bwd2 || lo.local_train) && p.split) ? 1 : 0;
         for (int dd = 0; dd < D; ++dd) {
             const float* const* wl = weights + (size_t)(l * D + dd) * 4;
             a.w_hh[dd] = wl[1]; a.wpT[dd] = R + lo.wpT[l][dd];
@@ -1002,7 +1050,8 @@ static int rnn_backward_impl(const dep_rnn_desc* d, const float* x, const int32_
         float* const dgi = a.dgi; float* const dghn = a.dghn;
         if (!fused) {
             rc = p.bwd == BWD_CLUSTER_LSTM ? dep_launch_cluster_lstm_bwd(a, W + lo.xbuf, lo.xbuf_bytes)
-               : p.bwd == BWD_CLUSTER_GRU ? dep_launch_cluster_bwd(a, W + lo.xbuf, lo.xbuf_bytes) : dep_launch_sweep_bwd(a);
+               : p.bwd == BWD_CLUSTER_GRU ? dep_launch_cluster_bwd(a, W + lo.xbuf, lo.xbuf_bytes)
+               : p.bwd == BWD_LOCAL_LSTM ? dep_launch_local_lstm_bwd(a) : dep_launch_sweep_bwd(a);
             if (rc) return rc;
         }
         if (pending_ptr) {

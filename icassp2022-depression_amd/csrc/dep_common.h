@@ -324,9 +324,11 @@ int dep_attn2_bwd(const float* dctx, const float* out, const float* alpha, const
 int dep_pack_cluster_fwd_split(const float* w_hh, float* out, int H, hipStream_t s);
 int dep_pack_cluster_lstm_split(const float* w_hh, float* wp, float* wpT, int H, hipStream_t s);
 int dep_launch_cluster16_fwd(const dep_sweep_args& a, void* xbuf, size_t xbuf_bytes);
-// rnn_local_lstm.hip: the exchange-free LSTM forward (impl 8; takes a.hx, a.cx, a.c_n and a.lengths, any batch in one launch)
+// rnn_local_lstm.hip: the exchange-free LSTM forward (impl 8 / 9; takes a.hx, a.cx, a.c_n and a.lengths, any batch in one launch; with
+// a.training == DEP_RUN_TRAIN it also fills a.sv0 / a.sv1) and backward (impl 9; fp32 saved gates and gate-gradient rows, every state member)
 bool dep_local_lstm_ok(int cell, int H, int dirs);
 int dep_launch_local_lstm_fwd(const dep_sweep_args& a);
+int dep_launch_local_lstm_bwd(const dep_sweep_bwd_args& a);
 // dep_instance_table_read: each cluster-family file hands `add` the text of every row its selection functions can return (it calls
 // them over their whole argument domain; duplicates are the caller's to drop).  Host only, no device call.
 typedef void (*dep_instance_sink)(const char* text);

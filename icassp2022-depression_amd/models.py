@@ -46,6 +46,20 @@ def _local_lstm_choice(value, what, F, H, Lyr):
     return L.IMPL_LOCAL_LSTM
 
 
+def _local_lstm_train_choice(value, what, F, H, Lyr):
+    """A model's choice of training sweeps for its text BiLSTM: None -> impl 0 (the default plan), 9 -> L.IMPL_LOCAL_LSTM_TRAIN, the
+    exchange-free forward and backward that need no co-resident workgroups (H = 128).  Anything else is a DepError."""
+    if value is None:
+        return L.IMPL_AUTO
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or int(value) != L.IMPL_LOCAL_LSTM_TRAIN:
+        raise L.DepError(f'{what}: None (the default sweeps) or {L.IMPL_LOCAL_LSTM_TRAIN} (the exchange-free LSTM sweeps, forward and backward), got {value!r}')
+    probe = L.RnnDesc(L.CELL_LSTM, 1, 1, F, H, Lyr, 2, L.RUN_TRAIN, 0.0, 0, L.POOL_NONE, L.IMPL_LOCAL_LSTM_TRAIN)
+    lib = L.load()
+    if lib.dep_rnn_workspace_bytes(probe) == 0:
+        raise L.DepError(f'{what} = {L.IMPL_LOCAL_LSTM_TRAIN}: ' + lib.dep_last_error().decode())
+    return L.IMPL_LOCAL_LSTM_TRAIN
+
+
 class _RnnCache:
     """dep_rnn descriptors + reserve/workspace per (B,T,run mode) so steady-state steps never allocate."""
 
@@ -687,7 +701,10 @@ class TextBiLSTM(nn.Module):
         self._finalize(init)
         self._rnn_w = [self._params[n].data for n, _ in rn]
         self._rnn_g = [self._params[n]._grad for n, _ in rn]
-        self._rnns = _RnnCache(L.CELL_LSTM, F, H, Lyr, 2, self.dropout, L.POOL_NONE, self.device)
+        # config['train_impl'] = 9: the model's one cache is built on the exchange-free sweeps -- train() and eval() forwards and the backward
+        # all run on it, dense and ragged, single GPU or data parallel
+        train_impl = _local_lstm_train_choice(config.get('train_impl'), "TextBiLSTM: config['train_impl']", F, H, Lyr)
+        self._rnns = _RnnCache(L.CELL_LSTM, F, H, Lyr, 2, self.dropout, L.POOL_NONE, self.device, impl=train_impl)
         # config['eval_impl'] = 8: a forward in eval() mode runs the exchange-free LSTM forward (no backward follows it); training keeps its cache
         eval_impl = _local_lstm_choice(config.get('eval_impl'), "TextBiLSTM: config['eval_impl']", F, H, Lyr)
         self._eval_rnns = None if eval_impl == L.IMPL_AUTO else _RnnCache(L.CELL_LSTM, F, H, Lyr, 2, self.dropout, L.POOL_NONE, self.device, impl=eval_impl)

@@ -26,7 +26,8 @@ config = {
     'learning_rate': 1e-5,
     'hidden_dims': 128,
     'bidirectional': True,
-    'cuda': False
+    'cuda': False,
+    'train_impl': None,      # 9: train() / eval() forwards and the backward on the exchange-free LSTM sweeps (models.TextBiLSTM; H = 128)
 }
 
 model = None

@@ -27,6 +27,7 @@ config = {
     'hidden_dims': 128,
     'bidirectional': True,
     'cuda': False,
+    'train_impl': None,      # 9: train() / eval() forwards and the backward on the exchange-free LSTM sweeps (models.TextBiLSTM; H = 128)
 }
 
 model = None

@@ -139,6 +139,23 @@ typedef struct {
                             runs the exact-fp32 instance, modes 1 / 2 / 3 the three-term split instance (a ragged call in modes
                             2 / 3 is refused as on every plan).  DEP_RUN_TRAIN, any other cell or H, and every backward entry point
                             are refused (size queries 0, entry points DEP_ERR_ARG) with the rule naming impl = 8 in dep_last_error.
+                            9 the exchange-free per-layer LSTM sweeps, forward and backward: the same LSTMs (H = 128, dirs 1 or 2, L 1 .. 8)
+                            in all three run modes.  DEP_RUN_EVAL and DEP_RUN_DROPOUT_ONLY forwards are impl = 8's in every respect (the
+                            same lstm_fwd_local launches, the same bits, all four GEMM modes).  A DEP_RUN_TRAIN forward launches the
+                            saving instance lstm_fwd_save_local of the same sweep, which also stores the four activated gates as fp32
+                            (B,T,dirs*4H) and c_t as (B,T,dirs*H) into the reserve, and packs the backward's W_hh image beside the
+                            forward's; y, dropout(y), h_n and c_n are bit for bit those of a DEP_RUN_DROPOUT_ONLY forward.  Every
+                            backward entry point runs ONE launch of lstm_bwd_local per layer -- again one workgroup per (direction,
+                            16-utterance tile) with the whole W_hh^T of its direction in registers, nothing exchanged -- which writes
+                            fp32 gate-gradient rows; the bias sums, the direction-stacked dX / dW_ih and the per-direction dW_hh behind
+                            it are the code the tile sweeps run.  No exchange buffer (dep_rnn_workspace_xbuf_offset is (size_t)-1),
+                            dep_rnn_status is always DEP_OK, dep_rnn_set_exclusive has no effect.  The reserve is laid out like any
+                            DEP_RUN_TRAIN LSTM descriptor's with fp32 saved gates (y / dropout(y) offsets are impl = 3's) and goes with
+                            the impl that wrote it.  The training forward and the backward run in GEMM modes 0 (exact fp32) and 1
+                            (three-term split) only, dense and ragged; modes 2 / 3 are refused before any launch with the rule naming
+                            impl = 9, and the mode must not change between a forward and its backward.  It takes every state member
+                            (below).  Any other cell, H or L is a bad descriptor with the rule naming impl = 9.  Gradients agree with
+                            impl = 3 to rounding; there are no 16-bit saved gates, no PK gate gradients and no paired dW_hh on it.
                             A bidirectional GRU otherwise has tile-MFMA kernels only: impl must be 0 or 2 (both mean those kernels)
                             and H a multiple of 16 they can tile -- H / 16 = waves x tiles per wave with waves in
                             {1,2,4,8} and at most 4 tiles per wave, inside the LDS bound: H in {16,32,48,64,96,128,192,256}.
@@ -356,6 +373,13 @@ int dep_rnn_backward_overlapped_varlen(const dep_rnn_desc* d, const float* x, co
  *     dep_rnn_forward_state_varlen: a workgroup loads its tile's rows of the direction's hx / cx slice in front of its first step and
  *     stores h_n / c_n behind its last, so h_n may be hx's buffer and c_n cx's at every T; a ragged row of length 0 returns its state
  *     bit for bit.  It has no backward, so every dep_rnn_backward* call is refused with the rule naming impl = 8;
+ *   - on an impl = 9 descriptor (the exchange-free per-layer LSTM sweeps, forward and backward) every member is accepted: hx, cx and c_n by
+ *     every forward as on impl = 8, DEP_RUN_TRAIN included, and hx, cx, dc_n, dhx and dcx (beside dh_n) by dep_rnn_backward_state and
+ *     dep_rnn_backward_state_varlen, in GEMM modes 0 and 1.  The backward sweep owns the whole W_hh, so dhx and dcx are simply what it
+ *     carries past its last step, stored by the kernel (no host-side recurrent term); a lane reads its own slice of dh_n / dc_n before it
+ *     stores, so dhx may be dh_n's buffer and dcx dc_n's.  c_prev of a row's first forward step is cx (direction 1 of a ragged row:
+ *     at t = len_b - 1).  A ragged row of length 0 returns dhx = dh_n and dcx = dc_n bit for bit and contributes exact zeros to every
+ *     gate gradient; dy at dead positions is ignored;
  *   - on any other descriptor (impl 0 / 3 with cluster kernels) the call returns DEP_ERR_ARG before anything is launched, with the rule
  *     in dep_last_error.
  * Scope
